@@ -9,8 +9,12 @@ One "step" = one full pass of the correction stage over a synthetic read set who
   (3) consensus stage (`nextcorrect` path): every pile that came out of (2) -- O(ND) alignments -> MSA -> scoring DP ->
       consensus.
 `value` = corrected bases / wall time of (1) + (2) + (3): the whole raw_align -> sort_align -> seed_cns chain of the reference
-with no file in between.  Each stage is checked byte-for-byte against the reference in tests/, and the run itself compares the
-records of its CPU-sample piles with the compiled reference (`parity`).
+with no file in between.  Each stage is checked byte-for-byte against the reference in tests/.
+
+A plain run sets up, warms up, times the K steps and prints its line; nothing else.  `--full` adds what needs work of its own
+after the timed steps: the compiled reference's CPU baselines (consensus sample, overlapper, ovl_sort) and the comparison of the
+records of the CPU-sample piles with the compiled reference (`parity`; a mismatch makes the run exit non-zero).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs) before the line.
 
 Workloads = BASELINE.json configs, `--config N`:
   2 (default)  E. coli-like 4.6 Mb, 50x ONT, N50 ~ 20 kb, seed_cutoff 1k, -x ava-ont, ovl_sort -k 40
@@ -76,12 +80,19 @@ def parse(argv=None):
                          "(nextdenovo_amd/stage.py: Exchange)")
     ap.add_argument("--analytic-piles", action="store_true",
                     help="run the overlap stage but feed the consensus stage with piles derived from the true read positions")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the compiled reference's CPU baselines and the parity check against it "
+                         "(--no-cpu-baseline / --no-overlap-baseline leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args(argv)
     small = args.config == 2
     if args.steps is None:
         args.steps = 8 if small else 2
     if args.warmup is None:
         args.warmup = 2 if small else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -332,6 +343,53 @@ def parity_block(ref, gpu_full, piles):
             "seeds_ge_100kb": sum(1 for x in lens if x >= 100000), "deepest_pile": max(depth) if depth else 0,
             "error_seeds": sum(1 for v in ref.values() if v[0] <= 4), "reference_out_of_memory_seeds": ref_oom,
             "device_out_of_memory_seeds": sum(1 for i in ref if gpu_full[i][0] == 3), "mismatches": bad[:8]}
+
+
+def read_cns_fasta(path):
+    """{seed: corrected bases} of a cns.fasta a timed step wrote (a header line and one sequence line per record)."""
+    by_name = {}
+    with open(path, "rb") as f:
+        blob = f.read()
+    at = 0
+    while at < len(blob):
+        e1 = blob.index(b"\n", at)
+        e2 = blob.index(b"\n", e1 + 1)
+        by_name[int(blob[at + 1:e1].split()[0])] = blob[e1 + 1:e2]
+        at = e2 + 1
+    return by_name
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays together
+DUMP_BASES = 4 << 20       # positions in the sample of the corrected bases
+
+
+def dump_outputs(out_dir, names, res, fa_path, prefix=""):
+    """--dump-outputs: what the last timed step handed its caller, one entry per pile in seed order --
+      seed_ids (float64), lengths (float64: the corrected length, or the error code 2 / 3 / 4), identity (float32, as returned);
+    and from the step's cns.fasta (the records the output filter kept; none with --lengths-only) --
+      sequence_md5_48 (float64: the first 48 bits of md5 of the record's bases, -1 where the file holds no record for the pile),
+      bases_sample (float32: ASCII codes of the bases of the records concatenated in seed order; beyond DUMP_BASES bases, those at a
+      fixed, seeded sample of positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    order = sorted(range(len(res)), key=lambda i: int(names[i]))
+    arrays = {"seed_ids": np.asarray([int(names[i]) for i in order], dtype=np.float64),
+              "lengths": np.asarray([res[i][0] for i in order], dtype=np.float64),
+              "identity": np.asarray([res[i][1] for i in order], dtype=np.float32)}
+    if fa_path and os.path.exists(fa_path):
+        seqs = read_cns_fasta(fa_path)
+        got = [seqs.get(int(names[i])) for i in order]
+        arrays["sequence_md5_48"] = np.asarray([int(hashlib.md5(s).hexdigest()[:12], 16) if s is not None else -1 for s in got],
+                                               dtype=np.float64)
+        bases = np.frombuffer(b"".join(s for s in got if s is not None), dtype=np.uint8)
+        n = max(0, min(DUMP_BASES, (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // 4))
+        if bases.size > n:   # (all of them when they fit)
+            bases = bases[np.sort(np.random.default_rng(20240617).integers(0, bases.size, n))]
+        arrays["bases_sample"] = bases.astype(np.float32)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d piles do not fit in %d bytes" % (len(res), DUMP_BYTES))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), a)
 
 
 def cpu_baseline_overlap(rs_dev, preset, device_records=None, sort_k=0):
@@ -652,12 +710,15 @@ def main():
                 b_ok += ln
         with acc_lock:
             write_wall[0] += time.perf_counter() - t_w
-        return b_ok, n_ok, res, path, time.perf_counter()
+        return b_ok, n_ok, res, path, time.perf_counter(), names
+
+    last_step = []   # (names, records, cns.fasta) of the last step: what --dump-outputs writes
 
     def step():
         r_, o_, names = get_piles()
-        b_ok, n_ok, res, _, _ = consensus(r_, o_, names, fa_path)
+        b_ok, n_ok, res, _, _, _ = consensus(r_, o_, names, fa_path)
         last_res[:] = [res]
+        last_step[:] = [names, res, fa_path]
         return b_ok, n_ok
 
     step_base = [0]   # the hand-over's step number of the last warm-up step: timed step k is step_base + 1 + k on every Shard of the rank
@@ -691,13 +752,15 @@ def main():
         line = stage.StagePipeline(get_piles, lambda k, piles: consensus(piles[0], piles[1], piles[2], fa_path + (".%d" % (k % 4))),
                                    depth=depth, prefetch=True, producers=len(shards))
         ends = []
-        for _k, (b, n, res, path, _t), t_end in line.run(range(args.steps)):
+        for _k, (b, n, res, path, _t, names), t_end in line.run(range(args.steps)):
             ends.append(t_end)
             bases += b
             n_ok += n
             if t_end >= max(ends):   # (the parity block reads the file of the call that ended last)
                 last_res[:] = [res]
                 last["fa_path"] = path
+            if _k == args.steps - 1:
+                last_step[:] = [names, res, path]
         # a step's time = from the end of the call before it to its own end, in the order the calls ended (two are in flight)
         t_last = t0
         for t_end in sorted(ends):
@@ -725,6 +788,11 @@ def main():
         per_rank = gather_rank_stats(dist, torch, dist_dev, [dt, sh.stats.get("overlap_s", 0.0) if not args.no_overlap else 0.0,
                                                            (sh.stats.get("sort_s", 0.0) + sh.stats.get("assemble_s", 0.0)) if not args.no_overlap else 0.0,
                                                            cns_wall[0], float(st["piles"]), float(st["path_items"])])
+
+    if args.dump_outputs:
+        names_, res_, path_ = last_step
+        dump_outputs(args.dump_outputs, names_, res_, None if args.lengths_only else path_,
+                              prefix="rank%d_" % rank if rank else "")
 
     if rank == 0:
         if analytic:
@@ -887,21 +955,13 @@ def main():
                 out["overlap"]["counters_last_index"] = {k: int(ost[k]) for k in ("bases_sketched", "minimizers", "anchors", "tie_reads",
                                                                                   "chain_cells", "chains", "overlaps") if k in ost}
         parity_fail = False
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N = 1 only
             out["cpu_baseline"], ref = cpu_baseline(rs, piles, read_type, args.cpu_sample, max_lq)
             fa_path = last.get("fa_path", fa_path)   # (the file of the step that ended last)
             if ref and not args.lengths_only and last_res and os.path.exists(fa_path):
                 # what the LAST TIMED STEP wrote: (len, identity) of every pile from the library's records, the bases from the
                 # step's cns.fasta (a record the output filter dropped has no bases there: length and identity only)
-                by_name = {}
-                with open(fa_path, "rb") as f:
-                    blob = f.read()
-                at = 0
-                while at < len(blob):
-                    e1 = blob.index(b"\n", at)
-                    e2 = blob.index(b"\n", e1 + 1)
-                    by_name[int(blob[at + 1:e1].split()[0])] = blob[e1 + 1:e2]
-                    at = e2 + 1
+                by_name = read_cns_fasta(fa_path)
                 full = [(ln, ide, by_name.get(int(piles[i]["seed"]))) for i, (ln, ide) in enumerate(last_res[0])]
                 out["parity"] = parity_block(ref, full, piles)
                 out["parity"]["fasta_records"] = len(by_name)

@@ -1,6 +1,7 @@
 """`bench.py` itself without a GPU: its main() on a 30 kb genome with the two libraries bound to the interpreted builds (tests/simt) --
-the overlap -> sort -> pile assembly -> consensus step, the JSON contract of the one line it prints (metric, roofline, cpu_baseline,
-parity, allocation counters), the parity block against the compiled reference and the overlap job's byte comparison."""
+the overlap -> sort -> pile assembly -> consensus step, the JSON contract of the one line it prints (metric, roofline, allocation
+counters; with --full cpu_baseline and parity), the parity block against the compiled reference, the overlap job's byte comparison
+and the arrays --dump-outputs writes."""
 import ctypes as C
 import io
 import json
@@ -25,7 +26,7 @@ def test_bench_line_on_a_tiny_genome(monkeypatch):
     monkeypatch.setenv("NDGPU_OVL_SLAB_MB", "64")   # the overlap library's block pool as on the device: slabs, carved up by the library
     monkeypatch.setattr(overlap, "_lib", overlap._bind(C.CDLL(build_simt.build_overlap())))
     monkeypatch.setattr(api, "_LIB", api._bind(C.CDLL(build_simt.build())))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--genome-size", "30000", "--depth", "14", "--steps", "1", "--warmup", "1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--genome-size", "30000", "--depth", "14", "--steps", "1", "--warmup", "1", "--full"])
     import bench
     buf = io.StringIO()
     with redirect_stdout(buf):
@@ -64,11 +65,13 @@ def test_bench_line_on_a_tiny_genome(monkeypatch):
     assert d["counters"]["piles"] == d["config"]["piles_rank0"] and d["counters"]["lq_declined"] == 0
 
 
-def test_bench_steps_in_a_pipeline(monkeypatch):
+def test_bench_steps_in_a_pipeline(monkeypatch, tmp_path):
     """Two timed steps: the overlap / sort / admission stage of step k + 1 runs on a thread of its own during the consensus of step
     k, and two consensus calls are in flight at a time (the contexts of the library serve both) -- the same records, the same parity
     block read back from the file of the step that ended last, K overlap stages and K consensus stages inside the timed region; and
-    the same bases per step as with one stage after the other."""
+    the same bases per step as with one stage after the other.  A plain run (no --full) carries no CPU leg; what --dump-outputs
+    writes of the last step is the same either way and agrees with the line."""
+    import numpy as np
     import build_simt
     from nextdenovo_amd import api, overlap
     monkeypatch.setenv("NDGPU_CONTEXTS", "2")
@@ -79,7 +82,7 @@ def test_bench_steps_in_a_pipeline(monkeypatch):
     got = {}
     for mode, extra in (("pipeline", []), ("serial", ["--no-pipeline"])):
         monkeypatch.setattr(sys, "argv", ["bench.py", "--genome-size", "30000", "--depth", "14", "--steps", "2", "--warmup", "1",
-                                          "--no-cpu-baseline"] + extra)
+                                          "--dump-outputs", str(tmp_path / mode)] + extra)
         buf = io.StringIO()
         with redirect_stdout(buf):
             bench.main()
@@ -87,6 +90,23 @@ def test_bench_steps_in_a_pipeline(monkeypatch):
         assert len(lines) == 1
         got[mode] = json.loads(lines[0])
     a, b = got["pipeline"], got["serial"]
+    for d in (a, b):
+        assert "cpu_baseline" not in d and "parity" not in d and "cpu_baseline" not in d["overlap"]
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["metric"] == "corrected bases/sec"
+    names = ("seed_ids", "lengths", "identity", "sequence_md5_48", "bases_sample")
+    assert sorted(os.listdir(str(tmp_path / "pipeline"))) == sorted(n + ".npy" for n in names)
+    arr = {mode: {n: np.load(str(tmp_path / mode / (n + ".npy"))) for n in names} for mode in got}
+    for n in names:
+        x, y = arr["pipeline"][n], arr["serial"][n]
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and np.array_equal(x, y), n
+    o = arr["pipeline"]
+    assert sum(x.nbytes for x in o.values()) <= 64 << 20
+    assert o["seed_ids"].size == a["config"]["piles_rank0"] and np.all(np.diff(o["seed_ids"]) > 0)
+    kept = (o["lengths"] >= 500) & (o["identity"] >= 0.8)   # the output filter: these records and no others are in cns.fasta
+    assert np.array_equal(kept, o["sequence_md5_48"] >= 0) and kept.any()
+    assert abs(o["lengths"][kept].sum() - a["value"] * a["ms_per_step"] * 1e-3) < 1e-6 * o["lengths"][kept].sum()
+    assert o["bases_sample"].size == min(bench.DUMP_BASES, int(o["lengths"][kept].sum()))
+    assert set(np.unique(o["bases_sample"]).tolist()) <= {float(c) for c in b"ACGTacgtN"}
     assert a["pipeline"]["next_stage_begins_during_consensus"] is True and a["pipeline"]["consensus_calls_in_flight"] == 2
     assert b["pipeline"]["next_stage_begins_during_consensus"] is False and b["pipeline"]["consensus_calls_in_flight"] == 1
     for d in (a, b):

@@ -16,7 +16,7 @@ for s in $stages; do
     testsx) timeout 1700 python -m pytest tests -m gpu -q -x --timeout=900 > "$out/pytest_x.log" 2>&1; echo "pytest -x exit $?" | tee -a "$out/pytest_x.log"; tail -5 "$out/pytest_x.log" ;;
     chain)  timeout 300 python tools/chain_latency.py "$out/chain_latency.json" > "$out/chain.log" 2>&1; tail -4 "$out/chain.log" ;;
     pressure) timeout 600 python tools/pressure_overlap.py 4.6e6 "$out/pressure_overlap.json" > "$out/pressure.log" 2>&1; echo "pressure exit $?"; grep -v "^\[ndgpu_overlap\]" "$out/pressure.log" | tail -20 ;;
-    bench)  timeout 900 python bench.py --steps 10 --warmup 3 > "$out/bench_config2.json" 2> "$out/bench_config2.err"; echo "bench exit $?"
+    bench)  timeout 900 python bench.py --steps 10 --warmup 3 --full > "$out/bench_config2.json" 2> "$out/bench_config2.err"; echo "bench exit $?"
             python - "$out/bench_config2.json" <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -65,7 +65,7 @@ P
             tail -c 400 "$out/bench_rccl_one_rank.err"; grep -o '"per_rank": [^]]*]' "$out/bench_rccl_one_rank.json" ;;
     cand)   # A/B of a kernel candidate (tools/kernel_candidate.py; CAND=<name>): the product library, then the candidate in its place with the parity leg
             timeout 120 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$out/bench_product.json" 2> "$out/bench_product.err"; echo "product exit $?"
-            timeout 200 python tools/kernel_candidate.py bench ${CAND:-snake32} --steps 10 --warmup 3 > "$out/bench_${CAND:-snake32}.json" 2> "$out/bench_${CAND:-snake32}.err"; echo "candidate exit $?"
+            timeout 200 python tools/kernel_candidate.py bench ${CAND:-snake32} --steps 10 --warmup 3 --full > "$out/bench_${CAND:-snake32}.json" 2> "$out/bench_${CAND:-snake32}.err"; echo "candidate exit $?"
             python - "$out/bench_product.json" "$out/bench_${CAND:-snake32}.json" <<'P'
 import json, sys
 for p in sys.argv[1:]:
