@@ -339,6 +339,7 @@ struct DeviceAligner::State {
     DevBuf<uint32_t> d_read_pile, d_acc, d_tags, d_colidx, d_cov /* coverage | insertion counts | longest insertion: one block, one fill */, d_cellbase, d_entbase;
     DevBuf<uint32_t> d_cell_start, d_cell_len, d_cell_bpp, d_cell_blink, d_ent_pp, d_ent_ppp, d_ent_cnt, d_err;
     DevBuf<long long> d_ent_score;
+    DevBuf<uint32_t> d_link_lists;  // K9's third attempt: allocated only when a sub-batch needs it
     DevBuf<int32_t> d_cell_best, d_spec, d_fin;  // K10 segments: cell bests, boundary scores (kSegEnts per segment)
     DevBuf<SegSum> d_sums;
     DevBuf<SegItem> d_items;
@@ -487,7 +488,7 @@ DeviceAligner::DeviceAligner() : s_(new State) {
     NDGPU_NAME(d_ids) NDGPU_NAME(d_reads) NDGPU_NAME(d_piles) NDGPU_NAME(d_read_pile) NDGPU_NAME(d_acc) NDGPU_NAME(d_tags)
     NDGPU_NAME(d_colidx) NDGPU_NAME(d_cov) NDGPU_NAME(d_cellbase) NDGPU_NAME(d_entbase)
     NDGPU_NAME(d_cell_start) NDGPU_NAME(d_cell_len) NDGPU_NAME(d_cell_bpp) NDGPU_NAME(d_cell_blink) NDGPU_NAME(d_ent_pp)
-    NDGPU_NAME(d_ent_ppp) NDGPU_NAME(d_ent_cnt) NDGPU_NAME(d_err) NDGPU_NAME(d_ent_score) NDGPU_NAME(d_cell_best) NDGPU_NAME(d_spec)
+    NDGPU_NAME(d_ent_ppp) NDGPU_NAME(d_ent_cnt) NDGPU_NAME(d_err) NDGPU_NAME(d_ent_score) NDGPU_NAME(d_link_lists) NDGPU_NAME(d_cell_best) NDGPU_NAME(d_spec)
     NDGPU_NAME(d_fin) NDGPU_NAME(d_sums) NDGPU_NAME(d_items) NDGPU_NAME(d_bt_exit) NDGPU_NAME(d_bt_steps) NDGPU_NAME(d_bt_entry)
     NDGPU_NAME(d_bt_off) NDGPU_NAME(d_path) NDGPU_NAME(d_blocks) NDGPU_NAME(d_regions) NDGPU_NAME(d_strpool) NDGPU_NAME(d_cursor)
 #undef NDGPU_NAME
@@ -597,7 +598,7 @@ void DeviceAligner::release_memory() {
     NDGPU_REL(d_ids) NDGPU_REL(d_reads) NDGPU_REL(d_piles) NDGPU_REL(d_read_pile) NDGPU_REL(d_acc) NDGPU_REL(d_tags)
     NDGPU_REL(d_colidx) NDGPU_REL(d_cov) NDGPU_REL(d_cellbase) NDGPU_REL(d_entbase)
     NDGPU_REL(d_cell_start) NDGPU_REL(d_cell_len) NDGPU_REL(d_cell_bpp) NDGPU_REL(d_cell_blink) NDGPU_REL(d_ent_pp)
-    NDGPU_REL(d_ent_ppp) NDGPU_REL(d_ent_cnt) NDGPU_REL(d_err) NDGPU_REL(d_ent_score) NDGPU_REL(d_cell_best) NDGPU_REL(d_spec)
+    NDGPU_REL(d_ent_ppp) NDGPU_REL(d_ent_cnt) NDGPU_REL(d_err) NDGPU_REL(d_ent_score) NDGPU_REL(d_link_lists) NDGPU_REL(d_cell_best) NDGPU_REL(d_spec)
     NDGPU_REL(d_fin) NDGPU_REL(d_sums) NDGPU_REL(d_items) NDGPU_REL(d_bt_exit) NDGPU_REL(d_bt_steps) NDGPU_REL(d_bt_entry)
     NDGPU_REL(d_bt_off) NDGPU_REL(d_path) NDGPU_REL(d_blocks) NDGPU_REL(d_regions) NDGPU_REL(d_strpool) NDGPU_REL(d_cursor)
     NDGPU_REL(h_ops) NDGPU_REL(h_outs) NDGPU_REL(up) NDGPU_REL(down)
@@ -1764,7 +1765,8 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     std::vector<PileDev> piles_out(np);
     uint32_t herr[4] = {0, 0, 0, 0};
     // attempt 0 counts links with the small LDS lists; a cell with more distinct links than they hold raises err[0] and the
-    // sub-batch is counted and scored again with the full capacity (everything the kernels write is rewritten)
+    // sub-batch is counted and scored again with the full capacity (everything the kernels write is rewritten), and if that
+    // overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap)
     K10Args ka;
     ka.piles = S.d_piles.p;
     ka.coverage = d_cov, ka.max_size = d_insmax, ka.cell_base = S.d_cellbase.p, ka.ent_base = S.d_entbase.p;
@@ -1773,16 +1775,26 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     ka.cell_best_pp = S.d_cell_bpp.p, ka.cell_best_link = S.d_cell_blink.p, ka.cell_best = S.d_cell_best.p;
     ka.sums = S.d_sums.p, ka.spec = S.d_spec.p, ka.fin = S.d_fin.p;
     ka.seg_len = k10.seg_len, ka.warm = k10.warm, ka.guard = k10.guard, ka.force_repair = k10.force_repair;
-    for (int attempt = 0; attempt < 2; attempt++) {
+    for (int attempt = S.k9_full_capacity ? 1 : 0, first = 1; attempt < 3; attempt++, first = 0) {
         S.reserve_down(np * sizeof(PileDev) + paths * sizeof(PathItem) + 1024, st);
         S.h2d(S.d_piles.p, piles.data(), np * sizeof(PileDev), st);
-        if (attempt) HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, 4 * sizeof(uint32_t), st));
+        if (!first) HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, 4 * sizeof(uint32_t), st));
         HIP_CHECK(hipEventRecord(S.evs[2], st));
         NDGPU_DBG(st, "main: count_links %zu blocks, cells %llu ents %llu segs %u", blocks.size(), (unsigned long long)cells,
                   (unsigned long long)ents, n_segs);
-        launch_count_links(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_blocks.p, S.d_tags.p, S.d_colidx.p, d_insmax,
-                           S.d_cellbase.p, S.d_entbase.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p, S.d_ent_ppp.p,
-                           S.d_ent_cnt.p, S.d_err.p, (int)blocks.size(), attempt != 0 || S.k9_full_capacity, st);
+        if (attempt < 2) {
+            launch_count_links(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_blocks.p, S.d_tags.p, S.d_colidx.p, d_insmax,
+                               S.d_cellbase.p, S.d_entbase.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p, S.d_ent_ppp.p,
+                               S.d_ent_cnt.p, S.d_err.p, (int)blocks.size(), attempt != 0, st);
+        } else {  // (the stream is idle here: the attempt before was waited for)
+            uint32_t cap = 1;
+            for (size_t p = 0; p < np; p++) cap = std::max(cap, piles[p].n_acc);
+            const int grid = (int)std::min<size_t>(blocks.size(), (size_t)kLinkGlobalGrid);
+            S.d_link_lists.reserve((size_t)grid * 18u * cap + 1);
+            launch_count_links_global(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_blocks.p, S.d_tags.p, S.d_colidx.p, d_insmax,
+                                      S.d_cellbase.p, S.d_entbase.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p,
+                                      S.d_ent_ppp.p, S.d_ent_cnt.p, S.d_err.p, S.d_link_lists.p, cap, (int)blocks.size(), grid, st);
+        }
         HIP_CHECK(hipEventRecord(S.evs[3], st));
         NDGPU_DBG(st, "main: score + walk");
         // a sub-batch small enough for the reserved compute units (4 two-wave blocks each) scores there
@@ -1828,15 +1840,19 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
             memcpy(piles_out.data(), v_piles, np * sizeof(PileDev));
         }
         static const bool force_retry = getenv("NDGPU_K9_FORCE_RETRY") != nullptr;  // test hook: take the overflow path
-        if ((!herr[0] && !force_retry) || attempt || S.k9_full_capacity) break;
+        if (attempt == 0 ? !herr[0] && !force_retry : !herr[0]) break;
+        if (attempt == 2) break;  // (cannot happen: the lists hold one entry per accepted read)
         S.k9_retries++;
-        if (getenv("NDGPU_TRACE")) fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with %d\n", kLinkCapSmall, kLinkCap);
+        if (getenv("NDGPU_TRACE")) {
+            if (attempt == 0) fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with %d\n", kLinkCapSmall, kLinkCap);
+            else fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with the lists in device memory\n", kLinkCap);
+        }
     }
     piles.swap(piles_out);
     uint64_t tp4 = wall_ns();
     g_prof.m_msa += tp4 - tp3;
     if (herr[0]) {
-        fprintf(stderr, "[ndgpu] FATAL: more than %d distinct links in one MSA cell (device capacity)\n", kLinkCap);
+        fprintf(stderr, "[ndgpu] FATAL: a cell of the MSA holds more links than its pile has reads\n");
         abort();
     }
     float ms = 0;

@@ -511,6 +511,122 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
     }
 }
 
+// The third way through K9, for a sub-batch in which a cell holds more than kLinkCap distinct links (nd_device.h says when that
+// happens: never in assembled read sets, at will in a pile built for it).  The same counting, with the lists of the six cells in
+// device memory -- `cap` entries each, the largest number of accepted reads of any pile of the sub-batch, and an accepted read
+// puts at most one tag into a cell -- so no cell can overflow.  Nothing is kept in registers across columns and every read
+// goes through its column index: this kernel is for piles nobody has seen outside a test, it has to be right, not fast.
+// The grid is a fixed number of one-wavefront blocks that take the work items in turn, so that the lists stay small.
+// The lists are read and written with device-scope atomics and a fence closes every round: what one lane stores is what the
+// other lanes of the wavefront read in the next round, whatever the vector cache holds.
+__device__ __forceinline__ uint32_t ld_list(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_list(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(64) void count_links_global_kernel(const PileDev *__restrict__ piles, const ReadDev *__restrict__ reads,
+                                                                 const uint32_t *__restrict__ acc_list, const ColBlock *__restrict__ blocks,
+                                                                 const uint32_t *__restrict__ tags, const uint32_t *__restrict__ colidx,
+                                                                 const uint32_t *__restrict__ max_size, const uint32_t *__restrict__ cell_base,
+                                                                 const uint32_t *__restrict__ ent_base, uint32_t *__restrict__ cell_start,
+                                                                 uint32_t *__restrict__ cell_len, uint32_t *__restrict__ ent_pp,
+                                                                 uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt,
+                                                                 uint32_t *__restrict__ err, uint32_t *lists, uint32_t cap, int n_blocks) {
+    uint32_t *const l_pp = lists + (size_t)blockIdx.x * 18u * cap;  // [6][cap] each
+    uint32_t *const l_ppp = l_pp + (size_t)6u * cap;
+    uint32_t *const l_cnt = l_ppp + (size_t)6u * cap;
+    const int lane = (int)threadIdx.x;
+    for (int bi = (int)blockIdx.x; bi < n_blocks; bi += (int)gridDim.x) {
+        const ColBlock B = blocks[bi];
+        const PileDev P = piles[B.pile];
+        const uint32_t *ms = max_size + P.col_off;
+        const uint32_t *cb = cell_base + P.col_off;
+        const uint32_t *eb = ent_base + P.col_off;
+        const uint32_t *acc = acc_list + P.acc_off;
+        const uint32_t t_end = B.col0 + kColBlock < P.seed_len ? B.col0 + kColBlock : P.seed_len;
+        const uint32_t n_chunks = (P.n_acc + 63u) / 64u;
+        for (uint32_t t = B.col0; t < t_end; t++) {
+            const uint32_t width = ms[t];
+            uint64_t e = P.ent_off + eb[t];
+            for (uint32_t d = 0; d < width; d++) {
+                uint32_t n_cell[6] = {0, 0, 0, 0, 0, 0};
+                for (uint32_t chn = 0; chn < n_chunks; chn++) {
+                    bool has = false;
+                    uint32_t cur = 0, pp = kTagHead, ppp = kTagHead;
+                    const uint32_t rank = chn * 64u + (uint32_t)lane;
+                    if (rank < P.n_acc) {
+                        const ReadDev *R = &reads[acc[rank]];
+                        const uint32_t ts = R->t_s, te = R->t_e;
+                        if (t >= ts && t <= te) {
+                            const uint32_t *ci = colidx + R->colidx_off;
+                            const uint32_t i = ci[t - ts] + d;
+                            const uint32_t nx = t == te ? R->aln_len : ci[t + 1 - ts];
+                            if (i < nx) {
+                                const uint32_t *tg = tags + R->tag_off;
+                                has = true;
+                                cur = tg[i];
+                                if (i > 0) pp = tg[i - 1];
+                                if (i > 1) ppp = tg[i - 2];
+                            }
+                        }
+                    }
+                    const uint32_t b = cur & 7u;
+                    for (uint32_t bb = 0; bb < 6; bb++) {
+                        const bool mine = has && b == bb;
+                        if (!__ballot(mine)) continue;
+                        uint32_t n0 = n_cell[bb];
+                        const size_t l0 = (size_t)bb * cap;
+                        int found = -1;
+                        if (mine) {
+                            for (uint32_t j = 0; j < n0; j++)
+                                if (ld_list(&l_pp[l0 + j]) == pp && ld_list(&l_ppp[l0 + j]) == ppp) {
+                                    found = (int)j;
+                                    break;
+                                }
+                            if (found >= 0) atomicAdd(&l_cnt[l0 + (uint32_t)found], 1u);
+                        }
+                        unsigned long long rem = __ballot(mine && found < 0);
+                        while (rem) {
+                            const int ld = __ffsll((long long)rem) - 1;  // earliest read that carries a new link
+                            const uint32_t kp = (uint32_t)__shfl((int)pp, ld, 64);
+                            const uint32_t kpp = (uint32_t)__shfl((int)ppp, ld, 64);
+                            const bool in_rem = (rem >> lane) & 1ull;
+                            const unsigned long long same = __ballot(in_rem && pp == kp && ppp == kpp);
+                            if (lane == ld) {
+                                if (n0 < cap) {
+                                    st_list(&l_pp[l0 + n0], pp);
+                                    st_list(&l_ppp[l0 + n0], ppp);
+                                    st_list(&l_cnt[l0 + n0], (uint32_t)__popcll(same));
+                                } else {
+                                    atomicExch(err, 1u);
+                                }
+                            }
+                            n0 = n0 < cap ? n0 + 1 : n0;
+                            rem &= ~same;
+                        }
+                        n_cell[bb] = n0;
+                        __threadfence();
+                    }
+                }
+                const uint64_t cell0 = P.cell_off + cb[t] + (uint64_t)d * 6u;
+                for (uint32_t bb = 0; bb < 6; bb++) {
+                    const uint32_t n = n_cell[bb];
+                    const size_t l0 = (size_t)bb * cap;
+                    if (lane == 0) {
+                        cell_start[cell0 + bb] = (uint32_t)(e - P.ent_off);
+                        cell_len[cell0 + bb] = n;
+                    }
+                    for (uint32_t j = (uint32_t)lane; j < n; j += 64) {
+                        ent_pp[e + j] = ld_list(&l_pp[l0 + j]);
+                        ent_ppp[e + j] = ld_list(&l_ppp[l0 + j]);
+                        ent_cnt[e + j] = ld_list(&l_cnt[l0 + j]);
+                    }
+                    e += n;
+                }
+                __threadfence();
+            }
+        }
+    }
+}
+
 // ---- K10 -------------------------------------------------------------------------
 __device__ __forceinline__ long long ld_score(const long long *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1570,6 +1686,17 @@ void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32
         hipLaunchKernelGGL(count_links_kernel<kLinkCapSmall>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, piles,
                            reads, acc_list, blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp,
                            ent_ppp, ent_cnt, err);
+}
+
+void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
+                               const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
+                               const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
+                               uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, uint32_t *lists, uint32_t cap,
+                               int n_blocks, int grid, void *stream) {
+    if (n_blocks <= 0) return;
+    hipLaunchKernelGGL(count_links_global_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, piles, reads, acc_list,
+                       blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt, err,
+                       lists, cap, n_blocks);
 }
 
 void launch_score_backtrack(const K10Args &a, const SegItem *items_small, int n_small, const SegItem *items_large, int n_large,

@@ -247,8 +247,21 @@ struct RegionDev {          // low-quality region whose candidate strings are wa
 };
 
 constexpr int kColBlock = 32;          // columns per link-counting work item
-constexpr int kLinkCap = 192;          // distinct (pp,ppp) links per cell held in LDS (<= 1.5 x max_cov_aln reads reach a cell)
-constexpr int kLinkCapSmall = 64;      // capacity of the first attempt of the link-counting kernel
+// Distinct (pp, ppp) links per cell that the link-counting kernel holds in LDS: kLinkCapSmall in its first attempt, kLinkCap in
+// its second.  Neither is a bound.  The reference has none (lib/nextcorrect.c:163-167 grows a cell's list by realloc, five links at
+// a time).  What its rules do bound: an accepted read puts at most one tag into a cell, so a cell has at most as many links as
+// its column has reads; the admission cut (total aligned length / seed length > max_cov_aln, :2271) bounds the AVERAGE depth, so
+// windows of min_len_aln bases on one spot of a long seed stack max_cov_aln x seed_len / min_len_aln reads on a column; and a
+// tag in front of a column is (column - 1, delta, base) with delta <= 250 (a longer gap fails the alignment, lib/align.c:542-545),
+// about 1,000 values of pp alone.  Assembled read sets stay far below either capacity, because reads agree on what stands in
+// front of a column.  A pile built for it does not: 192 reads on one window that each carry an insertion in front of the same
+// column, 96 lengths closed by one of two bases, so that the link differs by (length, last base)
+// (tests/golden/make_edge_piles_golden.py, family `links`: 201 records, default arguments, coverage 87), and the reference
+// corrects it.  So a sub-batch whose cell overflows kLinkCap is counted a third time by count_links_global_kernel, whose lists
+// live in device memory and hold one entry per accepted read of the deepest pile; the family `stack` runs it with more than 600.
+constexpr int kLinkCap = 192;
+constexpr int kLinkCapSmall = 64;
+constexpr int kLinkGlobalGrid = 1024;  // blocks of the third attempt (each owns 18 lists of `cap` words)
 
 void launch_shift_scan(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, ReadDev *reads, int n_reads,
                        void *stream);
@@ -265,6 +278,11 @@ void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32
                         const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
                         uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, int n_blocks, bool full_capacity,
                         void *stream);
+void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
+                               const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
+                               const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
+                               uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, uint32_t *lists, uint32_t cap,
+                               int n_blocks, int grid, void *stream);
 // segment kernels of both table tiers (the large one on stream_large at the same time) -> stitch -> int64 kernel for
 // the piles they left (err == 2) -> best_pp walk
 // (ent_score == nullptr: the int64 kernel is not launched and leaves err == 2 piles for a second call with rescue = true,

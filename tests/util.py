@@ -95,6 +95,84 @@ def load_piles():
     return piles
 
 
+EDGE_ARGS = ("min_len_aln", "max_cov_aln", "min_cov_base", "ratio")
+
+
+def load_edge_piles(died=False):
+    """tests/golden/edge_piles.npz (tests/golden/make_edge_piles_golden.py): hand-built piles with their own nextCorrect arguments.
+    Reads are stored once and shared between piles (`rec_read`).  died=True: the cases in which the reference died -- inputs and
+    arguments only, `signal` instead of an expectation."""
+    d = np.load(os.path.join(GOLD, "edge_piles.npz"))
+    pre = "died_" if died else ""
+    cache = {}
+
+    def read(r):
+        if r not in cache:
+            packed = d["codes"][d["codes_off"][r]:d["codes_off"][r + 1]]
+            cache[r] = ASC[unpack2(packed, int(d["lens"][r]))].tobytes()
+        return cache[r]
+
+    sig = dict(s.rsplit(" ", 1) for s in d["died"].tolist())
+    piles = []
+    off = d[pre + "pile_off"]
+    for p in range(off.size - 1):
+        a, b = int(off[p]), int(off[p + 1])
+        q = dict(tag=str(d[pre + "tag"][p]), seqs=[read(int(r)) for r in d[pre + "rec_read"][a:b]],
+                 aln_start=[int(x) for x in d[pre + "aln_start"][a:b]], aln_end=[int(x) for x in d[pre + "aln_end"][a:b]],
+                 max_aln=int(d[pre + "max_aln"][p]), max_lq=int(d[pre + "max_lq"][p]), read_type=int(d[pre + "read_type"][p]),
+                 fast=int(d[pre + "fast"][p]), split=int(d[pre + "split"][p]), min_len_aln=int(d[pre + "min_len_aln"][p]),
+                 max_cov_aln=int(d[pre + "max_cov_aln"][p]), min_cov_base=int(d[pre + "min_cov_base"][p]),
+                 ratio=float(d[pre + "ratio"][p]))
+        if died:
+            q["signal"] = sig[q["tag"]]
+        else:
+            q.update(exp_len=int(d["exp_len"][p]), exp_ide=float(d["exp_ide"][p]),
+                     exp_seq=d["exp_seq"][d["exp_seq_off"][p]:d["exp_seq_off"][p + 1]].tobytes())
+        piles.append(q)
+    return piles
+
+
+def edge_args(p):
+    """The recorded arguments of an edge pile, as call_correct's overrides."""
+    return {k: p[k] for k in EDGE_ARGS}
+
+
+EDGE_TRACE_REPEAT = "sub-batch repeated with 192"                           # NDGPU_TRACE: the link counter's second attempt
+EDGE_TRACE_THIRD = "sub-batch repeated with the lists in device memory"     # ... and its third
+EDGE_CAPACITY_FAMILIES = ("repeat/", "int64/", "links/", "stack/")
+EDGE_FAMILIES = ("args", "cut", "count", "seedlen", "window", "lowc", "repeat", "int64", "links", "stack")
+
+
+def edge_wrong(p, got):
+    """None, or what differs from the reference's recorded answer."""
+    ln, ide, seq = got
+    if ln != p["exp_len"]:
+        return "%s: len %d, reference %d" % (p["tag"], ln, p["exp_len"])
+    if ln > 4 and seq != p["exp_seq"]:
+        return "%s: sequence differs" % p["tag"]
+    if ln > 4 and np.float32(ide) != np.float32(p["exp_ide"]):
+        return "%s: identity %r, reference %r" % (p["tag"], np.float32(ide), np.float32(p["exp_ide"]))
+    return None
+
+
+def edge_group_key(p):
+    """What the batched entries take once per call."""
+    return (p["min_len_aln"], p["max_cov_aln"], p["min_cov_base"], p["ratio"], p["split"], p["fast"], p["read_type"])
+
+
+def edge_groups(piles):
+    g = {}
+    for p in piles:
+        g.setdefault(edge_group_key(p), []).append(p)
+    return g
+
+
+def edge_correct_group(api, key, members):
+    return api.correct_batch([(p["seqs"], p["aln_start"], p["aln_end"], p["max_aln"], p["max_lq"]) for p in members],
+                             min_len_aln=key[0], max_cov_aln=key[1], min_cov_base=key[2], min_error_corrected_ratio=key[3],
+                             split=key[4], fast=key[5], read_type=key[6], host_threads=4)
+
+
 def load_poa():
     d = np.load(os.path.join(GOLD, "poa.npz"))
     cases, k = [], 0
@@ -108,14 +186,16 @@ def load_poa():
 
 
 def call_correct(fn, free, p, **over):
-    """fn has the nextCorrect signature (lib/nextcorrect.h:161-162)."""
+    """fn has the nextCorrect signature (lib/nextcorrect.h:161-162).  Overrides: min_len_aln, max_cov_aln, min_cov_base, max_lq,
+    ratio, split, fast (defaults: the reference driver's, and what the pile records)."""
     seqs = p["seqs"]
     n = len(seqs)
     cs = (C.c_char_p * n)()
     cs[:] = seqs
     st = (C.c_uint * n)(*p["aln_start"])
     en = (C.c_uint * n)(*p["aln_end"])
-    r = fn(cs, st, en, n, p["max_aln"], over.get("min_len_aln", 500), 130, 4, p["max_lq"], 0.8,
+    r = fn(cs, st, en, n, p["max_aln"], over.get("min_len_aln", 500), over.get("max_cov_aln", 130), over.get("min_cov_base", 4),
+           over.get("max_lq", p["max_lq"]), over.get("ratio", 0.8),
            over.get("split", p["split"]), over.get("fast", p["fast"]), p["read_type"])
     ln, ide = r.contents.len, r.contents.identity
     seq = C.string_at(r.contents.seq, ln) if ln > 4 else b""
