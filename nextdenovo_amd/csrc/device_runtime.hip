@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <string>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <mutex>
 #include <set>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -265,6 +267,90 @@ bool pack_append(std::vector<uint32_t> &pool, const char *s, size_t n) {
     return (bad & 0x80u) == 0;
 }
 
+// Every grow-only buffer of a context, once: X(element type, member, device | pinned, levelled | on_demand).  The members of State, their
+// names (the strings key the high-water marks and are shared by all contexts), release_memory's releases and level_buffers' pass are all
+// generated from this list, in this order.
+//   device | pinned: a DevBuf in HBM or a PinBuf of page-locked host memory (level_buffers charges only device growth to its budget)
+//   on_demand: reserved only by the sub-batch that needs it and therefore never levelled -- bringing it up to another context's mark
+//   would spend device memory in every context on a path most sub-batches never take; levelled: everything else
+enum class BufPlace { device, pinned };
+enum class BufLevel { levelled, on_demand };
+#define NDGPU_BUFFERS(X)                                                                                                                  \
+    /* low-quality-region rounds (K12) */                                                                                                 \
+    X(LqPileDev, d_lq_piles, device, levelled)                                                                                            \
+    X(LqPieceDev, d_lq_pieces, device, levelled)                                                                                          \
+    X(uint32_t, d_lq_rec, device, levelled)                                                                                               \
+    X(LqJobDev, d_lq_jobs, device, levelled) /* K12a's jobs and their streams: a header per cell row, a word per link */                  \
+    X(uint64_t, d_lq_hdr, device, levelled)                                                                                               \
+    X(uint32_t, d_lq_lnk, device, levelled)                                                                                               \
+    X(char, d_lq_out, device, levelled) /* the piles' characters / the jobs' stretches of the walk (one slot per cell row) */             \
+    X(char, d_lq_tmp, device, levelled)                                                                                                   \
+    X(int32_t, d_lq_bnd, device, levelled) /* K12b's boundary planes: 4 x kLqLinkCap words per job */                                     \
+    /* forward / traceback (K7 / K8a) */                                                                                                  \
+    X(uint32_t, d_pool, device, levelled)                                                                                                 \
+    X(uint32_t, d_ops, device, levelled)                                                                                                  \
+    X(AlnTask, d_tasks, device, levelled)                                                                                                 \
+    X(AlnOut, d_outs, device, levelled)                                                                                                   \
+    X(uint64_t, d_trace, device, levelled)                                                                                                \
+    X(int32_t, d_v, device, levelled)                                                                                                     \
+    /* wide-band alignments (K7w): trace rows and their min_k -- members, not locals of run_wide: a local buffer was a hipMalloc +        \
+       hipFree per call, and hipFree waits for every stream of the device */                                                              \
+    X(uint64_t, d_wtrace, device, levelled)                                                                                               \
+    X(int32_t, d_wmink, device, levelled)                                                                                                 \
+    X(AlnTask, d_wtasks, device, levelled) /* the wide tasks' records of one group, in list order (one upload, not one per task) */       \
+    /* segmented traceback (ond_kernels.hip): checkpoint cells / headers the forward kernel leaves, the walkers and what they report */   \
+    X(uint32_t, d_ck_cells, device, levelled)                                                                                             \
+    X(uint2, d_ck_hdr, device, levelled)                                                                                                  \
+    X(TbSeg, d_tbseg, device, levelled)                                                                                                   \
+    X(TbSegOut, d_tbout, device, levelled)                                                                                                \
+    X(int32_t, d_ids, device, levelled)                                                                                                   \
+    /* main phase (alive from run_main to end_batch) */                                                                                   \
+    X(ReadDev, d_reads, device, levelled)                                                                                                 \
+    X(PileDev, d_piles, device, levelled)                                                                                                 \
+    X(uint32_t, d_read_pile, device, levelled)                                                                                            \
+    X(uint32_t, d_acc, device, levelled)                                                                                                  \
+    X(uint32_t, d_tags, device, levelled)                                                                                                 \
+    X(uint32_t, d_colidx, device, levelled)                                                                                               \
+    X(uint32_t, d_cov, device, levelled) /* coverage | insertion counts | longest insertion: one block, one fill */                       \
+    X(uint32_t, d_cellbase, device, levelled)                                                                                             \
+    X(uint32_t, d_entbase, device, levelled)                                                                                              \
+    X(uint32_t, d_cell_start, device, levelled)                                                                                           \
+    X(uint32_t, d_cell_len, device, levelled)                                                                                             \
+    X(uint32_t, d_cell_bpp, device, levelled)                                                                                             \
+    X(uint32_t, d_cell_blink, device, levelled)                                                                                           \
+    X(uint32_t, d_ent_pp, device, levelled)                                                                                               \
+    X(uint32_t, d_ent_ppp, device, levelled)                                                                                              \
+    X(uint32_t, d_ent_cnt, device, levelled)                                                                                              \
+    X(uint32_t, d_err, device, levelled)                                                                                                  \
+    X(long long, d_ent_score, device, on_demand) /* the int64 scoring kernel's 8 bytes per link: only when a pile needs that kernel */    \
+    X(uint32_t, d_link_lists, device, on_demand) /* K9's third attempt: allocated only when a sub-batch needs it */                       \
+    X(int32_t, d_cell_best, device, levelled) /* K10 segments: cell bests, boundary scores (kSegEnts per segment) */                      \
+    X(int32_t, d_spec, device, levelled)                                                                                                  \
+    X(int32_t, d_fin, device, levelled)                                                                                                   \
+    X(SegSum, d_sums, device, levelled)                                                                                                   \
+    X(SegItem, d_items, device, levelled)                                                                                                 \
+    X(uint32_t, d_bt_exit, device, levelled) /* best_pp walk by segments */                                                               \
+    X(uint32_t, d_bt_steps, device, levelled)                                                                                             \
+    X(uint32_t, d_bt_entry, device, levelled)                                                                                             \
+    X(uint32_t, d_bt_off, device, levelled)                                                                                               \
+    X(PathItem, d_path, device, levelled)                                                                                                 \
+    X(ColBlock, d_blocks, device, levelled)                                                                                               \
+    X(RegionDev, d_regions, device, levelled)                                                                                             \
+    X(char, d_strpool, device, levelled)                                                                                                  \
+    X(unsigned long long, d_cursor, device, levelled)                                                                                     \
+    /* host side: run_chunk's ops and every caller's AlnOut records; the two transfer arenas (see State::h2d / d2h) */                    \
+    X(uint32_t, h_ops, pinned, levelled)                                                                                                  \
+    X(AlnOut, h_outs, pinned, levelled)                                                                                                   \
+    X(char, up, pinned, levelled)                                                                                                         \
+    X(char, down, pinned, levelled)
+
+// One launch of the forward / traceback pair: tasks [begin, end) of a context's table (plan_chunks)
+struct AlignChunk {
+    size_t begin, end;
+    bool seg;        // the traceback runs in segments (tb_assign)
+    uint64_t slots;  // walker slots of the launch (0 unless seg)
+};
+
 }  // namespace
 
 
@@ -276,22 +362,11 @@ struct DeviceAligner::State {
     hipEvent_t ev_lat0 = nullptr, ev_lat1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
     int reserved_cus = 0;
     std::mutex mu;
-    DevBuf<uint32_t> d_pool, d_ops;
-    DevBuf<AlnTask> d_tasks;
-    DevBuf<AlnOut> d_outs;
-    DevBuf<uint64_t> d_trace;
-    DevBuf<uint64_t> d_wtrace;  // wide-band alignments (K7w): trace rows and their min_k -- members, not locals of run_wide: a local
-    DevBuf<int32_t> d_wmink;    // buffer was a hipMalloc + hipFree per call, and hipFree waits for every stream of the device
-    DevBuf<AlnTask> d_wtasks;   // the wide tasks' records of one group, in list order (one upload, not one per task)
-    DevBuf<int32_t> d_v, d_ids;
-    // segmented traceback (ond_kernels.hip): checkpoint cells / headers the forward kernel leaves, the walkers and what they report
-    DevBuf<uint32_t> d_ck_cells;
-    DevBuf<uint2> d_ck_hdr;
-    DevBuf<TbSeg> d_tbseg;
-    DevBuf<TbSegOut> d_tbout;
+#define NDGPU_MEMBER(T, x, place, level) std::conditional_t<BufPlace::place == BufPlace::device, DevBuf<T>, PinBuf<T>> x;
+    NDGPU_BUFFERS(NDGPU_MEMBER)
+#undef NDGPU_MEMBER
     std::vector<int32_t> order;
     std::vector<uint32_t> order_cls;
-    // main-phase state (alive from run_main to end_batch)
     // Held from begin_batch to end_batch.  Not a plain mutex: with two batch calls in flight (the caller's pipeline: the tail of one
     // call under the main phases of the next) the context must serve the OLDER call's sub-batches first, whichever thread asked first.
     struct OrderedLock {
@@ -334,36 +409,10 @@ struct DeviceAligner::State {
             return true;
         }
     } batch_mu;
-    DevBuf<ReadDev> d_reads;
-    DevBuf<PileDev> d_piles;
-    DevBuf<uint32_t> d_read_pile, d_acc, d_tags, d_colidx, d_cov /* coverage | insertion counts | longest insertion: one block, one fill */, d_cellbase, d_entbase;
-    DevBuf<uint32_t> d_cell_start, d_cell_len, d_cell_bpp, d_cell_blink, d_ent_pp, d_ent_ppp, d_ent_cnt, d_err;
-    DevBuf<long long> d_ent_score;
-    DevBuf<uint32_t> d_link_lists;  // K9's third attempt: allocated only when a sub-batch needs it
-    DevBuf<int32_t> d_cell_best, d_spec, d_fin;  // K10 segments: cell bests, boundary scores (kSegEnts per segment)
-    DevBuf<SegSum> d_sums;
-    DevBuf<SegItem> d_items;
-    DevBuf<uint32_t> d_bt_exit, d_bt_steps, d_bt_entry, d_bt_off;  // best_pp walk by segments
-    DevBuf<PathItem> d_path;
-    DevBuf<ColBlock> d_blocks;
-    DevBuf<RegionDev> d_regions;
-    DevBuf<char> d_strpool;
-    DevBuf<unsigned long long> d_cursor;
-    // low-quality-region rounds (K12)
-    DevBuf<LqPileDev> d_lq_piles;
-    DevBuf<LqPieceDev> d_lq_pieces;
-    DevBuf<uint32_t> d_lq_rec;
-    DevBuf<LqJobDev> d_lq_jobs;   // K12a's jobs and their streams: a header per cell row, a word per link
-    DevBuf<uint64_t> d_lq_hdr;
-    DevBuf<uint32_t> d_lq_lnk;
-    DevBuf<char> d_lq_out, d_lq_tmp;   // the piles' characters / the jobs' stretches of the walk (one slot per cell row)
-    DevBuf<int32_t> d_lq_bnd;          // K12b's boundary planes: 4 x kLqLinkCap words per job
-    std::vector<ReadDev> reads;
+    std::vector<ReadDev> reads;  // main-phase state (alive from run_main to end_batch)
     std::vector<PileDev> piles;
     hipEvent_t evs[8] = {nullptr};
     std::vector<hipEvent_t> lq_evs;  // run_lq: K7 / K8a brackets per chunk
-    PinBuf<uint32_t> h_ops;
-    PinBuf<AlnOut> h_outs;
     std::vector<uint32_t> pool;
     std::vector<AlnTask> tasks;
     RuntimeStats stats;
@@ -373,12 +422,11 @@ struct DeviceAligner::State {
     bool k9_full_capacity = getenv("NDGPU_K9_FULL") != nullptr;  // skip the small-capacity first attempt of K9
     uint64_t k9_retries = 0;
 
-    // Host <-> device transfers go through two pinned arenas of the context.  An asynchronous copy from / to pageable
+    // Host <-> device transfers go through two pinned arenas of the context (up, down).  An asynchronous copy from / to pageable
     // memory makes the runtime pin the caller's pages for the duration of the copy; with eight contexts doing that at
     // the same time from neighbouring heap blocks, one context's unpin took a page another context's copy was still
     // using (GPU memory access faults on host heap addresses).  Everything a kernel or a copy engine touches is now
     // either device memory or these arenas.
-    PinBuf<char> up, down;
     size_t up_used = 0, down_used = 0;
     struct Pending {
         void *dst;
@@ -424,6 +472,11 @@ struct DeviceAligner::State {
         down_used += need;
         return at;
     }
+
+    // The forward / traceback ("align") phase that run_chunk, run_lq and run_main share (defined with the traceback's set-up below)
+    std::vector<AlignChunk> plan_chunks(AlnTask *t, size_t nt);
+    void launch_chunk(const AlignChunk &c, const int32_t *order, const int32_t *tb_order, hipEvent_t ev_mid, hipEvent_t ev_end, const char *who);
+    void tally_outs(size_t nt, std::vector<int32_t> *wide);
 };
 
 static int g_ctx_creating = -1;  // index of the context under construction (guarded by g_ctx_mu)
@@ -479,18 +532,8 @@ DeviceAligner::DeviceAligner() : s_(new State) {
             HIP_CHECK(hipEventCreateWithFlags(&s_->ev_join, hipEventDisableTiming));
         }
     }
-#define NDGPU_NAME(x) s_->x.name = #x;
-    NDGPU_NAME(h_ops) NDGPU_NAME(h_outs) NDGPU_NAME(up) NDGPU_NAME(down)
-    NDGPU_NAME(d_lq_piles) NDGPU_NAME(d_lq_pieces) NDGPU_NAME(d_lq_rec) NDGPU_NAME(d_lq_jobs) NDGPU_NAME(d_lq_hdr) NDGPU_NAME(d_lq_lnk)
-    NDGPU_NAME(d_lq_out) NDGPU_NAME(d_lq_tmp) NDGPU_NAME(d_lq_bnd)
-    NDGPU_NAME(d_pool) NDGPU_NAME(d_ops) NDGPU_NAME(d_tasks) NDGPU_NAME(d_outs) NDGPU_NAME(d_trace) NDGPU_NAME(d_v) NDGPU_NAME(d_wtrace) NDGPU_NAME(d_wmink) NDGPU_NAME(d_wtasks)
-    NDGPU_NAME(d_ck_cells) NDGPU_NAME(d_ck_hdr) NDGPU_NAME(d_tbseg) NDGPU_NAME(d_tbout)
-    NDGPU_NAME(d_ids) NDGPU_NAME(d_reads) NDGPU_NAME(d_piles) NDGPU_NAME(d_read_pile) NDGPU_NAME(d_acc) NDGPU_NAME(d_tags)
-    NDGPU_NAME(d_colidx) NDGPU_NAME(d_cov) NDGPU_NAME(d_cellbase) NDGPU_NAME(d_entbase)
-    NDGPU_NAME(d_cell_start) NDGPU_NAME(d_cell_len) NDGPU_NAME(d_cell_bpp) NDGPU_NAME(d_cell_blink) NDGPU_NAME(d_ent_pp)
-    NDGPU_NAME(d_ent_ppp) NDGPU_NAME(d_ent_cnt) NDGPU_NAME(d_err) NDGPU_NAME(d_ent_score) NDGPU_NAME(d_link_lists) NDGPU_NAME(d_cell_best) NDGPU_NAME(d_spec)
-    NDGPU_NAME(d_fin) NDGPU_NAME(d_sums) NDGPU_NAME(d_items) NDGPU_NAME(d_bt_exit) NDGPU_NAME(d_bt_steps) NDGPU_NAME(d_bt_entry)
-    NDGPU_NAME(d_bt_off) NDGPU_NAME(d_path) NDGPU_NAME(d_blocks) NDGPU_NAME(d_regions) NDGPU_NAME(d_strpool) NDGPU_NAME(d_cursor)
+#define NDGPU_NAME(T, x, place, level) s_->x.name = #x;
+    NDGPU_BUFFERS(NDGPU_NAME)
 #undef NDGPU_NAME
     const unsigned ev_flags = getenv("NDGPU_SPIN_SYNC") ? hipEventDefault : hipEventBlockingSync;  // (hipEventSynchronize sleeps, see above)
     HIP_CHECK(hipEventCreateWithFlags(&s_->ev0, ev_flags));
@@ -590,18 +633,8 @@ void DeviceAligner::release_memory() {
     (void)hipGetLastError();
     S.pending.clear();
     S.up_used = S.down_used = 0;
-#define NDGPU_REL(x) S.x.release();
-    NDGPU_REL(d_lq_piles) NDGPU_REL(d_lq_pieces) NDGPU_REL(d_lq_rec) NDGPU_REL(d_lq_jobs) NDGPU_REL(d_lq_hdr) NDGPU_REL(d_lq_lnk)
-    NDGPU_REL(d_lq_out) NDGPU_REL(d_lq_tmp) NDGPU_REL(d_lq_bnd)
-    NDGPU_REL(d_pool) NDGPU_REL(d_ops) NDGPU_REL(d_tasks) NDGPU_REL(d_outs) NDGPU_REL(d_trace) NDGPU_REL(d_v) NDGPU_REL(d_wtrace) NDGPU_REL(d_wmink) NDGPU_REL(d_wtasks)
-    NDGPU_REL(d_ck_cells) NDGPU_REL(d_ck_hdr) NDGPU_REL(d_tbseg) NDGPU_REL(d_tbout)
-    NDGPU_REL(d_ids) NDGPU_REL(d_reads) NDGPU_REL(d_piles) NDGPU_REL(d_read_pile) NDGPU_REL(d_acc) NDGPU_REL(d_tags)
-    NDGPU_REL(d_colidx) NDGPU_REL(d_cov) NDGPU_REL(d_cellbase) NDGPU_REL(d_entbase)
-    NDGPU_REL(d_cell_start) NDGPU_REL(d_cell_len) NDGPU_REL(d_cell_bpp) NDGPU_REL(d_cell_blink) NDGPU_REL(d_ent_pp)
-    NDGPU_REL(d_ent_ppp) NDGPU_REL(d_ent_cnt) NDGPU_REL(d_err) NDGPU_REL(d_ent_score) NDGPU_REL(d_link_lists) NDGPU_REL(d_cell_best) NDGPU_REL(d_spec)
-    NDGPU_REL(d_fin) NDGPU_REL(d_sums) NDGPU_REL(d_items) NDGPU_REL(d_bt_exit) NDGPU_REL(d_bt_steps) NDGPU_REL(d_bt_entry)
-    NDGPU_REL(d_bt_off) NDGPU_REL(d_path) NDGPU_REL(d_blocks) NDGPU_REL(d_regions) NDGPU_REL(d_strpool) NDGPU_REL(d_cursor)
-    NDGPU_REL(h_ops) NDGPU_REL(h_outs) NDGPU_REL(up) NDGPU_REL(down)
+#define NDGPU_REL(T, x, place, level) S.x.release();
+    NDGPU_BUFFERS(NDGPU_REL)
 #undef NDGPU_REL
 }
 
@@ -636,17 +669,9 @@ void DeviceAligner::level_buffers(int drivers) {
             buf.level();
         };
         try {
-#define NDGPU_LVL(x) lvl(S.x, #x[0] == 'd');
-            NDGPU_LVL(d_lq_piles) NDGPU_LVL(d_lq_pieces) NDGPU_LVL(d_lq_rec) NDGPU_LVL(d_lq_jobs) NDGPU_LVL(d_lq_hdr) NDGPU_LVL(d_lq_lnk) NDGPU_LVL(d_lq_out) NDGPU_LVL(d_lq_tmp) NDGPU_LVL(d_lq_bnd)
-            NDGPU_LVL(d_pool) NDGPU_LVL(d_ops) NDGPU_LVL(d_tasks) NDGPU_LVL(d_outs) NDGPU_LVL(d_trace) NDGPU_LVL(d_v) NDGPU_LVL(d_wtrace) NDGPU_LVL(d_wmink) NDGPU_LVL(d_wtasks)
-            NDGPU_LVL(d_ck_cells) NDGPU_LVL(d_ck_hdr) NDGPU_LVL(d_tbseg) NDGPU_LVL(d_tbout)
-            NDGPU_LVL(d_ids) NDGPU_LVL(d_reads) NDGPU_LVL(d_piles) NDGPU_LVL(d_read_pile) NDGPU_LVL(d_acc) NDGPU_LVL(d_tags)
-            NDGPU_LVL(d_colidx) NDGPU_LVL(d_cov) NDGPU_LVL(d_cellbase) NDGPU_LVL(d_entbase)
-            NDGPU_LVL(d_cell_start) NDGPU_LVL(d_cell_len) NDGPU_LVL(d_cell_bpp) NDGPU_LVL(d_cell_blink) NDGPU_LVL(d_ent_pp)
-            NDGPU_LVL(d_ent_ppp) NDGPU_LVL(d_ent_cnt) NDGPU_LVL(d_err) NDGPU_LVL(d_cell_best) NDGPU_LVL(d_spec)
-            NDGPU_LVL(d_fin) NDGPU_LVL(d_sums) NDGPU_LVL(d_items) NDGPU_LVL(d_bt_exit) NDGPU_LVL(d_bt_steps) NDGPU_LVL(d_bt_entry)
-            NDGPU_LVL(d_bt_off) NDGPU_LVL(d_path) NDGPU_LVL(d_blocks) NDGPU_LVL(d_regions) NDGPU_LVL(d_strpool) NDGPU_LVL(d_cursor)
-            NDGPU_LVL(h_ops) NDGPU_LVL(h_outs) NDGPU_LVL(up) NDGPU_LVL(down)
+#define NDGPU_LVL(T, x, place, level) \
+    if (BufLevel::level == BufLevel::levelled) lvl(S.x, BufPlace::place == BufPlace::device);
+            NDGPU_BUFFERS(NDGPU_LVL)
 #undef NDGPU_LVL
         } catch (const DeviceOom &) {
         }
@@ -766,6 +791,94 @@ static bool tb_assign(AlnTask *tasks, size_t a, size_t b, uint64_t *ck_slots, ui
     return true;
 }
 
+// ---- the align phase: what run_chunk, run_lq and run_main do alike between "my tasks are built" and "the AlnOut records are here" ----
+// The fields of a task that follow from its lengths (q_len and t_len are set): the reference's limits, the register path's rows, its
+// region of the ops buffer -- and the counter of operand bases.  q_off / t_off and pool_bases differ by caller and stay there.
+static void task_limits(AlnTask &t, int hq, uint64_t &ops_words, RuntimeStats &stats) {
+    int md, bd;
+    limits_for(t.q_len + t.t_len, hq, &md, &bd);
+    t.max_d = md;
+    t.band = bd;
+    t.row_words = kFastRowWords;
+    t.ops_off = ops_words;
+    t.ops_cap = (uint32_t)(t.q_len + t.t_len);
+    ops_words += (uint64_t)(t.ops_cap + 15) / 16 + 1;
+    stats.seq_bases += (uint64_t)t.q_len + (uint64_t)t.t_len;
+}
+// device bytes a task adds to its launch: its trace rows and its share of the traceback in segments.  The one rule chunks are cut by.
+static inline uint64_t task_trace_bytes(int max_d) { return (uint64_t)max_d * (kFastRowWords * 8) + tb_bytes(max_d); }
+
+// Cuts tasks [0, nt) into launches bounded by the trace budget (a task on its own always fits), gives every task its trace rows and its
+// checkpoint / walker slots within its launch, and reserves d_trace and the traceback's four buffers for the largest launch.
+std::vector<AlignChunk> DeviceAligner::State::plan_chunks(AlnTask *t, size_t nt) {
+    std::vector<AlignChunk> chunks;
+    uint64_t max_tw = 0, max_ck = 0, max_sg = 0;
+    for (size_t a = 0; a < nt;) {
+        uint64_t tw = 0, bytes = 0;
+        size_t b = a;
+        for (; b < nt; b++) {
+            const uint64_t need = task_trace_bytes(t[b].max_d);
+            if (b > a && bytes + need > trace_budget_bytes) break;
+            t[b].trace_off = tw;
+            tw += (uint64_t)t[b].max_d * kFastRowWords;
+            bytes += need;
+        }
+        uint64_t ck = 0, sg = 0;
+        const bool seg = tb_assign(t, a, b, &ck, &sg);
+        max_tw = std::max(max_tw, tw);
+        max_ck = std::max(max_ck, ck);
+        max_sg = std::max(max_sg, sg);
+        chunks.push_back(AlignChunk{a, b, seg, sg});
+        a = b;
+    }
+    d_trace.reserve(max_tw + kTracePadWords);
+    if (max_sg) {
+        d_ck_cells.reserve(max_ck * kCkptCells + 1);
+        d_ck_hdr.reserve(max_ck + 1);
+        d_tbseg.reserve(max_sg);
+        d_tbout.reserve(max_sg);
+    }
+    return chunks;
+}
+
+// K7 + K8a of one chunk on the context's stream.  order / tb_order: device lists of the chunk's task ids (nullptr: table order).
+// ev_mid is recorded between the two kernels, ev_end (if given) behind the traceback; who names the caller in the debug lines.
+void DeviceAligner::State::launch_chunk(const AlignChunk &c, const int32_t *order, const int32_t *tb_order, hipEvent_t ev_mid,
+                                        hipEvent_t ev_end, const char *who) {
+    const AlnTask *tk = d_tasks.p + c.begin;
+    AlnOut *out = d_outs.p + c.begin;
+    const int n = (int)(c.end - c.begin);
+    const TbArgs tb{d_ck_cells.p, d_ck_hdr.p, d_tbseg.p, d_tbout.p, (int)c.slots, tb_config().cshift, tb_config().warm};
+    if (c.seg) launch_ond_forward_ckpt(tk, out, d_pool.p, db_pool, d_trace.p, d_ops.p, tb, n, stream, order);
+    else launch_ond_forward(tk, out, d_pool.p, db_pool, d_trace.p, n, stream, order);
+    HIP_CHECK(hipEventRecord(ev_mid, stream));
+    if (who) NDGPU_DBG(stream, "%s: traceback", who);
+    if (c.seg) launch_ond_traceback_seg(tk, out, d_pool.p, db_pool, d_trace.p, d_ops.p, tb, n, stream);
+    else launch_ond_traceback(tk, out, d_pool.p, db_pool, d_trace.p, nullptr, d_ops.p, nullptr, n, stream, tb_order);
+    if (ev_end) HIP_CHECK(hipEventRecord(ev_end, stream));
+}
+
+// The counters the AlnOut records h_outs[0, nt) feed; wide (if given) collects the tasks whose live band left the register path.
+void DeviceAligner::State::tally_outs(size_t nt, std::vector<int32_t> *wide) {
+    for (size_t i = 0; i < nt; i++) {
+        const AlnOut &o = h_outs.p[i];
+        stats.cells += (uint64_t)o.cells;
+        stats.d_steps += (uint64_t)o.d_steps;
+        stats.trace_words += (uint64_t)o.trace_end;
+        if (o.fin_idx & kTbSeen) {
+            stats.tb_tasks++;
+            stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> tb_config().cshift : 0) + 1;
+            if (o.fin_idx & kTbRefused) stats.tb_fallbacks++;
+        }
+        if ((uint32_t)o.max_band > stats.max_band) stats.max_band = (uint32_t)o.max_band;
+        if (wide && o.status == ST_NEED_WIDE) wide->push_back((int32_t)i);
+        if (o.status == ST_ALIGNED) {  // (K8a's output: 2-bit column kinds -- the term bench.py's roofline prices it with)
+            stats.trace_bits += (uint64_t)o.cells;
+            stats.columns += (uint64_t)o.n_cols;
+        }
+    }
+}
+
 void DeviceAligner::align_batch(AlnJob **jobs, size_t n) {
     if (n == 0) return;
     std::unique_lock<std::mutex> dbg_lock;
@@ -774,13 +887,14 @@ void DeviceAligner::align_batch(AlnJob **jobs, size_t n) {
     HIP_CHECK(hipSetDevice(s_->device));
     size_t done = 0;
     while (done < n) {
-        // take as many jobs as fit the trace budget
-        size_t take = 0, bytes = 0;
+        // take as many jobs as fit the trace budget: one chunk of plan_chunks, which run_chunk relies on
+        size_t take = 0;
+        uint64_t bytes = 0;
         while (done + take < n) {
             const AlnJob &j = *jobs[done + take];
             int md, bd;
             limits_for(j.q_len + j.t_len, j.hq, &md, &bd);
-            const size_t b = (size_t)md * (kFastRowWords * 8) + (size_t)tb_bytes(md);
+            const uint64_t b = task_trace_bytes(md);
             if (take && bytes + b > s_->trace_budget_bytes) break;
             bytes += b;
             take++;
@@ -845,7 +959,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     std::vector<uint8_t> bad(n, 0);
     // pass 1 (serial, O(1) per job): offsets of every per-task region
     std::vector<uint64_t> qw(n + 1), tw(n + 1);
-    uint64_t trace_words = 0, ops_words = 0, pool_words = 0;
+    uint64_t ops_words = 0, pool_words = 0;
     for (size_t i = 0; i < n; i++) {
         const AlnJob &j = *jobs[i];
         AlnTask &t = tasks[i];
@@ -855,17 +969,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
         if (j.q_dev < 0) pool_words += ((uint64_t)j.q_len + 15) / 16;
         tw[i] = pool_words;
         if (j.t_dev < 0) pool_words += ((uint64_t)j.t_len + 15) / 16;
-        int md, bd;
-        limits_for(j.q_len + j.t_len, j.hq, &md, &bd);
-        t.max_d = md;
-        t.band = bd;
-        t.row_words = kFastRowWords;
-        t.trace_off = trace_words;
-        t.ops_off = ops_words;
-        t.ops_cap = (uint32_t)(j.q_len + j.t_len);
-        trace_words += (uint64_t)md * kFastRowWords;
-        ops_words += (uint64_t)(t.ops_cap + 15) / 16 + 1;
-        S.stats.seq_bases += (uint64_t)j.q_len + (uint64_t)j.t_len;
+        task_limits(t, j.hq, ops_words, S.stats);
         S.stats.pool_bases += (j.q_dev < 0 ? (uint64_t)j.q_len : 0) + (j.t_dev < 0 ? (uint64_t)j.t_len : 0);
     }
     pool.assign(pool_words, 0);
@@ -895,20 +999,11 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     S.d_pool.reserve(pool.size());
     S.d_tasks.reserve(n);
     S.d_outs.reserve(n);
-    S.d_trace.reserve(trace_words + kTracePadWords);
+    const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), n);
+    assert(chunks.size() == 1);  // align_batch cut the jobs by the same rule (a task marked bad only shrinks the chunk)
     S.d_ops.reserve(ops_words + 2);
     S.h_ops.reserve(ops_words + 2);
     S.h_outs.reserve(n);
-    uint64_t ck_slots = 0, seg_slots = 0;
-    const bool seg = tb_assign(tasks.data(), 0, n, &ck_slots, &seg_slots);
-    TbArgs tb{};
-    if (seg) {
-        S.d_ck_cells.reserve(ck_slots * kCkptCells + 1);
-        S.d_ck_hdr.reserve(ck_slots + 1);
-        S.d_tbseg.reserve(seg_slots);
-        S.d_tbout.reserve(seg_slots);
-        tb = TbArgs{S.d_ck_cells.p, S.d_ck_hdr.p, S.d_tbseg.p, S.d_tbout.p, (int)seg_slots, tb_config().cshift, tb_config().warm};
-    }
 
     hipStream_t st = S.stream;
     const uint64_t tc1 = wall_ns();
@@ -916,12 +1011,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     S.h2d(S.d_tasks.p, tasks.data(), n * sizeof(AlnTask), st);
     HIP_CHECK(hipEventRecord(S.ev0, st));
     NDGPU_DBG(st, "chunk: forward %zu tasks", n);
-    if (seg) launch_ond_forward_ckpt(S.d_tasks.p, S.d_outs.p, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)n, st, nullptr);
-    else launch_ond_forward(S.d_tasks.p, S.d_outs.p, S.d_pool.p, S.db_pool, S.d_trace.p, (int)n, st);
-    HIP_CHECK(hipEventRecord(S.ev1, st));
-    NDGPU_DBG(st, "chunk: traceback");
-    if (seg) launch_ond_traceback_seg(S.d_tasks.p, S.d_outs.p, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)n, st);
-    else launch_ond_traceback(S.d_tasks.p, S.d_outs.p, S.d_pool.p, S.db_pool, S.d_trace.p, nullptr, S.d_ops.p, nullptr, (int)n, st);
+    S.launch_chunk(chunks[0], nullptr, nullptr, S.ev1, nullptr, "chunk");
     NDGPU_DBG(st, "chunk: done");
     HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, n * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(S.h_ops.p, S.d_ops.p, ops_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -929,7 +1019,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     HIP_CHECK(hipGetLastError());
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, S.ev0, S.ev1));
-    S.stats.forward_ms += ms;
+    S.stats.forward_ms += ms;  // (this path brackets K7 alone: its K8a is in neither traceback_ms nor traceback_launches)
     S.stats.forward_launches++;
     S.stats.tasks += n;
 
@@ -937,30 +1027,15 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     std::vector<int32_t> wide;
     for (size_t i = 0; i < n; i++)
         if (S.h_outs.p[i].status == ST_NEED_WIDE) wide.push_back((int32_t)i);
-    if (!wide.empty()) run_wide(jobs, n, wide);
+    if (!wide.empty()) run_wide(jobs, wide);
     const uint64_t tc2 = wall_ns();
 
-    for (size_t i = 0; i < n; i++) {
-        const AlnOut &o = S.h_outs.p[i];
-        S.stats.cells += (uint64_t)o.cells;
-        S.stats.d_steps += (uint64_t)o.d_steps;
-        S.stats.trace_words += (uint64_t)o.trace_end;
-        if (o.fin_idx & kTbSeen) {
-            S.stats.tb_tasks++;
-            S.stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> tb_config().cshift : 0) + 1;
-            if (o.fin_idx & kTbRefused) S.stats.tb_fallbacks++;
-        }
-        if ((uint32_t)o.max_band > S.stats.max_band) S.stats.max_band = (uint32_t)o.max_band;
-        if (o.status == ST_ALIGNED) {
-            S.stats.trace_bits += (uint64_t)o.cells;
-            S.stats.columns += (uint64_t)o.n_cols;
-        }
-        if (bad[i]) {
-            static bool warned = false;
-            if (!warned) {
-                fprintf(stderr, "[ndgpu] sequence with bytes outside [ACGT]: alignment skipped\n");
-                warned = true;
-            }
+    S.tally_outs(n, nullptr);  // (after run_wide: the wide tasks count with what the wide kernels reported)
+    if (std::find(bad.begin(), bad.end(), 1) != bad.end()) {
+        static bool warned = false;
+        if (!warned) {
+            fprintf(stderr, "[ndgpu] sequence with bytes outside [ACGT]: alignment skipped\n");
+            warned = true;
         }
     }
     par_ranges(n, S.host_threads, [&](size_t a, size_t b) {
@@ -999,7 +1074,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     g_prof.c_pack += tc1 - tc0, g_prof.c_dev += tc2 - tc1, g_prof.c_decode += wall_ns() - tc2, g_prof.c_jobs += n;
 }
 
-void DeviceAligner::run_wide(AlnJob **jobs, size_t n, const std::vector<int32_t> &ids) {
+void DeviceAligner::run_wide(AlnJob **jobs, const std::vector<int32_t> &ids) {
     State &S = *s_;
     const bool ops_to_host = jobs != nullptr;  // the device main phase keeps ops in HBM
     // process in groups bounded by the trace budget; wide rows are band-cap sized
@@ -1062,7 +1137,6 @@ void DeviceAligner::run_wide(AlnJob **jobs, size_t n, const std::vector<int32_t>
         S.stats.wide_tasks += take;
         at += take;
     }
-    (void)n;
 }
 
 // Low-quality-region rounds of a batch of piles on the device: K7 / K8a over every (row, region) alignment, then K12 (lq_links + lq_score:
@@ -1149,18 +1223,10 @@ void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
                     pool_words += ((uint64_t)j.t_len + 15) / 16;
                 }
                 t.t_off = t_off[g] * 16;
-                int md, bd;
-                limits_for(j.q_len + j.t_len, j.hq, &md, &bd);
-                t.max_d = md;
-                t.band = bd;
-                t.row_words = kFastRowWords;
-                t.ops_off = ops_words;
-                t.ops_cap = (uint32_t)(j.q_len + j.t_len);
-                ops_words += (uint64_t)(t.ops_cap + 15) / 16 + 1;
+                task_limits(t, j.hq, ops_words, S.stats);
                 ins_cap += (uint64_t)j.q_len;
                 d.task = (int32_t)tasks.size();
                 tasks.push_back(t);
-                S.stats.seq_bases += (uint64_t)j.q_len + (uint64_t)j.t_len;
                 S.stats.pool_bases += (uint64_t)j.q_len;
             }
             pieces.push_back(d);
@@ -1252,47 +1318,9 @@ void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     S.d_lq_tmp.reserve(cell_rows + 1);
     S.d_lq_bnd.reserve((jobs.size() + 1) * 4 * (size_t)kLqLinkCap);
 
-    // forward / traceback chunks bounded by the trace budget (the column streams of every chunk stay resident)
-    std::vector<size_t> chunk_end;
-    uint64_t max_tw = 0;
-    {
-        uint64_t tw = 0, extra = 0;
-        for (size_t i = 0; i < nt; i++) {
-            const uint64_t need = (uint64_t)tasks[i].max_d * kFastRowWords, tbb = tb_bytes(tasks[i].max_d);
-            if (i && (tw + need) * 8 + extra + tbb > S.trace_budget_bytes) {
-                chunk_end.push_back(i);
-                max_tw = std::max(max_tw, tw);
-                tw = extra = 0;
-            }
-            tasks[i].trace_off = tw;
-            tw += need;
-            extra += tbb;
-        }
-        chunk_end.push_back(nt);
-        max_tw = std::max(max_tw, tw);
-    }
-    S.d_trace.reserve(max_tw + kTracePadWords);
-    // the traceback in segments where a launch holds long pairs (regions of several kb): slots per launch
-    struct ChunkTb { bool seg; uint64_t slots; };
-    std::vector<ChunkTb> chunk_tb;
-    {
-        uint64_t max_ck = 0, max_sg = 0;
-        size_t a = 0;
-        for (size_t b : chunk_end) {
-            uint64_t ck = 0, sg = 0;
-            const bool seg = b > a && tb_assign(tasks.data(), a, b, &ck, &sg);
-            max_ck = std::max(max_ck, ck);
-            max_sg = std::max(max_sg, sg);
-            chunk_tb.push_back(ChunkTb{seg, sg});
-            a = b;
-        }
-        if (max_sg) {
-            S.d_ck_cells.reserve(max_ck * kCkptCells + 1);
-            S.d_ck_hdr.reserve(max_ck + 1);
-            S.d_tbseg.reserve(max_sg);
-            S.d_tbout.reserve(max_sg);
-        }
-    }
+    // forward / traceback chunks bounded by the trace budget (the column streams of every chunk stay resident); the traceback runs in
+    // segments where a launch holds long pairs (regions of several kb)
+    const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), nt);
 
     const uint64_t tc1 = wall_ns();
     S.h2d(S.d_pool.p, pool.data(), pool.size() * sizeof(uint32_t), st);
@@ -1301,31 +1329,15 @@ void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     S.h2d(S.d_lq_pieces.p, pieces.data(), pieces.size() * sizeof(LqPieceDev), st);
     if (!jobs.empty()) S.h2d(S.d_lq_jobs.p, jobs.data(), jobs.size() * sizeof(LqJobDev), st);
     // (HIP-event brackets per kernel: K7, K8a per chunk -- read after the round's one synchronisation)
-    while (S.lq_evs.size() < 2 * chunk_end.size() + 1) {
+    while (S.lq_evs.size() < 2 * chunks.size() + 1) {
         hipEvent_t e;
         HIP_CHECK(hipEventCreate(&e));
         S.lq_evs.push_back(e);
     }
     HIP_CHECK(hipEventRecord(S.lq_evs[0], st));
-    {
-        size_t a = 0, c = 0;
-        for (size_t b : chunk_end) {
-            NDGPU_DBG(st, "lq: forward / traceback %zu..%zu of %zu tasks", a, b, nt);
-            const ChunkTb ctb = chunk_tb[c];
-            const TbArgs tb{S.d_ck_cells.p, S.d_ck_hdr.p, S.d_tbseg.p, S.d_tbout.p, (int)ctb.slots, tb_config().cshift, tb_config().warm};
-            if (ctb.seg)
-                launch_ond_forward_ckpt(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)(b - a), st, nullptr);
-            else launch_ond_forward(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, (int)(b - a), st);
-            HIP_CHECK(hipEventRecord(S.lq_evs[2 * c + 1], st));
-            if (ctb.seg)
-                launch_ond_traceback_seg(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)(b - a), st);
-            else
-                launch_ond_traceback(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, nullptr, S.d_ops.p, nullptr,
-                                     (int)(b - a), st);
-            HIP_CHECK(hipEventRecord(S.lq_evs[2 * c + 2], st));
-            a = b;
-            c++;
-        }
+    for (size_t c = 0; c < chunks.size(); c++) {
+        NDGPU_DBG(st, "lq: forward / traceback %zu..%zu of %zu tasks", chunks[c].begin, chunks[c].end, nt);
+        S.launch_chunk(chunks[c], nullptr, nullptr, S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2], nullptr);
     }
     HIP_CHECK(hipEventRecord(S.evs[1], st));
     NDGPU_DBG(st, "lq: msa of %zu piles", n);
@@ -1344,36 +1356,21 @@ void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     S.sync_drain(st);
     HIP_CHECK(hipGetLastError());
     float ms = 0;
-    for (size_t c = 0; c < chunk_end.size(); c++) {
+    for (size_t c = 0; c < chunks.size(); c++) {
         HIP_CHECK(hipEventElapsedTime(&ms, S.lq_evs[2 * c], S.lq_evs[2 * c + 1]));
         S.stats.forward_ms += ms;
         HIP_CHECK(hipEventElapsedTime(&ms, S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2]));
         S.stats.traceback_ms += ms;
     }
-    S.stats.forward_launches += chunk_end.size();
-    S.stats.traceback_launches += chunk_end.size();
+    S.stats.forward_launches += chunks.size();
+    S.stats.traceback_launches += chunks.size();
     HIP_CHECK(hipEventElapsedTime(&ms, S.evs[1], S.evs[2]));
     S.stats.lq_ms += ms;
     S.stats.lq_launches++;
     S.stats.tasks += nt;
     const uint64_t tc2 = wall_ns();
 
-    for (size_t i = 0; i < nt; i++) {
-        const AlnOut &o = S.h_outs.p[i];
-        S.stats.cells += (uint64_t)o.cells;
-        S.stats.d_steps += (uint64_t)o.d_steps;
-        S.stats.trace_words += (uint64_t)o.trace_end;
-        if (o.fin_idx & kTbSeen) {
-            S.stats.tb_tasks++;
-            S.stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> tb_config().cshift : 0) + 1;
-            if (o.fin_idx & kTbRefused) S.stats.tb_fallbacks++;
-        }
-        if ((uint32_t)o.max_band > S.stats.max_band) S.stats.max_band = (uint32_t)o.max_band;
-        if (o.status == ST_ALIGNED) {
-            S.stats.trace_bits += (uint64_t)o.cells;
-            S.stats.columns += (uint64_t)o.n_cols;
-        }
-    }
+    S.tally_outs(nt, nullptr);  // (ST_NEED_WIDE is looked for piece by piece below)
     for (size_t r = 0; r < n; r++) {
         LqRound &R = *rounds[r];
         S.stats.lq_rounds++;
@@ -1483,15 +1480,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
                     S.stats.pool_bases += M.seq_len[i];
                 }
                 t.t_off = P.seed_off + M.aln_start[i];
-                int md, bd;
-                limits_for(t.q_len + t.t_len, M.hq, &md, &bd);
-                t.max_d = md;
-                t.band = bd;
-                t.row_words = kFastRowWords;
-                t.ops_off = ops_words;
-                t.ops_cap = (uint32_t)(t.q_len + t.t_len);
-                ops_words += (uint64_t)(t.ops_cap + 15) / 16 + 1;
-                S.stats.seq_bases += (uint64_t)t.q_len + (uint64_t)t.t_len;
+                task_limits(t, M.hq, ops_words, S.stats);
                 R.task = (int32_t)tasks.size();
                 tasks.push_back(t);
                 tag_cap = t.ops_cap;
@@ -1514,54 +1503,12 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     const size_t nt = tasks.size(), nr = reads.size();
 
     // forward/traceback chunks bounded by the trace budget
-    std::vector<size_t> chunk_end;
-    {
-        uint64_t tw = 0, extra = 0;
-        for (size_t i = 0; i < nt; i++) {
-            const uint64_t need = (uint64_t)tasks[i].max_d * (kFastRowWords * 8), tbb = tb_bytes(tasks[i].max_d);
-            if (i && (tw * 8 + extra + need + tbb) > S.trace_budget_bytes) {
-                chunk_end.push_back(i);
-                tw = extra = 0;
-            }
-            tasks[i].trace_off = tw;
-            tw += (uint64_t)tasks[i].max_d * kFastRowWords;
-            extra += tbb;
-        }
-        chunk_end.push_back(nt);
-    }
-    uint64_t max_tw = 0;
-    // the traceback in segments: checkpoint and walker slots per launch
-    struct ChunkTb { bool seg; uint64_t slots; };
-    std::vector<ChunkTb> chunk_tb;
-    uint64_t max_ck = 0, max_sg = 0;
-    {
-        size_t a = 0;
-        for (size_t b : chunk_end) {
-            uint64_t ck = 0, sg = 0;
-            bool seg = false;
-            if (b > a) {
-                const AlnTask &l = tasks[b - 1];
-                max_tw = std::max<uint64_t>(max_tw, l.trace_off + (uint64_t)l.max_d * kFastRowWords);
-                seg = tb_assign(tasks.data(), a, b, &ck, &sg);
-                max_ck = std::max(max_ck, ck);
-                max_sg = std::max(max_sg, sg);
-            }
-            chunk_tb.push_back(ChunkTb{seg, sg});
-            a = b;
-        }
-    }
-    if (max_sg) {
-        S.d_ck_cells.reserve(max_ck * kCkptCells + 1);
-        S.d_ck_hdr.reserve(max_ck + 1);
-        S.d_tbseg.reserve(max_sg);
-        S.d_tbout.reserve(max_sg);
-    }
+    const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), nt);
 
     S.d_pool.reserve(pool.size());
     S.d_tasks.reserve(nt + 1);
     S.d_outs.reserve(nt + 1);
     S.h_outs.reserve(nt + 1);
-    S.d_trace.reserve(max_tw + kTracePadWords);
     S.d_ops.reserve(ops_words + 2);
     S.d_reads.reserve(nr);
     S.d_piles.reserve(np);
@@ -1585,85 +1532,51 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     HIP_CHECK(hipMemsetAsync(d_cov, 0, 3 * (col_slots + 1) * sizeof(uint32_t), st));  // (one fill for the three)
     HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, 4 * sizeof(uint32_t), st));
 
-    {
-        size_t a = 0, ci = 0;
-        for (size_t b : chunk_end) {
-            const ChunkTb ctb = chunk_tb[ci++];
-            if (b > a) {
-                NDGPU_DBG(st, "main: forward %zu..%zu of %zu tasks, %zu piles", a, b, nt, np);
-                const int32_t *order = nullptr;
-                static const bool lpt = !getenv("NDGPU_K7_NO_ORDER");
-                if (lpt && b - a > 64) {
-                    // longest alignments first (their chains bound the launch): a counting sort over 64-base length classes
-                    // -- a sub-batch holds up to a million tasks and this runs on the context's critical path
-                    std::vector<int32_t> &ord = S.order;
-                    std::vector<uint32_t> &cls = S.order_cls;
-                    const size_t m = b - a;
-                    ord.resize(m);
-                    cls.assign(kLenClasses + 1, 0);
-                    auto cls_of = [&](size_t i) {
-                        const uint32_t c = ((uint32_t)tasks[a + i].q_len + (uint32_t)tasks[a + i].t_len) >> 6;
-                        return (kLenClasses - 1) - std::min<uint32_t>(c, kLenClasses - 1);  // class 0 = the longest
-                    };
-                    for (size_t i = 0; i < m; i++) cls[cls_of(i) + 1]++;
-                    for (uint32_t c = 0; c < kLenClasses; c++) cls[c + 1] += cls[c];
-                    for (size_t i = 0; i < m; i++) ord[cls[cls_of(i)]++] = (int32_t)i;
-                    S.d_ids.reserve(m);
-                    S.h2d(S.d_ids.p, ord.data(), m * sizeof(int32_t), st);
-                    order = S.d_ids.p;
-                }
-                const TbArgs tb{S.d_ck_cells.p, S.d_ck_hdr.p, S.d_tbseg.p, S.d_tbout.p, (int)ctb.slots, tb_config().cshift, tb_config().warm};
-                HIP_CHECK(hipEventRecord(S.evs[0], st));
-                if (ctb.seg)
-                    launch_ond_forward_ckpt(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)(b - a), st, order);
-                else launch_ond_forward(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, (int)(b - a), st, order);
-                HIP_CHECK(hipEventRecord(S.evs[1], st));
-                NDGPU_DBG(st, "main: traceback");
-                // (K8a stays in table order: measured in round 5, the 64 walks of a wavefront ordered longest first like K7's --
-                // equal lengths, long walks first -- cost 605 ms of traceback per step against 496: the lanes of a wavefront in pile
-                // order walk neighbouring windows of one seed and share its cache lines; NDGPU_K8_ORDER=1 switches the order on)
-                static const bool k8_order = getenv("NDGPU_K8_ORDER") != nullptr;
-                if (ctb.seg)
-                    launch_ond_traceback_seg(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, S.d_ops.p, tb, (int)(b - a), st);
-                else
-                    launch_ond_traceback(S.d_tasks.p + a, S.d_outs.p + a, S.d_pool.p, S.db_pool, S.d_trace.p, nullptr,
-                                         S.d_ops.p, nullptr, (int)(b - a), st, k8_order ? order : nullptr);
-                NDGPU_DBG(st, "main: traceback done");
-                HIP_CHECK(hipEventRecord(S.evs[2], st));
-                HIP_CHECK(hipEventSynchronize(S.evs[2]));
-                float ms = 0;
-                HIP_CHECK(hipEventElapsedTime(&ms, S.evs[0], S.evs[1]));
-                S.stats.forward_ms += ms;
-                S.stats.forward_launches++;
-                HIP_CHECK(hipEventElapsedTime(&ms, S.evs[1], S.evs[2]));
-                S.stats.traceback_ms += ms;
-                S.stats.traceback_launches++;
-            }
-            a = b;
+    for (const AlignChunk &ch : chunks) {
+        const size_t a = ch.begin, m = ch.end - ch.begin;
+        NDGPU_DBG(st, "main: forward %zu..%zu of %zu tasks, %zu piles", a, ch.end, nt, np);
+        const int32_t *order = nullptr;
+        static const bool lpt = !getenv("NDGPU_K7_NO_ORDER");
+        if (lpt && m > 64) {
+            // longest alignments first (their chains bound the launch): a counting sort over 64-base length classes
+            // -- a sub-batch holds up to a million tasks and this runs on the context's critical path
+            std::vector<int32_t> &ord = S.order;
+            std::vector<uint32_t> &cls = S.order_cls;
+            ord.resize(m);
+            cls.assign(kLenClasses + 1, 0);
+            auto cls_of = [&](size_t i) {
+                const uint32_t c = ((uint32_t)tasks[a + i].q_len + (uint32_t)tasks[a + i].t_len) >> 6;
+                return (kLenClasses - 1) - std::min<uint32_t>(c, kLenClasses - 1);  // class 0 = the longest
+            };
+            for (size_t i = 0; i < m; i++) cls[cls_of(i) + 1]++;
+            for (uint32_t c = 0; c < kLenClasses; c++) cls[c + 1] += cls[c];
+            for (size_t i = 0; i < m; i++) ord[cls[cls_of(i)]++] = (int32_t)i;
+            S.d_ids.reserve(m);
+            S.h2d(S.d_ids.p, ord.data(), m * sizeof(int32_t), st);
+            order = S.d_ids.p;
         }
+        // (K8a stays in table order: measured in round 5, the 64 walks of a wavefront ordered longest first like K7's --
+        // equal lengths, long walks first -- cost 605 ms of traceback per step against 496: the lanes of a wavefront in pile
+        // order walk neighbouring windows of one seed and share its cache lines; NDGPU_K8_ORDER=1 switches the order on)
+        static const bool k8_order = getenv("NDGPU_K8_ORDER") != nullptr;
+        HIP_CHECK(hipEventRecord(S.evs[0], st));
+        S.launch_chunk(ch, order, k8_order ? order : nullptr, S.evs[1], S.evs[2], "main");
+        NDGPU_DBG(st, "main: traceback done");
+        HIP_CHECK(hipEventSynchronize(S.evs[2]));  // (chunk by chunk: the next one records the same three events)
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[0], S.evs[1]));
+        S.stats.forward_ms += ms;
+        S.stats.forward_launches++;
+        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[1], S.evs[2]));
+        S.stats.traceback_ms += ms;
+        S.stats.traceback_launches++;
     }
     if (nt) {
         HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, nt * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
         S.sync_drain(st);
         std::vector<int32_t> wide;
-        for (size_t i = 0; i < nt; i++) {
-            const AlnOut &o = S.h_outs.p[i];
-            S.stats.cells += (uint64_t)o.cells;
-            S.stats.d_steps += (uint64_t)o.d_steps;
-            S.stats.trace_words += (uint64_t)o.trace_end;
-        if (o.fin_idx & kTbSeen) {
-            S.stats.tb_tasks++;
-            S.stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> tb_config().cshift : 0) + 1;
-            if (o.fin_idx & kTbRefused) S.stats.tb_fallbacks++;
-        }
-            if ((uint32_t)o.max_band > S.stats.max_band) S.stats.max_band = (uint32_t)o.max_band;
-            if (o.status == ST_NEED_WIDE) wide.push_back((int32_t)i);
-            if (o.status == ST_ALIGNED) {   // (K8a's output: 2-bit column kinds -- the term bench.py's roofline prices it with)
-                S.stats.trace_bits += (uint64_t)o.cells;
-                S.stats.columns += (uint64_t)o.n_cols;
-            }
-        }
-        if (!wide.empty()) run_wide(nullptr, nt, wide);
+        S.tally_outs(nt, &wide);  // (before run_wide: a wide task counts with what the register path reported)
+        if (!wide.empty()) run_wide(nullptr, wide);
         S.stats.tasks += nt;
     }
 

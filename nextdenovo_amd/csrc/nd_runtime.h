@@ -117,7 +117,7 @@ class DeviceAligner {
     DeviceAligner();
     ~DeviceAligner();
     void run_chunk(AlnJob **jobs, size_t n);
-    void run_wide(AlnJob **jobs, size_t n, const std::vector<int32_t> &ids);
+    void run_wide(AlnJob **jobs, const std::vector<int32_t> &ids);
     struct State;
     State *s_;
 };
