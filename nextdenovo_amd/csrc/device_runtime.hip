@@ -1519,7 +1519,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     S.d_cov.reserve(3 * (col_slots + 1));  // per column: coverage, insertion count, longest insertion -- three arrays in one block
     S.d_cellbase.reserve(col_slots + 1);
     S.d_entbase.reserve(col_slots + 1);
-    S.d_err.reserve(4);
+    S.d_err.reserve(kErrWords);
 
     uint64_t tp1 = wall_ns();
     g_prof.m_prep += tp1 - tp0;
@@ -1530,7 +1530,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     S.h2d(S.d_read_pile.p, read_pile.data(), nr * sizeof(uint32_t), st);
     uint32_t *const d_cov = S.d_cov.p, *const d_inscnt = d_cov + (col_slots + 1), *const d_insmax = d_inscnt + (col_slots + 1);
     HIP_CHECK(hipMemsetAsync(d_cov, 0, 3 * (col_slots + 1) * sizeof(uint32_t), st));  // (one fill for the three)
-    HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, 4 * sizeof(uint32_t), st));
+    HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, kErrWords * sizeof(uint32_t), st));
 
     for (const AlignChunk &ch : chunks) {
         const size_t a = ch.begin, m = ch.end - ch.begin;
@@ -1676,7 +1676,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     S.h2d(S.d_items.p + items_small.size() + items_large.size(), items_slow.data(), items_slow.size() * sizeof(SegItem), st);
     const PathItem *hpath = nullptr;  // view into the download arena
     std::vector<PileDev> piles_out(np);
-    uint32_t herr[4] = {0, 0, 0, 0};
+    uint32_t herr[kErrWords] = {};
     // attempt 0 counts links with the small LDS lists; a cell with more distinct links than they hold raises err[0] and the
     // sub-batch is counted and scored again with the full capacity (everything the kernels write is rewritten), and if that
     // overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap)
@@ -1691,7 +1691,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     for (int attempt = S.k9_full_capacity ? 1 : 0, first = 1; attempt < 3; attempt++, first = 0) {
         S.reserve_down(np * sizeof(PileDev) + paths * sizeof(PathItem) + 1024, st);
         S.h2d(S.d_piles.p, piles.data(), np * sizeof(PileDev), st);
-        if (!first) HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, 4 * sizeof(uint32_t), st));
+        if (!first) HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, kErrWords * sizeof(uint32_t), st));
         HIP_CHECK(hipEventRecord(S.evs[2], st));
         NDGPU_DBG(st, "main: count_links %zu blocks, cells %llu ents %llu segs %u", blocks.size(), (unsigned long long)cells,
                   (unsigned long long)ents, n_segs);
@@ -1752,6 +1752,9 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
             HIP_CHECK(hipGetLastError());
             memcpy(piles_out.data(), v_piles, np * sizeof(PileDev));
         }
+        if (attempt < 2 && getenv("NDGPU_TRACE"))
+            fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", herr[1], herr[3], herr[2],
+                    herr[4] ? ~herr[4] : 0u);
         static const bool force_retry = getenv("NDGPU_K9_FORCE_RETRY") != nullptr;  // test hook: take the overflow path
         if (attempt == 0 ? !herr[0] && !force_retry : !herr[0]) break;
         if (attempt == 2) break;  // (cannot happen: the lists hold one entry per accepted read)

@@ -307,34 +307,112 @@ __global__ __launch_bounds__(64) void col_scan_kernel(PileDev *__restrict__ pile
 // ---- K9 --------------------------------------------------------------------------
 // CAP = links per cell the LDS lists hold.  The launch tries the small capacity first (4.6 KB of LDS per wavefront instead
 // of 13.8 KB: the kernel is latency-bound and lives on resident wavefronts); a cell that overflows raises err[0] and the
-// host repeats the sub-batch with kLinkCap.  Seven wavefronts per SIMD for the small capacity (72 VGPRs, 36 B of scratch per lane):
-// 148 -> 127 ms per config-2 step with the kernel alone on the device; at 6 (80 VGPRs) 133 ms, at 8 (64 VGPRs, 76 B of scratch) 134 ms.
-// Round 6: the second chunk of reads lost its register window (it was what spilled), and at EIGHT wavefronts per SIMD the kernel now takes
-// 63 registers with 12 bytes of scratch per lane and column: 124.2 (seven, no scratch) -> 118.8 ms.
+// host repeats the sub-batch with kLinkCap.
+//
+// A wavefront owns the 32 columns of one ColBlock.  A seed of tens of kilobases has far more accepted reads than 64, but the
+// overlap sort keeps the local depth near 40, so almost none of them reach a given block.  The block's prologue therefore goes
+// once over the pile's accepted reads (rank = chunk * 64 + lane) and keeps those that can put a tag into the block
+// (t_s < t_end && t_e >= col0); ballot and prefix popcount give every kept read a slot, in rank order.  If the kept reads
+// number <= `compact_max` (at most 64), lane s takes the read in slot s and the block runs the compact path: ONE chunk, every
+// read with its 32-byte register window, no loop over chunks.  Otherwise the block runs the deep path: the loop over all
+// ceil(n_acc / 64) chunks (the first with windows, the second one load per row, the others through the column index).
+//
+// Why the tables are the same whichever path a block takes:
+//   * the links of a cell are written in first-seen order by rank.  A read that is not kept has no tag in the block, so it is
+//     seen by no cell; the kept reads sit in one chunk in rank order, and a single chunk elects its leaders lowest lane first;
+//   * counts are sums over the reads that carry a link, and sums do not depend on which lane a read sits in.
+//
+// max_size, cell_base and ent_base of the block's 32 columns are loaded by lanes 0..31 in the prologue and read per column with
+// readlane (compact path); the deep path, which has no registers to spare, loads them per column.
+//
+// Lane 0 of every block counts into err[1..4]: blocks compact, blocks deep, largest cover among compact blocks, ~(smallest
+// cover among deep blocks) (zero: none).  NDGPU_TRACE prints them; nothing else reads them.
+//
+// Registers: eight wavefronts per SIMD for the small capacity (63 VGPRs).  The deep path carries two chunks' state and spills
+// 16 bytes per lane around a column (four scratch instructions, all inside its column loop); the compact column loop holds no
+// scratch access.  A deep path behind a call (noinline) was worse for everybody: its arguments arrive in vector registers, the
+// pile record goes through the stack, 284 bytes of scratch per lane.
 template <int CAP>
-__global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(const PileDev *__restrict__ piles,
-                                                          const ReadDev *__restrict__ reads,
-                                                          const uint32_t *__restrict__ acc_list,
-                                                          const ColBlock *__restrict__ blocks,
-                                                          const uint32_t *__restrict__ tags,
-                                                          const uint32_t *__restrict__ colidx,
-                                                          const uint32_t *__restrict__ max_size,
-                                                          const uint32_t *__restrict__ cell_base,
-                                                          const uint32_t *__restrict__ ent_base,
-                                                          uint32_t *__restrict__ cell_start,
-                                                          uint32_t *__restrict__ cell_len, uint32_t *__restrict__ ent_pp,
-                                                          uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt,
-                                                          uint32_t *__restrict__ err) {
-    __shared__ uint32_t l_pp[6][CAP], l_ppp[6][CAP], l_cnt[6][CAP];
-    const ColBlock B = blocks[blockIdx.x];
-    const PileDev P = piles[B.pile];
-    const int lane = (int)threadIdx.x;
-    const uint32_t *ms = max_size + P.col_off;
-    const uint32_t *cb = cell_base + P.col_off;
-    const uint32_t *eb = ent_base + P.col_off;
-    const uint32_t *acc = acc_list + P.acc_off;
-    const uint32_t t_end = B.col0 + kColBlock < P.seed_len ? B.col0 + kColBlock : P.seed_len;
+struct K9Lists {
+    uint32_t pp[6][CAP], ppp[6][CAP], cnt[6][CAP];
+};
 
+// The tags `cur` (valid where `has`) of one chunk of reads in cell row (t, d), with their two predecessors: into the lists of the six cells.
+template <int CAP>
+__device__ __forceinline__ void k9_collect(K9Lists<CAP> &L, uint32_t (&n_cell)[6], bool has, uint32_t cur, uint32_t pp, uint32_t ppp,
+                                           int lane, uint32_t *__restrict__ err) {
+    const uint32_t b = cur & 7u;
+#pragma unroll
+    for (uint32_t bb = 0; bb < 6; bb++) {
+        const bool mine = has && b == bb;
+        if (!__ballot(mine)) continue;
+        uint32_t n0 = n_cell[bb];
+        int found = -1;
+        if (mine) {
+            for (uint32_t j = 0; j < n0; j++)
+                if (L.pp[bb][j] == pp && L.ppp[bb][j] == ppp) {
+                    found = (int)j;
+                    break;
+                }
+            if (found >= 0) atomicAdd(&L.cnt[bb][found], 1u);
+        }
+        unsigned long long rem = __ballot(mine && found < 0);
+        while (rem) {
+            const int ld = __ffsll((long long)rem) - 1;  // earliest read that carries a new link
+            const uint32_t kp = (uint32_t)__shfl((int)pp, ld, 64);
+            const uint32_t kpp = (uint32_t)__shfl((int)ppp, ld, 64);
+            const bool in_rem = (rem >> lane) & 1ull;
+            const unsigned long long same = __ballot(in_rem && pp == kp && ppp == kpp);
+            if (lane == ld) {
+                if (n0 < (uint32_t)CAP) {
+                    L.pp[bb][n0] = pp;
+                    L.ppp[bb][n0] = ppp;
+                    L.cnt[bb][n0] = (uint32_t)__popcll(same);
+                } else {
+                    atomicExch(err, 1u);
+                }
+            }
+            n0 = n0 < (uint32_t)CAP ? n0 + 1 : n0;
+            rem &= ~same;
+        }
+        n_cell[bb] = n0;
+        __builtin_amdgcn_wave_barrier();  // one wavefront: LDS operations complete in program order
+    }
+}
+
+// The six cells of (t, d) to the tables, links contiguous per cell in first-seen order.  `cell0`: the row's first cell, `e`: the
+// next free link slot of the column (both absolute; cell_start holds it counted from the pile's first slot, `ent_off`).
+template <int CAP>
+__device__ __forceinline__ void k9_flush(const K9Lists<CAP> &L, const uint32_t (&n_cell)[6], uint64_t cell0, uint64_t &e, uint64_t ent_off,
+                                         int lane, uint32_t *__restrict__ cell_start, uint32_t *__restrict__ cell_len,
+                                         uint32_t *__restrict__ ent_pp, uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt) {
+#pragma unroll
+    for (uint32_t bb = 0; bb < 6; bb++) {
+        const uint32_t n = n_cell[bb];
+        if (lane == 0) {
+            cell_start[cell0 + bb] = (uint32_t)(e - ent_off);
+            cell_len[cell0 + bb] = n;
+        }
+        for (uint32_t j = (uint32_t)lane; j < n; j += 64) {
+            ent_pp[e + j] = L.pp[bb][j];
+            ent_ppp[e + j] = L.ppp[bb][j];
+            ent_cnt[e + j] = L.cnt[bb][j];
+        }
+        e += n;
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The deep path: every accepted read of the pile, 64 at a time.
+template <int CAP>
+__device__ __forceinline__ void count_links_deep(K9Lists<CAP> &L, const PileDev &P, const ColBlock B, const uint32_t t_end, const int lane,
+                                                const ReadDev *__restrict__ reads, const uint32_t *__restrict__ acc,
+                                                const uint32_t *__restrict__ tags, const uint32_t *__restrict__ colidx,
+                                                const uint32_t *__restrict__ ms, const uint32_t *__restrict__ cb,
+                                                const uint32_t *__restrict__ eb, uint32_t *__restrict__ cell_start,
+                                                uint32_t *__restrict__ cell_len, uint32_t *__restrict__ ent_pp,
+                                                uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt,
+                                                uint32_t *__restrict__ err) {
     // Per-lane read descriptors of the first kRegChunks x 64 accepted reads stay in registers for
     // the whole column block; deeper piles reload the rest from HBM.
     constexpr int kRegChunks = 2;
@@ -452,61 +530,133 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
                         if (i > 1) ppp = tg[i - 2];
                     }
                 }
-                const uint32_t b = cur & 7u;
-#pragma unroll
-                for (uint32_t bb = 0; bb < 6; bb++) {
-                    const bool mine = has && b == bb;
-                    if (!__ballot(mine)) continue;
-                    uint32_t n0 = n_cell[bb];
-                    int found = -1;
-                    if (mine) {
-                        for (uint32_t j = 0; j < n0; j++)
-                            if (l_pp[bb][j] == pp && l_ppp[bb][j] == ppp) {
-                                found = (int)j;
-                                break;
-                            }
-                        if (found >= 0) atomicAdd(&l_cnt[bb][found], 1u);
-                    }
-                    unsigned long long rem = __ballot(mine && found < 0);
-                    while (rem) {
-                        const int ld = __ffsll((long long)rem) - 1;  // earliest read that carries a new link
-                        const uint32_t kp = (uint32_t)__shfl((int)pp, ld, 64);
-                        const uint32_t kpp = (uint32_t)__shfl((int)ppp, ld, 64);
-                        const bool in_rem = (rem >> lane) & 1ull;
-                        const unsigned long long same = __ballot(in_rem && pp == kp && ppp == kpp);
-                        if (lane == ld) {
-                            if (n0 < (uint32_t)CAP) {
-                                l_pp[bb][n0] = pp;
-                                l_ppp[bb][n0] = ppp;
-                                l_cnt[bb][n0] = (uint32_t)__popcll(same);
-                            } else {
-                                atomicExch(err, 1u);
-                            }
-                        }
-                        n0 = n0 < (uint32_t)CAP ? n0 + 1 : n0;
-                        rem &= ~same;
-                    }
-                    n_cell[bb] = n0;
-                    __builtin_amdgcn_wave_barrier();  // one wavefront: LDS operations complete in program order
+                k9_collect<CAP>(L, n_cell, has, cur, pp, ppp, lane, err);
+            }
+            k9_flush<CAP>(L, n_cell, P.cell_off + cb[t] + (uint64_t)d * 6u, e, P.ent_off, lane, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt);
+        }
+    }
+}
+
+template <int CAP>
+__global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(const PileDev *__restrict__ piles,
+                                                          const ReadDev *__restrict__ reads,
+                                                          const uint32_t *__restrict__ acc_list,
+                                                          const ColBlock *__restrict__ blocks,
+                                                          const uint32_t *__restrict__ tags,
+                                                          const uint32_t *__restrict__ colidx,
+                                                          const uint32_t *__restrict__ max_size,
+                                                          const uint32_t *__restrict__ cell_base,
+                                                          const uint32_t *__restrict__ ent_base,
+                                                          uint32_t *__restrict__ cell_start,
+                                                          uint32_t *__restrict__ cell_len, uint32_t *__restrict__ ent_pp,
+                                                          uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt,
+                                                          uint32_t *__restrict__ err, uint32_t compact_max) {
+    __shared__ K9Lists<CAP> L;
+    const ColBlock B = blocks[blockIdx.x];
+    const PileDev P = piles[B.pile];
+    const int lane = (int)threadIdx.x;
+    const uint32_t *ms = max_size + P.col_off;
+    const uint32_t *cb = cell_base + P.col_off;
+    const uint32_t *eb = ent_base + P.col_off;
+    const uint32_t *acc = acc_list + P.acc_off;
+    const uint32_t t_end = B.col0 + kColBlock < P.seed_len ? B.col0 + kColBlock : P.seed_len;
+
+    // ---- prologue: the reads that reach this block, compacted in rank order.  The slot -> read table goes through 64 words of
+    // LDS (the first 64 counters of the lists, which nothing uses before the column loop).
+    uint32_t *const slot_read = &L.cnt[0][0];
+    static_assert(CAP >= 64, "the slot table borrows 64 words of the lists");
+    const uint32_t n_chunks = (P.n_acc + 63u) / 64u;
+    uint32_t cover = 0;
+    for (uint32_t chn = 0; chn < n_chunks; chn++) {
+        const uint32_t rank = chn * 64u + (uint32_t)lane;
+        bool keep = false;
+        uint32_t ridx = 0;
+        if (rank < P.n_acc) {
+            ridx = acc[rank];
+            const ReadDev *R = &reads[ridx];
+            keep = R->t_s < t_end && R->t_e >= B.col0;
+        }
+        const unsigned long long m = __ballot(keep);
+        const uint32_t slot = cover + (uint32_t)__popcll(m & (lanes_le(lane) >> 1));
+        if (keep && slot < 64u) slot_read[slot] = ridx;
+        cover += (uint32_t)__popcll(m);
+    }
+    __builtin_amdgcn_wave_barrier();
+    const bool compact = cover <= compact_max;  // (compact_max <= 64)
+    if (lane == 0) {
+        atomicAdd(&err[compact ? 1 : 2], 1u);
+        if (compact) atomicMax(&err[3], cover);
+        else atomicMax(&err[4], ~cover);
+    }
+    if (!compact) {
+        count_links_deep<CAP>(L, P, B, t_end, lane, reads, acc, tags, colidx, ms, cb, eb, cell_start, cell_len, ent_pp, ent_ppp,
+                              ent_cnt, err);
+        return;
+    }
+
+    // ---- compact path: lane s owns the read in slot s for the whole block.  Its stream is read once in tag order, 32 bytes at
+    // a time, and the two previous tags of every tag are carried along; which (column, delta) a tag belongs to is written in
+    // the tag itself, so the read's column index is consulted once, where its stream enters the block.
+    uint32_t g_len = 0, g_tg = 0;        // tags of the read (0: this lane has none), its first tag slot (the table of a sub-batch holds < 2^32)
+    uint32_t w_pos = 0xffffffffu;        // next tag of the read
+    uint32_t w_i = 0xffffffffu;          // tag the register window begins at (none yet)
+    uint32_t w_p1 = kTagHead, w_p2 = kTagHead;
+    uint4 w_lo = make_uint4(0, 0, 0, 0), w_hi = make_uint4(0, 0, 0, 0);
+    if ((uint32_t)lane < cover) {
+        const ReadDev *R = &reads[slot_read[lane]];
+        const uint32_t ts = R->t_s;
+        const uint32_t t_first = B.col0 > ts ? B.col0 : ts;  // (kept: t_first < t_end && t_first <= t_e)
+        g_len = R->aln_len;
+        g_tg = (uint32_t)R->tag_off;
+        w_pos = (colidx + R->colidx_off)[t_first - ts];
+    }
+    // max_size, cell_base, ent_base of the block's columns: lane j holds those of column col0 + j
+    uint32_t m_ms = 0, m_cb = 0, m_eb = 0;
+    if (B.col0 + (uint32_t)lane < t_end) {
+        m_ms = ms[B.col0 + (uint32_t)lane];
+        m_cb = cb[B.col0 + (uint32_t)lane];
+        m_eb = eb[B.col0 + (uint32_t)lane];
+    }
+    __builtin_amdgcn_wave_barrier();  // the slot table has been read: the counters are the lists' again
+    const uint32_t *const tp = tags + g_tg;
+
+    for (uint32_t t = B.col0; t < t_end; t++) {
+        const int j = (int)(t - B.col0);
+        const uint32_t width = (uint32_t)__builtin_amdgcn_readlane((int)m_ms, j);
+        const uint64_t cell_t = P.cell_off + (uint32_t)__builtin_amdgcn_readlane((int)m_cb, j);
+        uint64_t e = P.ent_off + (uint32_t)__builtin_amdgcn_readlane((int)m_eb, j);
+        for (uint32_t d = 0; d < width; d++) {
+            uint32_t n_cell[6] = {0, 0, 0, 0, 0, 0};  // links collected so far in the six cells of (t, d): the same in every lane
+            bool has = false;
+            uint32_t cur = 0, pp = kTagHead, ppp = kTagHead;
+            const uint32_t key = ((t + 1u) << 8) | d;  // tag >> 3 of a tag of cell row (t, d)
+            const uint32_t i = w_pos;
+            if (i < g_len) {
+                if (w_i == 0xffffffffu) {  // first tag of this read inside the column block
+                    if (i > 0) w_p1 = tp[i - 1];
+                    if (i > 1) w_p2 = tp[i - 2];
+                }
+                if (w_i == 0xffffffffu || i - w_i >= 8u) {
+                    w_lo = *reinterpret_cast<const uint4 *>(tp + i);
+                    w_hi = *reinterpret_cast<const uint4 *>(tp + i + 4);
+                    w_i = i;
+                }
+                const uint32_t k = i - w_i;
+                const uint4 w = k < 4u ? w_lo : w_hi;
+                const uint32_t k4 = k & 3u;
+                const uint32_t c = k4 == 0 ? w.x : k4 == 1 ? w.y : k4 == 2 ? w.z : w.w;
+                if ((c >> 3) == key) {  // the read's next tag sits in this cell row: consume it
+                    cur = c;
+                    pp = w_p1;
+                    ppp = w_p2;
+                    w_p2 = w_p1;
+                    w_p1 = c;
+                    w_pos = i + 1;
+                    has = true;
                 }
             }
-            // flush the six cells of (t, d), links contiguous per cell in first-seen order
-            const uint64_t cell0 = P.cell_off + cb[t] + (uint64_t)d * 6u;
-#pragma unroll
-            for (uint32_t bb = 0; bb < 6; bb++) {
-                const uint32_t n = n_cell[bb];
-                if (lane == 0) {
-                    cell_start[cell0 + bb] = (uint32_t)(e - P.ent_off);
-                    cell_len[cell0 + bb] = n;
-                }
-                for (uint32_t j = (uint32_t)lane; j < n; j += 64) {
-                    ent_pp[e + j] = l_pp[bb][j];
-                    ent_ppp[e + j] = l_ppp[bb][j];
-                    ent_cnt[e + j] = l_cnt[bb][j];
-                }
-                e += n;
-            }
-            __builtin_amdgcn_wave_barrier();
+            k9_collect<CAP>(L, n_cell, has, cur, pp, ppp, lane, err);
+            k9_flush<CAP>(L, n_cell, cell_t + (uint64_t)d * 6u, e, P.ent_off, lane, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt);
         }
     }
 }
@@ -1678,14 +1828,20 @@ void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32
                         uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, int n_blocks,
                         bool full_capacity, void *stream) {
     if (n_blocks <= 0) return;
+    // NDGPU_K9_COMPACT=<T>: a column block that at most T reads reach takes the compact path (0..64, default 64; 0: none does)
+    static const uint32_t compact_max = [] {
+        const char *v = getenv("NDGPU_K9_COMPACT");
+        const long t = v ? strtol(v, nullptr, 10) : 64;
+        return (uint32_t)(t < 0 ? 0 : t > 64 ? 64 : t);
+    }();
     if (full_capacity)
         hipLaunchKernelGGL(count_links_kernel<kLinkCap>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, piles, reads,
                            acc_list, blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp,
-                           ent_ppp, ent_cnt, err);
+                           ent_ppp, ent_cnt, err, compact_max);
     else
         hipLaunchKernelGGL(count_links_kernel<kLinkCapSmall>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, piles,
                            reads, acc_list, blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp,
-                           ent_ppp, ent_cnt, err);
+                           ent_ppp, ent_cnt, err, compact_max);
 }
 
 void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,

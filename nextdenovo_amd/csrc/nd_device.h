@@ -261,6 +261,9 @@ constexpr int kColBlock = 32;          // columns per link-counting work item
 // live in device memory and hold one entry per accepted read of the deepest pile; the family `stack` runs it with more than 600.
 constexpr int kLinkCap = 192;
 constexpr int kLinkCapSmall = 64;
+// Words of the link counter's error block: [0] a cell overflowed its lists; [1..4] what count_links_kernel's blocks did (blocks
+// on the compact path, blocks on the deep path, largest cover among the former, ~(smallest cover among the latter), 0: none).
+constexpr int kErrWords = 8;
 constexpr int kLinkGlobalGrid = 1024;  // blocks of the third attempt (each owns 18 lists of `cap` words)
 
 void launch_shift_scan(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, ReadDev *reads, int n_reads,
@@ -273,6 +276,8 @@ void launch_make_tags(const PileDev *piles, const ReadDev *reads, const AlnTask 
 // in: cov_diff (difference array), ins_max; out (in place): coverage, max_size; plus offsets
 void launch_col_scan(PileDev *piles, uint32_t *cov_diff, const uint32_t *ins_count, uint32_t *ins_max,
                      uint32_t *cell_base, uint32_t *ent_base, int n_piles, void *stream);
+// err: kErrWords words, zero before the launch.  A column block that at most NDGPU_K9_COMPACT (0..64, default 64; read once) accepted
+// reads reach is counted on the compact path -- one lane per covering read --, any other by the loop over all accepted reads.
 void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
                         const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
                         const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
