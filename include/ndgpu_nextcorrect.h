@@ -113,7 +113,8 @@ int ndgpu_ext_batch(const ndgpu_ext_job *jobs, int n, ndgpu_ext_result *res);
 
 /* replaces: reference lib/nextcorrect.h:166 / lib/dag.c:658-694.  `seqs` points at
  * `seq_count` records laid out as the reference's `struct seq_`
- * (lib/nextcorrect.h:63-68: u16 order, u16 kscore, u16 len, char seq[10000]). */
+ * (lib/nextcorrect.h:63-68: u16 order, u16 kscore, u16 len, char seq[10000]).
+ * A host routine: one small problem is not worth a kernel launch.  Many problems at once: ndgpu_poa_batch below. */
 char *poa_to_consensus(const void *seqs, const int seq_count);
 
 /* ---- additive entry points (not in the reference) ---- */
@@ -129,6 +130,14 @@ int ndgpu_correct_batch(int n_piles, char ***seqs, unsigned int **aln_start, uns
                         const unsigned int *lqseq_max_length, unsigned int min_len_aln, unsigned int max_cov_aln,
                         unsigned int min_cov, float min_error_corrected_ratio, unsigned int split, unsigned int fast,
                         int read_type, int host_threads, consensus_trimed **out);
+
+/* poa_to_consensus for many problems in one call: the alignment of every further sequence against its problem's graph -- the
+ * O(X * Y) step -- runs on the device, sequence r of all problems in one launch; graph growth, topological order and heaviest path stay
+ * on the host.  Sequences are len[k] bytes each (1..9,999 on the device; a problem with another length, or too large for the device
+ * memory plan, is computed by the host routine inside the same call), at most 64 per problem.
+ * out[i]: malloc'd, NUL-terminated, what poa_to_consensus returns for job i's sequences.  Returns 0, < 0 on error. */
+typedef struct ndgpu_poa_job { const char *const *seqs; const uint16_t *len; int32_t seq_count; } ndgpu_poa_job;
+int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out);
 
 /* The output loop of lib/nextcorrect.py:236-260 (without -s) over finished records: for every ids[k] in order, a record with
  * len >= min_len_seed, len > 4 and identity >= min_ratio is written to fd_out as ">NAME LEN IDENTITY\nBASES\n" (IDENTITY as Python's
@@ -211,6 +220,12 @@ typedef struct {
     uint64_t tb_tasks;         /* alignments whose traceback ran in segments (one lane per 2^k edit steps) */
     uint64_t tb_walkers;       /* segments they were cut into */
     uint64_t tb_fallbacks;     /* of the alignments: walked again in one piece (a segment boundary did not agree) */
+    uint64_t poa_jobs;         /* POA problems offered to the device (ndgpu_poa_batch, the engine's pseudo-seeds) */
+    uint64_t poa_declined;     /* of which declined: the host path took them */
+    uint64_t poa_rounds;       /* lockstep rounds: sequence r of every problem that has one */
+    uint64_t poa_launches;     /* kernel launches */
+    uint64_t poa_cells;        /* (X + 1)(Y + 1) alignment cells filled */
+    double poa_ms;             /* HIP-event time of the POA kernels */
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);

@@ -19,6 +19,11 @@ class ConsensusTrimed(C.Structure):
     _fields_ = [("len", C.c_uint), ("identity", C.c_float), ("seq", C.c_void_p)]
 
 
+class PoaJob(C.Structure):
+    # ndgpu_poa_job
+    _fields_ = [("seqs", C.POINTER(C.c_char_p)), ("len", C.POINTER(C.c_uint16)), ("seq_count", C.c_int32)]
+
+
 PILES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.c_int)   # ndgpu_piles_done_fn
 
 
@@ -34,7 +39,9 @@ class Stats(C.Structure):
                 ("lq_ms", C.c_double), ("allocs", C.c_uint64), ("alloc_ms", C.c_double), ("level_allocs", C.c_uint64), ("level_ms", C.c_double),
                 ("traceback_launches", C.c_uint64), ("lq_launches", C.c_uint64), ("lq_columns", C.c_uint64), ("lq_aln_columns", C.c_uint64),
                 ("lq_bases", C.c_uint64), ("lq_out", C.c_uint64), ("lq_jobs", C.c_uint64), ("lq_repairs", C.c_uint64),
-                ("tb_tasks", C.c_uint64), ("tb_walkers", C.c_uint64), ("tb_fallbacks", C.c_uint64)]
+                ("tb_tasks", C.c_uint64), ("tb_walkers", C.c_uint64), ("tb_fallbacks", C.c_uint64),
+                ("poa_jobs", C.c_uint64), ("poa_declined", C.c_uint64), ("poa_rounds", C.c_uint64), ("poa_launches", C.c_uint64),
+                ("poa_cells", C.c_uint64), ("poa_ms", C.c_double)]
 
 
 def lib_path() -> str:
@@ -78,6 +85,8 @@ def _bind(lib):
     lib.ndgpu_write_records.argtypes = [C.POINTER(C.POINTER(ConsensusTrimed)), C.POINTER(C.c_uint32), C.c_int, C.c_void_p, C.c_uint32, C.c_double,
                                         C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
     lib.ndgpu_write_records.restype = C.c_int
+    lib.ndgpu_poa_batch.argtypes = [C.POINTER(PoaJob), C.c_int, C.POINTER(C.c_void_p)]
+    lib.ndgpu_poa_batch.restype = C.c_int
     lib.ndgpu_get_stats.argtypes = [C.POINTER(Stats)]
     lib.ndgpu_reset_stats.argtypes = []
     lib.ndgpu_device_count.restype = C.c_int
@@ -300,6 +309,33 @@ def ext_batch(jobs):
     if lib.ndgpu_ext_batch(arr, n, res) != 0:
         raise RuntimeError("ndgpu_ext_batch failed: no usable HIP device?")
     return [(r.done, r.a, r.b, list(r.pos)) for r in res[:n]]
+
+
+def poa_batch(jobs):
+    """jobs: [[bytes, ...]] -> [bytes]: what poa_to_consensus returns for every job's sequences, through ndgpu_poa_batch (the
+    alignments of all jobs on the device in lockstep rounds; lib/dag.c:658-694)."""
+    lib = load()
+    n = len(jobs)
+    arr = (PoaJob * max(1, n))()
+    keep = []
+    for i, seqs in enumerate(jobs):
+        k = len(seqs)
+        cs = (C.c_char_p * max(1, k))()
+        cs[:k] = list(seqs)
+        ln = (C.c_uint16 * max(1, k))(*[len(s) for s in seqs])
+        keep.append((cs, ln))
+        arr[i] = PoaJob(C.cast(cs, C.POINTER(C.c_char_p)), C.cast(ln, C.POINTER(C.c_uint16)), k)
+    out = (C.c_void_p * max(1, n))()
+    rc = lib.ndgpu_poa_batch(arr, n, out)
+    if rc != 0:
+        raise RuntimeError("ndgpu_poa_batch failed (%d)" % rc)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    res = []
+    for i in range(n):
+        res.append(C.string_at(out[i]))
+        libc.free(out[i])
+    return res
 
 
 def stats() -> dict:

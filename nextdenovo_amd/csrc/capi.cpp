@@ -763,6 +763,62 @@ char *poa_to_consensus(const void *seqs, const int seq_count) {
     return out;
 }
 
+// poa_to_consensus for a batch of problems: the alignments on the device in lockstep rounds (DeviceAligner::run_poa); a problem
+// the device declines is computed by the host path here, in the same call
+int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) {
+    if (n <= 0) return 0;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_poa_batch runs its alignments on the device\n");
+        return -1;
+    }
+    std::vector<PoaReq> reqs((size_t)n);
+    std::vector<PoaReq *> ptr((size_t)n);
+    for (int i = 0; i < n; i++) {
+        out[i] = nullptr;
+        if (jobs[i].seq_count < 0 || jobs[i].seq_count > kPoaMaxSeqs) return -2;
+        for (int k = 0; k < jobs[i].seq_count; k++) reqs[i].seqs.emplace_back(jobs[i].seqs[k], (size_t)jobs[i].len[k]);
+        ptr[i] = &reqs[i];
+    }
+    const int threads = effective_cpus();
+    // (out of device memory: the range is halved until it fits; a single problem that does not fit goes the host way)
+    std::vector<std::pair<size_t, size_t>> todo{{0, (size_t)n}};
+    while (!todo.empty()) {
+        const auto [a, b] = todo.back();
+        todo.pop_back();
+        try {
+            HipBackend be(0, threads);
+            (void)be.run_poa(ptr.data() + a, b - a);
+        } catch (const DeviceOom &) {
+            DeviceAligner::context(0).release_memory();
+            DeviceAligner::forget_sizes();
+            if (b - a > 1) {
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    int rc = 0;
+    parallel_for((size_t)n, threads, [&](size_t i) {
+        PoaReq &rq = reqs[i];
+        if (!rq.done && !rq.failed) {
+            rq.out = poa_consensus(rq.seqs);
+            rq.done = true;
+        }
+    });
+    for (int i = 0; i < n; i++) {
+        if (reqs[i].failed) {
+            rc = -3;
+            continue;
+        }
+        out[i] = (char *)malloc(reqs[i].out.size() + 1);
+        memcpy(out[i], reqs[i].out.c_str(), reqs[i].out.size() + 1);
+    }
+    if (rc)
+        for (int i = 0; i < n; i++) free(out[i]), out[i] = nullptr;
+    return rc;
+}
+
 void ndgpu_get_stats(ndgpu_stats *o) {
     RuntimeStats s = DeviceAligner::total_stats();
     o->tasks = s.tasks;
@@ -800,6 +856,8 @@ void ndgpu_get_stats(ndgpu_stats *o) {
     o->lq_aln_columns = s.lq_aln_columns, o->lq_bases = s.lq_bases, o->lq_out = s.lq_out;
     o->lq_jobs = s.lq_jobs, o->lq_repairs = s.lq_repairs;
     o->tb_tasks = s.tb_tasks, o->tb_walkers = s.tb_walkers, o->tb_fallbacks = s.tb_fallbacks;
+    o->poa_jobs = s.poa_jobs, o->poa_declined = s.poa_declined, o->poa_rounds = s.poa_rounds, o->poa_launches = s.poa_launches;
+    o->poa_cells = s.poa_cells, o->poa_ms = s.poa_ms;
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }

@@ -526,9 +526,10 @@ class PileImpl {
 
     void advance() {
         const uint64_t t0 = now_ns();
-        const int ph = phase == PileEngine::MAIN ? 0 : phase == PileEngine::EXTRACT ? 1 : lq_iter <= 1 ? 2 : 3;
+        const int ph = phase == PileEngine::MAIN ? 0 : phase == PileEngine::EXTRACT || phase == PileEngine::POA ? 1 : lq_iter <= 1 ? 2 : 3;
         if (phase == PileEngine::MAIN) after_main();
         else if (phase == PileEngine::EXTRACT) after_extract();
+        else if (phase == PileEngine::POA) after_poa();
         else if (phase == PileEngine::LQ_ROUND) after_lq_round();
         g_prof.adv_ns[ph] += now_ns() - t0;  // per-thread sums: after main / after extract / after LQ round 1 / after round 2 + splice
     }
@@ -571,15 +572,65 @@ class PileImpl {
     }
 
     uint64_t poa_ns_local = 0;
+    // The regions' POA problems as backend requests (Backend::run_poa): after_extract ranks and selects as ever and posts a request
+    // where it used to call poa_consensus; run_engines offers the requests of all live piles to the backend in one batch; after_poa
+    // takes a region's turn up again where the call stood.  What the backend does not take (or declines) is computed here, by
+    // poa_consensus.  Off (the default, see DESIGN.md section 0a''): the call stays where it was.
+    struct PoaPending {
+        size_t region;
+        int add_len;       // what the region adds to its pseudo-seed's length for the alignment buffers' bound
+        bool check_len;    // check_pseudo_seed_length follows (not in the HiFi path)
+    };
+    std::vector<PoaReq> poa_reqs;
+    std::vector<PoaPending> poa_pending;
+    static bool poa_as_request() {
+        static const bool on = getenv("NDGPU_POA_DEVICE") != nullptr && atoi(getenv("NDGPU_POA_DEVICE")) != 0;
+        return on;
+    }
+    void post_poa(size_t region, std::vector<std::string> &&in, int add_len, bool check_len) {
+        poa_reqs.emplace_back();
+        poa_reqs.back().seqs = std::move(in);
+        poa_pending.push_back(PoaPending{region, add_len, check_len});
+    }
+    void collect_poa(std::vector<PoaReq *> &out) {
+        if (phase != PileEngine::POA) return;
+        for (PoaReq &r : poa_reqs) out.push_back(&r);
+    }
+
     void after_extract() {
         const uint64_t t0 = now_ns();
         poa_ns_local = 0;
+        poa_reqs.clear(), poa_pending.clear();
         lq_max_aln_length = prm.read_type == 3 ? lqseqs_from_candidates_kmer() : lqseqs_from_candidates();
         extract.regions.clear();
         const uint64_t t1 = now_ns();
-        start_lq_round();
         g_prof.poa_ns += poa_ns_local;
         g_prof.rank_ns += t1 - t0 - poa_ns_local;
+        if (!poa_reqs.empty()) {
+            phase = PileEngine::POA;
+            return;
+        }
+        start_lq_round();
+        g_prof.lqstart_ns += now_ns() - t1;
+    }
+
+    void after_poa() {
+        const uint64_t t0 = now_ns();
+        for (size_t i = 0; i < poa_reqs.size(); i++) {
+            PoaReq &rq = poa_reqs[i];
+            const PoaPending &pp = poa_pending[i];
+            LqRegion &lq = regions[pp.region];
+            if (!rq.done) rq.out = poa_consensus(rq.seqs);
+            lq.sudoseed.swap(rq.out);
+            lq.has_seed = true;
+            lq.sudoseed_len = (unsigned)lq.sudoseed.size();
+            if (pp.check_len) check_pseudo_seed_length(lq);
+            if (pp.add_len + (int)lq.sudoseed_len > lq_max_aln_length) lq_max_aln_length = pp.add_len + (int)lq.sudoseed_len;
+        }
+        poa_reqs.clear(), poa_pending.clear();
+        const uint64_t t1 = now_ns();
+        g_prof.poa_ns += t1 - t0;
+        start_lq_round();
         g_prof.lqstart_ns += now_ns() - t1;
     }
 
@@ -1037,6 +1088,10 @@ class PileImpl {
                 if (lq.seqs[0].len < 20000) {
                     std::vector<std::string> in;
                     for (int x = 0; x < k; x++) in.push_back(lq.seqs[j + x].seq);
+                    if (poa_as_request()) {  // (the rest of this region's turn: after_poa)
+                        post_poa((size_t)(&lq - regions.data()), std::move(in), max_aln_lqseq_len, false);
+                        continue;
+                    }
                     { const uint64_t tp = now_ns(); lq.sudoseed = poa_consensus(in); poa_ns_local += now_ns() - tp; }
                 } else lq.sudoseed = lq.seqs[0].seq;
                 lq.has_seed = true;
@@ -1125,10 +1180,24 @@ class PileImpl {
             {
                 std::vector<std::string> in;
                 for (int x = 0; x < k; x++) in.push_back(lq.seqs[j + x].seq);
+                if (poa_as_request()) {  // (the rest of this region's turn: after_poa)
+                    post_poa(ri, std::move(in), max_len_here, true);
+                    continue;
+                }
                 { const uint64_t tp = now_ns(); lq.sudoseed = poa_consensus(in); poa_ns_local += now_ns() - tp; }
             }
             lq.has_seed = true;
             lq.sudoseed_len = (unsigned)lq.sudoseed.size();
+            check_pseudo_seed_length(lq);
+            if (max_len_here + (int)lq.sudoseed_len > max_aln_length) max_aln_length = max_len_here + (int)lq.sudoseed_len;
+        }
+        return max_aln_length;
+    }
+
+    // a POA consensus of more than 500 bases that is over a tenth longer than its candidates' trimmed mean gives way to one of them
+    void check_pseudo_seed_length(LqRegion &lq) {
+        int j, k;
+        {
             if (lq.sudoseed_len > 500) {
                 int kmax, kmin;
                 k = kmax = kmin = lq.seqs[lq.indexs].len;
@@ -1148,9 +1217,7 @@ class PileImpl {
                     lq.sudoseed_len = lq.seqs[k].len;
                 }
             }
-            if (max_len_here + (int)lq.sudoseed_len > max_aln_length) max_aln_length = max_len_here + (int)lq.sudoseed_len;
         }
-        return max_aln_length;
     }
 
     // -- low-quality-region rounds (lib/nextcorrect.c:1671-1715, 1538-1669) ----------
@@ -1438,6 +1505,7 @@ MainPile *PileEngine::main_request() { return &impl_->main; }
 ExtractPile *PileEngine::extract_request() { return &impl_->extract; }
 void PileEngine::collect_jobs(std::vector<AlnJob *> &out) { impl_->collect(out); }
 LqRound *PileEngine::lq_request() { return impl_->phase == LQ_ROUND && !impl_->jobs.empty() ? &impl_->lq : nullptr; }
+void PileEngine::collect_poa(std::vector<PoaReq *> &out) { impl_->collect_poa(out); }
 void PileEngine::advance() { impl_->advance(); }
 ConsensusTrimed *PileEngine::take_result() { return impl_->take(); }
 
@@ -1560,18 +1628,21 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
     std::vector<ExtractPile *> extracts;
     std::vector<AlnJob *> jobs;
     std::vector<LqRound *> lqs;
+    std::vector<PoaReq *> poas;
     std::vector<size_t> live, in_lq;
     for (;;) {
         mains.clear();
         extracts.clear();
         jobs.clear();
         lqs.clear();
+        poas.clear();
         live.clear();
         in_lq.clear();
         for (size_t i = 0; i < n; i++) {
             switch (eng[i]->phase()) {
                 case PileEngine::MAIN: mains.push_back(eng[i]->main_request()); break;
                 case PileEngine::EXTRACT: extracts.push_back(eng[i]->extract_request()); break;
+                case PileEngine::POA: eng[i]->collect_poa(poas); break;
                 case PileEngine::LQ_ROUND:
                     in_lq.push_back(i);
                     if (LqRound *r = eng[i]->lq_request()) lqs.push_back(r);
@@ -1585,6 +1656,8 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
         if (!mains.empty()) be.run_main(mains.data(), mains.size());
         uint64_t t1 = now_ns();
         if (!extracts.empty()) be.run_extract(extracts.data(), extracts.size());
+        // the regions' POA problems: one batch on the backend where it offers that; what it does not take is computed in advance()
+        if (!poas.empty()) (void)be.run_poa(poas.data(), poas.size());
         uint64_t t2 = now_ns();
         // low-quality-region rounds: whole rounds on the backend where it offers that; what it does not take (or declines)
         // goes the host way -- the alignments as a batch, the second MSA in the engine

@@ -286,6 +286,15 @@ enum class BufLevel { levelled, on_demand };
     X(char, d_lq_out, device, levelled) /* the piles' characters / the jobs' stretches of the walk (one slot per cell row) */             \
     X(char, d_lq_tmp, device, levelled)                                                                                                   \
     X(int32_t, d_lq_bnd, device, levelled) /* K12b's boundary planes: 4 x kLqLinkCap words per job */                                     \
+    /* POA (K13): jobs, the ids each kernel form takes, query bytes, rows, predecessor rows, scores, origins, routes */                    \
+    X(PoaJobDev, d_poa_jobs, device, levelled)                                                                                            \
+    X(uint32_t, d_poa_ids, device, levelled)                                                                                              \
+    X(char, d_poa_q, device, levelled)                                                                                                    \
+    X(PoaRowDev, d_poa_rows, device, levelled)                                                                                            \
+    X(uint16_t, d_poa_preds, device, levelled)                                                                                            \
+    X(int32_t, d_poa_s, device, levelled)                                                                                                 \
+    X(uint16_t, d_poa_f, device, levelled)                                                                                                \
+    X(uint32_t, d_poa_route, device, levelled)                                                                                            \
     /* forward / traceback (K7 / K8a) */                                                                                                  \
     X(uint32_t, d_pool, device, levelled)                                                                                                 \
     X(uint32_t, d_ops, device, levelled)                                                                                                  \
@@ -588,6 +597,8 @@ RuntimeStats DeviceAligner::total_stats() {
         t.traceback_launches += s.traceback_launches; t.lq_launches += s.lq_launches; t.lq_columns += s.lq_columns;
         t.lq_aln_columns += s.lq_aln_columns; t.lq_bases += s.lq_bases; t.lq_out += s.lq_out; t.lq_jobs += s.lq_jobs; t.lq_repairs += s.lq_repairs;
         t.tb_tasks += s.tb_tasks; t.tb_walkers += s.tb_walkers; t.tb_fallbacks += s.tb_fallbacks;
+        t.poa_jobs += s.poa_jobs; t.poa_declined += s.poa_declined; t.poa_rounds += s.poa_rounds; t.poa_launches += s.poa_launches;
+        t.poa_cells += s.poa_cells; t.poa_ms += s.poa_ms;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -1842,6 +1853,177 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
         }
     }
     g_prof.m_post += wall_ns() - tp4;
+}
+
+// ---- POA problems as a batch (K13): lockstep rounds -- round r aligns sequence r of every problem that has one against the
+// problem's graph, one launch pair (wave form, workgroup form) per slice of the round that fits the memory plan; between rounds the
+// context's host threads thread the routes through the graphs and sort them (poa.cpp).  The workspace -- 6 bytes per cell of
+// (X + 1)(Y + 1) -- is charged to the trace budget of the memory plan.  A problem outside the device's limits (a sequence of 0 or
+// more than 9,999 bases) or whose round alone exceeds the budget is declined: req.done stays false and the caller takes the host path.
+void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    std::unique_lock<std::mutex> dbg_lock;
+    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
+    std::lock_guard<std::mutex> lock(S.mu);
+    HIP_CHECK(hipSetDevice(S.device));
+    hipStream_t st = S.stream;
+    // test hooks, read once: the cell budget of a launch (0: every problem is declined), the kernel form every job takes, the row
+    // length from which the workgroup form takes over
+    static const char *e_budget = getenv("NDGPU_POA_BUDGET");
+    static const char *e_form = getenv("NDGPU_POA_FORM");
+    static const uint32_t group_min = getenv("NDGPU_POA_GROUP_MIN") ? (uint32_t)atoll(getenv("NDGPU_POA_GROUP_MIN")) : kPoaGroupMinLen;
+    static const int form = !e_form ? 0 : !strcmp(e_form, "wave") ? 1 : !strcmp(e_form, "group") ? 2 : 0;
+    const uint64_t budget = e_budget ? strtoull(e_budget, nullptr, 10) : (uint64_t)(S.trace_budget_bytes / 6);
+
+    struct Prob {
+        PoaGraph g;
+        PoaRows rows;
+        bool live = false;       // still on the device path
+        uint64_t cells = 0;      // of the round in progress
+        uint32_t job = 0;        // its job of the launch in progress
+    };
+    std::vector<Prob> probs(n);
+    size_t max_seqs = 0;
+    S.stats.poa_jobs += n;
+    for (size_t i = 0; i < n; i++) {
+        PoaReq &rq = *reqs[i];
+        rq.done = false, rq.failed = false;
+        if (rq.seqs.size() > (size_t)kPoaMaxSeqs) {
+            rq.failed = true;
+            continue;
+        }
+        bool ok = !rq.seqs.empty() && budget > 0;
+        for (const std::string &q : rq.seqs) ok = ok && !q.empty() && q.size() <= (size_t)kPoaMaxSeqLen;
+        probs[i].live = ok;
+        if (!ok) continue;
+        probs[i].g.start(rq.seqs[0].c_str(), rq.seqs[0].size());
+        max_seqs = std::max(max_seqs, rq.seqs.size());
+    }
+
+    auto host_for = [&](const std::vector<size_t> &ids, auto f) {  // f(problem) over the context's host threads
+        if (ids.size() < 8 || S.host_threads <= 1) {
+            for (size_t i : ids) f(i);
+            return;
+        }
+        CoreLease lease(S.host_threads);
+        const size_t nt = std::min<size_t>((size_t)lease.n, ids.size() / 4);
+        std::atomic<size_t> next(0);
+        auto work = [&] {
+            for (size_t k; (k = next.fetch_add(1)) < ids.size();) f(ids[k]);
+        };
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < nt; t++) th.emplace_back(work);
+        work();
+        for (auto &x : th) x.join();
+    };
+
+    std::vector<size_t> round_ids, slice;
+    std::vector<PoaJobDev> jobs;
+    std::vector<PoaRowDev> rows;
+    std::vector<uint16_t> preds;
+    std::vector<char> qpool;
+    std::vector<uint32_t> ids, routes;
+    for (size_t r = 1; r < max_seqs; r++) {
+        round_ids.clear();
+        for (size_t i = 0; i < n; i++)
+            if (probs[i].live && reqs[i]->seqs.size() > r) round_ids.push_back(i);
+        if (round_ids.empty()) break;
+        S.stats.poa_rounds++;
+        host_for(round_ids, [&](size_t i) {
+            Prob &p = probs[i];
+            p.g.export_rows(p.rows);
+            p.cells = (uint64_t)(p.g.rows() + 1) * (uint64_t)(reqs[i]->seqs[r].size() + 1);
+        });
+        for (size_t a = 0; a < round_ids.size();) {
+            // ---- a slice of the round: as many jobs as fit the budget; a job over the budget on its own is declined
+            slice.clear();
+            uint64_t cells = 0;
+            for (; a < round_ids.size(); a++) {
+                Prob &p = probs[round_ids[a]];
+                if (p.cells > budget || p.g.rows() > 65535) {
+                    p.live = false;
+                    continue;
+                }
+                if (!slice.empty() && cells + p.cells > budget) break;
+                cells += p.cells;
+                slice.push_back(round_ids[a]);
+            }
+            if (slice.empty()) continue;
+            jobs.clear(), rows.clear(), preds.clear(), qpool.clear();
+            std::vector<uint32_t> ids_wave, ids_group;
+            uint64_t cell_at = 0, route_at = 0;
+            for (size_t i : slice) {
+                Prob &p = probs[i];
+                const std::string &q = reqs[i]->seqs[r];
+                PoaJobDev J;
+                memset(&J, 0, sizeof(J));
+                J.X = (uint32_t)p.g.rows(), J.Y = (uint32_t)q.size();
+                J.q_off = qpool.size(), J.row_off = rows.size(), J.pred_off = preds.size();
+                J.cell_off = cell_at, J.route_off = route_at;
+                cell_at += p.cells, route_at += (uint64_t)J.X + J.Y;
+                qpool.insert(qpool.end(), q.begin(), q.end());
+                for (uint32_t x = 0; x < J.X; x++) {
+                    PoaRowDev rw;
+                    rw.pred_off = p.rows.pred_off[x];
+                    rw.n_pred = (uint16_t)(p.rows.pred_off[x + 1] - p.rows.pred_off[x]);
+                    rw.base = p.rows.base[x], rw.sink = p.rows.sink[x];
+                    rows.push_back(rw);
+                }
+                preds.insert(preds.end(), p.rows.preds.begin(), p.rows.preds.end());
+                p.job = (uint32_t)jobs.size();
+                const bool group = form ? form == 2 : J.Y >= group_min;
+                (group ? ids_group : ids_wave).push_back(p.job);
+                jobs.push_back(J);
+            }
+            ids = ids_wave;
+            ids.insert(ids.end(), ids_group.begin(), ids_group.end());
+            S.d_poa_jobs.reserve(jobs.size()), S.d_poa_ids.reserve(ids.size()), S.d_poa_q.reserve(qpool.size());
+            S.d_poa_rows.reserve(rows.size()), S.d_poa_preds.reserve(preds.size());
+            S.d_poa_s.reserve(cell_at), S.d_poa_f.reserve(cell_at), S.d_poa_route.reserve(route_at);
+            S.h2d(S.d_poa_jobs.p, jobs.data(), jobs.size() * sizeof(PoaJobDev), st);
+            S.h2d(S.d_poa_ids.p, ids.data(), ids.size() * sizeof(uint32_t), st);
+            S.h2d(S.d_poa_q.p, qpool.data(), qpool.size(), st);
+            S.h2d(S.d_poa_rows.p, rows.data(), rows.size() * sizeof(PoaRowDev), st);
+            S.h2d(S.d_poa_preds.p, preds.data(), preds.size() * sizeof(uint16_t), st);
+            HIP_CHECK(hipEventRecord(S.evs[5], st));
+            NDGPU_DBG(st, "poa: round %zu, %zu + %zu jobs, %llu cells", r, ids_wave.size(), ids_group.size(), (unsigned long long)cell_at);
+            launch_poa_align(S.d_poa_jobs.p, S.d_poa_ids.p, (int)ids_wave.size(), S.d_poa_ids.p + ids_wave.size(), (int)ids_group.size(),
+                             S.d_poa_q.p, S.d_poa_rows.p, S.d_poa_preds.p, S.d_poa_s.p, S.d_poa_f.p, S.d_poa_route.p, st);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventRecord(S.evs[6], st));
+            routes.resize(route_at);
+            S.d2h(jobs.data(), S.d_poa_jobs.p, jobs.size() * sizeof(PoaJobDev), st);
+            S.d2h(routes.data(), S.d_poa_route.p, route_at * sizeof(uint32_t), st);
+            S.sync_drain(st);
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
+            S.stats.poa_ms += ms;
+            S.stats.poa_launches += (ids_wave.empty() ? 0 : 1) + (ids_group.empty() ? 0 : 1);
+            S.stats.poa_cells += cell_at;
+            // ---- graph growth and the new order, on the host
+            host_for(slice, [&](size_t i) {
+                Prob &p = probs[i];
+                const PoaJobDev &J = jobs[p.job];
+                const std::string &q = reqs[i]->seqs[r];
+                if (J.route_len > J.X + J.Y) {  // (the walk did not reach the origin: cannot happen)
+                    fprintf(stderr, "[ndgpu] FATAL: POA route of a %u x %u problem did not end\n", J.X, J.Y);
+                    abort();
+                }
+                p.g.set_route(routes.data() + J.route_off, J.route_len);
+                if (!p.g.thread((int)r, q.c_str(), (int)q.size())) p.live = false, reqs[i]->failed = true;
+            });
+        }
+    }
+    round_ids.clear();
+    for (size_t i = 0; i < n; i++)
+        if (probs[i].live) round_ids.push_back(i);
+    host_for(round_ids, [&](size_t i) {
+        reqs[i]->out = probs[i].g.consensus((int)reqs[i]->seqs.size());
+        reqs[i]->done = true;
+    });
+    for (size_t i = 0; i < n; i++)
+        if (!reqs[i]->done && !reqs[i]->failed) S.stats.poa_declined++;
 }
 
 void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {

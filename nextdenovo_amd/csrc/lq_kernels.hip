@@ -26,6 +26,9 @@
 //             stream fetched a row ahead.
 // A pile that does not fit the LDS tables (an insertion run of >= 48 columns, > 384 links in a column) or whose alignments do
 // not end at both sequence ends is declined (err != 0): the host path (consensus.cpp) takes it.
+//
+// K13 poa_align  the pseudo-seeds themselves: one sequence of a region's POA against its graph, a batch of regions per launch (at the
+//             end of this file; DeviceAligner::run_poa drives it in lockstep rounds).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -839,6 +842,188 @@ __global__ __launch_bounds__(64) void lq_gather_kernel(LqPileDev *__restrict__ p
     if (lane == 0) PD.out_len = at;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// K13: POA -- one sequence against the graph (poa.cpp: Graph::align; lib/dag.c:88-134, 261-343), the step of the pseudo-seed
+// consensus that costs O(X * Y).  The host hands over the query bytes and, per row in topological order, the node's byte, its
+// predecessor rows in in-edge insertion order (row 0 alone when it has none) and whether it has an out-edge; the kernel fills the
+// scores S (int32) and the origins F (uint16: [1:0] kind, [15:2] which in-edge) in HBM, picks the best sink row -- the first in
+// topological order with the strictly greatest last-column score -- walks back and returns the route, nothing else.
+//
+// A row: lane l of a 64-column chunk owns column j.  The candidates through the in-edges read finished rows only -- per edge the
+// deletion (the cell above-right + gap) beats the match (the cell above + 1 / - 2, bases compared as bytes) on >=, a later edge
+// replaces an earlier one only when strictly greater: cv[j], ct[j].  The one dependence along the row is
+//     row[j + 1] = max(cv[j], row[j] - 2), the horizontal move keeping ties (poa.cpp: `up = cv[j] > h`),
+// and with a[j] = cv[j] + 2(j + 1), R[j] = row[j] + 2j it is R[j + 1] = max(a[j], R[j]): R[j] = max(R[0], a[0 .. j - 1]), the exclusive
+// prefix maximum E[j]; the cell takes its candidate exactly when a[j] > E[j] (strictly: the tie is the horizontal move's).  Six
+// data-parallel-primitive moves give the prefix maximum of a chunk, one more shifts it by a lane, and the chunk's last value is the
+// carry into the next chunk.
+//
+// Two forms.  NW = 1: one wavefront per job walks the row chunk by chunk (most regions are a few hundred bases; thousands of jobs
+// are resident and hide each other's row-to-row latency).  NW = kPoaGroupWaves: one workgroup per job, wave w owns a fixed segment
+// [c0, c1) of every row (whole chunks): it stores its raw candidates and publishes its segment's maximum of a[] (wave 0 folds the
+// row's column 0 in), ONE barrier, then every wave knows its carry-in = the maximum of the segments before it and finishes its
+// cells.  A wave reads other rows only inside cells [c0, c1]: cells (c0, c1] are its own stores, and cell c0 -- the last cell of the
+// wave before -- equals its carry-in, so of the row just finished it keeps that cell in a register and never waits for a
+// neighbour's store that no barrier has covered yet (older rows' cell c0 lies behind a barrier).
+constexpr int32_t kPoaGap = -2;
+constexpr int32_t kPoaNeg = INT_MIN / 2;
+enum : uint32_t { kPoaH = 0, kPoaMat = 1, kPoaDel = 2, kPoaOrigin = 3 };   // (poa.cpp: FROM_*)
+
+__device__ __forceinline__ int32_t poa_max(int32_t a, int32_t b) { return a > b ? a : b; }
+// inclusive prefix maximum over the 64 lanes
+__device__ __forceinline__ int32_t poa_prefix_max(int32_t v) {
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x111, 0xf, 0xf, false));  // row_shr:1
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x112, 0xf, 0xf, false));  // row_shr:2
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x114, 0xf, 0xf, false));  // row_shr:4
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x118, 0xf, 0xf, false));  // row_shr:8: every row of 16 scanned
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x142, 0xa, 0xf, false));  // row_bcast:15 into rows 1 and 3
+    v = poa_max(v, __builtin_amdgcn_update_dpp(kPoaNeg, v, 0x143, 0xc, 0xf, false));  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void poa_align_kernel(PoaJobDev *__restrict__ jobs, const uint32_t *__restrict__ ids,
+                                                            const char *__restrict__ qpool, const PoaRowDev *__restrict__ rows,
+                                                            const uint16_t *__restrict__ preds, int32_t *S_all, uint16_t *F_all,
+                                                            uint32_t *__restrict__ route_all) {
+    __shared__ int32_t seg_max[2][NW];
+    __shared__ int32_t s_bx;
+    PoaJobDev &JD = jobs[ids[blockIdx.x]];
+    const PoaJobDev J = JD;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int X = (int)J.X, Y = (int)J.Y;
+    const uint64_t W = (uint64_t)Y + 1u;
+    int32_t *const S = S_all + J.cell_off;
+    uint16_t *const F = F_all + J.cell_off;
+    const unsigned char *__restrict__ q = (const unsigned char *)qpool + J.q_off;
+    const PoaRowDev *__restrict__ R = rows + J.row_off;
+    const uint16_t *__restrict__ P = preds + J.pred_off;
+    // the wave's columns [c0, c1) (cells c0 + 1 .. c1); a wave behind the row's end has none
+    const int seg = NW == 1 ? ((Y + 63) & ~63) : ((((Y + NW - 1) / NW) + 63) & ~63);
+    const int c0 = wave * seg, c1 = c0 + seg < Y ? c0 + seg : Y;
+    const bool own_last = c0 < Y && c1 == Y && lane == ((Y - 1 - c0) & 63);   // the thread of the row's last cell
+
+    // row 0 (dag.c:88-134): the boundary cells point at the origin
+    for (int c = tid; c <= Y; c += NW * 64) S[c] = c * kPoaGap, F[c] = (uint16_t)kPoaOrigin;
+    if (NW == 1) {
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+    } else __syncthreads();
+
+    int32_t best = 0, edge_prev = c0 * kPoaGap;   // edge_prev (NW > 1): cell c0 of the row just finished (row 0 to begin with)
+    int bx = 0;
+    bool any = false;
+    for (int i = 0; i < X; i++) {
+        const PoaRowDev rw = R[i];
+        int32_t *const row = S + (uint64_t)(i + 1) * W;
+        uint16_t *const frow = F + (uint64_t)(i + 1) * W;
+        const uint16_t *__restrict__ pr = P + rw.pred_off;
+        const uint32_t base = rw.base;
+        // column 0: the best of the predecessors' column 0 + gap (wave 0; the others meet it in their carry-in)
+        int32_t carry = kPoaNeg;
+        if (wave == 0) {
+            int32_t b = S[(uint64_t)pr[0] * W];
+            for (uint32_t k = 1; k < rw.n_pred; k++) {
+                const int32_t t = S[(uint64_t)pr[k] * W];
+                b = t > b ? t : b;
+            }
+            carry = b + kPoaGap;
+            if (lane == 0) frow[0] = (uint16_t)kPoaOrigin;
+        }
+        // ---- the candidates through the in-edges, chunk by chunk
+        int32_t m = kPoaNeg;   // NW > 1: the segment's maximum of a[]
+        for (int c = c0; c < c1; c += 64) {
+            const int j = c + lane;
+            const bool in = j < c1;
+            int32_t cv = kPoaNeg;
+            uint32_t ct = 0;
+            if (in) {
+                const uint32_t qb = q[j];
+                for (uint32_t k = 0; k < rw.n_pred; k++) {
+                    const int32_t *prev = S + (uint64_t)pr[k] * W;
+                    const int32_t del = prev[j + 1] + kPoaGap;
+                    const int32_t left = (NW > 1 && j == c0 && (int)pr[k] == i) ? edge_prev : prev[j];
+                    const int32_t mat = left + (qb == base ? 1 : -2);
+                    const bool d = del >= mat;
+                    const int32_t cand = d ? del : mat;
+                    if (k == 0 || cand > cv) cv = cand, ct = k << 2 | (d ? kPoaDel : kPoaMat);
+                }
+            }
+            const int32_t a = in ? cv + 2 * (j + 1) : kPoaNeg;
+            if (NW == 1) {
+                // ---- and the horizontal move at once: exclusive prefix maximum, the carry in lane 0
+                const int32_t incl = poa_prefix_max(a);
+                const int32_t e = poa_max(__builtin_amdgcn_update_dpp(carry, incl, 0x138, 0xf, 0xf, false), carry);  // wave_shr:1
+                const bool up = a > e;
+                const int32_t r = (up ? a : e) - 2 * (j + 1);
+                if (in) {
+                    row[j + 1] = r;
+                    frow[j + 1] = (uint16_t)(up ? ct : kPoaH);
+                }
+                if (c == 0 && lane == 0) row[0] = carry;
+                if (own_last && j == Y - 1 && rw.sink && (!any || r > best)) bx = i + 1, best = r, any = true;
+                carry = poa_max(__builtin_amdgcn_readlane(incl, 63), carry);
+            } else {
+                if (in) {
+                    row[j + 1] = cv;
+                    frow[j + 1] = (uint16_t)ct;
+                }
+                m = a > m ? a : m;
+            }
+        }
+        if (NW > 1) {
+            // ---- one exchange per row: every wave's segment maximum (wave 0's with column 0 folded in)
+            const int32_t mw = poa_max(__builtin_amdgcn_readlane(poa_prefix_max(m), 63), carry);
+            if (lane == 0) seg_max[i & 1][wave] = mw;
+            __syncthreads();
+            for (int w = 0; w < wave; w++) carry = poa_max(carry, seg_max[i & 1][w]);
+            edge_prev = carry - 2 * c0;
+            if (wave == 0 && lane == 0) row[0] = carry;
+            for (int c = c0; c < c1; c += 64) {
+                const int j = c + lane;
+                const bool in = j < c1;
+                const int32_t cv = in ? row[j + 1] : kPoaNeg;     // (this thread's own stores)
+                const uint32_t ct = in ? frow[j + 1] : 0u;
+                const int32_t a = in ? cv + 2 * (j + 1) : kPoaNeg;
+                const int32_t incl = poa_prefix_max(a);
+                const int32_t e = poa_max(__builtin_amdgcn_update_dpp(carry, incl, 0x138, 0xf, 0xf, false), carry);  // wave_shr:1
+                const bool up = a > e;
+                const int32_t r = (up ? a : e) - 2 * (j + 1);
+                if (in) {
+                    row[j + 1] = r;
+                    frow[j + 1] = (uint16_t)(up ? ct : kPoaH);
+                }
+                if (own_last && j == Y - 1 && rw.sink && (!any || r > best)) bx = i + 1, best = r, any = true;
+                carry = poa_max(__builtin_amdgcn_readlane(incl, 63), carry);
+            }
+        }
+        // the next row reads this one: the lanes of a wave read each other's cells (and only those, see above)
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+    }
+    // ---- dag.c:302-313 the best sink row, dag.c:327-343 the route (one thread; the host reverses it)
+    if (own_last) s_bx = bx;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t *__restrict__ rt = route_all + J.route_off;
+        uint32_t n = 0;
+        const uint32_t cap = J.X + J.Y;
+        int x = s_bx, y = Y;
+        while ((x | y) != 0 && n < cap) {
+            const uint32_t f = F[(uint64_t)x * W + (uint64_t)y];
+            int nx = 0, ny = 0;   // (kPoaOrigin)
+            const uint32_t kind = f & 3u;
+            if (kind == kPoaH) nx = x, ny = y - 1;
+            else if (kind == kPoaMat) nx = P[R[x - 1].pred_off + (f >> 2)], ny = y - 1;
+            else if (kind == kPoaDel) nx = P[R[x - 1].pred_off + (f >> 2)], ny = y;
+            rt[n++] = (nx != x ? (uint32_t)x : 0u) | (ny != y ? (uint32_t)y << 16 : 0u);
+            x = nx, y = ny;
+        }
+        JD.route_len = (x | y) != 0 ? 0xffffffffu : n;   // (cannot happen: every step leaves a row or a column)
+    }
+}
+
 }  // namespace
 
 void launch_lq_msa(LqPileDev *piles, LqJobDev *jobs, const LqPieceDev *pieces, const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops,
@@ -853,6 +1038,17 @@ void launch_lq_msa(LqPileDev *piles, LqJobDev *jobs, const LqPieceDev *pieces, c
     hipLaunchKernelGGL(lq_stitch_kernel, dim3((unsigned)n_piles), dim3(64), 0, st, piles, jobs, hdr, lnk, cell_rec, bnd, force_repair);
     if (n_jobs > 0) hipLaunchKernelGGL(lq_walk_kernel, dim3((unsigned)n_jobs), dim3(64), 0, st, piles, jobs, cell_rec, tmp_chars);
     hipLaunchKernelGGL(lq_gather_kernel, dim3((unsigned)n_piles), dim3(64), 0, st, piles, jobs, tmp_chars, out_chars);
+}
+
+
+void launch_poa_align(PoaJobDev *jobs, const uint32_t *ids_wave, int n_wave, const uint32_t *ids_group, int n_group, const char *qpool,
+                      const PoaRowDev *rows, const uint16_t *preds, int32_t *S, uint16_t *F, uint32_t *route, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n_wave > 0)
+        hipLaunchKernelGGL(poa_align_kernel<1>, dim3((unsigned)n_wave), dim3(64), 0, st, jobs, ids_wave, qpool, rows, preds, S, F, route);
+    if (n_group > 0)
+        hipLaunchKernelGGL(poa_align_kernel<kPoaGroupWaves>, dim3((unsigned)n_group), dim3(kPoaGroupWaves * 64), 0, st, jobs, ids_group, qpool,
+                           rows, preds, S, F, route);
 }
 
 }  // namespace ndgpu

@@ -191,6 +191,29 @@ void launch_lq_msa(LqPileDev *piles, LqJobDev *jobs, const LqPieceDev *pieces, c
                    const uint32_t *pool, uint64_t *hdr, uint32_t *lnk, uint32_t *cell_rec, int32_t *bnd, char *tmp_chars, char *out_chars,
                    int n_piles, int n_jobs, uint32_t warm, uint32_t force_repair, void *stream);
 
+// ---- POA: one sequence against the graph (K13, lq_kernels.hip) ----
+struct PoaRowDev {           // row i + 1 of a job = the i-th node of its graph in topological order
+    uint32_t pred_off;       // first predecessor row (uint16 units, relative to the job's pred_off)
+    uint16_t n_pred;         // >= 1: in-edge rows in insertion order, or row 0 alone
+    uint8_t base;            // the node's byte
+    uint8_t sink;            // the node has no out-edge
+};
+struct PoaJobDev {
+    uint32_t X, Y;           // rows of the graph, bases of the query (1..65535, 1..9999)
+    uint64_t q_off;          // first query byte
+    uint64_t row_off;        // first PoaRowDev
+    uint64_t pred_off;       // first predecessor entry
+    uint64_t cell_off;       // first cell of the job's (X + 1)(Y + 1) scores / origins
+    uint64_t route_off;      // first route word (capacity X + Y)
+    uint32_t route_len;      // written by the kernel: steps of the walk back from the best sink
+    uint32_t pad_;
+};
+constexpr int kPoaGroupWaves = 8;   // wavefronts of the workgroup form
+constexpr uint32_t kPoaGroupMinLen = 1024;   // query bases from which the workgroup form takes a job (DESIGN.md section 0a'')
+// ids_wave / ids_group: the jobs each form takes (device, n_wave / n_group indices into jobs)
+void launch_poa_align(PoaJobDev *jobs, const uint32_t *ids_wave, int n_wave, const uint32_t *ids_group, int n_group, const char *qpool,
+                      const PoaRowDev *rows, const uint16_t *preds, int32_t *S, uint16_t *F, uint32_t *route, void *stream);
+
 // ---- scoring DP (K10), segment-parallel: see the head comment of the K10 section in msa_kernels.hip ----
 struct SegItem {            // work item of the segment kernel
     uint32_t pile;

@@ -113,6 +113,8 @@ struct LqRound {
 // other byte.  out must hold (n + 15) / 16 words.
 bool pack_2bit_lsb(uint32_t *out, const char *s, size_t n);
 
+struct PoaReq;   // one POA problem as a backend request (below)
+
 // Executes the device-side work of a batch of piles.  The product has exactly one
 // implementation (HipBackend, device_runtime.hip); tests plug the CPU oracle here to
 // exercise the host logic without a GPU.
@@ -124,6 +126,8 @@ class Backend {
     virtual void run_align(AlnJob **jobs, size_t n) = 0;
     // low-quality-region rounds on the backend; false: not offered (every round goes the host way)
     virtual bool run_lq(LqRound **rounds, size_t n) { (void)rounds; (void)n; return false; }
+    // a batch of POA problems on the backend; false: not offered (the caller computes every one on the host)
+    virtual bool run_poa(PoaReq **reqs, size_t n) { (void)reqs; (void)n; return false; }
     virtual void end_batch() = 0;  // releases whatever run_main kept for run_extract
 };
 
@@ -141,14 +145,53 @@ struct CorrectParams {
 
 std::string poa_consensus(const std::vector<std::string> &seqs);
 
+// The same consensus taken one sequence at a time (poa.cpp), so that a batch of problems can hand the one O(X * Y) step -- the
+// alignment of a sequence against the graph, up to and including its route -- to the device in lockstep rounds
+// (DeviceAligner::run_poa) while graph growth, topological order and heaviest path stay on the host.  poa_consensus() is
+// start() + add_sequence() for every further sequence + consensus().
+struct PoaRows {                      // the graph as an alignment sees it: row i + 1 = the i-th node in topological order
+    std::vector<uint8_t> base, sink;  // the node's byte (compared as a byte: the NUL-tail node matches nothing); it has no out-edge
+    std::vector<uint32_t> pred_off;   // rows() + 1 offsets into preds
+    std::vector<uint16_t> preds;      // predecessor rows in in-edge insertion order (row 0 for a node without in-edges)
+};
+class PoaGraph {
+  public:
+    PoaGraph();
+    ~PoaGraph();
+    PoaGraph(const PoaGraph &) = delete;
+    PoaGraph &operator=(const PoaGraph &) = delete;
+    void start(const char *s, size_t len);                  // the first sequence: a chain
+    size_t rows() const;                                     // X: nodes of the graph
+    void export_rows(PoaRows &out);                          // "export rows"
+    void set_route(const uint32_t *walk, size_t n);          // "align", done elsewhere: the route in walk order (see poa.cpp)
+    bool thread(int seq, const char *s, int len);            // "thread + toposort"; false: the graph outgrew its 16-bit node ids
+    void add_sequence(int seq, const char *s, int len);      // all three on the host
+    std::string consensus(int nseq);                         // heaviest path, cut at the first NUL
+
+  private:
+    struct Impl;
+    Impl *impl_;
+};
+
+// One POA problem as a backend request (Backend::run_poa).  done: `out` holds what poa_consensus(seqs) returns; otherwise the
+// backend declined the problem (outside the device's limits or its memory plan) and the caller computes it on the host.
+struct PoaReq {
+    std::vector<std::string> seqs;
+    std::string out;
+    bool done = false;
+    bool failed = false;   // no path can compute it: more than 64 sequences, or a graph beyond 65,535 nodes
+};
+constexpr int kPoaMaxSeqs = 64;       // labels are one bit per sequence in a 64-bit word
+constexpr int kPoaMaxSeqLen = 9999;   // the reference's struct seq_ (lib/nextcorrect.h:63-68)
+
 class PileImpl;
 
 // Per-seed consensus state machine.  Device work is exposed as requests so that many
 // piles share each launch:
-//     MAIN (MainPile) -> EXTRACT (ExtractPile) -> LQ round 1 (AlnJob) -> LQ round 2 -> DONE
+//     MAIN (MainPile) -> EXTRACT (ExtractPile) [-> POA (PoaReq)] -> LQ round 1 (AlnJob) -> LQ round 2 -> DONE
 class PileEngine {
   public:
-    enum Phase { MAIN = 0, EXTRACT = 1, LQ_ROUND = 2, DONE = 3 };
+    enum Phase { MAIN = 0, EXTRACT = 1, LQ_ROUND = 2, DONE = 3, POA = 4 };  // POA: between EXTRACT and LQ round 1, when the regions' POA problems go out as requests
     // ASCII form (the nextCorrect ABI): seqs[i] NUL-terminated.
     PileEngine(const char *const *seqs, const unsigned *aln_start, const unsigned *aln_end, unsigned seq_count,
                const CorrectParams &prm);
@@ -166,6 +209,7 @@ class PileEngine {
     ExtractPile *extract_request();  // valid in EXTRACT
     void collect_jobs(std::vector<AlnJob *> &out);  // LQ_ROUND (host path)
     LqRound *lq_request();           // LQ_ROUND: the round as one device request (nullptr: nothing to hand over)
+    void collect_poa(std::vector<PoaReq *> &out);   // POA: the regions' problems
     void advance();                  // consume the finished request(s), move on
     ConsensusTrimed *take_result();  // malloc'd, caller frees with free_consensus_trimed
 

@@ -59,6 +59,13 @@ struct RuntimeStats {
     uint64_t tb_tasks = 0;            // alignments whose traceback ran in segments
     uint64_t tb_walkers = 0;          // walkers (segments) of those
     uint64_t tb_fallbacks = 0;        // of the alignments: refused by the stitch, walked again by the one-lane kernel
+    // POA problems as device batches (K13)
+    uint64_t poa_jobs = 0;            // problems offered to run_poa
+    uint64_t poa_declined = 0;        // of which declined (outside the device's limits or the memory plan): the host path took them
+    uint64_t poa_rounds = 0;          // lockstep rounds (sequence r of every problem that has one)
+    uint64_t poa_launches = 0;        // kernel launches
+    uint64_t poa_cells = 0;           // (X + 1)(Y + 1) cells filled
+    double poa_ms = 0;                // HIP-event time of K13
 };
 
 // Thrown when a device (or pinned host) allocation fails for lack of memory.  The C ABI catches it, releases the
@@ -93,6 +100,7 @@ class DeviceAligner {
     void run_main(MainPile **piles, size_t n);
     void run_extract(ExtractPile **piles, size_t n);
     void run_lq(LqRound **rounds, size_t n);
+    void run_poa(PoaReq **reqs, size_t n);   // req.done = false: declined, the caller's host path takes it
     void end_batch();
     // resident read DB: every ndgpu_db handle owns its device copy (upload_db / free_db); a batch names the one its
     // AlnJob::q_dev / t_dev and MainPile::dev_off index into (use_db; nullptr: sequences come with the batch)
@@ -139,6 +147,12 @@ class HipBackend : public Backend {
         static const bool host_lq = getenv("NDGPU_LQ_HOST") != nullptr;  // test hook: the host path of the rounds
         if (host_lq) return false;
         dev_.run_lq(rounds, n);
+        return true;
+    }
+    bool run_poa(PoaReq **reqs, size_t n) override {
+        static const bool host_poa = getenv("NDGPU_POA_HOST") != nullptr;  // test hook: every POA problem on the host
+        if (host_poa) return false;
+        dev_.run_poa(reqs, n);
         return true;
     }
     void end_batch() override { finish(); }

@@ -151,7 +151,18 @@ class Graph {
     }
 
     void toposort();
-    void add_sequence(int seq, const char *s, int len);
+    // One more sequence = three steps (the batched device path, DeviceAligner::run_poa, takes the middle one): the rows an alignment
+    // sees, the alignment of the sequence against them (-> the route), the route threaded through the graph + the new order.
+    void build_rows();
+    void export_rows(PoaRows &out) const;
+    void align(const char *s, int len);
+    void set_route(const uint32_t *walk, size_t n);
+    void thread_route(int seq, const char *s, int len);
+    void add_sequence(int seq, const char *s, int len) {
+        build_rows();
+        align(s, len);
+        thread_route(seq, s, len);
+    }
     std::string heaviest_path(int nseq);
 
   private:
@@ -234,19 +245,11 @@ void Graph::toposort() {
     }
 }
 
-void Graph::add_sequence(int seq, const char *s, int len) {
+// in-edge rows of every node's row, in insertion order (row of node v = rank[v] + 1; a node without in-edges hangs on row 0)
+void Graph::build_rows() {
     const int X = (int)n_nodes;
-    const int Y = len;
-    const size_t W = (size_t)Y + 1;
-    // (not cleared: row 0, column 0 and every interior cell are written before they are read)
-    if (score_.size() < (size_t)(X + 1) * W) score_.resize((size_t)(X + 1) * W), from_.resize((size_t)(X + 1) * W);
-    int32_t *const S = score_.data();
-    uint16_t *const F = from_.data();
-    if (cv_.size() < W) cv_.resize(W), ct_.resize(W);
     std::vector<uint16_t> &rank = rank_;
     rank.resize(X);
-
-    // in-edge rows of every node's row, in insertion order (row of node v = rank[v] + 1; a node without in-edges hangs on row 0)
     pred_off_.resize((size_t)X + 1);
     preds_.clear();
     for (int i = 0; i < X; i++) rank[order[i]] = (uint16_t)i;
@@ -257,6 +260,45 @@ void Graph::add_sequence(int seq, const char *s, int len) {
         if (nd.in_e.empty()) preds_.push_back(0);
     }
     pred_off_[X] = (uint32_t)preds_.size();
+}
+
+// The rows as the device kernel reads them (lq_kernels.hip, poa_align_kernel): per row the node's byte, whether the node has no
+// out-edge, and its predecessor rows.
+void Graph::export_rows(PoaRows &out) const {
+    const size_t X = n_nodes;
+    out.base.resize(X), out.sink.resize(X);
+    for (size_t i = 0; i < X; i++) {
+        const PNode &nd = nodes[order[i]];
+        out.base[i] = nd.base;
+        out.sink[i] = nd.out_e.empty();
+    }
+    out.pred_off.assign(pred_off_.begin(), pred_off_.begin() + X + 1);
+    out.preds.resize(preds_.size());
+    for (size_t k = 0; k < preds_.size(); k++) out.preds[k] = (uint16_t)preds_[k];
+}
+
+// A route as the device kernel returns it: one word per step of the walk back from the best sink, [15:0] the row left (0: the step
+// stayed in its row), [31:16] the column left (0: it stayed in its column).
+void Graph::set_route(const uint32_t *walk, size_t n) {
+    route_.resize(n);
+    for (size_t a = 0; a < n; a++) {
+        const uint32_t w = walk[n - 1 - a], x = w & 0xffffu, y = w >> 16;
+        Route r;
+        if (x) r.node = order[x - 1];
+        if (y) r.qpos = (int32_t)y - 1;
+        route_[a] = r;
+    }
+}
+
+void Graph::align(const char *s, int len) {
+    const int X = (int)n_nodes;
+    const int Y = len;
+    const size_t W = (size_t)Y + 1;
+    // (not cleared: row 0, column 0 and every interior cell are written before they are read)
+    if (score_.size() < (size_t)(X + 1) * W) score_.resize((size_t)(X + 1) * W), from_.resize((size_t)(X + 1) * W);
+    int32_t *const S = score_.data();
+    uint16_t *const F = from_.data();
+    if (cv_.size() < W) cv_.resize(W), ct_.resize(W);
 
     // dag.c:88-134 boundary scores; the boundary cells point at the origin
     for (int c = 0; c <= Y; c++) S[c] = c * kGap, F[c] = FROM_ORIGIN;
@@ -311,7 +353,6 @@ void Graph::add_sequence(int seq, const char *s, int len) {
     // dag.c:327-343 route (collected backwards, then reversed)
     std::vector<Route> &route = route_;
     route.clear();
-    long start_q = -1, end_q = -1;
     {
         int x = bx, y = Y;
         while (x != 0 || y != 0) {
@@ -325,19 +366,25 @@ void Graph::add_sequence(int seq, const char *s, int len) {
             }
             Route r;
             if (nx != x) r.node = order[x - 1];
-            if (ny != y) {
-                r.qpos = y - 1;
-                start_q = y - 1;
-                if (end_q == -1) end_q = r.qpos;
-            }
+            if (ny != y) r.qpos = y - 1;
             route.push_back(r);
             x = nx;
             y = ny;
         }
         for (size_t a = 0, b = route.size(); a + 1 < b; a++, b--) std::swap(route[a], route[b - 1]);
     }
+}
 
-    // dag.c:345-401 thread the sequence through the graph
+// dag.c:345-401 thread the sequence through the graph
+void Graph::thread_route(int seq, const char *s, int len) {
+    const int Y = len;
+    const std::vector<Route> &route = route_;
+    long start_q = -1, end_q = -1;  // first / last query offset the route consumes
+    for (const Route &r : route)
+        if (r.qpos != -1) {
+            if (start_q == -1) start_q = r.qpos;
+            end_q = r.qpos;
+        }
     int first = -1, head = -1, tail_first = -1, tail_last = -1;
     if (start_q > 0) add_chain(seq, s, (size_t)start_q, first, head);
     if (end_q < Y - 1) add_chain(seq, s + end_q + 1, (size_t)(Y - end_q), tail_first, tail_last);  // includes s[Y] == NUL
@@ -421,27 +468,49 @@ std::string Graph::heaviest_path(int nseq) {
 
 }  // namespace
 
+struct PoaGraph::Impl {
+    Graph g;
+};
+PoaGraph::PoaGraph() : impl_(new Impl) {}
+PoaGraph::~PoaGraph() { delete impl_; }
+void PoaGraph::start(const char *s, size_t len) {
+    Graph &g = impl_->g;
+    g.clear();
+    int first = -1, head = -1;
+    g.add_chain(0, s, len, first, head);
+    g.order.resize(g.n_nodes);
+    for (size_t x = 0; x < g.n_nodes; x++) g.order[x] = (uint16_t)x;
+}
+size_t PoaGraph::rows() const { return impl_->g.n_nodes; }
+void PoaGraph::export_rows(PoaRows &out) {
+    impl_->g.build_rows();
+    impl_->g.export_rows(out);
+}
+void PoaGraph::set_route(const uint32_t *walk, size_t n) { impl_->g.set_route(walk, n); }
+void PoaGraph::add_sequence(int seq, const char *s, int len) { impl_->g.add_sequence(seq, s, len); }
+bool PoaGraph::thread(int seq, const char *s, int len) {
+    impl_->g.thread_route(seq, s, len);
+    return impl_->g.n_nodes <= 65535;
+}
+std::string PoaGraph::consensus(int nseq) {
+    std::string raw = impl_->g.heaviest_path(nseq);
+    size_t z = raw.find('\0');
+    if (z != std::string::npos) raw.resize(z);
+    return raw;
+}
+
 // Returns the raw path (may contain an embedded NUL, see header comment); the
 // caller truncates at the first NUL exactly as strlen() does in
 // lib/nextcorrect.c:462.
 std::string poa_consensus(const std::vector<std::string> &seqs) {
-    static thread_local Graph g;   // (its buffers are the workspace of this thread's calls)
-    g.clear();
+    static thread_local PoaGraph g;   // (its buffers are the workspace of this thread's calls)
     for (size_t i = 0; i < seqs.size(); i++) {
         const std::string &s = seqs[i];
-        if (i == 0) {
-            int first = -1, head = -1;
-            g.add_chain(0, s.c_str(), s.size(), first, head);
-            g.order.resize(g.n_nodes);
-            for (size_t x = 0; x < g.n_nodes; x++) g.order[x] = (uint16_t)x;
-        } else {
-            g.add_sequence((int)i, s.c_str(), (int)s.size());
-        }
+        if (i == 0) g.start(s.c_str(), s.size());
+        else g.add_sequence((int)i, s.c_str(), (int)s.size());
     }
-    std::string raw = g.heaviest_path((int)seqs.size());
-    size_t z = raw.find('\0');
-    if (z != std::string::npos) raw.resize(z);
-    return raw;
+    if (seqs.empty()) g.start("", 0);
+    return g.consensus((int)seqs.size());
 }
 
 }  // namespace ndgpu
