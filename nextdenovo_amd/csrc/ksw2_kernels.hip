@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "../../include/ndgpu_overlap.h"
-#include "ovl_pool.h"
+#include "ovl_host.h"
 
 namespace {
 
@@ -339,22 +339,6 @@ bool hip_ok(hipError_t e, const char *what) {
     return false;
 }
 
-template <class T> struct Dev {  // a block of the overlap library's pool (csrc/ovl_pool.h): no driver call per batch in steady state
-    T *p = nullptr;
-    bool alloc(size_t n) {
-        try {
-            p = (T *)ndovl::pool_alloc(sizeof(T) * (n ? n : 1));
-        } catch (const std::exception &) {
-            p = nullptr;
-            return false;
-        }
-        return true;
-    }
-    ~Dev() {
-        if (p) ndovl::pool_free(p);
-    }
-};
-
 }  // namespace
 
 static int run_batch(const ndgpu_ksw_job *jobs, int n, ndgpu_ksw_result *res);
@@ -394,102 +378,91 @@ extern "C" int ndgpu_ksw_extd2_batch(const ndgpu_ksw_job *jobs, int n, ndgpu_ksw
 
 static int run_batch(const ndgpu_ksw_job *jobs, int n, ndgpu_ksw_result *res) {
     if (n <= 0) return 0;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        fprintf(stderr, "[ndgpu_overlap] FATAL: no HIP device visible: ksw_extd2 has no CPU fallback\n");
+    try {   // (a block the pool cannot give throws, like everywhere in the library: every failure of the device is -1 to the caller)
+        if (ndovl::select_device(true) < 0) return -1;
+        std::vector<KswJobDev> h((size_t)n);
+        std::vector<uint8_t> pool;
+        uint64_t diff_total = 0, h_total = 0, p_total = 0, off_total = 0, cigar_total = 0;
+        std::vector<int32_t> tier[3];  // by target length: small LDS tables, large LDS tables, difference arrays in HBM
+        for (int i = 0; i < n; i++) {
+            const ndgpu_ksw_job &J = jobs[i];
+            if (J.qlen < 0 || J.tlen < 0 || J.m < 0 || J.m > 5 || (J.qlen > 0 && !J.query) || (J.tlen > 0 && !J.target) || (J.m > 0 && !J.mat)) return -2;
+            KswJobDev &D = h[(size_t)i];
+            memset(&D, 0, sizeof(D));
+            D.qlen = J.qlen, D.tlen = J.tlen, D.w = J.w, D.zdrop = J.zdrop, D.end_bonus = J.end_bonus, D.flag = J.flag;
+            D.m = J.m, D.q = J.gapo, D.e = J.gape, D.q2 = J.gapo2, D.e2 = J.gape2;
+            for (int k = 0; k < J.m * J.m; k++) D.mat[k] = J.mat[k];
+            D.q_off = pool.size();
+            pool.insert(pool.end(), J.query, J.query + J.qlen);
+            D.t_off = pool.size();
+            pool.insert(pool.end(), J.target, J.target + J.tlen);
+            for (int k = 0; k < J.qlen && J.m > 0; k++)
+                if (J.query[k] >= (uint8_t)J.m) return -2;
+            for (int k = 0; k < J.tlen && J.m > 0; k++)
+                if (J.target[k] >= (uint8_t)J.m) return -2;
+            const uint64_t tl16 = ((uint64_t)J.tlen + 15) / 16 * 16, diags = (uint64_t)(J.qlen + J.tlen > 0 ? J.qlen + J.tlen - 1 : 0);
+            int w = J.w < 0 ? (J.tlen > J.qlen ? J.tlen : J.qlen) : J.w;
+            uint64_t n_col = (uint64_t)(J.qlen < J.tlen ? J.qlen : J.tlen);
+            n_col = (((n_col < (uint64_t)w + 1 ? n_col : (uint64_t)w + 1) + 15) / 16 + 1) * 16;
+            D.diff_off = diff_total, D.h_off = h_total;
+            if (tl16 > (uint64_t)kLdsTarget) diff_total += 7 * tl16, h_total += tl16;
+            tier[tl16 <= (uint64_t)kLdsSmall ? 0 : tl16 <= (uint64_t)kLdsTarget ? 1 : 2].push_back(i);
+            D.p_off = p_total, D.off_off = off_total, D.cigar_off = cigar_total;
+            if (!(J.flag & F_SCORE_ONLY)) p_total += diags * n_col + 16, off_total += 2 * diags;
+            cigar_total += (uint64_t)J.qlen + (uint64_t)J.tlen + 2;
+        }
+        pool.push_back(0);
+        std::vector<int32_t> ids;
+        for (auto &t : tier) {  // the longest problems of a tier first: a launch lasts as long as its last wavefront
+            std::stable_sort(t.begin(), t.end(), [&](int32_t a_, int32_t b_) { return jobs[a_].qlen + jobs[a_].tlen > jobs[b_].qlen + jobs[b_].tlen; });
+            ids.insert(ids.end(), t.begin(), t.end());
+        }
+        // (an array nothing goes into still gets a block: the kernel is handed no null pointer)
+        ndovl::DevBuf<KswJobDev> d_jobs((size_t)n);
+        ndovl::DevBuf<uint8_t> d_pool(pool.size()), d_p(std::max<uint64_t>(p_total, 1));
+        ndovl::DevBuf<int8_t> d_diff(std::max<uint64_t>(diff_total, 1));
+        ndovl::DevBuf<int32_t> d_h(std::max<uint64_t>(h_total, 1)), d_off(std::max<uint64_t>(off_total, 1));
+        ndovl::DevBuf<uint32_t> d_cigar(cigar_total);
+        ndovl::DevBuf<Ez> d_res((size_t)n);
+        ndovl::DevBuf<int32_t> d_ids((size_t)n);
+        hipStream_t st = nullptr;
+        if (!hip_ok(hipStreamCreate(&st), "hipStreamCreate")) return -1;
+        const ndovl::StreamGuard guard{st};   // (declared after the blocks: whatever still runs on `st` ends before they go back to the pool)
+        std::vector<Ez> h_res((size_t)n);
+        std::vector<uint32_t> h_cigar((size_t)cigar_total + 1);
+        if (!(hip_ok(hipMemcpyAsync(d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, st), "upload") &&
+              hip_ok(hipMemcpyAsync(d_jobs.p, h.data(), sizeof(KswJobDev) * (size_t)n, hipMemcpyHostToDevice, st), "upload") &&
+              hip_ok(hipMemcpyAsync(d_ids.p, ids.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st), "upload")))
+            return -1;
+        const int caps[3] = {kLdsSmall, kLdsTarget, 0};
+        size_t first = 0;
+        for (int k = 0; k < 3; k++) {
+            if (!tier[k].empty())
+                hipLaunchKernelGGL(ksw_extd2_kernel, dim3((unsigned)tier[k].size()), dim3(64), (size_t)caps[k] * 11, st, d_jobs.p, d_pool.p,
+                                   d_diff.p, d_h.p, d_p.p, d_off.p, d_cigar.p, d_res.p, d_ids.p + first, caps[k]);
+            first += tier[k].size();
+        }
+        if (!(hip_ok(hipGetLastError(), "launch") &&
+              hip_ok(hipMemcpyAsync(h_res.data(), d_res.p, sizeof(Ez) * (size_t)n, hipMemcpyDeviceToHost, st), "download") &&
+              hip_ok(hipMemcpyAsync(h_cigar.data(), d_cigar.p, sizeof(uint32_t) * (size_t)cigar_total, hipMemcpyDeviceToHost, st), "download") &&
+              hip_ok(hipStreamSynchronize(st), "sync")))
+            return -1;
+        for (int i = 0; i < n; i++) {
+            const Ez &z = h_res[(size_t)i];
+            ndgpu_ksw_result &R = res[i];
+            R.max = z.max, R.zdropped = z.zdropped, R.max_q = z.max_q, R.max_t = z.max_t, R.mqe = z.mqe, R.mqe_t = z.mqe_t, R.mte = z.mte;
+            R.mte_q = z.mte_q, R.score = z.score, R.n_cigar = z.n_cigar, R.reach_end = z.reach_end;
+            R.cigar = nullptr;
+            if (z.n_cigar > 0) {
+                R.cigar = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)z.n_cigar);
+                if (!R.cigar) return -1;
+                memcpy(R.cigar, h_cigar.data() + h[(size_t)i].cigar_off, sizeof(uint32_t) * (size_t)z.n_cigar);
+            }
+        }
+        return 0;
+    } catch (const std::exception &) {
         return -1;
     }
-    int dev = 0;
-    if (const char *e = getenv("NDGPU_DEVICE")) dev = atoi(e) % n_dev;
-    if (!hip_ok(hipSetDevice(dev), "hipSetDevice")) return -1;
-    std::vector<KswJobDev> h((size_t)n);
-    std::vector<uint8_t> pool;
-    uint64_t diff_total = 0, h_total = 0, p_total = 0, off_total = 0, cigar_total = 0;
-    std::vector<int32_t> tier[3];  // by target length: small LDS tables, large LDS tables, difference arrays in HBM
-    for (int i = 0; i < n; i++) {
-        const ndgpu_ksw_job &J = jobs[i];
-        if (J.qlen < 0 || J.tlen < 0 || J.m < 0 || J.m > 5 || (J.qlen > 0 && !J.query) || (J.tlen > 0 && !J.target) || (J.m > 0 && !J.mat)) return -2;
-        KswJobDev &D = h[(size_t)i];
-        memset(&D, 0, sizeof(D));
-        D.qlen = J.qlen, D.tlen = J.tlen, D.w = J.w, D.zdrop = J.zdrop, D.end_bonus = J.end_bonus, D.flag = J.flag;
-        D.m = J.m, D.q = J.gapo, D.e = J.gape, D.q2 = J.gapo2, D.e2 = J.gape2;
-        for (int k = 0; k < J.m * J.m; k++) D.mat[k] = J.mat[k];
-        D.q_off = pool.size();
-        pool.insert(pool.end(), J.query, J.query + J.qlen);
-        D.t_off = pool.size();
-        pool.insert(pool.end(), J.target, J.target + J.tlen);
-        for (int k = 0; k < J.qlen && J.m > 0; k++)
-            if (J.query[k] >= (uint8_t)J.m) return -2;
-        for (int k = 0; k < J.tlen && J.m > 0; k++)
-            if (J.target[k] >= (uint8_t)J.m) return -2;
-        const uint64_t tl16 = ((uint64_t)J.tlen + 15) / 16 * 16, diags = (uint64_t)(J.qlen + J.tlen > 0 ? J.qlen + J.tlen - 1 : 0);
-        int w = J.w < 0 ? (J.tlen > J.qlen ? J.tlen : J.qlen) : J.w;
-        uint64_t n_col = (uint64_t)(J.qlen < J.tlen ? J.qlen : J.tlen);
-        n_col = (((n_col < (uint64_t)w + 1 ? n_col : (uint64_t)w + 1) + 15) / 16 + 1) * 16;
-        D.diff_off = diff_total, D.h_off = h_total;
-        if (tl16 > (uint64_t)kLdsTarget) diff_total += 7 * tl16, h_total += tl16;
-        tier[tl16 <= (uint64_t)kLdsSmall ? 0 : tl16 <= (uint64_t)kLdsTarget ? 1 : 2].push_back(i);
-        D.p_off = p_total, D.off_off = off_total, D.cigar_off = cigar_total;
-        if (!(J.flag & F_SCORE_ONLY)) p_total += diags * n_col + 16, off_total += 2 * diags;
-        cigar_total += (uint64_t)J.qlen + (uint64_t)J.tlen + 2;
-    }
-    pool.push_back(0);
-    Dev<KswJobDev> d_jobs;
-    Dev<uint8_t> d_pool, d_p;
-    Dev<int8_t> d_diff;
-    Dev<int32_t> d_h, d_off;
-    Dev<uint32_t> d_cigar;
-    Dev<Ez> d_res;
-    Dev<int32_t> d_ids;
-    std::vector<int32_t> ids;
-    for (auto &t : tier) {  // the longest problems of a tier first: a launch lasts as long as its last wavefront
-        std::stable_sort(t.begin(), t.end(), [&](int32_t a_, int32_t b_) { return jobs[a_].qlen + jobs[a_].tlen > jobs[b_].qlen + jobs[b_].tlen; });
-        ids.insert(ids.end(), t.begin(), t.end());
-    }
-    hipStream_t st = nullptr;
-    bool ok = hip_ok(hipStreamCreate(&st), "hipStreamCreate") && d_jobs.alloc((size_t)n) && d_pool.alloc(pool.size()) && d_p.alloc(p_total) &&
-              d_diff.alloc(diff_total) && d_h.alloc(h_total) && d_off.alloc(off_total) && d_cigar.alloc(cigar_total) && d_res.alloc((size_t)n) && d_ids.alloc((size_t)n);
-    std::vector<Ez> h_res((size_t)n);
-    std::vector<uint32_t> h_cigar((size_t)cigar_total + 1);
-    if (ok) {
-        ok = hip_ok(hipMemcpyAsync(d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, st), "upload") &&
-             hip_ok(hipMemcpyAsync(d_jobs.p, h.data(), sizeof(KswJobDev) * (size_t)n, hipMemcpyHostToDevice, st), "upload") &&
-             hip_ok(hipMemcpyAsync(d_ids.p, ids.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st), "upload");
-        if (ok) {
-            const int caps[3] = {kLdsSmall, kLdsTarget, 0};
-            size_t first = 0;
-            for (int k = 0; k < 3; k++) {
-                if (!tier[k].empty())
-                    hipLaunchKernelGGL(ksw_extd2_kernel, dim3((unsigned)tier[k].size()), dim3(64), (size_t)caps[k] * 11, st, d_jobs.p, d_pool.p,
-                                       d_diff.p, d_h.p, d_p.p, d_off.p, d_cigar.p, d_res.p, d_ids.p + first, caps[k]);
-                first += tier[k].size();
-            }
-            ok = hip_ok(hipGetLastError(), "launch") &&
-                 hip_ok(hipMemcpyAsync(h_res.data(), d_res.p, sizeof(Ez) * (size_t)n, hipMemcpyDeviceToHost, st), "download") &&
-                 hip_ok(hipMemcpyAsync(h_cigar.data(), d_cigar.p, sizeof(uint32_t) * (size_t)cigar_total, hipMemcpyDeviceToHost, st), "download") &&
-                 hip_ok(hipStreamSynchronize(st), "sync");
-        }
-    }
-    if (st) {
-        // (a failure after the launches: the kernels may still be running on `st`, and the blocks below go back to a pool that hands
-        // them to the next caller at once -- hipStreamDestroy does not wait)
-        if (!ok) (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
-    if (!ok) return -1;
-    for (int i = 0; i < n; i++) {
-        const Ez &z = h_res[(size_t)i];
-        ndgpu_ksw_result &R = res[i];
-        R.max = z.max, R.zdropped = z.zdropped, R.max_q = z.max_q, R.max_t = z.max_t, R.mqe = z.mqe, R.mqe_t = z.mqe_t, R.mte = z.mte;
-        R.mte_q = z.mte_q, R.score = z.score, R.n_cigar = z.n_cigar, R.reach_end = z.reach_end;
-        R.cigar = nullptr;
-        if (z.n_cigar > 0) {
-            R.cigar = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)z.n_cigar);
-            if (!R.cigar) return -1;
-            memcpy(R.cigar, h_cigar.data() + h[(size_t)i].cigar_off, sizeof(uint32_t) * (size_t)z.n_cigar);
-        }
-    }
-    return 0;
 }
 
 // minimap2/ksw2.h:60-61.  ez->cigar is the caller's grow-by-doubling buffer (ksw_push_cigar, ksw2.h:96-110): with km == NULL it
@@ -632,61 +605,49 @@ __global__ __launch_bounds__(64) void ksw_ll_kernel(const LlJobDev *__restrict__
 // a batch of ksw_ll_i16 problems (see above; include/ndgpu_overlap.h); used by csrc/ovl_cigar.cpp
 extern "C" int ndgpu_ksw_ll_batch(const ndgpu_ll_job *jobs, int n, ndgpu_ll_result *out) {
     if (n <= 0) return 0;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        fprintf(stderr, "[ndgpu_overlap] FATAL: no HIP device visible: ksw_ll has no CPU fallback\n");
+    try {   // (as in run_batch)
+        if (ndovl::select_device(true) < 0) return -1;
+        std::vector<LlJobDev> h((size_t)n);
+        std::vector<uint8_t> pool;
+        uint64_t h_total = 0;
+        for (int i = 0; i < n; i++) {
+            const ndgpu_ll_job &J = jobs[i];
+            if (J.qlen < 0 || J.tlen < 0 || (J.qlen > 0 && !J.query) || (J.tlen > 0 && !J.target) || !J.mat) return -2;
+            LlJobDev &D = h[(size_t)i];
+            memset(&D, 0, sizeof(D));
+            D.qlen = J.qlen, D.tlen = J.tlen, D.gapo = J.gapo, D.gape = J.gape;
+            for (int k = 0; k < 25; k++) D.mat[k] = J.mat[k];
+            for (int k = 0; k < J.qlen; k++)
+                if (J.query[k] > 4) return -2;
+            for (int k = 0; k < J.tlen; k++)
+                if (J.target[k] > 4) return -2;
+            D.q_off = pool.size();
+            pool.insert(pool.end(), J.query, J.query + J.qlen);
+            D.t_off = pool.size();
+            pool.insert(pool.end(), J.target, J.target + J.tlen);
+            D.h_off = h_total;
+            h_total += 4ull * 8ull * (uint64_t)((J.qlen + 7) / 8);
+        }
+        pool.push_back(0);
+        ndovl::DevBuf<LlJobDev> d_jobs((size_t)n);
+        ndovl::DevBuf<uint8_t> d_pool(pool.size());
+        ndovl::DevBuf<int16_t> d_h(h_total + 1);
+        ndovl::DevBuf<LlRes> d_res((size_t)n);
+        hipStream_t st = nullptr;
+        if (!hip_ok(hipStreamCreate(&st), "hipStreamCreate")) return -1;
+        const ndovl::StreamGuard guard{st};
+        std::vector<LlRes> r((size_t)n);
+        if (!(hip_ok(hipMemcpyAsync(d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, st), "upload") &&
+              hip_ok(hipMemcpyAsync(d_jobs.p, h.data(), sizeof(LlJobDev) * (size_t)n, hipMemcpyHostToDevice, st), "upload")))
+            return -1;
+        hipLaunchKernelGGL(ksw_ll_kernel, dim3((unsigned)n), dim3(64), 0, st, d_jobs.p, d_pool.p, d_h.p, d_res.p);
+        if (!(hip_ok(hipGetLastError(), "launch") &&
+              hip_ok(hipMemcpyAsync(r.data(), d_res.p, sizeof(LlRes) * (size_t)n, hipMemcpyDeviceToHost, st), "download") &&
+              hip_ok(hipStreamSynchronize(st), "sync")))
+            return -1;
+        for (int i = 0; i < n; i++) out[i].score = r[(size_t)i].score, out[i].qe = r[(size_t)i].qe, out[i].te = r[(size_t)i].te;
+        return 0;
+    } catch (const std::exception &) {
         return -1;
     }
-    int dev = 0;
-    if (const char *e = getenv("NDGPU_DEVICE")) dev = atoi(e) % n_dev;
-    if (!hip_ok(hipSetDevice(dev), "hipSetDevice")) return -1;
-    std::vector<LlJobDev> h((size_t)n);
-    std::vector<uint8_t> pool;
-    uint64_t h_total = 0;
-    for (int i = 0; i < n; i++) {
-        const ndgpu_ll_job &J = jobs[i];
-        if (J.qlen < 0 || J.tlen < 0 || (J.qlen > 0 && !J.query) || (J.tlen > 0 && !J.target) || !J.mat) return -2;
-        LlJobDev &D = h[(size_t)i];
-        memset(&D, 0, sizeof(D));
-        D.qlen = J.qlen, D.tlen = J.tlen, D.gapo = J.gapo, D.gape = J.gape;
-        for (int k = 0; k < 25; k++) D.mat[k] = J.mat[k];
-        for (int k = 0; k < J.qlen; k++)
-            if (J.query[k] > 4) return -2;
-        for (int k = 0; k < J.tlen; k++)
-            if (J.target[k] > 4) return -2;
-        D.q_off = pool.size();
-        pool.insert(pool.end(), J.query, J.query + J.qlen);
-        D.t_off = pool.size();
-        pool.insert(pool.end(), J.target, J.target + J.tlen);
-        D.h_off = h_total;
-        h_total += 4ull * 8ull * (uint64_t)((J.qlen + 7) / 8);
-    }
-    pool.push_back(0);
-    Dev<LlJobDev> d_jobs;
-    Dev<uint8_t> d_pool;
-    Dev<int16_t> d_h;
-    Dev<LlRes> d_res;
-    hipStream_t st = nullptr;
-    bool ok = hip_ok(hipStreamCreate(&st), "hipStreamCreate") && d_jobs.alloc((size_t)n) && d_pool.alloc(pool.size()) && d_h.alloc(h_total + 1) &&
-              d_res.alloc((size_t)n);
-    std::vector<LlRes> r((size_t)n);
-    if (ok) {
-        ok = hip_ok(hipMemcpyAsync(d_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, st), "upload") &&
-             hip_ok(hipMemcpyAsync(d_jobs.p, h.data(), sizeof(LlJobDev) * (size_t)n, hipMemcpyHostToDevice, st), "upload");
-        if (ok) {
-            hipLaunchKernelGGL(ksw_ll_kernel, dim3((unsigned)n), dim3(64), 0, st, d_jobs.p, d_pool.p, d_h.p, d_res.p);
-            ok = hip_ok(hipGetLastError(), "launch") &&
-                 hip_ok(hipMemcpyAsync(r.data(), d_res.p, sizeof(LlRes) * (size_t)n, hipMemcpyDeviceToHost, st), "download") &&
-                 hip_ok(hipStreamSynchronize(st), "sync");
-        }
-    }
-    if (st) {
-        // (a failure after the launches: the kernels may still be running on `st`, and the blocks below go back to a pool that hands
-        // them to the next caller at once -- hipStreamDestroy does not wait)
-        if (!ok) (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
-    if (!ok) return -1;
-    for (int i = 0; i < n; i++) out[i].score = r[(size_t)i].score, out[i].qe = r[(size_t)i].qe, out[i].te = r[(size_t)i].te;
-    return 0;
 }

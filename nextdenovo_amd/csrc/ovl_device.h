@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nd_lockstep.h"
+#include "ovl_pool.h"
 
 namespace ndovl {
 
@@ -23,15 +24,7 @@ inline hipError_t create_stage_stream(hipStream_t *s)
 }
 
 
-// Every device operation of the overlap library reports its failure by throwing (defined in ovl_engine.hip): a rocPRIM primitive
-// that returns an error, a kernel launch the runtime refuses.  Until round 4 the primitives' return values were dropped -- and a
-// primitive that fails also clears the runtime's sticky error, so the stage-end hipGetLastError() saw nothing: on a device short
-// of memory a sort or a scan that never ran left its output buffer as it was and the call returned fewer records, silently.
-// Out of memory is noted for ndgpu_ovl_last_error() (1), so that the caller can release memory and try again.
-void device_check(int hip_error, const char *what);
-// Test hook: NDGPU_OVL_FAIL_AT=k makes the k-th checked device operation of the process (block-pool allocation, rocPRIM primitive,
-// kernel launch) fail as if the device were out of memory; read at every operation, so a test can move it between calls.
-bool fault_injected();
+// a kernel launch as a checked device operation (ovl_pool.h)
 #define ND_LAUNCH(...)                                                                     \
 	do {                                                                                   \
 		if (ndovl::fault_injected()) ndovl::device_check((int)hipErrorOutOfMemory, __func__); \
@@ -137,12 +130,12 @@ void launch_shift_keys(const uint64_t *x, uint64_t *key, uint64_t n, hipStream_t
 void launch_build_buckets(const uint64_t *ukey, uint64_t n_keys, uint32_t shift, uint32_t *bucket, hipStream_t s);
 void launch_build_hash(const uint64_t *ukey, const uint64_t *ustart, uint64_t n_keys, HashSlot *tab, uint64_t size, hipStream_t s);  // tab zeroed by the caller
 
-int sort_pairs_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin, uint64_t *vout,
+void sort_pairs_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin, uint64_t *vout,
                    size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t s);
-int sort_keys_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, hipStream_t s);
-int rle_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, size_t n, uint64_t *uniq, uint32_t *cnt, uint64_t *n_runs,
+void sort_keys_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, hipStream_t s);
+void rle_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, size_t n, uint64_t *uniq, uint32_t *cnt, uint64_t *n_runs,
             hipStream_t s);
-int exscan_u32_to_u64(void *tmp, size_t &tmp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s);
+void exscan_u32_to_u64(void *tmp, size_t &tmp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s);
 
 void launch_seed_count(const uint64_t *mx, const uint64_t *my, const uint32_t *m_read, uint64_t n_m, const IndexDev &ix,
                        const QueryDev &q, const OvlParams &P, int mid_occ, uint32_t *m_start, uint32_t *m_cnt, uint32_t *m_surv,
@@ -155,7 +148,7 @@ void launch_gather_read_off(const uint64_t *a_off, const uint64_t *m_off, uint32
 void launch_local_off(const uint64_t *r_aoff_all, uint32_t r0, uint32_t n, uint64_t *r_aoff, hipStream_t s);
 void launch_anchor_decode(const uint64_t *skey, uint64_t n, const KeyLayout &L, uint64_t *ax, uint32_t *tie_flag, uint64_t *segval,
                           hipStream_t s);
-int incl_max_scan_u64(void *tmp, size_t &tmp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t s);
+void incl_max_scan_u64(void *tmp, size_t &tmp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t s);
 void launch_slab_flag(const uint64_t *skey, const uint64_t *segstart1, uint64_t n, const KeyLayout &L, const uint64_t *r_aoff,
                       uint32_t *flag, hipStream_t s);
 void launch_slab_write(const uint64_t *skey, const uint32_t *flag, const uint64_t *rank, uint64_t n, const KeyLayout &L,

@@ -22,7 +22,7 @@
 
 #include "../../include/ndgpu_overlap.h"
 #include "ovl_device.h"
-#include "ovl_pool.h"
+#include "ovl_host.h"
 
 #include <map>
 #include <chrono>
@@ -223,27 +223,6 @@ size_t pool_cached_bytes() { std::lock_guard<std::mutex> g(g_pool_mu); return g_
 void pool_bytes(uint64_t out[3]) { std::lock_guard<std::mutex> g(g_pool_mu); out[0] = g_pool_live, out[1] = g_pool_slab_bytes - g_pool_live, out[2] = g_pool_peak; }
 void pool_calls(uint64_t out[2], int reset) { out[0] = g_pool_calls.load(), out[1] = g_pool_ns.load(); if (reset) g_pool_calls = 0, g_pool_ns = 0; }
 
-// (a device filled to the brim makes the runtime's own allocations fail too -- launch arguments, staging: "out of memory" may
-// surface at any call; it is reported as what it is, so that the caller can release memory and try again)
-#define HIP_OK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "[ndgpu_overlap] HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); if (_e == hipErrorOutOfMemory) { ndovl::note_oom(); (void)hipGetLastError(); } throw std::runtime_error("hip"); } } while (0)
-
-template <class T> struct DevBuf {
-	T *p = nullptr;
-	size_t n = 0;
-	DevBuf() = default;
-	explicit DevBuf(size_t count) { alloc(count); }
-	DevBuf(const DevBuf&) = delete;
-	DevBuf &operator=(const DevBuf&) = delete;
-	DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
-	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p, n = o.n; o.p = nullptr, o.n = 0; } return *this; }
-	~DevBuf() { release(); }
-	void alloc(size_t count) { release(); n = count; if (count) p = (T*)pool_alloc(count * sizeof(T)); }
-	void release() { if (p) pool_free(p); p = nullptr, n = 0; }
-	void upload(const T *src, size_t count, hipStream_t s) { if (count) HIP_OK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s)); }
-	void download(T *dst, size_t count, hipStream_t s, size_t from = 0) const { if (count) HIP_OK(hipMemcpyAsync(dst, p + from, count * sizeof(T), hipMemcpyDeviceToHost, s)); }
-	void zero(hipStream_t s) { if (n) HIP_OK(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
-};
-
 // strcmp() order of "%u" names as an integer key: digits left-aligned to 10 places, length as tie-break
 static uint64_t name_key(uint32_t id)
 {
@@ -278,15 +257,6 @@ static unsigned bits_for(uint64_t max_value) // bits needed to hold values 0..ma
 	while (b < 64 && (max_value >> b)) ++b;
 	return b;
 }
-
-struct EvTimer {
-	hipEvent_t a, b;
-	hipStream_t s;
-	EvTimer(hipStream_t st) : s(st) { HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); }
-	~EvTimer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-	void start() { HIP_OK(hipEventRecord(a, s)); }
-	double stop() { HIP_OK(hipEventRecord(b, s)); HIP_OK(hipEventSynchronize(b)); float ms = 0; HIP_OK(hipEventElapsedTime(&ms, a, b)); return ms; }
-};
 
 // Resident read words (ndgpu_ovl_words_resident): a host buffer of 2-bit words the caller has declared resident is uploaded once;
 // every read set that names words inside it afterwards works on the device copy.  The stage maps the same reads step after step and job
@@ -351,10 +321,366 @@ struct Regs {
 	bool thin = false;              // chain with mm_chain_dp_nextdenovo (anchor thinning beyond 100,000 anchors)
 };
 
+static OvlParams to_params(const ndgpu_ovl_opt &o)
+{
+	OvlParams P{};
+	P.k = o.k, P.w = o.w, P.hpc = o.hpc, P.no_diag = o.no_diag, P.no_dual = o.no_dual, P.min_cnt = o.min_cnt, P.min_sc = o.min_chain_score;
+	P.bw = o.bw, P.max_gap = o.max_gap, P.max_skip = o.max_chain_skip, P.max_iter = o.max_chain_iter, P.minlen = o.minlen, P.dvt = o.dvt;
+	P.maxhan1 = o.maxhan1, P.maxhan2 = o.maxhan2;
+	P.mode3 = o.mode == 3, P.ide_ml = 6000 /* mm_mapopt_t::ide_ml, options.c:60: no command-line switch */, P.d_factor = o.d_factor;
+	P.step2 = o.step == 2, P.minmatch = o.minmatch, P.minide = o.minide;
+	return P;
+}
+
+static const char *check_opt(const ndgpu_ovl_opt &o)
+{
+	if (o.k < 1 || o.k > 127 || (o.k > 28 && !(o.k & 31)))
+		return "k must be in 1..127 and not 32, 64 or 96 (the reference's long k-mer mask is undefined there: sketch.c:286-287)";
+	if (o.w < 1 || o.w > 64) return "w must be in 1..64";
+	if (o.max_chain_iter < 1 || o.max_chain_iter >= 8192) return "max_chain_iter must be in 1..8191";
+	if (o.max_gap < 0 || o.bw < 0) return "negative max_gap / bw";
+	if (o.step == 2 && (o.mode < 0 || o.mode > 2)) return "--step 2 is built for --mode 0 (no re-alignment), 1 and 2 (the default)";
+	return nullptr;
+}
+
+// exclusive prefix sums of n counts, as 64-bit offsets
+static void exscan(Scratch &tmp, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
+{
+	tmp.run([&](void *t, size_t &tb) { exscan_u32_to_u64(t, tb, in, out, n, s); });
+}
+
+// -f FLOAT,INT (Engine::map): what the re-chaining passes hand to, and ask of, one pass over the query set
+struct Rechain {
+	const int32_t *read_mid = nullptr;        // one occurrence threshold per query read (nullptr: the call's one)
+	std::vector<uint32_t> *chains = nullptr;  // asked for: the number of chains every read ended with
+	std::vector<uint32_t> *rep = nullptr;     // (with chains) != 0: a minimizer of the read was dropped for its occurrences
+};
+
+// the sorted anchors and the chain DP's f / p of a map call's last batch (ndgpu_ovl_debug_anchors)
+struct DebugView {
+	uint32_t r0 = 0, n = 0;
+	std::vector<uint64_t> aoff;
+	DevBuf<uint64_t> ax, ay;
+	DevBuf<int32_t> f, p;
+};
+
+// What a batch of query reads gives back -- the only thing a batch writes.  Engine::map_once puts the batches' outputs together.
+struct BatchOut {
+	std::vector<OvlRec> recs;
+	std::vector<OvlRec10> recs10;
+	std::vector<uint32_t> counts, chains;
+	std::vector<uint64_t> ca_x, ca_y, ca_off{0};   // (ca_off: relative to the batch)
+	ndgpu_ovl_stats st{};
+	DebugView dbg;                                 // (taken by the call's last batch only)
+};
+
+// What the batches of a map call read, and none of them writes: the call's parameters, the index, the query set with its
+// minimizers and their seed counts (K3a ran over all of them), the batches' read ranges.
+struct MapCall {
+	OvlParams P;
+	int32_t mid;
+	IndexDev ix;
+	QueryDev qd;
+	const ReadSetDev &T, &Q;   // index reads, query reads
+	const Sketch &S;           // the query minimizers
+	const uint32_t *m_start, *m_cnt;        // per minimizer: its first occurrence in the index, its occurrences
+	const uint64_t *a_off, *r_aoff_all;     // anchor offsets per minimizer and per read
+	const std::vector<uint64_t> &h_raoff, &h_moff;   // per read, on the host: anchor offsets, minimizer offsets
+	const std::vector<std::pair<uint32_t, uint32_t>> &ranges;   // the reads [first, second) of every batch
+	unsigned pos_bits, rid_bits;   // sort key: bits of a target position, of a target read
+	bool hit_counts;    // the caller wants the hits of every read counted (Regs)
+	bool read_chains;   // ... the chains of every read (Rechain)
+};
+
+// One batch on its way through the steps of map_batch: its reads [r0, r0 + nb), its slice of the call's anchors, its stream, scratch,
+// timer and output.
+struct Batch {
+	const MapCall &c;
+	uint32_t r0, nb;
+	uint64_t a_base, na;
+	KeyLayout L;
+	hipStream_t stream;
+	Scratch &tmp;
+	BatchOut &out;
+	EvTimer tm;
+};
+
+struct BatchAnchors {   // the batch's anchors once sorted: (ax, ay) of read i at [r_aoff[i], r_aoff[i + 1])
+	DevBuf<uint64_t> r_aoff, ax, ay;
+};
+
+struct SortKeys {   // what the sort leaves for the replay of tie reads and for K4's work units; released before K4
+	DevBuf<uint64_t> ckey, uy, skey, segval, segstart1, slab_rank;
+	DevBuf<uint32_t> slab_flag, tie;
+	uint64_t n_slabs = 0;
+	std::vector<uint32_t> tie_reads;   // batch-local reads some of whose anchors have equal keys
+	void release() { ckey.release(); uy.release(); skey.release(); segval.release(); segstart1.release(); slab_flag.release(); slab_rank.release(); tie.release(); }
+};
+
+struct ChainBufs {   // per anchor: K4's scores and K5's marks and chain buffers
+	DevBuf<uint8_t> stacks;
+	DevBuf<uint64_t> bx, by;   // K5 chain buffers; scratch of the replay passes before that
+	DevBuf<int32_t> t;         // K4/K5 marks; scratch of the replay passes before that
+	DevBuf<int32_t> f, p, v;
+	DevBuf<uint64_t> u;
+	DevBuf<uint32_t> n_end;
+	DevBuf<unsigned long long> cells;
+};
+
+// K3b fill, K3s sort, and K4's work units flagged: runs of whole (strand, target) segments of a read, ~1024 anchors each
+static void seed_sort(Batch &b, BatchAnchors &A, SortKeys &K)
+{
+	const MapCall &c = b.c;
+	ndgpu_ovl_stats &st = b.out.st;
+	A.r_aoff.alloc(b.nb + 1);
+	launch_local_off(c.r_aoff_all, b.r0, b.nb, A.r_aoff.p, b.stream);
+	K.ckey.alloc(b.na), K.uy.alloc(b.na), K.skey.alloc(b.na), A.ay.alloc(b.na);
+	b.tm.start();
+	launch_seed_fill(c.S.x.p, c.S.y.p, c.S.read.p, c.h_moff[b.r0], c.h_moff[b.r0 + b.nb], c.ix, c.qd, c.P, c.m_start, c.m_cnt, c.a_off, b.a_base, b.L,
+	                 K.ckey.p, K.uy.p, b.stream);
+	HIP_OK(hipGetLastError());
+	st.seed_ms += b.tm.stop();
+
+	b.tm.start();
+	b.tmp.run([&](void *t, size_t &tb) { sort_pairs_u64(t, tb, K.ckey.p, K.skey.p, K.uy.p, A.ay.p, b.na, 0, b.L.total_bits, b.stream); });
+	A.ax.alloc(b.na);
+	K.tie.alloc(b.nb);
+	K.tie.zero(b.stream);
+	K.segval.alloc(b.na), K.segstart1.alloc(b.na);
+	launch_anchor_decode(K.skey.p, b.na, b.L, A.ax.p, K.tie.p, K.segval.p, b.stream);
+	b.tmp.run([&](void *t, size_t &tb) { incl_max_scan_u64(t, tb, K.segval.p, K.segstart1.p, b.na, b.stream); });
+	K.slab_flag.alloc(b.na + 1);
+	K.slab_flag.zero(b.stream);
+	launch_slab_flag(K.skey.p, K.segstart1.p, b.na, b.L, A.r_aoff.p, K.slab_flag.p, b.stream);
+	K.slab_rank.alloc(b.na + 1);
+	exscan(b.tmp, K.slab_flag.p, K.slab_rank.p, b.na + 1, b.stream);
+	K.slab_rank.download(&K.n_slabs, 1, b.stream, b.na);
+	std::vector<uint32_t> h_tie(b.nb);
+	K.tie.download(h_tie.data(), b.nb, b.stream);
+	HIP_OK(hipGetLastError());
+	st.sort_ms += b.tm.stop();
+	for (uint32_t i = 0; i < b.nb; ++i) if (h_tie[i]) K.tie_reads.push_back(i);
+	st.tie_reads += K.tie_reads.size();
+}
+
+// exact replay for the reads with equal keys: their anchors sorted again by the whole (x, y), a digit a round (C.bx / by / t: scratch)
+static void replay_ties(Batch &b, BatchAnchors &A, const SortKeys &K, ChainBufs &C)
+{
+	b.tm.start();
+	DevBuf<uint32_t> d_tie(K.tie_reads.size());
+	d_tie.upload(K.tie_reads.data(), K.tie_reads.size(), b.stream);
+	const size_t job_cap = b.na / 64 + K.tie_reads.size() + 4;
+	DevBuf<uint8_t> jobs_a(job_cap * sort_job_bytes()), jobs_b(job_cap * sort_job_bytes());
+	DevBuf<uint32_t> n_jobs(2);
+	n_jobs.zero(b.stream);
+	launch_sort_init(d_tie.p, (uint32_t)K.tie_reads.size(), A.r_aoff.p, K.ckey.p, K.uy.p, b.L, A.ax.p, A.ay.p, jobs_a.p, n_jobs.p, b.stream);
+	uint32_t cur = 0;
+	n_jobs.download(&cur, 1, b.stream);
+	HIP_OK(hipStreamSynchronize(b.stream));
+	DevBuf<uint8_t> *ja = &jobs_a, *jb = &jobs_b;
+	int which = 0;
+	while (cur) { // at most 8 rounds (digit positions 56, 48, ..., 0)
+		HIP_OK(hipMemsetAsync(n_jobs.p + (1 - which), 0, 4, b.stream));
+		launch_sort_pass(ja->p, cur, A.ax.p, A.ay.p, C.bx.p, C.by.p, (uint32_t*)C.t.p, jb->p, n_jobs.p + (1 - which), b.stream);
+		n_jobs.download(&cur, 1, b.stream, 1 - which);
+		HIP_OK(hipStreamSynchronize(b.stream));
+		std::swap(ja, jb);
+		which = 1 - which;
+	}
+	HIP_OK(hipGetLastError());
+	b.out.st.exact_sort_ms += b.tm.stop();
+}
+
+// K4: the work units written out, the sort's keys released, then the chain DP and the chain ends.  *h_cells arrives with the stream's next
+// synchronisation.
+static void chain(Batch &b, BatchAnchors &A, SortKeys &K, ChainBufs &C, unsigned long long *h_cells)
+{
+	const MapCall &c = b.c;
+	DevBuf<uint64_t> slab_i0(K.n_slabs + 1);
+	DevBuf<uint32_t> slab_read(K.n_slabs + 1);
+	launch_slab_write(K.skey.p, K.slab_flag.p, K.slab_rank.p, b.na, b.L, slab_i0.p, slab_read.p, b.stream);
+	DevBuf<float> avg_span(b.nb + 1);
+	launch_read_span(A.r_aoff.p, b.nb, A.ay.p, avg_span.p, b.stream);
+	HIP_OK(hipStreamSynchronize(b.stream));
+	K.release();
+
+	C.f.alloc(b.na), C.p.alloc(b.na), C.v.alloc(b.na);
+	C.u.alloc(b.na);
+	C.n_end.alloc(b.nb + 1);
+	C.cells.alloc(1);
+	C.cells.zero(b.stream);
+	C.t.zero(b.stream);
+	b.tm.start();
+	if (c.P.thin) launch_thin_anchors(A.r_aoff.p, b.nb, A.ax.p, C.t.p, C.v.p, c.qd.read_mid, b.r0, c.mid, b.stream);
+	launch_chain(slab_i0.p, slab_read.p, (uint32_t)K.n_slabs, b.na, A.r_aoff.p, avg_span.p, A.ax.p, A.ay.p, c.P, C.f.p, C.p.p, C.v.p, C.cells.p, b.stream);
+	launch_chain_ends(A.r_aoff.p, b.nb, c.P, C.f.p, C.p.p, C.v.p, C.t.p, C.u.p, C.n_end.p, b.stream);
+	HIP_OK(hipGetLastError());
+	b.out.st.chain_ms += b.tm.stop();
+	C.cells.download(h_cells, 1, b.stream);
+}
+
+// K5 (reuses C.v and C.t; f / p stay for the debug view) and the compaction of its records into `dense` (`dense10`: --step 2's record).
+// The per-read counts the call asked for and, with -c, the chained anchors go to the batch's output.  Returns the number of records.
+static uint64_t hits(Batch &b, const BatchAnchors &A, ChainBufs &C, DevBuf<OvlRec> &dense, DevBuf<OvlRec10> &dense10)
+{
+	const MapCall &c = b.c;
+	const OvlParams &P = c.P;
+	BatchOut &out = b.out;
+	const uint64_t rec_cap = b.na / (uint64_t)std::max(1, P.min_cnt) + b.nb + 1;
+	const uint64_t n_w = P.min_cnt < 2 ? 2 * b.na : b.na;   // (K5's chain tables: see hits_kernel)
+	DevBuf<uint64_t> wx(n_w), wy(n_w);
+	DevBuf<uint32_t> tables((size_t)b.nb * 512), n_rec(b.nb + 1), n_chain(b.nb);
+	DevBuf<OvlRec> recs(rec_cap);
+	DevBuf<OvlRec10> recs10(P.step2 ? rec_cap : 0);
+	DevBuf<uint64_t> cx(P.chains ? b.na : 0), cy(P.chains ? b.na : 0);
+	DevBuf<uint32_t> n_ca(P.chains ? b.nb + 1 : 0);
+	n_rec.zero(b.stream);
+	if (P.chains) n_ca.zero(b.stream);
+	b.tm.start();
+	launch_hits(A.r_aoff.p, b.nb, b.r0, A.ax.p, A.ay.p, c.ix, c.qd, P, C.f.p, C.p.p, C.v.p, C.t.p, C.u.p, C.bx.p, C.by.p, wx.p, wy.p, tables.p, C.stacks.p,
+	            C.n_end.p, recs.p, n_rec.p, n_chain.p, recs10.p, cx.p, cy.p, n_ca.p, b.stream);
+	DevBuf<uint64_t> rec_off(b.nb + 1);
+	exscan(b.tmp, n_rec.p, rec_off.p, b.nb + 1, b.stream);
+	uint64_t n_out = 0;
+	rec_off.download(&n_out, 1, b.stream, b.nb);
+	std::vector<uint32_t> h_chain(b.nb);
+	n_chain.download(h_chain.data(), b.nb, b.stream);
+	if (c.hit_counts) {
+		out.counts.resize(b.nb);
+		n_rec.download(out.counts.data(), b.nb, b.stream);
+	}
+	HIP_OK(hipStreamSynchronize(b.stream));
+	for (uint32_t n : h_chain) out.st.chains += n;
+	if (c.read_chains) out.chains = std::move(h_chain);
+	if (P.chains) {
+		DevBuf<uint64_t> ca_off(b.nb + 1);
+		exscan(b.tmp, n_ca.p, ca_off.p, b.nb + 1, b.stream);
+		std::vector<uint64_t> h_off(b.nb + 1);
+		ca_off.download(h_off.data(), b.nb + 1, b.stream);
+		HIP_OK(hipStreamSynchronize(b.stream));
+		const uint64_t n_c = h_off[b.nb];
+		DevBuf<uint64_t> dx(n_c + 1), dy(n_c + 1);
+		launch_compact_anchors(A.r_aoff.p, b.nb, cx.p, cy.p, n_ca.p, ca_off.p, dx.p, dy.p, b.stream);
+		HIP_OK(hipGetLastError());
+		out.ca_x.resize(n_c), out.ca_y.resize(n_c);
+		dx.download(out.ca_x.data(), n_c, b.stream);
+		dy.download(out.ca_y.data(), n_c, b.stream);
+		HIP_OK(hipStreamSynchronize(b.stream));
+		out.ca_off.insert(out.ca_off.end(), h_off.begin() + 1, h_off.end());
+	}
+	if (P.step2) {
+		dense10.alloc(n_out + 1);
+		launch_compact_recs10(A.r_aoff.p, b.nb, P.min_cnt, recs10.p, n_rec.p, rec_off.p, dense10.p, b.stream);
+	} else {
+		dense.alloc(n_out + 1);
+		launch_compact_recs(A.r_aoff.p, b.nb, P.min_cnt, recs.p, n_rec.p, rec_off.p, dense.p, b.stream);
+	}
+	HIP_OK(hipGetLastError());
+	out.st.hits_ms += b.tm.stop();
+	return n_out;
+}
+
+// --mode 3: the records are provisional (see K5); extend both ends of every hit, then filter and name them
+static void extend_hits(Batch &b, DevBuf<OvlRec> &dense, uint64_t &n_out)
+{
+	const MapCall &c = b.c;
+	ndgpu_ovl_stats &st = b.out.st;
+	b.tm.start();
+	const uint64_t n_task = 2 * n_out;
+	DevBuf<uint32_t> need(n_task + 1);
+	need.zero(b.stream);
+	launch_ext_size(dense.p, n_out, c.Q.len.p, c.T.len.p, c.P, need.p, b.stream);
+	DevBuf<uint64_t> fr_off(n_task + 1);
+	exscan(b.tmp, need.p, fr_off.p, n_task + 1, b.stream);
+	std::vector<uint64_t> h_off(n_task + 1);
+	fr_off.download(h_off.data(), n_task + 1, b.stream);
+	HIP_OK(hipStreamSynchronize(b.stream));
+	DevBuf<int32_t> ext_x(n_task), ext_y(n_task), fr;
+	uint64_t budget = 256ULL << 20; // ints of furthest-reaching scratch per launch (1 GB)
+	if (const char *e = getenv("NDGPU_OVL_EXT_SCRATCH")) budget = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));
+	for (uint64_t t0 = 0; t0 < n_task;) {
+		uint64_t t1 = t0;
+		while (t1 < n_task && (t1 == t0 || h_off[t1 + 1] - h_off[t0] <= budget)) ++t1;
+		const uint64_t ints = h_off[t1] - h_off[t0];
+		if (fr.n < ints + 1) fr.alloc(ints + 1);
+		fr.zero(ints, b.stream);
+		launch_ext_ends(dense.p, t0, t1, c.Q.wp, c.Q.woff.p, c.Q.len.p, c.T.wp, c.T.woff.p, c.T.len.p, c.P, fr_off.p, h_off[t0], fr.p, ext_x.p, ext_y.p,
+		                b.stream);
+		++st.ext_launches;
+		t0 = t1;
+	}
+	for (uint64_t t = 0; t < n_task; ++t) st.ext_problems += h_off[t + 1] != h_off[t];
+	DevBuf<uint32_t> keep(n_out + 1);
+	keep.zero(b.stream);
+	launch_ext_apply(dense.p, n_out, ext_x.p, ext_y.p, c.Q.id.p, c.Q.len.p, c.T.id.p, c.T.len.p, c.P, keep.p, b.stream);
+	DevBuf<uint64_t> pos(n_out + 1);
+	exscan(b.tmp, keep.p, pos.p, n_out + 1, b.stream);
+	uint64_t n_keep = 0;
+	pos.download(&n_keep, 1, b.stream, n_out);
+	HIP_OK(hipStreamSynchronize(b.stream));
+	DevBuf<OvlRec> fin(n_keep + 1);
+	launch_scatter_recs(dense.p, n_out, keep.p, pos.p, fin.p, b.stream);
+	HIP_OK(hipGetLastError());
+	dense = std::move(fin);
+	n_out = n_keep;
+	st.ext_ms += b.tm.stop();
+}
+
+// Batch `bi` of a map call on `stream`: K3b fill, K3s sort (+ exact replay for reads with equal keys), K4 chain DP, K5 hits, compaction
+// (+ the extension of --mode 3), D2H of the records.  The reads of a batch know nothing of the other batches.
+static void map_batch(const MapCall &c, size_t bi, hipStream_t stream, Scratch &tmp, BatchOut &out)
+{
+	const uint32_t r0 = c.ranges[bi].first, nb = c.ranges[bi].second - r0;
+	const uint64_t a_base = c.h_raoff[r0], na = c.h_raoff[r0 + nb] - a_base;
+	if (c.read_chains) out.chains.assign(nb, 0u);
+	++out.st.batches;
+	if (na == 0) {
+		if (c.hit_counts) out.counts.assign(nb, 0u);
+		if (c.P.chains) out.ca_off.insert(out.ca_off.end(), nb, 0);
+		return;
+	}
+	KeyLayout L;
+	L.pos_bits = c.pos_bits, L.rev_shift = c.pos_bits + c.rid_bits, L.read_shift = L.rev_shift + 1, L.read_base = r0;
+	L.total_bits = L.read_shift + bits_for(nb - 1);
+	Batch b{c, r0, nb, a_base, na, L, stream, tmp, out, EvTimer(stream)};
+
+	BatchAnchors A;
+	SortKeys K;
+	seed_sort(b, A, K);
+	ChainBufs C;
+	C.stacks.alloc((na / 64 + 2 * (size_t)nb + 4) * sort_job_bytes());
+	C.bx.alloc(na), C.by.alloc(na);
+	C.t.alloc(na);
+	if (!K.tie_reads.empty()) replay_ties(b, A, K, C);
+	unsigned long long h_cells = 0;
+	chain(b, A, K, C, &h_cells);
+	DevBuf<OvlRec> dense;
+	DevBuf<OvlRec10> dense10;
+	uint64_t n_out = hits(b, A, C, dense, dense10);
+	if (c.P.step2) {
+		out.recs10.resize(n_out);
+		dense10.download(out.recs10.data(), n_out, stream);
+	} else {
+		if (c.P.mode3 && n_out) extend_hits(b, dense, n_out);
+		out.recs.resize(n_out);
+		dense.download(out.recs.data(), n_out, stream);
+	}
+	HIP_OK(hipStreamSynchronize(stream));
+	out.st.chain_cells += h_cells;
+	out.st.overlaps += n_out;
+	if (!c.P.step2 && bi + 1 == c.ranges.size()) {   // debug view (last batch)
+		DebugView &d = out.dbg;
+		d.r0 = r0, d.n = nb;
+		d.aoff.assign(c.h_raoff.begin() + r0, c.h_raoff.begin() + r0 + nb + 1);
+		for (auto &x : d.aoff) x -= a_base;
+		d.ax = std::move(A.ax); d.ay = std::move(A.ay); d.f = std::move(C.f); d.p = std::move(C.p);
+	}
+}
+
 struct Engine {
 	int device = 0;
 	hipStream_t stream = nullptr;
-	OvlParams P{};
+	OvlParams P{};           // the index's parameters (a map call has its own: call_params)
 	ReadSetDev T;
 	uint64_t n_min = 0, n_keys = 0;
 	DevBuf<uint64_t> ukey, ustart, pos;
@@ -365,15 +691,9 @@ struct Engine {
 	uint32_t maps_served = 0;
 	double query_minimizers_seen = 0;   // estimate (2 / (w + 1) per base) over the map calls of this index: what decides the lookup table
 	ndgpu_ovl_stats st{};
-	// debug view of the last map batch
-	std::vector<uint64_t> dbg_aoff;
-	DevBuf<uint64_t> dbg_ax, dbg_ay;
-	DevBuf<int32_t> dbg_f, dbg_p;
-	uint32_t dbg_r0 = 0, dbg_n = 0;
-
-	DevBuf<uint8_t> tmp;
+	DebugView dbg;           // of the last map call
+	Scratch tmp;
 	std::vector<hipStream_t> lane_streams;   // the streams of map()'s concurrent batches (created on first use)
-	void *temp(size_t bytes) { if (tmp.n < bytes) tmp.alloc(bytes + bytes / 4); return tmp.p; }
 
 	IndexDev index_dev() const { return IndexDev{n_keys, ukey.p, ustart.p, pos.p, T.len.p, T.id.p, T.namekey.p, bucket.p, bucket_shift, htab.p, hsize}; }
 
@@ -390,15 +710,8 @@ struct Engine {
 		first[n] = (uint32_t)tiles.size();
 	}
 
-	void exscan(const uint32_t *in, uint64_t *out, size_t n)
-	{
-		size_t tb = 0;
-		exscan_u32_to_u64(nullptr, tb, in, out, n, stream);
-		exscan_u32_to_u64(temp(tb), tb, in, out, n, stream);
-	}
-
 	// K1, position-parallel form (odd k)
-	void sketch_tiled(const ReadSetDev &R, int rid_is_index, bool want_read, Sketch &out)
+	void sketch_tiled(const OvlParams &P, const ReadSetDev &R, int rid_is_index, bool want_read, Sketch &out)
 	{
 		const uint32_t TS = (uint32_t)sketch_tile_symbols();
 		EvTimer tm(stream);
@@ -427,7 +740,7 @@ struct Engine {
 			launch_run_compact(false, R.wp, R.woff.p, R.len.p, d_tiles.p, nt, nullptr, d_first.p, roff.p, cnt.p, sym.p, rstart.p,
 			                   n_sym_d.p, stream);
 			DevBuf<uint64_t> prefix(nt + 1);
-			exscan(cnt.p, prefix.p, nt + 1);
+			exscan(tmp, cnt.p, prefix.p, nt + 1, stream);
 			launch_run_compact(true, R.wp, R.woff.p, R.len.p, d_tiles.p, nt, prefix.p, d_first.p, roff.p, cnt.p, sym.p, rstart.p,
 			                   n_sym_d.p, stream);
 			h_nsym.resize(R.n);
@@ -445,7 +758,7 @@ struct Engine {
 		launch_sketch_tiles(false, P.hpc != 0, R.wp, R.woff.p, R.len.p, sym.p, rstart.p, roff.p, n_sym_d.p, d_tiles.p, nt, P, rid_is_index,
 		                    nullptr, cnt.p, nullptr, nullptr, nullptr, stream);
 		DevBuf<uint64_t> tile_off(nt + 1);
-		exscan(cnt.p, tile_off.p, nt + 1);
+		exscan(tmp, cnt.p, tile_off.p, nt + 1, stream);
 		uint64_t total = 0;
 		tile_off.download(&total, 1, stream, nt);
 		HIP_OK(hipStreamSynchronize(stream));
@@ -462,19 +775,17 @@ struct Engine {
 		st.minimizers += total;
 	}
 
-	void sketch(const ReadSetDev &R, int rid_is_index, bool want_read, Sketch &out)
+	void sketch(const OvlParams &P, const ReadSetDev &R, int rid_is_index, bool want_read, Sketch &out)
 	{
 		// (the position-parallel kernels take an odd k of one word up to 28, or of two words: 33..63)
-		if ((P.k & 1) && (P.k <= 28 || (P.k >= 33 && P.k <= 63)) && !getenv("NDGPU_OVL_SEQ_SKETCH")) { sketch_tiled(R, rid_is_index, want_read, out); return; }
+		if ((P.k & 1) && (P.k <= 28 || (P.k >= 33 && P.k <= 63)) && !getenv("NDGPU_OVL_SEQ_SKETCH")) { sketch_tiled(P, R, rid_is_index, want_read, out); return; }
 		DevBuf<uint32_t> cnt(R.n + 1);
 		cnt.zero(stream);
 		EvTimer tm(stream);
 		tm.start();
 		launch_sketch(false, R.wp, R.woff.p, R.len.p, R.order.p, R.n, P, rid_is_index, nullptr, nullptr, nullptr, nullptr, cnt.p, stream);
 		out.off.alloc(R.n + 1);
-		size_t tb = 0;
-		exscan_u32_to_u64(nullptr, tb, cnt.p, out.off.p, R.n + 1, stream);
-		exscan_u32_to_u64(temp(tb), tb, cnt.p, out.off.p, R.n + 1, stream);
+		exscan(tmp, cnt.p, out.off.p, R.n + 1, stream);
 		uint64_t total = 0;
 		out.off.download(&total, 1, stream, R.n);
 		HIP_OK(hipStreamSynchronize(stream));
@@ -492,7 +803,7 @@ struct Engine {
 	void build_index()
 	{
 		Sketch S;
-		sketch(T, 1, false, S);
+		sketch(P, T, 1, false, S);
 		n_min = S.n;
 		EvTimer tm(stream);
 		tm.start();
@@ -500,32 +811,24 @@ struct Engine {
 		launch_shift_keys(S.x.p, key.p, n_min, stream);
 		// by position first (read<<32 | pos<<1 | strand), then stably by minimizer
 		const unsigned ybits = 32 + bits_for(T.n ? T.n - 1 : 0);
-		size_t tb = 0;
-		sort_pairs_u64(nullptr, tb, S.y.p, y2.p, key.p, key2.p, n_min, 0, ybits, stream);
-		if (n_min) sort_pairs_u64(temp(tb), tb, S.y.p, y2.p, key.p, key2.p, n_min, 0, ybits, stream);
+		tmp.run([&](void *t, size_t &tb) { sort_pairs_u64(t, tb, S.y.p, y2.p, key.p, key2.p, n_min, 0, ybits, stream); }, n_min != 0);
 		pos.alloc(n_min + 1);
 		const unsigned kbits = std::min(56u, 2u * (unsigned)P.k); // x >> 8: the long k-mer hash of ava-hifi fills all 56 bits
-		tb = 0;
-		sort_pairs_u64(nullptr, tb, key2.p, key.p, y2.p, pos.p, n_min, 0, kbits, stream);
-		if (n_min) sort_pairs_u64(temp(tb), tb, key2.p, key.p, y2.p, pos.p, n_min, 0, kbits, stream);
+		tmp.run([&](void *t, size_t &tb) { sort_pairs_u64(t, tb, key2.p, key.p, y2.p, pos.p, n_min, 0, kbits, stream); }, n_min != 0);
 		// distinct minimizers and their occurrence counts
 		DevBuf<uint64_t> uniq(n_min + 1), n_runs(1);
 		ucnt.alloc(n_min + 2);
 		ucnt.zero(stream);
 		n_keys = 0;
 		if (n_min) {
-			tb = 0;
-			rle_u64(nullptr, tb, key.p, n_min, uniq.p, ucnt.p, n_runs.p, stream);
-			rle_u64(temp(tb), tb, key.p, n_min, uniq.p, ucnt.p, n_runs.p, stream);
+			tmp.run([&](void *t, size_t &tb) { rle_u64(t, tb, key.p, n_min, uniq.p, ucnt.p, n_runs.p, stream); });
 			n_runs.download(&n_keys, 1, stream);
 			HIP_OK(hipStreamSynchronize(stream));
 		}
 		ukey.alloc(n_keys + 1);
 		if (n_keys) HIP_OK(hipMemcpyAsync(ukey.p, uniq.p, n_keys * 8, hipMemcpyDeviceToDevice, stream));
 		ustart.alloc(n_keys + 2);
-		tb = 0;
-		exscan_u32_to_u64(nullptr, tb, ucnt.p, ustart.p, n_keys + 1, stream);
-		exscan_u32_to_u64(temp(tb), tb, ucnt.p, ustart.p, n_keys + 1, stream);
+		exscan(tmp, ucnt.p, ustart.p, n_keys + 1, stream);
 		// top-bits table over the distinct keys (hash values have 2k bits)
 		const unsigned key_bits = std::min(56u, 2u * (unsigned)P.k);
 		bucket_shift = key_bits > (unsigned)kBucketBits ? key_bits - (unsigned)kBucketBits : 0;
@@ -574,9 +877,7 @@ struct Engine {
 		if (f <= 0.) return INT32_MAX;
 		if (!n_keys) return 1;
 		DevBuf<uint32_t> sorted(n_keys);
-		size_t tb = 0;
-		sort_keys_u32(nullptr, tb, ucnt.p, sorted.p, n_keys, stream);
-		sort_keys_u32(temp(tb), tb, ucnt.p, sorted.p, n_keys, stream);
+		tmp.run([&](void *t, size_t &tb) { sort_keys_u32(t, tb, ucnt.p, sorted.p, n_keys, stream); });
 		const uint32_t kth = (uint32_t)((1. - f) * n_keys);
 		uint32_t v = 0;
 		sorted.download(&v, 1, stream, kth);
@@ -584,14 +885,68 @@ struct Engine {
 		return (int32_t)(v + 1);
 	}
 
-	// One pass over the query set.  read_mid (one occurrence threshold per query read) and chains_per_read (what the pass found)
-	// belong to map_rechain() below.
-	const int32_t *read_mid = nullptr;
-	std::vector<uint32_t> *chains_per_read = nullptr;
-	std::vector<uint32_t> *rep_per_read = nullptr;   // (with chains_per_read) != 0: a minimizer of the read was dropped for its occurrences
+	// The parameters of a map call: the caller's, with the index's sketch parameters, and what the hits-only passes (Regs) switch off
+	OvlParams call_params(const ndgpu_ovl_opt &o, const Regs *regs) const
+	{
+		OvlParams Pc = to_params(o);
+		Pc.k = P.k, Pc.w = P.w, Pc.hpc = P.hpc; // the sketch parameters belong to the index
+		if (regs) {
+			Pc.provisional = 1, Pc.step2 = 0, Pc.mode3 = 0, Pc.dvt = 0, Pc.nameless = regs->nameless, Pc.thin = regs->thin, Pc.chains = regs->ca_x != nullptr;
+			if (regs->nameless) Pc.no_diag = Pc.no_dual = 0; // skip_seed looks at names only when there is one (minimap2/map.c:129)
+		}
+		return Pc;
+	}
+
+	// The batches can run side by side (NDGPU_OVL_LANES of them at a time, a host thread and a stream each; the reads of a batch know
+	// nothing of the other batches).  Measured in round 5 on the config-2 job (one batch cut into `lanes`): 1 lane 91.5 ms, 2 lanes
+	// 97.5, 3 lanes 96.8, 4 lanes 100.4, 6 lanes 133.9 -- the kernels of a batch are not the idle chains they look like in a trace
+	// (K4 and K5 fill the device while their heaviest read pair finishes), and every further stream costs what more device contexts
+	// cost the consensus stage.  So one lane is the default; the lanes stay for sets whose batches are many and small.
+	void run_batches(const MapCall &call, size_t n_lanes, std::vector<BatchOut> &outs)
+	{
+		const size_t n_batches = call.ranges.size();
+		auto run = [&](size_t bi, hipStream_t s, Scratch &scratch) {
+			map_batch(call, bi, s, scratch, outs[bi]);
+			if (outs[bi].dbg.n) dbg = std::move(outs[bi].dbg);   // (the last batch alone has one)
+		};
+		if (n_lanes <= 1) {
+			for (size_t bi = 0; bi < n_batches; ++bi) run(bi, stream, tmp);
+			return;
+		}
+		HIP_OK(hipStreamSynchronize(stream));   // (the minimizers, their seed counts and offsets are final)
+		while (lane_streams.size() < n_lanes) {
+			hipStream_t ls = nullptr;
+			HIP_OK(hipStreamCreate(&ls));
+			lane_streams.push_back(ls);
+		}
+		std::atomic<size_t> next{0};
+		std::vector<std::exception_ptr> errs(n_lanes);
+		std::vector<std::thread> th;
+		for (size_t w = 0; w < n_lanes; ++w)
+			th.emplace_back([&, w] {
+				try {
+					HIP_OK(hipSetDevice(device));
+					Scratch lane_tmp;
+					for (;;) {
+						const size_t bi = next.fetch_add(1);
+						if (bi >= n_batches) break;
+						run(bi, lane_streams[w], lane_tmp);
+					}
+					HIP_OK(hipStreamSynchronize(lane_streams[w]));
+				} catch (...) {
+					errs[w] = std::current_exception();
+					next = n_batches;   // (the other lanes stop at their next batch)
+					(void)hipStreamSynchronize(lane_streams[w]);   // nothing of this lane is in flight when its blocks go back to the pool
+				}
+			});
+		for (auto &t : th) t.join();
+		for (auto &e : errs) if (e) std::rethrow_exception(e);
+	}
+
+	// One pass over the query set.  `rc` belongs to map() below.
 	int64_t map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, const uint32_t *words, uint64_t n_words, const uint64_t *woff,
-	                 const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10 = nullptr,
-	                 const Regs *regs = nullptr);
+	                 const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10, const Regs *regs,
+	                 const Rechain &rc);
 	// -f FLOAT,INT (mm_mapopt_t::max_occ > mid_occ; minimap2/map.c:553-575 and :678-700): a query read that ends its chaining without a
 	// chain is seeded again with every minimizer below max_occ occurrences and chained again (with one segment per query that is the
 	// test together with `rep_len > 0`: a read none of whose minimizers was dropped would collect the same seeds again -- and in the
@@ -603,14 +958,9 @@ struct Engine {
 	            const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10 = nullptr,
 	            const Regs *regs = nullptr)
 	{
-		if (o.max_occ <= mid) return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs);
+		if (o.max_occ <= mid) return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{});
 		std::vector<uint32_t> chains, rep;
-		struct Unset { Engine *e; ~Unset() { e->read_mid = nullptr, e->chains_per_read = nullptr, e->rep_per_read = nullptr; } } unset{this};
-		chains_per_read = &chains;
-		rep_per_read = &rep;
-		int64_t n = map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs);
-		chains_per_read = nullptr;
-		rep_per_read = nullptr;
+		int64_t n = map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{nullptr, &chains, &rep});
 		if (n < 0) return n;
 		chains.resize(n_q, 0u);
 		rep.resize(n_q, 0u);
@@ -620,47 +970,19 @@ struct Engine {
 			if (!chains[i] && rep[i]) thr[i] = o.max_occ, ++again;   // map.c:553 / :678: no chain AND rep_len > 0
 		if (!again) return n;
 		st.rechained += again;
-		read_mid = thr.data();
-		return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs);
+		return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{thr.data(), nullptr, nullptr});
 	}
 };
 
-static OvlParams to_params(const ndgpu_ovl_opt &o)
-{
-	OvlParams P{};
-	P.k = o.k, P.w = o.w, P.hpc = o.hpc, P.no_diag = o.no_diag, P.no_dual = o.no_dual, P.min_cnt = o.min_cnt, P.min_sc = o.min_chain_score;
-	P.bw = o.bw, P.max_gap = o.max_gap, P.max_skip = o.max_chain_skip, P.max_iter = o.max_chain_iter, P.minlen = o.minlen, P.dvt = o.dvt;
-	P.maxhan1 = o.maxhan1, P.maxhan2 = o.maxhan2;
-	P.mode3 = o.mode == 3, P.ide_ml = 6000 /* mm_mapopt_t::ide_ml, options.c:60: no command-line switch */, P.d_factor = o.d_factor;
-	P.step2 = o.step == 2, P.minmatch = o.minmatch, P.minide = o.minide;
-	return P;
-}
-
-static const char *check_opt(const ndgpu_ovl_opt &o)
-{
-	if (o.k < 1 || o.k > 127 || (o.k > 28 && !(o.k & 31)))
-		return "k must be in 1..127 and not 32, 64 or 96 (the reference's long k-mer mask is undefined there: sketch.c:286-287)";
-	if (o.w < 1 || o.w > 64) return "w must be in 1..64";
-	if (o.max_chain_iter < 1 || o.max_chain_iter >= 8192) return "max_chain_iter must be in 1..8191";
-	if (o.max_gap < 0 || o.bw < 0) return "negative max_gap / bw";
-	if (o.step == 2 && (o.mode < 0 || o.mode > 2)) return "--step 2 is built for --mode 0 (no re-alignment), 1 and 2 (the default)";
-	return nullptr;
-}
-
 int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, const uint32_t *words, uint64_t n_words, const uint64_t *woff,
-                    const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10, const Regs *regs)
+                         const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10, const Regs *regs,
+                         const Rechain &rc)
 {
-	OvlParams Pm = to_params(o);
-	Pm.k = P.k, Pm.w = P.w, Pm.hpc = P.hpc; // the sketch parameters belong to the index
+	const OvlParams Pc = call_params(o, regs);
 	if (regs) {
-		Pm.provisional = 1, Pm.step2 = 0, Pm.mode3 = 0, Pm.dvt = 0, Pm.nameless = regs->nameless, Pm.thin = regs->thin, Pm.chains = regs->ca_x != nullptr;
 		if (regs->ca_x) regs->ca_x->clear(), regs->ca_y->clear(), regs->ca_off->assign(1, 0);
-		if (regs->nameless) Pm.no_diag = Pm.no_dual = 0; // skip_seed looks at names only when there is one (minimap2/map.c:129)
 		regs->counts->clear();
 	}
-	const OvlParams Pi = P;
-	P = Pm;
-	struct Restore { Engine *e; OvlParams p; ~Restore() { e->P = p; } } restore{this, Pi};
 	++st.map_calls;
 	// The lookup table is built when it pays, by cost and not by the number of calls (one fused call may carry the query files of eight
 	// jobs): config 2 measured 25 ps saved per query minimizer looked up (seed pass 13.5 -> 9.6 ms for 156 M) against 86 ps per distinct
@@ -675,8 +997,8 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 	}
 	out.clear();
 	if (out10) out10->clear();
-	if (chains_per_read) chains_per_read->clear();
-	if ((P.step2 != 0) != (out10 != nullptr)) return -1; // the two record types have an entry point each
+	if (rc.chains) rc.chains->clear();
+	if ((Pc.step2 != 0) != (out10 != nullptr)) return -1; // the two record types have an entry point each
 	if (!n_q) return 0;
 
 	ReadSetDev Q;
@@ -688,7 +1010,7 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 	qhash.upload(qh.data(), n_q, stream);
 
 	Sketch S;
-	sketch(Q, 0, true, S);
+	sketch(Pc, Q, 0, true, S);
 	const uint64_t n_m = S.n;
 	const IndexDev ix = index_dev();
 	DevBuf<uint64_t> d_want_off;
@@ -697,15 +1019,15 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 		const uint64_t nw = regs->want_off[n_q];
 		d_want_off.alloc(n_q + 1), d_want.alloc(nw + 1);
 		d_want_off.upload(regs->want_off, n_q + 1, stream);
-		if (nw) d_want.upload(regs->want, nw, stream);
+		d_want.upload(regs->want, nw, stream);
 	}
 	DevBuf<int32_t> d_read_mid;
-	if (read_mid) {
+	if (rc.read_mid) {
 		d_read_mid.alloc(n_q);
-		d_read_mid.upload(read_mid, n_q, stream);
+		d_read_mid.upload(rc.read_mid, n_q, stream);
 	}
 	DevBuf<uint32_t> d_rep;
-	if (rep_per_read) {
+	if (rc.rep) {
 		d_rep.alloc(n_q);
 		d_rep.zero(stream);
 	}
@@ -716,11 +1038,9 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 	tm.start();
 	DevBuf<uint32_t> m_start(n_m + 1), m_cnt(n_m + 1), m_surv(n_m + 2);
 	m_surv.zero(stream);
-	launch_seed_count(S.x.p, S.y.p, S.read.p, n_m, ix, qd, P, mid, m_start.p, m_cnt.p, m_surv.p, stream);
+	launch_seed_count(S.x.p, S.y.p, S.read.p, n_m, ix, qd, Pc, mid, m_start.p, m_cnt.p, m_surv.p, stream);
 	DevBuf<uint64_t> a_off(n_m + 2);
-	size_t tb = 0;
-	exscan_u32_to_u64(nullptr, tb, m_surv.p, a_off.p, n_m + 1, stream);
-	exscan_u32_to_u64(temp(tb), tb, m_surv.p, a_off.p, n_m + 1, stream);
+	exscan(tmp, m_surv.p, a_off.p, n_m + 1, stream);
 	uint64_t total_a = 0;
 	a_off.download(&total_a, 1, stream, n_m);
 	HIP_OK(hipStreamSynchronize(stream));
@@ -747,13 +1067,7 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 	const uint64_t max_batch_reads = read_bits_max >= 32 ? 0xffffffffULL : (1ULL << read_bits_max);
 	uint64_t budget = 192ULL << 20; // anchors per batch (~100 B of HBM each)
 	if (const char *e = getenv("NDGPU_OVL_BATCH_ANCHORS")) budget = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));
-
-	// The batches can run side by side (NDGPU_OVL_LANES of them at a time, a host thread and a stream each; the reads of a batch know
-	// nothing of the other batches).  Measured in round 5 on the config-2 job (one batch cut into `lanes`): 1 lane 91.5 ms, 2 lanes
-	// 97.5, 3 lanes 96.8, 4 lanes 100.4, 6 lanes 133.9 -- the kernels of a batch are not the idle chains they look like in a trace
-	// (K4 and K5 fill the device while their heaviest read pair finishes), and every further stream costs what more device contexts
-	// cost the consensus stage.  So one lane is the default; the lanes stay for sets whose batches are many and small.
-	int lanes = 1;
+	int lanes = 1;   // (see run_batches)
 	if (const char *e = getenv("NDGPU_OVL_LANES")) lanes = std::max(1, atoi(e));
 	if (lanes > 1 && total_a >= (uint64_t)lanes * (2ULL << 20)) budget = std::min<uint64_t>(budget, total_a / (uint64_t)lanes + 1);
 	std::vector<std::pair<uint32_t, uint32_t>> ranges;
@@ -763,300 +1077,11 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 		ranges.push_back({r0, r1});
 		r0 = r1;
 	}
-	struct BatchOut {
-		std::vector<OvlRec> recs;
-		std::vector<OvlRec10> recs10;
-		std::vector<uint32_t> counts, chains;
-		std::vector<uint64_t> ca_x, ca_y, ca_off{0};   // (ca_off: relative to the batch)
-		ndgpu_ovl_stats st{};
-	};
+	const MapCall call{Pc, mid, ix, qd, T, Q, S, m_start.p, m_cnt.p, a_off.p, r_aoff_all.p, h_raoff, h_moff, ranges, pos_bits, rid_bits,
+	                   regs != nullptr, rc.chains != nullptr};
 	std::vector<BatchOut> outs(ranges.size());
-	const Regs *const regs_all = regs;
-	const bool want10 = out10 != nullptr;
-	std::mutex dbg_mu;
-	const size_t n_lanes = std::min<size_t>((size_t)lanes, ranges.size());
-	auto run_batch = [&](size_t bi, hipStream_t stream, DevBuf<uint8_t> &lane_tmp) {
-		// (everything the batch touches by these names is its own: its stream, its scratch, its counters, its output)
-		BatchOut &BO = outs[bi];
-		ndgpu_ovl_stats &st = BO.st;
-		std::vector<OvlRec> &out = BO.recs;
-		std::vector<OvlRec10> *const out10 = want10 ? &BO.recs10 : nullptr;
-		Regs lregs{};
-		if (regs_all) {
-			lregs = *regs_all;
-			lregs.counts = &BO.counts, lregs.max_anchors = nullptr;
-			if (regs_all->ca_x) lregs.ca_x = &BO.ca_x, lregs.ca_y = &BO.ca_y, lregs.ca_off = &BO.ca_off;
-		}
-		const Regs *const regs = regs_all ? &lregs : nullptr;
-		auto temp = [&](size_t bytes) -> void * { if (lane_tmp.n < bytes) lane_tmp.alloc(bytes + bytes / 4); return lane_tmp.p; };
-		auto exscan = [&](const uint32_t *in, uint64_t *o, size_t n) {
-			size_t tb2 = 0;
-			exscan_u32_to_u64(nullptr, tb2, in, o, n, stream);
-			exscan_u32_to_u64(temp(tb2), tb2, in, o, n, stream);
-		};
-		EvTimer tm(stream);
-		size_t tb = 0;
-		const uint32_t r0 = ranges[bi].first, r1 = ranges[bi].second;
-		if (chains_per_read) BO.chains.assign(r1 - r0, 0u);
-		const uint32_t nb = r1 - r0;
-		const uint64_t a_base = h_raoff[r0], na = h_raoff[r1] - a_base;
-		++st.batches;
-		if (na == 0) {
-			if (regs) regs->counts->insert(regs->counts->end(), nb, 0u);
-			if (regs && regs->ca_off) regs->ca_off->insert(regs->ca_off->end(), nb, regs->ca_off->back());
-			return;
-		}
-		KeyLayout L;
-		L.pos_bits = pos_bits, L.rev_shift = pos_bits + rid_bits, L.read_shift = L.rev_shift + 1, L.read_base = r0;
-		L.total_bits = L.read_shift + bits_for(nb - 1);
+	run_batches(call, std::min<size_t>((size_t)lanes, ranges.size()), outs);
 
-		DevBuf<uint64_t> r_aoff(nb + 1);
-		launch_local_off(r_aoff_all.p, r0, nb, r_aoff.p, stream);
-		DevBuf<uint64_t> ckey(na), uy(na), skey(na), ay(na);
-		tm.start();
-		launch_seed_fill(S.x.p, S.y.p, S.read.p, h_moff[r0], h_moff[r1], ix, qd, P, m_start.p, m_cnt.p, a_off.p, a_base, L, ckey.p, uy.p,
-		                 stream);
-		HIP_OK(hipGetLastError());
-		st.seed_ms += tm.stop();
-
-		tm.start();
-		tb = 0;
-		sort_pairs_u64(nullptr, tb, ckey.p, skey.p, uy.p, ay.p, na, 0, L.total_bits, stream);
-		sort_pairs_u64(temp(tb), tb, ckey.p, skey.p, uy.p, ay.p, na, 0, L.total_bits, stream);
-		DevBuf<uint64_t> ax(na);
-		DevBuf<uint32_t> tie(nb);
-		tie.zero(stream);
-		DevBuf<uint64_t> segval(na), segstart1(na);
-		launch_anchor_decode(skey.p, na, L, ax.p, tie.p, segval.p, stream);
-		// K4 work units: runs of whole (strand, target) segments of a read, ~1024 anchors each
-		tb = 0;
-		incl_max_scan_u64(nullptr, tb, segval.p, segstart1.p, na, stream);
-		incl_max_scan_u64(temp(tb), tb, segval.p, segstart1.p, na, stream);
-		DevBuf<uint32_t> slab_flag(na + 1);
-		slab_flag.zero(stream);
-		launch_slab_flag(skey.p, segstart1.p, na, L, r_aoff.p, slab_flag.p, stream);
-		DevBuf<uint64_t> slab_rank(na + 1);
-		exscan(slab_flag.p, slab_rank.p, na + 1);
-		uint64_t n_slabs = 0;
-		slab_rank.download(&n_slabs, 1, stream, na);
-		std::vector<uint32_t> h_tie(nb);
-		tie.download(h_tie.data(), nb, stream);
-		HIP_OK(hipGetLastError());
-		st.sort_ms += tm.stop();
-		std::vector<uint32_t> tie_reads;
-		for (uint32_t i = 0; i < nb; ++i) if (h_tie[i]) tie_reads.push_back(i);
-		st.tie_reads += tie_reads.size();
-		DevBuf<uint8_t> stacks((na / 64 + 2 * (size_t)nb + 4) * sort_job_bytes());
-		DevBuf<uint64_t> bx(na), by(na);   // K5 chain buffers; scratch of the replay passes before that
-		DevBuf<int32_t> t(na);             // K4/K5 marks; scratch of the replay passes before that
-		if (!tie_reads.empty()) {
-			tm.start();
-			DevBuf<uint32_t> d_tie(tie_reads.size());
-			d_tie.upload(tie_reads.data(), tie_reads.size(), stream);
-			const size_t job_cap = na / 64 + tie_reads.size() + 4;
-			DevBuf<uint8_t> jobs_a(job_cap * sort_job_bytes()), jobs_b(job_cap * sort_job_bytes());
-			DevBuf<uint32_t> n_jobs(2);
-			n_jobs.zero(stream);
-			launch_sort_init(d_tie.p, (uint32_t)tie_reads.size(), r_aoff.p, ckey.p, uy.p, L, ax.p, ay.p, jobs_a.p, n_jobs.p, stream);
-			uint32_t cur = 0;
-			n_jobs.download(&cur, 1, stream);
-			HIP_OK(hipStreamSynchronize(stream));
-			DevBuf<uint8_t> *ja = &jobs_a, *jb = &jobs_b;
-			int which = 0;
-			while (cur) { // at most 8 rounds (digit positions 56, 48, ..., 0)
-				HIP_OK(hipMemsetAsync(n_jobs.p + (1 - which), 0, 4, stream));
-				launch_sort_pass(ja->p, cur, ax.p, ay.p, bx.p, by.p, (uint32_t*)t.p, jb->p, n_jobs.p + (1 - which), stream);
-				n_jobs.download(&cur, 1, stream, 1 - which);
-				HIP_OK(hipStreamSynchronize(stream));
-				std::swap(ja, jb);
-				which = 1 - which;
-			}
-			HIP_OK(hipGetLastError());
-			st.exact_sort_ms += tm.stop();
-		}
-		DevBuf<uint64_t> slab_i0(n_slabs + 1);
-		DevBuf<uint32_t> slab_read(n_slabs + 1);
-		launch_slab_write(skey.p, slab_flag.p, slab_rank.p, na, L, slab_i0.p, slab_read.p, stream);
-		DevBuf<float> avg_span(nb + 1);
-		launch_read_span(r_aoff.p, nb, ay.p, avg_span.p, stream);
-		HIP_OK(hipStreamSynchronize(stream));
-		ckey.release(); uy.release(); skey.release(); segval.release(); segstart1.release(); slab_flag.release(); slab_rank.release();
-
-		// K4
-		DevBuf<int32_t> f(na), p(na), v(na);
-		DevBuf<uint64_t> u(na);
-		DevBuf<uint32_t> n_end(nb + 1);
-		DevBuf<unsigned long long> cells(1);
-		cells.zero(stream);
-		t.zero(stream);
-		tm.start();
-		if (P.thin) launch_thin_anchors(r_aoff.p, nb, ax.p, t.p, v.p, qd.read_mid, r0, mid, stream);
-		launch_chain(slab_i0.p, slab_read.p, (uint32_t)n_slabs, na, r_aoff.p, avg_span.p, ax.p, ay.p, P, f.p, p.p, v.p, cells.p, stream);
-		launch_chain_ends(r_aoff.p, nb, P, f.p, p.p, v.p, t.p, u.p, n_end.p, stream);
-		HIP_OK(hipGetLastError());
-		st.chain_ms += tm.stop();
-		unsigned long long h_cells = 0;
-		cells.download(&h_cells, 1, stream);
-
-		// K5 (keeps copies of f/p for the debug view first: K5 reuses v and t only)
-		const uint64_t rec_cap = na / (uint64_t)std::max(1, P.min_cnt) + nb + 1;
-		const uint64_t n_w = P.min_cnt < 2 ? 2 * na : na;   // (K5's chain tables: see hits_kernel)
-		DevBuf<uint64_t> wx(n_w), wy(n_w);
-		DevBuf<uint32_t> tables((size_t)nb * 512), n_rec(nb + 1), n_chain(nb);
-		DevBuf<OvlRec> recs(rec_cap);
-		DevBuf<OvlRec10> recs10(P.step2 ? rec_cap : 0);
-		DevBuf<uint64_t> cx(P.chains ? na : 0), cy(P.chains ? na : 0);
-		DevBuf<uint32_t> n_ca(P.chains ? nb + 1 : 0);
-		n_rec.zero(stream);
-		if (P.chains) n_ca.zero(stream);
-		tm.start();
-		launch_hits(r_aoff.p, nb, r0, ax.p, ay.p, ix, qd, P, f.p, p.p, v.p, t.p, u.p, bx.p, by.p, wx.p, wy.p, tables.p, stacks.p, n_end.p,
-		            recs.p, n_rec.p, n_chain.p, recs10.p, cx.p, cy.p, n_ca.p, stream);
-		DevBuf<uint64_t> rec_off(nb + 1);
-		tb = 0;
-		exscan_u32_to_u64(nullptr, tb, n_rec.p, rec_off.p, nb + 1, stream);
-		exscan_u32_to_u64(temp(tb), tb, n_rec.p, rec_off.p, nb + 1, stream);
-		uint64_t n_out = 0;
-		rec_off.download(&n_out, 1, stream, nb);
-		std::vector<uint32_t> h_chain(nb);
-		n_chain.download(h_chain.data(), nb, stream);
-		if (regs) {
-			const size_t at = regs->counts->size();
-			regs->counts->resize(at + nb);
-			n_rec.download(regs->counts->data() + at, nb, stream);
-		}
-		HIP_OK(hipStreamSynchronize(stream));
-		if (chains_per_read) BO.chains = h_chain;
-		if (P.chains) {
-			DevBuf<uint64_t> ca_off(nb + 1);
-			tb = 0;
-			exscan_u32_to_u64(nullptr, tb, n_ca.p, ca_off.p, nb + 1, stream);
-			exscan_u32_to_u64(temp(tb), tb, n_ca.p, ca_off.p, nb + 1, stream);
-			std::vector<uint64_t> h_off(nb + 1);
-			ca_off.download(h_off.data(), nb + 1, stream);
-			HIP_OK(hipStreamSynchronize(stream));
-			const uint64_t n_c = h_off[nb], base = regs->ca_off->back();
-			DevBuf<uint64_t> dx(n_c + 1), dy(n_c + 1);
-			launch_compact_anchors(r_aoff.p, nb, cx.p, cy.p, n_ca.p, ca_off.p, dx.p, dy.p, stream);
-			HIP_OK(hipGetLastError());
-			const size_t at = regs->ca_x->size();
-			regs->ca_x->resize(at + n_c), regs->ca_y->resize(at + n_c);
-			if (n_c) {
-				HIP_OK(hipMemcpyAsync(regs->ca_x->data() + at, dx.p, n_c * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-				HIP_OK(hipMemcpyAsync(regs->ca_y->data() + at, dy.p, n_c * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-			}
-			HIP_OK(hipStreamSynchronize(stream));
-			for (uint32_t i = 1; i <= nb; ++i) regs->ca_off->push_back(base + h_off[i]);
-		}
-		if (P.step2) {
-			DevBuf<OvlRec10> dense10(n_out + 1);
-			launch_compact_recs10(r_aoff.p, nb, P.min_cnt, recs10.p, n_rec.p, rec_off.p, dense10.p, stream);
-			HIP_OK(hipGetLastError());
-			st.hits_ms += tm.stop();
-			const size_t old10 = out10->size();
-			out10->resize(old10 + n_out);
-			if (n_out) HIP_OK(hipMemcpyAsync(out10->data() + old10, dense10.p, n_out * sizeof(OvlRec10), hipMemcpyDeviceToHost, stream));
-			HIP_OK(hipStreamSynchronize(stream));
-			st.chain_cells += h_cells;
-			for (uint32_t c : h_chain) st.chains += c;
-			st.overlaps += n_out;
-			return;
-		}
-		DevBuf<OvlRec> dense(n_out + 1);
-		launch_compact_recs(r_aoff.p, nb, P.min_cnt, recs.p, n_rec.p, rec_off.p, dense.p, stream);
-		HIP_OK(hipGetLastError());
-		st.hits_ms += tm.stop();
-		if (P.mode3 && n_out) {
-			// --mode 3: the records are provisional (see K5); extend both ends of every hit, then filter and name them
-			tm.start();
-			const uint64_t n_task = 2 * n_out;
-			DevBuf<uint32_t> need(n_task + 1);
-			need.zero(stream);
-			launch_ext_size(dense.p, n_out, Q.len.p, T.len.p, P, need.p, stream);
-			DevBuf<uint64_t> fr_off(n_task + 1);
-			exscan(need.p, fr_off.p, n_task + 1);
-			std::vector<uint64_t> h_off(n_task + 1);
-			fr_off.download(h_off.data(), n_task + 1, stream);
-			HIP_OK(hipStreamSynchronize(stream));
-			DevBuf<int32_t> ext_x(n_task), ext_y(n_task), fr;
-			uint64_t scratch = 256ULL << 20; // ints of furthest-reaching scratch per launch (1 GB)
-			if (const char *e = getenv("NDGPU_OVL_EXT_SCRATCH")) scratch = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));
-			for (uint64_t t0 = 0; t0 < n_task;) {
-				uint64_t t1 = t0;
-				while (t1 < n_task && (t1 == t0 || h_off[t1 + 1] - h_off[t0] <= scratch)) ++t1;
-				const uint64_t ints = h_off[t1] - h_off[t0];
-				if (fr.n < ints + 1) fr.alloc(ints + 1);
-				if (ints) HIP_OK(hipMemsetAsync(fr.p, 0, ints * sizeof(int32_t), stream));
-				launch_ext_ends(dense.p, t0, t1, Q.wp, Q.woff.p, Q.len.p, T.wp, T.woff.p, T.len.p, P, fr_off.p, h_off[t0], fr.p,
-				                ext_x.p, ext_y.p, stream);
-				++st.ext_launches;
-				t0 = t1;
-			}
-			for (uint64_t t = 0; t < n_task; ++t) st.ext_problems += h_off[t + 1] != h_off[t];
-			DevBuf<uint32_t> keep(n_out + 1);
-			keep.zero(stream);
-			launch_ext_apply(dense.p, n_out, ext_x.p, ext_y.p, Q.id.p, Q.len.p, T.id.p, T.len.p, P, keep.p, stream);
-			DevBuf<uint64_t> pos(n_out + 1);
-			exscan(keep.p, pos.p, n_out + 1);
-			uint64_t n_keep = 0;
-			pos.download(&n_keep, 1, stream, n_out);
-			HIP_OK(hipStreamSynchronize(stream));
-			DevBuf<OvlRec> fin(n_keep + 1);
-			launch_scatter_recs(dense.p, n_out, keep.p, pos.p, fin.p, stream);
-			HIP_OK(hipGetLastError());
-			dense = std::move(fin);
-			n_out = n_keep;
-			st.ext_ms += tm.stop();
-		}
-		const size_t old = out.size();
-		out.resize(old + n_out);
-		if (n_out) HIP_OK(hipMemcpyAsync(out.data() + old, dense.p, n_out * sizeof(OvlRec), hipMemcpyDeviceToHost, stream));
-		HIP_OK(hipStreamSynchronize(stream));
-		st.chain_cells += h_cells;
-		for (uint32_t c : h_chain) st.chains += c;
-		st.overlaps += n_out;
-
-		// debug view (last batch)
-		if (bi + 1 == ranges.size()) {
-			std::lock_guard<std::mutex> g(dbg_mu);
-			dbg_r0 = r0, dbg_n = nb;
-			dbg_aoff.assign(h_raoff.begin() + r0, h_raoff.begin() + r1 + 1);
-			for (auto &x : dbg_aoff) x -= a_base;
-			dbg_ax = std::move(ax); dbg_ay = std::move(ay); dbg_f = std::move(f); dbg_p = std::move(p);
-		}
-	};
-	if (n_lanes <= 1) {
-		for (size_t bi = 0; bi < ranges.size(); ++bi) run_batch(bi, stream, tmp);
-	} else {
-		HIP_OK(hipStreamSynchronize(stream));   // (the minimizers, their seed counts and offsets are final)
-		while (lane_streams.size() < n_lanes) {
-			hipStream_t ls = nullptr;
-			HIP_OK(hipStreamCreate(&ls));
-			lane_streams.push_back(ls);
-		}
-		std::atomic<size_t> next{0};
-		std::vector<std::exception_ptr> errs(n_lanes);
-		std::vector<std::thread> th;
-		for (size_t w = 0; w < n_lanes; ++w)
-			th.emplace_back([&, w] {
-				try {
-					HIP_OK(hipSetDevice(device));
-					DevBuf<uint8_t> lane_tmp;
-					for (;;) {
-						const size_t bi = next.fetch_add(1);
-						if (bi >= ranges.size()) break;
-						run_batch(bi, lane_streams[w], lane_tmp);
-					}
-					HIP_OK(hipStreamSynchronize(lane_streams[w]));
-				} catch (...) {
-					errs[w] = std::current_exception();
-					next = ranges.size();   // (the other lanes stop at their next batch)
-					(void)hipStreamSynchronize(lane_streams[w]);   // nothing of this lane is in flight when its blocks go back to the pool
-				}
-			});
-		for (auto &t : th) t.join();
-		for (auto &e : errs) if (e) std::rethrow_exception(e);
-	}
 	// the batches' outputs, in read order
 	for (BatchOut &BO : outs) {
 		if (out.empty()) out = std::move(BO.recs);   // (the usual call is one batch: its vector is the result)
@@ -1065,7 +1090,7 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 			if (out10->empty()) *out10 = std::move(BO.recs10);
 			else out10->insert(out10->end(), BO.recs10.begin(), BO.recs10.end());
 		}
-		if (chains_per_read) chains_per_read->insert(chains_per_read->end(), BO.chains.begin(), BO.chains.end());
+		if (rc.chains) rc.chains->insert(rc.chains->end(), BO.chains.begin(), BO.chains.end());
 		if (regs) {
 			regs->counts->insert(regs->counts->end(), BO.counts.begin(), BO.counts.end());
 			if (regs->ca_x) {
@@ -1080,9 +1105,9 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 		st.ext_ms += b.ext_ms, st.tie_reads += b.tie_reads, st.chain_cells += b.chain_cells, st.chains += b.chains, st.overlaps += b.overlaps;
 		st.batches += b.batches, st.ext_problems += b.ext_problems, st.ext_launches += b.ext_launches;
 	}
-	if (rep_per_read) {   // (K3a ran over every query minimizer before the first batch: the flags are whole)
-		rep_per_read->assign(n_q, 0u);
-		d_rep.download(rep_per_read->data(), n_q, stream);
+	if (rc.rep) {   // (K3a ran over every query minimizer before the first batch: the flags are whole)
+		rc.rep->assign(n_q, 0u);
+		d_rep.download(rc.rep->data(), n_q, stream);
 		HIP_OK(hipStreamSynchronize(stream));
 	}
 	return out10 ? (int64_t)out10->size() : (int64_t)out.size();
@@ -1129,14 +1154,8 @@ ndgpu_ovl_index *ndgpu_ovl_index_create(const ndgpu_ovl_opt *opt, uint32_t n_rea
 	ndgpu_ovl_index *h = nullptr;
 	try {
 		setenv("GPU_MAX_HW_QUEUES", "16", 0); // see csrc/device_runtime.hip: the process may go on to drive 8 consensus streams
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-			fprintf(stderr, "[ndgpu_overlap] no HIP device: the overlap engine has no CPU path\n");
-			return nullptr;
-		}
-		int dev = 0;
-		if (const char *e = getenv("NDGPU_DEVICE")) dev = atoi(e);
-		HIP_OK(hipSetDevice(dev));
+		const int dev = select_device(false);
+		if (dev < 0) return nullptr;
 		if (!getenv("NDGPU_SPIN_SYNC")) (void)hipSetDeviceFlags(hipDeviceScheduleBlockingSync);  // (a waiting host thread sleeps: see device_runtime.hip)
 		h = new ndgpu_ovl_index();
 		h->e.device = dev;
@@ -1182,9 +1201,7 @@ int64_t ndgpu_ovl_map2(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32_t mid
 		std::vector<OvlRec10> out;
 		int64_t n = h->e.map(*opt, mid_occ, n_reads, words, n_words, word_off, lens, ids, none, &out);
 		if (n < 0) return n;
-		static_assert(sizeof(OvlRec10) == sizeof(ndgpu_ovl_rec10), "record layout");
-		*recs = (ndgpu_ovl_rec10*)malloc(sizeof(ndgpu_ovl_rec10) * (size_t)(n ? n : 1));
-		if (n) memcpy(*recs, out.data(), sizeof(ndgpu_ovl_rec10) * (size_t)n);
+		*recs = malloc_copy<ndgpu_ovl_rec10>(out);
 		return n;
 	} catch (...) {
 		return -2;
@@ -1202,9 +1219,7 @@ int64_t ndgpu_ovl_map(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32_t mid_
 		std::vector<OvlRec> out;
 		int64_t n = h->e.map(*opt, mid_occ, n_reads, words, n_words, word_off, lens, ids, out);
 		if (n < 0) return n;
-		static_assert(sizeof(OvlRec) == sizeof(ndgpu_ovl_rec), "record layout");
-		*recs = (ndgpu_ovl_rec*)malloc(sizeof(ndgpu_ovl_rec) * (size_t)(n ? n : 1));
-		if (n) memcpy(*recs, out.data(), sizeof(ndgpu_ovl_rec) * (size_t)n);
+		*recs = malloc_copy<ndgpu_ovl_rec>(out);
 		return n;
 	} catch (...) {
 		return -2;
@@ -1230,10 +1245,8 @@ int64_t ndgpu_ovl_map_regs(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32_t
 		int64_t n = h->e.map(*opt, mid_occ, n_reads, words, n_words, word_off, lens, ids, out, nullptr, &rg);
 		if (n < 0) return n;
 		if (cnt.size() != n_reads) cnt.resize(n_reads, 0u);
-		*recs = (ndgpu_ovl_rec*)malloc(sizeof(ndgpu_ovl_rec) * (size_t)(n ? n : 1));
-		*counts = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n_reads ? n_reads : 1));
-		if (n) memcpy(*recs, out.data(), sizeof(ndgpu_ovl_rec) * (size_t)n);
-		if (n_reads) memcpy(*counts, cnt.data(), sizeof(uint32_t) * n_reads);
+		*recs = malloc_copy<ndgpu_ovl_rec>(out);
+		*counts = malloc_copy<uint32_t>(cnt);
 		return n;
 	} catch (...) {
 		return -2;
@@ -1262,16 +1275,9 @@ int64_t ndgpu_ovl_map_chains(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32
 		if (n < 0) return n;
 		if (cnt.size() != n_reads) cnt.resize(n_reads, 0u);
 		if (off.size() != (size_t)n_reads + 1) off.resize((size_t)n_reads + 1, off.empty() ? 0 : off.back());
-		*chains = (ndgpu_ovl_rec*)malloc(sizeof(ndgpu_ovl_rec) * (size_t)(n ? n : 1));
-		*counts = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(n_reads ? n_reads : 1));
-		*ax = (uint64_t*)malloc(sizeof(uint64_t) * (x.size() ? x.size() : 1));
-		*ay = (uint64_t*)malloc(sizeof(uint64_t) * (y.size() ? y.size() : 1));
-		*a_off = (uint64_t*)malloc(sizeof(uint64_t) * ((size_t)n_reads + 1));
-		if (!*chains || !*counts || !*ax || !*ay || !*a_off) return -2;
-		if (n) memcpy(*chains, out.data(), sizeof(ndgpu_ovl_rec) * (size_t)n);
-		if (n_reads) memcpy(*counts, cnt.data(), sizeof(uint32_t) * n_reads);
-		if (!x.empty()) memcpy(*ax, x.data(), sizeof(uint64_t) * x.size()), memcpy(*ay, y.data(), sizeof(uint64_t) * y.size());
-		memcpy(*a_off, off.data(), sizeof(uint64_t) * ((size_t)n_reads + 1));
+		*chains = malloc_copy<ndgpu_ovl_rec>(out);
+		*counts = malloc_copy<uint32_t>(cnt);
+		*ax = malloc_copy<uint64_t>(x), *ay = malloc_copy<uint64_t>(y), *a_off = malloc_copy<uint64_t>(off);
 		return n;
 	} catch (...) {
 		return -2;
@@ -1364,7 +1370,7 @@ int64_t ndgpu_2bit_index(const uint32_t *w, uint64_t n_words, uint32_t *ids, uin
 void ndgpu_ovl_free(void *p) { free(p); }
 
 // 1 if an entry point has failed for lack of device memory since the last call of this function (the caller may free
-// memory and try again), 2 for another allocation error, 0 otherwise; reading it clears it
+// memory and try again), 2 for another failed device operation, 0 otherwise; reading it clears it
 int ndgpu_ovl_last_error(void) { return ndovl::last_error_take(); }
 
 // device bytes of the library's block pool: in use now, cached for reuse, the most that ever were in use at once
@@ -1376,9 +1382,7 @@ int ndgpu_ovl_words_resident(const uint32_t *words, uint64_t n_words)
 {
 	if (!words || !n_words) return -1;
 	try {
-		int device = 0;
-		if (const char *d = getenv("NDGPU_DEVICE")) device = atoi(d);
-		HIP_OK(hipSetDevice(device));
+		(void)select_device(false, false);   // (no look at the device count here: without a device the call fails at hipSetDevice)
 		{
 			std::lock_guard<std::mutex> g(ndovl::g_res_mu);
 			for (const ndovl::ResidentWords &r : ndovl::g_resident)
@@ -1417,11 +1421,7 @@ int64_t ndgpu_pack_2bit(uint32_t n_reads, const uint8_t *ascii, uint64_t n_bytes
 {
 	if (!n_reads) return 0;
 	try {
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { fprintf(stderr, "[ndgpu_overlap] no HIP device\n"); return -1; }
-		int device = 0;
-		if (const char *d = getenv("NDGPU_DEVICE")) device = atoi(d);
-		HIP_OK(hipSetDevice(device));
+		if (select_device(false) < 0) return -1;
 		hipStream_t st;
 		HIP_OK(hipStreamCreate(&st));
 		const uint64_t n_words = word_off[n_reads - 1] + ((uint64_t)lens[n_reads - 1] + 15) / 16;
@@ -1448,23 +1448,19 @@ int64_t ndgpu_ovl_sketch(const ndgpu_ovl_opt *opt, uint32_t n_reads, const uint3
 	*x = *y = nullptr;
 	if (const char *msg = check_opt(*opt)) { fprintf(stderr, "[ndgpu_overlap] %s\n", msg); return -1; }
 	try {
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { fprintf(stderr, "[ndgpu_overlap] no HIP device\n"); return -1; }
 		Engine e;
-		if (const char *d = getenv("NDGPU_DEVICE")) e.device = atoi(d);
-		HIP_OK(hipSetDevice(e.device));
+		if ((e.device = select_device(false)) < 0) return -1;
 		HIP_OK(ndovl::create_stage_stream(&e.stream));
-		e.P = to_params(*opt);
 		std::vector<uint32_t> ids(n_reads, 0);
 		ReadSetDev R;
 		R.upload(n_reads, words, n_words, word_off, lens, ids.data(), e.stream);
 		Sketch S;
-		e.sketch(R, rid_is_index, false, S);
+		e.sketch(to_params(*opt), R, rid_is_index, false, S);
 		*x = (uint64_t*)malloc(8 * (S.n + 1)), *y = (uint64_t*)malloc(8 * (S.n + 1));
 		S.x.download(*x, S.n, e.stream); S.y.download(*y, S.n, e.stream); S.off.download(off, n_reads + 1, e.stream);
 		HIP_OK(hipStreamSynchronize(e.stream));
 		const int64_t n = (int64_t)S.n;
-		S = Sketch(); R = ReadSetDev(); e.tmp.release();
+		S = Sketch(); R = ReadSetDev(); e.tmp.buf.release();
 		(void)hipStreamDestroy(e.stream);
 		return n;
 	} catch (...) {
@@ -1485,12 +1481,13 @@ int64_t ndgpu_ovl_debug_anchors(ndgpu_ovl_index *h, uint32_t q, uint64_t **ax, u
 {
 	Engine &e = h->e;
 	*ax = *ay = nullptr, *f = *p = nullptr;
-	if (q < e.dbg_r0 || q >= e.dbg_r0 + e.dbg_n) return -1;
-	const uint64_t a0 = e.dbg_aoff[q - e.dbg_r0], n = e.dbg_aoff[q - e.dbg_r0 + 1] - a0;
+	const DebugView &d = e.dbg;
+	if (q < d.r0 || q >= d.r0 + d.n) return -1;
+	const uint64_t a0 = d.aoff[q - d.r0], n = d.aoff[q - d.r0 + 1] - a0;
 	*ax = (uint64_t*)malloc(8 * (n + 1)), *ay = (uint64_t*)malloc(8 * (n + 1));
 	*f = (int32_t*)malloc(4 * (n + 1)), *p = (int32_t*)malloc(4 * (n + 1));
-	e.dbg_ax.download(*ax, n, e.stream, a0); e.dbg_ay.download(*ay, n, e.stream, a0);
-	e.dbg_f.download(*f, n, e.stream, a0); e.dbg_p.download(*p, n, e.stream, a0);
+	d.ax.download(*ax, n, e.stream, a0); d.ay.download(*ay, n, e.stream, a0);
+	d.f.download(*f, n, e.stream, a0); d.p.download(*p, n, e.stream, a0);
 	(void)hipStreamSynchronize(e.stream);
 	return (int64_t)n;
 }

@@ -540,31 +540,27 @@ void launch_shift_keys(const uint64_t *x, uint64_t *key, uint64_t n, hipStream_t
 // (the size query -- tmp == nullptr -- touches nothing; the call that works is a checked device operation)
 #define RP_CHECK(e) do { if (tmp && ndovl::fault_injected()) ndovl::device_check((int)hipErrorOutOfMemory, __func__); ndovl::device_check((int)(e), __func__); } while (0)
 
-int sort_pairs_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin, uint64_t *vout,
+void sort_pairs_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint64_t *vin, uint64_t *vout,
                    size_t n, unsigned begin_bit, unsigned end_bit, hipStream_t s)
 {
 	RP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s));
-	return 0;
 }
 
-int sort_keys_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, hipStream_t s)
+void sort_keys_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, hipStream_t s)
 {
 	RP_CHECK(rocprim::radix_sort_keys(tmp, tmp_bytes, kin, kout, n, 0, 32, s));
-	return 0;
 }
 
-int rle_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, size_t n, uint64_t *uniq, uint32_t *cnt, uint64_t *n_runs,
+void rle_u64(void *tmp, size_t &tmp_bytes, const uint64_t *kin, size_t n, uint64_t *uniq, uint32_t *cnt, uint64_t *n_runs,
             hipStream_t s)
 {
 	RP_CHECK(rocprim::run_length_encode(tmp, tmp_bytes, kin, (unsigned int)n, uniq, cnt, n_runs, s));
-	return 0;
 }
 
-int exscan_u32_to_u64(void *tmp, size_t &tmp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
+void exscan_u32_to_u64(void *tmp, size_t &tmp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
 {
 	auto it = rocprim::make_transform_iterator(in, [] __device__(uint32_t v) { return (uint64_t)v; });
 	RP_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-	return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -840,10 +836,9 @@ void launch_anchor_decode(const uint64_t *skey, uint64_t n, const KeyLayout &L, 
 	if (n) ND_LAUNCH(anchor_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, skey, n, L, ax, tie_flag, segval);
 }
 
-int incl_max_scan_u64(void *tmp, size_t &tmp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t s)
+void incl_max_scan_u64(void *tmp, size_t &tmp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t s)
 {
 	RP_CHECK(rocprim::inclusive_scan(tmp, tmp_bytes, in, out, n, rocprim::maximum<uint64_t>(), s));
-	return 0;
 }
 
 // K4 work units ("slabs"): runs of whole segments of one read, cut where the running anchor count since the read's

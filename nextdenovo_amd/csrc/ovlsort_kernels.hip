@@ -196,12 +196,11 @@ void launch_seed_start(const uint32_t *flag, const uint64_t *rank, uint64_t n, u
 	if (n) ND_LAUNCH(seed_start_kernel, GRID1(n), 0, s, flag, rank, n, start);
 }
 
-int sort_pairs_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n,
+void sort_pairs_u32(void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n,
                    hipStream_t s)
 {
 	if (tmp && fault_injected()) device_check((int)hipErrorOutOfMemory, __func__);
 	device_check((int)rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0, 32, s), __func__);
-	return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
