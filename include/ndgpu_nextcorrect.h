@@ -139,6 +139,16 @@ int ndgpu_correct_batch(int n_piles, char ***seqs, unsigned int **aln_start, uns
 typedef struct ndgpu_poa_job { const char *const *seqs; const uint16_t *len; int32_t seq_count; } ndgpu_poa_job;
 int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out);
 
+/* The 8-mer ranking of a low-quality region's candidates (reference lib/nextcorrect.c:281-337, 405-440) for many candidate sets in
+ * one call, one wavefront per set on the device.  A job is seq_count (1..40) sequences of len[k] bytes (0..9,999) in input order;
+ * only the first and last 40 bytes of a sequence are read.  res[i].order[r]: the input index of the sequence at rank r,
+ * res[i].kscore[r]: its score (entries from seq_count on are 0), res[i].tail: whether the tail windows were ranked too.
+ * flags bit 0: compute with the engine's own host routine instead of the device.
+ * Returns 0; < 0, with nothing written, when a job has seq_count outside 1..40 or no device can be used.  n = 0 is valid. */
+typedef struct ndgpu_rank_job { const char *const *seqs; const uint16_t *len; int32_t seq_count; } ndgpu_rank_job;
+typedef struct ndgpu_rank_result { uint8_t order[40]; uint16_t kscore[40]; int32_t tail; } ndgpu_rank_result;
+int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank_result *res);
+
 /* The output loop of lib/nextcorrect.py:236-260 (without -s) over finished records: for every ids[k] in order, a record with
  * len >= min_len_seed, len > 4 and identity >= min_ratio is written to fd_out as ">NAME LEN IDENTITY\nBASES\n" (IDENTITY as Python's
  * '%f') and, if fd_idx >= 0, "NAME\tOFFSET\tLEN\n" to fd_idx (OFFSET = where the bases start in the output file); any other record
@@ -226,6 +236,10 @@ typedef struct {
     uint64_t poa_launches;     /* kernel launches */
     uint64_t poa_cells;        /* (X + 1)(Y + 1) alignment cells filled */
     double poa_ms;             /* HIP-event time of the POA kernels */
+    uint64_t rank_jobs;        /* candidate sets ranked on the device (ndgpu_lq_rank_batch, the engine's regions with NDGPU_RANK_DEVICE=1) */
+    uint64_t rank_tail;        /* of which took the tail pass */
+    uint64_t rank_launches;    /* launches of the ranking kernel */
+    double rank_ms;            /* HIP-event time of the ranking kernel */
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);

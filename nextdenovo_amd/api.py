@@ -24,6 +24,16 @@ class PoaJob(C.Structure):
     _fields_ = [("seqs", C.POINTER(C.c_char_p)), ("len", C.POINTER(C.c_uint16)), ("seq_count", C.c_int32)]
 
 
+class RankJob(C.Structure):
+    # ndgpu_rank_job
+    _fields_ = [("seqs", C.POINTER(C.c_char_p)), ("len", C.POINTER(C.c_uint16)), ("seq_count", C.c_int32)]
+
+
+class RankResult(C.Structure):
+    # ndgpu_rank_result
+    _fields_ = [("order", C.c_uint8 * 40), ("kscore", C.c_uint16 * 40), ("tail", C.c_int32)]
+
+
 PILES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.c_int)   # ndgpu_piles_done_fn
 
 
@@ -41,7 +51,8 @@ class Stats(C.Structure):
                 ("lq_bases", C.c_uint64), ("lq_out", C.c_uint64), ("lq_jobs", C.c_uint64), ("lq_repairs", C.c_uint64),
                 ("tb_tasks", C.c_uint64), ("tb_walkers", C.c_uint64), ("tb_fallbacks", C.c_uint64),
                 ("poa_jobs", C.c_uint64), ("poa_declined", C.c_uint64), ("poa_rounds", C.c_uint64), ("poa_launches", C.c_uint64),
-                ("poa_cells", C.c_uint64), ("poa_ms", C.c_double)]
+                ("poa_cells", C.c_uint64), ("poa_ms", C.c_double),
+                ("rank_jobs", C.c_uint64), ("rank_tail", C.c_uint64), ("rank_launches", C.c_uint64), ("rank_ms", C.c_double)]
 
 
 def lib_path() -> str:
@@ -87,6 +98,8 @@ def _bind(lib):
     lib.ndgpu_write_records.restype = C.c_int
     lib.ndgpu_poa_batch.argtypes = [C.POINTER(PoaJob), C.c_int, C.POINTER(C.c_void_p)]
     lib.ndgpu_poa_batch.restype = C.c_int
+    lib.ndgpu_lq_rank_batch.argtypes = [C.POINTER(RankJob), C.c_int, C.c_int, C.POINTER(RankResult)]
+    lib.ndgpu_lq_rank_batch.restype = C.c_int
     lib.ndgpu_get_stats.argtypes = [C.POINTER(Stats)]
     lib.ndgpu_reset_stats.argtypes = []
     lib.ndgpu_device_count.restype = C.c_int
@@ -336,6 +349,28 @@ def poa_batch(jobs):
         res.append(C.string_at(out[i]))
         libc.free(out[i])
     return res
+
+
+def lq_rank_batch(jobs, host=False):
+    """jobs: [[bytes, ...]] (1..40 sequences each) -> [(order, kscore, tail)]: the 8-mer ranking of every job's sequences through
+    ndgpu_lq_rank_batch (lib/nextcorrect.c:281-337, 405-440) -- order[r] = the input index of the sequence at rank r, kscore[r] its
+    score, tail = whether the tail windows were ranked too.  host=True: the engine's own host routine instead of the device."""
+    lib = load()
+    n = len(jobs)
+    arr = (RankJob * max(1, n))()
+    keep = []
+    for i, seqs in enumerate(jobs):
+        k = len(seqs)
+        cs = (C.c_char_p * max(1, k))()
+        cs[:k] = list(seqs)
+        ln = (C.c_uint16 * max(1, k))(*[len(s) for s in seqs])
+        keep.append((cs, ln))
+        arr[i] = RankJob(C.cast(cs, C.POINTER(C.c_char_p)), C.cast(ln, C.POINTER(C.c_uint16)), k)
+    res = (RankResult * max(1, n))()
+    rc = lib.ndgpu_lq_rank_batch(arr, n, 1 if host else 0, res)
+    if rc != 0:
+        raise RuntimeError("ndgpu_lq_rank_batch failed (%d)" % rc)
+    return [(list(res[i].order[:len(jobs[i])]), list(res[i].kscore[:len(jobs[i])]), int(res[i].tail)) for i in range(n)]
 
 
 def stats() -> dict:

@@ -819,6 +819,51 @@ int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) {
     return rc;
 }
 
+// The 8-mer ranking of a batch of candidate sets: K14 on the device (DeviceAligner::run_rank), or -- flags bit 0 -- the engine's own
+// host routine (lq_rank_host)
+int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank_result *res) {
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; i++)
+        if (jobs[i].seq_count < 1 || jobs[i].seq_count > kLqRankMax) return -2;
+    std::vector<RankReq> reqs((size_t)n);
+    for (int i = 0; i < n; i++) reqs[i].seqs = jobs[i].seqs, reqs[i].len = jobs[i].len, reqs[i].n = jobs[i].seq_count;
+    if (flags & 1) {
+        parallel_for((size_t)n, effective_cpus(), [&](size_t i) {
+            RankReq &rq = reqs[i];
+            lq_rank_host(rq.seqs, rq.len, rq.n, rq.order, rq.kscore, &rq.tail);
+        });
+    } else {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+            fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_lq_rank_batch ranks on the device unless flags bit 0 is set\n");
+            return -1;
+        }
+        // (out of device memory: the range is halved until it fits)
+        std::vector<std::pair<size_t, size_t>> todo{{0, (size_t)n}};
+        while (!todo.empty()) {
+            const auto [a, b] = todo.back();
+            todo.pop_back();
+            try {
+                HipBackend be(0, 1);
+                be.run_rank(reqs.data() + a, b - a);
+            } catch (const DeviceOom &) {
+                DeviceAligner::context(0).release_memory();
+                DeviceAligner::forget_sizes();
+                if (b - a <= 1) return -3;
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        memset(&res[i], 0, sizeof(res[i]));
+        memcpy(res[i].order, reqs[i].order, (size_t)reqs[i].n);
+        memcpy(res[i].kscore, reqs[i].kscore, (size_t)reqs[i].n * sizeof(uint16_t));
+        res[i].tail = reqs[i].tail;
+    }
+    return 0;
+}
+
 void ndgpu_get_stats(ndgpu_stats *o) {
     RuntimeStats s = DeviceAligner::total_stats();
     o->tasks = s.tasks;
@@ -858,6 +903,7 @@ void ndgpu_get_stats(ndgpu_stats *o) {
     o->tb_tasks = s.tb_tasks, o->tb_walkers = s.tb_walkers, o->tb_fallbacks = s.tb_fallbacks;
     o->poa_jobs = s.poa_jobs, o->poa_declined = s.poa_declined, o->poa_rounds = s.poa_rounds, o->poa_launches = s.poa_launches;
     o->poa_cells = s.poa_cells, o->poa_ms = s.poa_ms;
+    o->rank_jobs = s.rank_jobs, o->rank_tail = s.rank_tail, o->rank_launches = s.rank_launches, o->rank_ms = s.rank_ms;
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }

@@ -292,49 +292,111 @@ struct KmerBins {
     uint16_t *data() { return v.data(); }
 };
 
-void count_kmers(const LqRegion &lq, KmerBins &kb, int c, int from_tail) {
+// The sequences are seen through seq_bytes / s.len, so that the routines serve the engine's LqSeq records and the plain views of
+// lq_rank_host alike.
+inline const char *seq_bytes(const LqSeq &s) { return s.seq.data(); }
+
+template <class S>
+void count_kmers(const S *seqs, int len, KmerBins &kb, int c, int from_tail) {
     uint16_t *bins = kb.v.data();
     for (uint16_t t : kb.touched) bins[t] = 0;
     kb.touched.clear();
-    const int lim = std::min(lq.len, c);
+    const int lim = std::min(len, c);
     for (int j = 0; j < lim; j++) {
-        const LqSeq &s = lq.seqs[j];
+        const S &s = seqs[j];
         if (s.len < kKmerLen) continue;
+        const char *q = seq_bytes(s);
         const int off = from_tail && s.len > kKmerRange ? s.len - kKmerRange : 0;
         const int n = std::min<int>(s.len, kKmerRange) - kKmerLen;
         uint16_t km = 0;
         for (int k = 0; k < n; k++) {
-            if (k) km = (uint16_t)(km << 2 | base_code(s.seq[off + k + kKmerLen - 1]));
+            if (k) km = (uint16_t)(km << 2 | base_code(q[off + k + kKmerLen - 1]));
             else
-                for (int x = 0; x < kKmerLen; x++) km = (uint16_t)(km << 2 | base_code(s.seq[off + x]));
+                for (int x = 0; x < kKmerLen; x++) km = (uint16_t)(km << 2 | base_code(q[off + x]));
             if (bins[km]++ == 0) kb.touched.push_back(km);
         }
     }
 }
 
-void count_kscore(LqRegion &lq, const uint16_t *bins, int from_tail) {
-    for (int j = 0; j < lq.len; j++) {
-        LqSeq &s = lq.seqs[j];
+template <class S>
+void count_kscore(S *seqs, int len, const uint16_t *bins, int from_tail) {
+    for (int j = 0; j < len; j++) {
+        S &s = seqs[j];
         s.kscore = 0;
         if (s.len < kKmerLen) continue;
+        const char *q = seq_bytes(s);
         const int off = from_tail && s.len > kKmerRange ? s.len - kKmerRange : 0;
         const int n = std::min<int>(s.len, kKmerRange) - kKmerLen;
         uint16_t km = 0;
         for (int k = 0; k < n; k++) {
-            if (k) km = (uint16_t)(km << 2 | base_code(s.seq[off + k + kKmerLen - 1]));
+            if (k) km = (uint16_t)(km << 2 | base_code(q[off + k + kKmerLen - 1]));
             else
-                for (int x = 0; x < kKmerLen; x++) km = (uint16_t)(km << 2 | base_code(s.seq[off + x]));
+                for (int x = 0; x < kKmerLen; x++) km = (uint16_t)(km << 2 | base_code(q[off + x]));
             s.kscore = (uint16_t)(s.kscore + bins[km]);
         }
     }
 }
 
-void sort_by_kscore_desc(LqRegion &lq) {
+template <class S>
+void sort_by_kscore_desc(S *seqs, int len) {
     // qsort(compare_seq_by_kscore) (lib/nextcorrect.c:254-258,413); glibc qsort is a
     // stable merge sort, so the permutation equals std::stable_sort's.
-    std::stable_sort(lq.seqs.begin(), lq.seqs.begin() + lq.len,
-                     [](const LqSeq &a, const LqSeq &b) { return a.kscore > b.kscore; });
+    std::stable_sort(seqs, seqs + len, [](const S &a, const S &b) { return a.kscore > b.kscore; });
 }
+
+void count_kmers(const LqRegion &lq, KmerBins &kb, int c, int from_tail) { count_kmers(lq.seqs.data(), lq.len, kb, c, from_tail); }
+void count_kscore(LqRegion &lq, const uint16_t *bins, int from_tail) { count_kscore(lq.seqs.data(), lq.len, bins, from_tail); }
+void sort_by_kscore_desc(LqRegion &lq) { sort_by_kscore_desc(lq.seqs.data(), lq.len); }
+
+// The ranking of a raw-read region's candidates, stated once (lib/nextcorrect.c:405-440): the head windows ranked against the first
+// candidate, then against the ten best; where the best one is long (or long-ish and scores low) the same over the tail windows
+// with candidate 0 in front (find_ref_lqseq: a swap), the two scores added.  K14 (lq_kernels.hip: lq_rank_kernel) computes the same.
+struct RankView {
+    uint16_t order, kscore, len;
+    const char *seq;
+};
+inline const char *seq_bytes(const RankView &s) { return s.seq; }
+
+void rank_views(RankView *v, int n, KmerBins &bins, int *tail) {
+    count_kmers(v, n, bins, 1, 0);
+    count_kscore(v, n, bins.data(), 0);
+    sort_by_kscore_desc(v, n);
+    count_kmers(v, n, bins, kKmerMaxSeq, 0);
+    count_kscore(v, n, bins.data(), 0);
+    const unsigned kmaxscore = v[0].kscore, kmaxlen = v[0].len;
+    *tail = 0;
+    if (kmaxlen > 500 || (kmaxlen > 200 && kmaxscore < 200)) {
+        *tail = 1;
+        uint16_t saved[kLqCanMax];
+        if (v[0].order) {
+            for (int j = 1; j < n; j++)
+                if (!v[j].order) {
+                    std::swap(v[0], v[j]);
+                    break;
+                }
+        }
+        for (int j = 0; j < n; j++) saved[v[j].order] = v[j].kscore;
+        count_kmers(v, n, bins, 1, 1);
+        count_kscore(v, n, bins.data(), 1);
+        sort_by_kscore_desc(v, n);
+        count_kmers(v, n, bins, kKmerMaxSeq, 1);
+        count_kscore(v, n, bins.data(), 1);
+        for (int j = 0; j < n; j++) v[j].kscore = (uint16_t)(v[j].kscore + saved[v[j].order]);
+    }
+    sort_by_kscore_desc(v, n);
+}
+
+}  // namespace
+
+void lq_rank_host(const char *const *seqs, const uint16_t *len, int n, uint8_t *order, uint16_t *kscore, int *tail) {
+    static thread_local KmerBins bins;
+    RankView v[kLqCanMax];
+    for (int i = 0; i < n; i++) v[i] = RankView{(uint16_t)i, 0, len[i], seqs[i]};
+    rank_views(v, n, bins, tail);
+    for (int r = 0; r < n; r++) order[r] = (uint8_t)v[r].order, kscore[r] = v[r].kscore;
+}
+
+namespace {
 
 // ---- terminal SSR clipping (lib/nextcorrect.c:2008-2128)
 int terminal_ssr(int *bins, int range, int klen, const char *seq, int s) {
@@ -561,6 +623,7 @@ class PileImpl {
             return;
         }
         extract.slot = main.slot;
+        extract.rank = rank_on_device() && prm.read_type != 3;  // (HiFi: its ranking sits behind the phasing, on the host)
         extract.regions.resize(regions.size());
         for (size_t i = 0; i < regions.size(); i++) {
             extract.regions[i].start = regions[i].start;
@@ -585,6 +648,11 @@ class PileImpl {
     std::vector<PoaPending> poa_pending;
     static bool poa_as_request() {
         static const bool on = getenv("NDGPU_POA_DEVICE") != nullptr && atoi(getenv("NDGPU_POA_DEVICE")) != 0;
+        return on;
+    }
+    // The 8-mer ranking of the regions' candidates by the backend, behind its extraction (K14; opt-in, see DESIGN.md section 0a''').
+    static bool rank_on_device() {
+        static const bool on = getenv("NDGPU_RANK_DEVICE") != nullptr && atoi(getenv("NDGPU_RANK_DEVICE")) != 0;
         return on;
     }
     void post_poa(size_t region, std::vector<std::string> &&in, int add_len, bool check_len) {
@@ -1106,7 +1174,6 @@ class PileImpl {
     // gathered by the backend
     int lqseqs_from_candidates() {
         int max_aln_length = 0;
-        KmerBins bins;
         for (size_t ri = 0; ri < regions.size(); ri++) {
             LqRegion &lq = regions[ri];
             RegionReq &rq = extract.regions[ri];
@@ -1128,32 +1195,29 @@ class PileImpl {
                 lq.len = 0;
                 continue;
             }
-            count_kmers(lq, bins, 1, 0);
-            count_kscore(lq, bins.data(), 0);
-            sort_by_kscore_desc(lq);
-            count_kmers(lq, bins, kKmerMaxSeq, 0);
-            count_kscore(lq, bins.data(), 0);
-            unsigned klastscore, kmaxscore = lq.seqs[0].kscore;
-            unsigned kmaxlen = lq.seqs[0].len, kminlen;
-            if (kmaxlen > 500 || (kmaxlen > 200 && kmaxscore < 200)) {
-                uint16_t saved[kLqCanMax];
-                if (lq.seqs[0].order) {
-                    for (int j = 1; j < lq.len; j++)
-                        if (!lq.seqs[j].order) {
-                            std::swap(lq.seqs[0], lq.seqs[j]);
-                            break;
-                        }
+            // the ranking: the backend's (K14 behind K11, where the region carries one) or the host routine's -- either way as
+            // (order, kscore), in which the candidates are then laid out
+            unsigned klastscore, kmaxscore, kmaxlen, kminlen;
+            {
+                uint8_t order_h[kLqCanMax];
+                uint16_t kscore_h[kLqCanMax];
+                const uint8_t *order = rq.rank_order;
+                const uint16_t *kscore = rq.rank_kscore;
+                if (!rq.ranked) {
+                    const char *ptr[kLqCanMax];
+                    uint16_t len[kLqCanMax];
+                    int tail = 0;
+                    for (int j = 0; j < lq.len; j++) ptr[j] = lq.seqs[j].seq.data(), len[j] = lq.seqs[j].len;
+                    lq_rank_host(ptr, len, lq.len, order_h, kscore_h, &tail);
+                    order = order_h, kscore = kscore_h;
                 }
-                for (int j = 0; j < lq.len; j++) saved[lq.seqs[j].order] = lq.seqs[j].kscore;
-                count_kmers(lq, bins, 1, 1);
-                count_kscore(lq, bins.data(), 1);
-                sort_by_kscore_desc(lq);
-                count_kmers(lq, bins, kKmerMaxSeq, 1);
-                count_kscore(lq, bins.data(), 1);
-                for (int j = 0; j < lq.len; j++)
-                    lq.seqs[j].kscore = (uint16_t)(lq.seqs[j].kscore + saved[lq.seqs[j].order]);
+                std::vector<LqSeq> ranked((size_t)lq.len);
+                for (int j = 0; j < lq.len; j++) {
+                    ranked[j] = std::move(lq.seqs[order[j]]);
+                    ranked[j].kscore = kscore[j];
+                }
+                lq.seqs.swap(ranked);
             }
-            sort_by_kscore_desc(lq);
             kminlen = kmaxlen = lq.seqs[0].len;
             klastscore = kmaxscore = lq.seqs[0].kscore;
             int j, k;

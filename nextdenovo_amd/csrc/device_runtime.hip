@@ -599,6 +599,7 @@ RuntimeStats DeviceAligner::total_stats() {
         t.tb_tasks += s.tb_tasks; t.tb_walkers += s.tb_walkers; t.tb_fallbacks += s.tb_fallbacks;
         t.poa_jobs += s.poa_jobs; t.poa_declined += s.poa_declined; t.poa_rounds += s.poa_rounds; t.poa_launches += s.poa_launches;
         t.poa_cells += s.poa_cells; t.poa_ms += s.poa_ms;
+        t.rank_jobs += s.rank_jobs; t.rank_tail += s.rank_tail; t.rank_launches += s.rank_launches; t.rank_ms += s.rank_ms;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -2026,7 +2027,71 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
         if (!reqs[i]->done && !reqs[i]->failed) S.stats.poa_declined++;
 }
 
-void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
+// ---- the 8-mer ranking as a batch (K14): the problems' sequences go up as one pool, laid out as K11 leaves a region's candidates
+// (RegionDev::cand_off / cand_len), one launch per slice of at most kRankSliceBytes, the records come back in one copy.
+void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    std::unique_lock<std::mutex> dbg_lock;
+    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
+    std::lock_guard<std::mutex> lock(S.mu);
+    HIP_CHECK(hipSetDevice(S.device));
+    hipStream_t st = S.stream;
+    constexpr size_t kRankSliceBytes = (size_t)256 << 20, kRankSliceJobs = 1 << 20;
+    std::vector<RegionDev> regs;
+    std::vector<char> pool;
+    for (size_t a = 0; a < n;) {
+        regs.clear(), pool.clear();
+        size_t b = a;
+        for (; b < n && b - a < kRankSliceJobs; b++) {
+            const RankReq &rq = reqs[b];
+            size_t bytes = 0;
+            for (int k = 0; k < rq.n; k++) bytes += rq.len[k];
+            if (b > a && pool.size() + bytes > kRankSliceBytes) break;
+            RegionDev g;
+            memset(&g, 0, sizeof(g));
+            g.n_ok = (uint32_t)rq.n;
+            g.want_rank = 1;
+            for (int k = 0; k < rq.n; k++) {
+                g.cand_off[k] = (uint32_t)pool.size();
+                g.cand_len[k] = rq.len[k];
+                pool.insert(pool.end(), rq.seqs[k], rq.seqs[k] + rq.len[k]);
+            }
+            regs.push_back(g);
+        }
+        S.d_regions.reserve(regs.size());
+        S.d_strpool.reserve(pool.size() + 1);
+        S.h2d(S.d_regions.p, regs.data(), regs.size() * sizeof(RegionDev), st);
+        S.h2d(S.d_strpool.p, pool.data(), pool.size(), st);
+        HIP_CHECK(hipEventRecord(S.evs[5], st));
+        NDGPU_DBG(st, "rank: %zu problems, %zu bytes", regs.size(), pool.size());
+        launch_lq_rank(S.d_regions.p, S.d_strpool.p, (unsigned long long)pool.size(), 1u, (int)regs.size(), st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(S.evs[6], st));
+        S.d2h(regs.data(), S.d_regions.p, regs.size() * sizeof(RegionDev), st);
+        S.sync_drain(st);
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
+        S.stats.rank_ms += ms;
+        S.stats.rank_launches++;
+        for (size_t i = a; i < b; i++) {
+            const RegionDev &g = regs[i - a];
+            RankReq &rq = reqs[i];
+            if (!g.ranked) {  // (cannot happen: every problem has 1..40 sequences inside the pool)
+                fprintf(stderr, "[ndgpu] FATAL: the ranking kernel left a problem of %d sequences\n", rq.n);
+                abort();
+            }
+            memcpy(rq.order, g.rank_order, sizeof(rq.order));
+            memcpy(rq.kscore, g.rank_kscore, sizeof(rq.kscore));
+            rq.tail = g.rank_tail;
+            S.stats.rank_jobs++;
+            S.stats.rank_tail += g.rank_tail;
+        }
+        a = b;
+    }
+}
+
+void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
     State &S = *s_;
     std::unique_lock<std::mutex> dbg_lock;
     if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
@@ -2034,6 +2099,7 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
     HIP_CHECK(hipSetDevice(S.device));
     hipStream_t st = S.stream;
     std::vector<RegionDev> regs;
+    bool rank = false;   // K14 behind K11: some pile of this launch takes a ranking
     for (size_t i = 0; i < n; i++)
         for (RegionReq &r : ep[i]->regions) {
             RegionDev g;
@@ -2043,6 +2109,9 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
             g.end = r.end;
             g.max_len = r.max_len;
             g.max_len0 = r.max_len0 ? r.max_len0 : r.max_len;
+            g.want_rank = offer_rank && ep[i]->rank ? 1 : 0;
+            rank = rank || g.want_rank;
+            r.ranked = false;
             regs.push_back(g);
         }
     if (regs.empty()) return;
@@ -2064,12 +2133,23 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
         launch_extract(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_tags.p, S.d_colidx.p, S.d_regions.p, S.d_strpool.p,
                        S.d_cursor.p, (unsigned long long)cap, (int)regs.size(), st);
         HIP_CHECK(hipEventRecord(S.evs[6], st));
+        // the ranking of the regions with five or more candidates (fewer: the engine drops the region), on the strings where K11
+        // left them; with a pool that was too small K14 leaves the regions it cannot read and runs again with K11
+        if (rank) {
+            launch_lq_rank(S.d_regions.p, S.d_strpool.p, (unsigned long long)cap, 5u, (int)regs.size(), st);
+            HIP_CHECK(hipEventRecord(S.evs[7], st));
+        }
         unsigned long long used = 0;
         S.d2h(&used, S.d_cursor.p, sizeof(used), st);
         S.sync_drain(st);
         float ms = 0;
         HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
         S.stats.extract_ms += ms;
+        if (rank) {
+            HIP_CHECK(hipEventElapsedTime(&ms, S.evs[6], S.evs[7]));
+            S.stats.rank_ms += ms;
+            S.stats.rank_launches++;
+        }
         if (used <= cap) {
             hstr.resize((size_t)used + 1);
             S.d2h(regs.data(), S.d_regions.p, regs.size() * sizeof(RegionDev), st);
@@ -2079,6 +2159,15 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
         }
         cap = (size_t)used + ((size_t)16 << 20);  // pool too small: rerun with the exact size
     }
+    {
+        uint64_t n_ranked = 0, n_tail = 0;
+        for (const RegionDev &g : regs) n_ranked += g.ranked ? 1 : 0, n_tail += g.ranked ? g.rank_tail : 0;
+        S.stats.rank_jobs += n_ranked, S.stats.rank_tail += n_tail;
+        static const bool trace = getenv("NDGPU_TRACE") != nullptr;
+        if (trace)
+            fprintf(stderr, "[ndgpu] extract: %zu regions, %llu ranked on the device, %llu tail passes\n", regs.size(),
+                    (unsigned long long)n_ranked, (unsigned long long)n_tail);
+    }
     std::vector<size_t> first(n + 1, 0);
     for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + ep[i]->regions.size();
     auto fill = [&](size_t a, size_t b) {
@@ -2087,6 +2176,12 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n) {
             for (RegionReq &r : ep[i]->regions) {
                 const RegionDev &g = regs[k++];
                 r.n_large = g.n_large;
+                r.ranked = g.ranked != 0;
+                if (r.ranked) {
+                    r.rank_tail = g.rank_tail;
+                    memcpy(r.rank_order, g.rank_order, sizeof(r.rank_order));
+                    memcpy(r.rank_kscore, g.rank_kscore, sizeof(r.rank_kscore));
+                }
                 r.cands.resize(g.n_ok);
                 r.cand_rank.resize(g.n_ok);
                 for (uint32_t c = 0; c < g.n_ok; c++) {

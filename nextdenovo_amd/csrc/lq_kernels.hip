@@ -29,6 +29,7 @@
 //
 // K13 poa_align  the pseudo-seeds themselves: one sequence of a region's POA against its graph, a batch of regions per launch (at the
 //             end of this file; DeviceAligner::run_poa drives it in lockstep rounds).
+// K14 lq_rank    the 8-mer ranking of a region's candidates, one wavefront per region, behind K11 (after K13 in this file).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -1024,6 +1025,161 @@ __global__ __launch_bounds__(NW * 64) void poa_align_kernel(PoaJobDev *__restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// K14: the 8-mer ranking of a region's candidates (consensus.cpp: lq_rank_host; lib/nextcorrect.c:281-337, 405-440), one wavefront
+// per region, right behind K11 on the strings K11 left in the pool (or on the pool of a batch of problems: DeviceAligner::run_rank).
+// A sequence gives min(len, 40) - 8 k-mers of its head window (offset 0) or its tail window (offset len - 40 beyond 40 bases), each
+// the 16 low bits of eight 3-bit codes shifted by two -- codes of 4 and more spill into the neighbour, as in the reference.
+// A pass counts the k-mers of the first min(n, c) sequences of the current order and scores every sequence with the sum of its own
+// k-mers' counts.  The reference counts in a 65,536-bin histogram; a pass touches at most 10 x 32 distinct k-mers, so the counts
+// live in a 512-slot open-addressing table in LDS (key and count in one word, filled with atomicCAS / atomicAdd: sums, whatever the
+// lane order).  The stable sort is a rank by counting: scores greater + equal scores earlier in the current order.
+// LDS: 1,600 B codes + 2,560 B k-mers + 2,048 B table + 400 B per-sequence state; the tail windows are staged over the head
+// windows, and only in the regions that take the tail pass.
+constexpr int kRankMax = 40, kRankWin = 40, kRankK = 8, kRankKm = kRankWin - kRankK, kRankTop = 10, kRankSlots = 512;
+
+struct RankLds {
+    uint32_t tab[kRankSlots];              // [31:16] k-mer, [15:0] count; 0: empty
+    uint32_t off[kRankMax];                // input order: pool offset, length
+    uint16_t len[kRankMax];
+    uint16_t km[kRankMax * kRankKm];       // input order: the staged window's k-mers
+    uint16_t sc[kRankMax], saved[kRankMax];  // sc: by position; saved: by input index
+    uint8_t code[kRankMax * kRankWin];     // input order: the staged window's byte codes
+    uint8_t ord[kRankMax];                 // position -> input index
+};
+
+// A/a 0, T/t 1, G/g 2, C/c 3, N 5, M 6, any other byte 4 (consensus.cpp: BaseLut)
+__device__ __forceinline__ uint32_t rank_code(uint32_t c) {
+    const uint32_t u = c & 0xdfu;   // (equals an upper-case letter only for that letter in either case)
+    return u == 'A' ? 0u : u == 'T' ? 1u : u == 'G' ? 2u : u == 'C' ? 3u : c == 'N' ? 5u : c == 'M' ? 6u : 4u;
+}
+__device__ __forceinline__ int rank_nkm(int len) { return len < kRankK ? 0 : (len < kRankWin ? len : kRankWin) - kRankK; }
+__device__ __forceinline__ uint32_t rank_slot(uint32_t km) { return (km * 0x9e3bu >> 4) & (uint32_t)(kRankSlots - 1); }
+
+// the window's k-mers of every sequence, input order
+__device__ __forceinline__ void rank_stage(RankLds &T, const unsigned char *__restrict__ pool, int n, int from_tail, int lane) {
+    for (int i = lane; i < n * kRankWin; i += 64) {
+        const int s = i / kRankWin, b = i - s * kRankWin, len = (int)T.len[s];
+        const int o = from_tail && len > kRankWin ? len - kRankWin : 0;
+        T.code[i] = b < len ? (uint8_t)rank_code(pool[(size_t)T.off[s] + (size_t)(o + b)]) : (uint8_t)0;
+    }
+    __syncthreads();
+    for (int i = lane; i < n * kRankKm; i += 64) {
+        const int s = i / kRankKm, k = i - s * kRankKm;
+        uint32_t km = 0;
+        if (k < rank_nkm((int)T.len[s])) {
+            const uint8_t *c = &T.code[s * kRankWin + k];
+#pragma unroll
+            for (int x = 0; x < kRankK; x++) km = km << 2 | c[x];
+        }
+        T.km[i] = (uint16_t)km;
+    }
+    __syncthreads();
+}
+
+// count the k-mers of positions [0, min(n, c)), score every position
+__device__ __forceinline__ void rank_pass(RankLds &T, int n, int c, int lane) {
+    for (int i = lane; i < kRankSlots; i += 64) T.tab[i] = 0u;
+    __syncthreads();
+    const int lim = n < c ? n : c;
+    for (int i = lane; i < lim * kRankKm; i += 64) {
+        const int p = i / kRankKm, k = i - p * kRankKm, s = (int)T.ord[p];
+        if (k >= rank_nkm((int)T.len[s])) continue;
+        const uint32_t km = T.km[s * kRankKm + k];
+        for (uint32_t h = rank_slot(km);; h = (h + 1u) & (uint32_t)(kRankSlots - 1)) {   // (<= 320 keys in 512 slots: an empty one exists)
+            uint32_t cur = T.tab[h];
+            if (cur == 0u) {
+                cur = atomicCAS(&T.tab[h], 0u, km << 16 | 1u);
+                if (cur == 0u) break;
+            }
+            if ((cur >> 16) == km) {
+                atomicAdd(&T.tab[h], 1u);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    // a position per half wavefront, a k-mer per lane of it
+    for (int i0 = 0; i0 < n * kRankKm; i0 += 64) {
+        const int i = i0 + lane, p = i / kRankKm, k = i - p * kRankKm;
+        uint32_t v = 0;
+        if (p < n) {
+            const int s = (int)T.ord[p];
+            if (k < rank_nkm((int)T.len[s])) {
+                const uint32_t km = T.km[s * kRankKm + k];
+                for (uint32_t h = rank_slot(km);; h = (h + 1u) & (uint32_t)(kRankSlots - 1)) {
+                    const uint32_t cur = T.tab[h];
+                    if (cur == 0u) break;
+                    if ((cur >> 16) == km) {
+                        v = cur & 0xffffu;
+                        break;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = kRankKm / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+        if (p < n && k == 0) T.sc[p] = (uint16_t)v;
+    }
+    __syncthreads();
+}
+
+// stable, descending by score
+__device__ __forceinline__ void rank_sort(RankLds &T, int n, int lane) {
+    uint32_t s = 0, o = 0, r = 0;
+    if (lane < n) {
+        s = T.sc[lane], o = T.ord[lane];
+        for (int q = 0; q < n; q++) {
+            const uint32_t t = T.sc[q];
+            r += (t > s || (t == s && q < lane)) ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    if (lane < n) T.sc[r] = (uint16_t)s, T.ord[r] = (uint8_t)o;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void lq_rank_kernel(RegionDev *__restrict__ regions, const char *__restrict__ strpool,
+                                                      unsigned long long cap, uint32_t min_n) {
+    __shared__ RankLds T;
+    static_assert(kRankKm == 32, "a position's k-mers are one half wavefront");
+    RegionDev &G = regions[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const uint32_t n_ok = G.n_ok;
+    if (!G.want_rank || n_ok < min_n || n_ok < 1u || n_ok > (uint32_t)kRankMax) return;   // (ranked stays 0)
+    const int n = (int)n_ok;
+    uint32_t off = 0, len = 0;
+    if (lane < n) off = G.cand_off[lane], len = G.cand_len[lane];
+    if (__ballot((unsigned long long)off + len > cap) != 0ull) return;   // the pool was too small: this launch is repeated
+    if (lane < n) T.off[lane] = off, T.len[lane] = (uint16_t)len, T.ord[lane] = (uint8_t)lane;
+    __syncthreads();
+    const unsigned char *pool = (const unsigned char *)strpool;
+    rank_stage(T, pool, n, 0, lane);
+    rank_pass(T, n, 1, lane);
+    rank_sort(T, n, lane);
+    rank_pass(T, n, kRankTop, lane);
+    const uint32_t kmaxlen = T.len[T.ord[0]], kmaxscore = T.sc[0];
+    const bool tail = kmaxlen > 500u || (kmaxlen > 200u && kmaxscore < 200u);
+    if (tail) {
+        __syncthreads();
+        if (lane >= 1 && lane < n && T.ord[lane] == 0u) {   // find_ref_lqseq: input 0 to the front, a swap
+            const uint16_t s0 = T.sc[0];
+            T.ord[lane] = T.ord[0], T.sc[0] = T.sc[lane], T.sc[lane] = s0, T.ord[0] = 0u;
+        }
+        __syncthreads();
+        if (lane < n) T.saved[T.ord[lane]] = T.sc[lane];
+        rank_stage(T, pool, n, 1, lane);
+        rank_pass(T, n, 1, lane);
+        rank_sort(T, n, lane);
+        rank_pass(T, n, kRankTop, lane);
+        if (lane < n) T.sc[lane] = (uint16_t)(T.sc[lane] + T.saved[T.ord[lane]]);
+        __syncthreads();
+    }
+    rank_sort(T, n, lane);
+    if (lane < n) G.rank_order[lane] = T.ord[lane], G.rank_kscore[lane] = T.sc[lane];
+    if (lane == 0) G.rank_tail = tail ? 1u : 0u, G.ranked = 1u;
+}
+
 }  // namespace
 
 void launch_lq_msa(LqPileDev *piles, LqJobDev *jobs, const LqPieceDev *pieces, const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops,
@@ -1049,6 +1205,11 @@ void launch_poa_align(PoaJobDev *jobs, const uint32_t *ids_wave, int n_wave, con
     if (n_group > 0)
         hipLaunchKernelGGL(poa_align_kernel<kPoaGroupWaves>, dim3((unsigned)n_group), dim3(kPoaGroupWaves * 64), 0, st, jobs, ids_group, qpool,
                            rows, preds, S, F, route);
+}
+
+void launch_lq_rank(RegionDev *regions, const char *strpool, unsigned long long strpool_cap, uint32_t min_n, int n_regions, void *stream) {
+    if (n_regions <= 0) return;
+    hipLaunchKernelGGL(lq_rank_kernel, dim3((unsigned)n_regions), dim3(64), 0, (hipStream_t)stream, regions, strpool, strpool_cap, min_n);
 }
 
 }  // namespace ndgpu

@@ -267,6 +267,10 @@ struct RegionDev {          // low-quality region whose candidate strings are wa
     uint32_t cand_off[40];  // byte offsets into the string pool
     uint16_t cand_len[40];
     uint16_t cand_rank[40]; // position of the source read among the pile's aligned reads
+    // K14 (lq_rank_kernel): in: want_rank; out: the 8-mer ranking of the candidates, where ranked != 0
+    uint16_t rank_kscore[40];
+    uint8_t rank_order[40];
+    uint8_t want_rank, ranked, rank_tail, pad_;
 };
 
 constexpr int kColBlock = 32;          // columns per link-counting work item
@@ -324,6 +328,9 @@ constexpr int kBtSlots = 192;
 void launch_extract(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const uint32_t *tags,
                     const uint32_t *colidx, RegionDev *regions, char *strpool, unsigned long long *strpool_cursor,
                     unsigned long long strpool_cap, int n_regions, void *stream);
+
+// K14: ranks the candidates of every region with want_rank and min_n <= n_ok <= 40 whose strings lie inside strpool[0, strpool_cap)
+void launch_lq_rank(RegionDev *regions, const char *strpool, unsigned long long strpool_cap, uint32_t min_n, int n_regions, void *stream);
 
 constexpr uint64_t kOffDb = 1ull << 63;   // offset flag: sequence lives in the resident read DB
 constexpr uint64_t kOffMask = kOffDb - 1;

@@ -84,11 +84,33 @@ struct RegionReq {
     std::vector<std::string> cands;      // <= 40, in pile order
     std::vector<uint16_t> cand_rank;     // source read of each candidate (index among aligned reads)
     unsigned n_large = 0;                // reads longer than max_len - 1 seen before the 40th candidate
+    // optional: the 8-mer ranking of `cands` (lq_rank_host below), where ExtractPile::rank asked for it and the backend offers it.
+    // A backend that does not fill these leaves ranked false, and the engine ranks on the host.
+    bool ranked = false;
+    uint8_t rank_tail = 0;               // the tail windows were ranked too
+    uint8_t rank_order[40] = {0};        // candidate index at rank r
+    uint16_t rank_kscore[40] = {0};      // its score
 };
 
 struct ExtractPile {
     int slot = -1;
+    bool rank = false;                   // the engine would take a ranking of every region with five or more candidates
     std::vector<RegionReq> regions;
+};
+
+// The 8-mer ranking of a low-quality region's candidates (lib/nextcorrect.c:281-337, 405-440): n sequences (1..40) in input order ->
+// order[r] = input index of the sequence at rank r, kscore[r] = its score, tail = whether the tail windows were ranked too.
+constexpr int kLqRankMax = 40;           // LQ_CAN_MAX
+void lq_rank_host(const char *const *seqs, const uint16_t *len, int n, uint8_t *order, uint16_t *kscore, int *tail);
+
+// One ranking problem of the batched entry (DeviceAligner::run_rank)
+struct RankReq {
+    const char *const *seqs = nullptr;
+    const uint16_t *len = nullptr;
+    int n = 0;
+    uint8_t order[40] = {0};
+    uint16_t kscore[40] = {0};
+    int tail = 0;
 };
 
 // One low-quality-region round of a pile (generate_consensus_trimed + get_lqseqs_from_align_tags, lib/nextcorrect.c:1538-1669,

@@ -66,6 +66,11 @@ struct RuntimeStats {
     uint64_t poa_launches = 0;        // kernel launches
     uint64_t poa_cells = 0;           // (X + 1)(Y + 1) cells filled
     double poa_ms = 0;                // HIP-event time of K13
+    // the 8-mer ranking of low-quality-region candidates on the device (K14)
+    uint64_t rank_jobs = 0;           // regions / problems ranked
+    uint64_t rank_tail = 0;           // of which took the tail pass
+    uint64_t rank_launches = 0;       // kernel launches
+    double rank_ms = 0;               // HIP-event time of K14
 };
 
 // Thrown when a device (or pinned host) allocation fails for lack of memory.  The C ABI catches it, releases the
@@ -98,7 +103,9 @@ class DeviceAligner {
     void unreserve_batches(uint64_t order);
     static uint64_t next_order();
     void run_main(MainPile **piles, size_t n);
-    void run_extract(ExtractPile **piles, size_t n);
+    // offer_rank: piles that ask for it (ExtractPile::rank) get their regions ranked by K14 behind K11
+    void run_extract(ExtractPile **piles, size_t n, bool offer_rank = true);
+    void run_rank(RankReq *reqs, size_t n);   // the batched entry's problems: one pool up, one copy back
     void run_lq(LqRound **rounds, size_t n);
     void run_poa(PoaReq **reqs, size_t n);   // req.done = false: declined, the caller's host path takes it
     void end_batch();
@@ -141,7 +148,11 @@ class HipBackend : public Backend {
     }
     ~HipBackend() override { finish(); }
     void run_main(MainPile **piles, size_t n) override { dev_.run_main(piles, n); }
-    void run_extract(ExtractPile **piles, size_t n) override { dev_.run_extract(piles, n); }
+    void run_extract(ExtractPile **piles, size_t n) override {
+        static const bool host_rank = getenv("NDGPU_RANK_HOST") != nullptr;  // test hook: no ranking offered, the engine ranks on the host
+        dev_.run_extract(piles, n, !host_rank);
+    }
+    void run_rank(RankReq *reqs, size_t n) { dev_.run_rank(reqs, n); }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
     bool run_lq(LqRound **rounds, size_t n) override {
         static const bool host_lq = getenv("NDGPU_LQ_HOST") != nullptr;  // test hook: the host path of the rounds
