@@ -149,6 +149,30 @@ typedef struct ndgpu_rank_job { const char *const *seqs; const uint16_t *len; in
 typedef struct ndgpu_rank_result { uint8_t order[40]; uint16_t kscore[40]; int32_t tail; } ndgpu_rank_result;
 int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank_result *res);
 
+/* align() / align_hq() for many pairs in one call.  The pairs share the launches of the forward and traceback kernels; a further kernel
+ * pair run-length-encodes every alignment's columns on the device, so that what comes back per job is its summary and its CIGAR, not a
+ * byte per column.  res[i]: status (0: none -- align() would leave its argument untouched, which includes a sequence with a byte
+ * outside ACGT; 1: aligned; 2: the > 250-gap abort, reported as align() reports it: aln_len 2, the last two columns), aln_len,
+ * q_used / t_used (align()'s aln_q_len / aln_t_len), the columns by kind (n_match: equal pairs -- the O(ND) aligner has no mismatch
+ * column; n_ins: query-only; n_del: target-only), max_gap_run (the longest run of one gap kind) and n_cigar runs from
+ * (*cigar)[cigar_off] on: length << 4 | op in BAM numbering, 7 '=', 1 'I', 2 'D'.  *cigar is one malloc'd block (free() it).
+ * hq != 0: align_hq's limits.  flags bit 0: the summaries and runs are computed on the host from the downloaded columns (the same
+ * result; a cross-check).  flags bit 1: *q_aln / *t_aln receive one malloc'd block each with every job's gapped strings exactly as
+ * align() writes q_aln_str / t_aln_str: job i's string starts at the sum of (aln_len + 1) over the jobs before it, is aln_len
+ * bytes long and NUL-terminated (a job with status 0 has the NUL alone); without bit 1 q_aln / t_aln may be NULL.
+ * Lengths are >= 0 and q_len + t_len < 2^28.  Returns 0; < 0, with nothing written, when n < 0, a pointer is NULL with n > 0, a length
+ * is out of range, a DB job names a read or a window outside the DB, or no device can be used.  n = 0 is valid.
+ * ndgpu_align_db_batch: both sides are windows of a resident read DB (inclusive ends, reverse-complemented when *_rev, as the
+ * records of ndgpu_correct_piles name them): nothing is packed or uploaded. */
+typedef struct ndgpu_aln_job { const char *q; int32_t q_len; const char *t; int32_t t_len; int32_t hq; } ndgpu_aln_job;
+typedef struct ndgpu_aln_dbjob { uint32_t q_read, q_start, q_end, q_rev, t_read, t_start, t_end, t_rev; int32_t hq; } ndgpu_aln_dbjob;
+typedef struct ndgpu_aln_result {
+    int32_t status;
+    uint32_t aln_len, q_used, t_used, n_match, n_ins, n_del, max_gap_run, n_cigar;
+    uint64_t cigar_off;
+} ndgpu_aln_result;
+int ndgpu_align_batch(const ndgpu_aln_job *jobs, int n, int flags, ndgpu_aln_result *res, uint32_t **cigar, char **q_aln, char **t_aln);
+
 /* The output loop of lib/nextcorrect.py:236-260 (without -s) over finished records: for every ids[k] in order, a record with
  * len >= min_len_seed, len > 4 and identity >= min_ratio is written to fd_out as ">NAME LEN IDENTITY\nBASES\n" (IDENTITY as Python's
  * '%f') and, if fd_idx >= 0, "NAME\tOFFSET\tLEN\n" to fd_idx (OFFSET = where the bases start in the output file); any other record
@@ -199,6 +223,10 @@ int ndgpu_correct_piles_stream(ndgpu_db *db, int n_piles, const uint32_t *recs, 
                                unsigned int fast, int read_type, int host_threads, consensus_trimed **out,
                                ndgpu_piles_done_fn done, void *user);
 
+/* ndgpu_align_batch (above) over windows of the resident DB. */
+int ndgpu_align_db_batch(ndgpu_db *db, const ndgpu_aln_dbjob *jobs, int n, int flags, ndgpu_aln_result *res, uint32_t **cigar,
+                         char **q_aln, char **t_aln);
+
 /* Counters accumulated by this process's device runtime since the last reset. */
 typedef struct {
     uint64_t tasks, wide_tasks, cells, d_steps, trace_bits, columns, pool_bases, seq_bases;
@@ -240,6 +268,10 @@ typedef struct {
     uint64_t rank_tail;        /* of which took the tail pass */
     uint64_t rank_launches;    /* launches of the ranking kernel */
     double rank_ms;            /* HIP-event time of the ranking kernel */
+    uint64_t aln_batch_jobs;     /* jobs through ndgpu_align_batch / ndgpu_align_db_batch with the device tail (not with flags bit 0) */
+    uint64_t aln_batch_launches; /* launches of the kernel that writes the runs (one per chunk of jobs that has a run) */
+    uint64_t aln_batch_runs;     /* CIGAR runs written on the device */
+    double aln_batch_ms;         /* HIP-event time of the run-length kernels (count + emit) */
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);

@@ -34,6 +34,24 @@ class RankResult(C.Structure):
     _fields_ = [("order", C.c_uint8 * 40), ("kscore", C.c_uint16 * 40), ("tail", C.c_int32)]
 
 
+class AlnJob(C.Structure):
+    # ndgpu_aln_job
+    _fields_ = [("q", C.c_char_p), ("q_len", C.c_int32), ("t", C.c_char_p), ("t_len", C.c_int32), ("hq", C.c_int32)]
+
+
+class AlnDbJob(C.Structure):
+    # ndgpu_aln_dbjob (ends inclusive)
+    _fields_ = [("q_read", C.c_uint32), ("q_start", C.c_uint32), ("q_end", C.c_uint32), ("q_rev", C.c_uint32),
+                ("t_read", C.c_uint32), ("t_start", C.c_uint32), ("t_end", C.c_uint32), ("t_rev", C.c_uint32), ("hq", C.c_int32)]
+
+
+class AlnResult(C.Structure):
+    # ndgpu_aln_result
+    _fields_ = [("status", C.c_int32), ("aln_len", C.c_uint32), ("q_used", C.c_uint32), ("t_used", C.c_uint32),
+                ("n_match", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32), ("max_gap_run", C.c_uint32),
+                ("n_cigar", C.c_uint32), ("cigar_off", C.c_uint64)]
+
+
 PILES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.c_int)   # ndgpu_piles_done_fn
 
 
@@ -52,7 +70,9 @@ class Stats(C.Structure):
                 ("tb_tasks", C.c_uint64), ("tb_walkers", C.c_uint64), ("tb_fallbacks", C.c_uint64),
                 ("poa_jobs", C.c_uint64), ("poa_declined", C.c_uint64), ("poa_rounds", C.c_uint64), ("poa_launches", C.c_uint64),
                 ("poa_cells", C.c_uint64), ("poa_ms", C.c_double),
-                ("rank_jobs", C.c_uint64), ("rank_tail", C.c_uint64), ("rank_launches", C.c_uint64), ("rank_ms", C.c_double)]
+                ("rank_jobs", C.c_uint64), ("rank_tail", C.c_uint64), ("rank_launches", C.c_uint64), ("rank_ms", C.c_double),
+                ("aln_batch_jobs", C.c_uint64), ("aln_batch_launches", C.c_uint64), ("aln_batch_runs", C.c_uint64),
+                ("aln_batch_ms", C.c_double)]
 
 
 def lib_path() -> str:
@@ -100,6 +120,11 @@ def _bind(lib):
     lib.ndgpu_poa_batch.restype = C.c_int
     lib.ndgpu_lq_rank_batch.argtypes = [C.POINTER(RankJob), C.c_int, C.c_int, C.POINTER(RankResult)]
     lib.ndgpu_lq_rank_batch.restype = C.c_int
+    lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.ndgpu_align_batch.restype = C.c_int
+    lib.ndgpu_align_db_batch.argtypes = [C.c_void_p, C.POINTER(AlnDbJob)] + lib.ndgpu_align_batch.argtypes[1:]
+    lib.ndgpu_align_db_batch.restype = C.c_int
     lib.ndgpu_get_stats.argtypes = [C.POINTER(Stats)]
     lib.ndgpu_reset_stats.argtypes = []
     lib.ndgpu_device_count.restype = C.c_int
@@ -271,6 +296,14 @@ class ReadDB:
             return res
         return [_take(self._lib, out[i]) for i in range(n)]
 
+    def align_batch(self, jobs, hq=False, host=False, strings=False):
+        """jobs: [(q_read, q_start, q_end, q_rev, t_read, t_start, t_end, t_rev[, hq])], ends inclusive -> what align_batch() returns,
+        for windows of this DB (ndgpu_align_db_batch: nothing is packed or uploaded)."""
+        arr = (AlnDbJob * max(1, len(jobs)))()
+        for i, j in enumerate(jobs):
+            arr[i] = AlnDbJob(*[int(x) for x in j[:8]], int(j[8]) if len(j) > 8 else int(bool(hq)))
+        return _align_call(lambda *a: self._lib.ndgpu_align_db_batch(self._h, *a), "ndgpu_align_db_batch", arr, len(jobs), host, strings)
+
     def _write_records(self, out, ids, res, state, OUT, IDX, names, min_len_seed, min_ratio):
         """The output loop of lib/nextcorrect.py:236-260 (no -s) straight from the library's records: header, the bases as the
         library holds them (one copy, into the file), the .idx line.  OUT / IDX are binary files; res[i] = (len, identity)."""
@@ -371,6 +404,55 @@ def lq_rank_batch(jobs, host=False):
     if rc != 0:
         raise RuntimeError("ndgpu_lq_rank_batch failed (%d)" % rc)
     return [(list(res[i].order[:len(jobs[i])]), list(res[i].kscore[:len(jobs[i])]), int(res[i].tail)) for i in range(n)]
+
+
+def _align_call(fn, name, arr, n, host, strings):
+    import numpy as np
+    if n == 0:
+        return []
+    res = (AlnResult * n)()
+    cg, qa, ta = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    rc = fn(arr, n, (1 if host else 0) | (2 if strings else 0), res, C.byref(cg), C.byref(qa) if strings else None,
+            C.byref(ta) if strings else None)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("%s failed (%d)" % (name, rc))
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    total = sum(r.n_cigar for r in res)
+    runs = np.ctypeslib.as_array(C.cast(cg, C.POINTER(C.c_uint32)), shape=(max(1, total),))[:total].copy()
+    out, at = [], 0
+    for r in res:
+        d = dict(status=int(r.status), aln_len=int(r.aln_len), q_used=int(r.q_used), t_used=int(r.t_used), n_match=int(r.n_match),
+                 n_ins=int(r.n_ins), n_del=int(r.n_del), max_gap_run=int(r.max_gap_run),
+                 cigar=runs[r.cigar_off:r.cigar_off + r.n_cigar])
+        if strings:
+            d["q_aln"] = C.string_at(qa.value + at, r.aln_len)
+            d["t_aln"] = C.string_at(ta.value + at, r.aln_len)
+            at += r.aln_len + 1
+        out.append(d)
+    libc.free(cg)
+    if strings:
+        libc.free(qa)
+        libc.free(ta)
+    return out
+
+
+def align_batch(pairs, hq=False, host=False, strings=False):
+    """pairs: [(q, t)] or [(q, t, hq)] (bytes) -> one dict per pair: what align() / align_hq() would report -- status (0 none,
+    1 aligned, 2 the > 250-gap abort), aln_len, q_used, t_used --, the columns by kind (n_match, n_ins, n_del), max_gap_run and
+    `cigar`, a numpy.uint32 array of length << 4 | op (7 '=', 1 'I', 2 'D'; cigar_string() prints it), through ndgpu_align_batch:
+    all pairs share the kernel launches and the CIGARs are built on the device.  host=True: summaries and runs from the
+    downloaded columns on the host instead.  strings=True: also q_aln / t_aln, the gapped strings as align() writes them."""
+    lib = load()
+    arr = (AlnJob * max(1, len(pairs)))()
+    for i, p in enumerate(pairs):
+        arr[i] = AlnJob(p[0], len(p[0]), p[1], len(p[1]), int(p[2]) if len(p) > 2 else int(bool(hq)))
+    return _align_call(lib.ndgpu_align_batch, "ndgpu_align_batch", arr, len(pairs), host, strings)
+
+
+def cigar_string(cigar) -> str:
+    """'12=1I3D...' of a cigar array as align_batch() returns it (BAM operation numbers)."""
+    return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in cigar)
 
 
 def stats() -> dict:

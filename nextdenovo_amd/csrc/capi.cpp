@@ -864,6 +864,148 @@ int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank
     return 0;
 }
 
+// ---- batched global alignment: align() / align_hq() for many pairs in one call, CIGARs built on the device (K15) ----
+namespace {
+struct AlnBatchSrc {            // where job i's bases are, for the strings flag
+    const char *q, *t;
+    std::string q_own, t_own;   // DB form: host copies of the two windows
+};
+
+// `run`: K7 / K8a + K15 (or, flags bit 0, the old tail and the host's run-length loop) over jobs[0, n); everything the caller sees
+// is written only after the whole batch is done
+int align_batch_common(std::vector<AlnJob> &jobs, const uint32_t *db_pool, int flags, ndgpu_aln_result *res, uint32_t **cigar, char **q_aln,
+                       char **t_aln, const std::function<void(size_t, AlnBatchSrc &)> &source) {
+    const size_t n = jobs.size();
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_align_batch aligns on the device\n");
+        return -1;
+    }
+    std::vector<AlnJob *> ptr(n);
+    for (size_t i = 0; i < n; i++) ptr[i] = &jobs[i];
+    std::vector<AlnRunsResult> sum(n);
+    std::vector<uint32_t> runs;
+    const int threads = effective_cpus();
+    // (out of device memory: the range is halved until it fits; ranges are served in job order, so the runs stay in job order)
+    std::vector<std::pair<size_t, size_t>> todo{{0, n}};
+    while (!todo.empty()) {
+        const auto [a, b] = todo.back();
+        todo.pop_back();
+        const size_t runs_before = runs.size();
+        try {
+            HipBackend be(0, threads, db_pool);
+            if (flags & 1) {
+                be.run_align(ptr.data() + a, b - a);
+                for (size_t i = a; i < b; i++) {
+                    sum[i] = AlnRunsResult();
+                    sum[i].run_off = runs.size();
+                    if (jobs[i].status == ALN_NONE) continue;
+                    aln_runs_host(jobs[i].ops.data(), jobs[i].ops.size(), sum[i], runs);
+                    sum[i].status = jobs[i].status, sum[i].q_used = (uint32_t)jobs[i].q_used, sum[i].t_used = (uint32_t)jobs[i].t_used;
+                    std::vector<uint8_t>().swap(jobs[i].ops);
+                }
+            } else {
+                std::vector<uint32_t> part;
+                be.run_align_runs(ptr.data() + a, b - a, sum.data() + a, part);
+                for (size_t i = a; i < b; i++) sum[i].run_off += runs.size();
+                runs.insert(runs.end(), part.begin(), part.end());
+            }
+        } catch (const DeviceOom &) {
+            DeviceAligner::context(0).release_memory();
+            DeviceAligner::forget_sizes();
+            runs.resize(runs_before);
+            if (b - a <= 1) return -3;
+            todo.push_back({a + (b - a) / 2, b});
+            todo.push_back({a, a + (b - a) / 2});
+        }
+    }
+    // the two gapped strings exactly as align() writes them, rebuilt from the runs: job i's at the sum of (aln_len + 1) of the jobs before it
+    char *qs = nullptr, *ts = nullptr;
+    if (flags & 2) {
+        std::vector<uint64_t> at(n + 1, 0);
+        for (size_t i = 0; i < n; i++) at[i + 1] = at[i] + sum[i].aln_len + 1;
+        qs = (char *)malloc((size_t)at[n] + 1), ts = (char *)malloc((size_t)at[n] + 1);
+        if (!qs || !ts) {
+            free(qs), free(ts);
+            return -3;
+        }
+        parallel_for(n, threads, [&](size_t i) {
+            const AlnRunsResult &r = sum[i];
+            char *qa = qs + at[i], *ta = ts + at[i];
+            size_t c = 0;
+            if (r.status != ALN_NONE) {
+                AlnBatchSrc src;
+                source(i, src);
+                // (the > 250-gap abort keeps the last two columns: their bases end at q_used / t_used)
+                size_t qi = r.status == ALN_GAP_ABORT ? r.q_used - (r.n_match + r.n_ins) : 0;
+                size_t ti = r.status == ALN_GAP_ABORT ? r.t_used - (r.n_match + r.n_del) : 0;
+                for (uint32_t k = 0; k < r.n_runs; k++) {
+                    const uint32_t w = runs[r.run_off + k], op = w & 15u;
+                    for (uint32_t len = w >> 4; len; len--, c++) {
+                        ta[c] = op == 1u ? '-' : src.t[ti++];
+                        qa[c] = op == 2u ? '-' : src.q[qi++];
+                    }
+                }
+            }
+            qa[c] = ta[c] = '\0';
+        });
+    }
+    uint32_t *cg = (uint32_t *)malloc(std::max<size_t>(1, runs.size()) * sizeof(uint32_t));
+    if (!cg) {
+        free(qs), free(ts);
+        return -3;
+    }
+    if (!runs.empty()) memcpy(cg, runs.data(), runs.size() * sizeof(uint32_t));
+    for (size_t i = 0; i < n; i++) {
+        const AlnRunsResult &r = sum[i];
+        ndgpu_aln_result &o = res[i];
+        o.status = r.status, o.aln_len = r.aln_len, o.q_used = r.q_used, o.t_used = r.t_used;
+        o.n_match = r.n_match, o.n_ins = r.n_ins, o.n_del = r.n_del, o.max_gap_run = r.max_gap_run;
+        o.n_cigar = r.n_runs, o.cigar_off = r.run_off;
+    }
+    *cigar = cg;
+    if (flags & 2) *q_aln = qs, *t_aln = ts;
+    return 0;
+}
+}  // namespace
+
+int ndgpu_align_batch(const ndgpu_aln_job *jobs, int n, int flags, ndgpu_aln_result *res, uint32_t **cigar, char **q_aln, char **t_aln) {
+    if (n == 0) return 0;
+    if (n < 0 || !jobs || !res || !cigar || ((flags & 2) && (!q_aln || !t_aln))) return -2;
+    for (int i = 0; i < n; i++) {
+        const ndgpu_aln_job &j = jobs[i];
+        if (j.q_len < 0 || j.t_len < 0 || (int64_t)j.q_len + j.t_len >= (1 << 28) || (!j.q && j.q_len) || (!j.t && j.t_len)) return -2;
+    }
+    std::vector<AlnJob> aj((size_t)n);
+    for (int i = 0; i < n; i++) aj[i].q = jobs[i].q, aj[i].q_len = jobs[i].q_len, aj[i].t = jobs[i].t, aj[i].t_len = jobs[i].t_len, aj[i].hq = jobs[i].hq != 0;
+    return align_batch_common(aj, nullptr, flags, res, cigar, q_aln, t_aln, [&](size_t i, AlnBatchSrc &s) { s.q = jobs[i].q, s.t = jobs[i].t; });
+}
+
+int ndgpu_align_db_batch(ndgpu_db *h, const ndgpu_aln_dbjob *jobs, int n, int flags, ndgpu_aln_result *res, uint32_t **cigar, char **q_aln,
+                         char **t_aln) {
+    if (n == 0) return 0;
+    if (n < 0 || !h || !h->db || !h->dev_pool || !jobs || !res || !cigar || ((flags & 2) && (!q_aln || !t_aln))) return -2;
+    const ReadDb &db = *h->db;
+    auto inside = [&](uint32_t r, uint32_t s, uint32_t e) { return r < db.n_reads() && s <= e && e < db.length(r); };
+    for (int i = 0; i < n; i++) {
+        const ndgpu_aln_dbjob &j = jobs[i];
+        if (!inside(j.q_read, j.q_start, j.q_end) || !inside(j.t_read, j.t_start, j.t_end)) return -2;
+        if ((uint64_t)(j.q_end - j.q_start) + (j.t_end - j.t_start) + 2 >= (1u << 28)) return -2;
+    }
+    std::vector<AlnJob> aj((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const ndgpu_aln_dbjob &j = jobs[i];
+        aj[i].q_len = (int)(j.q_end - j.q_start + 1), aj[i].t_len = (int)(j.t_end - j.t_start + 1), aj[i].hq = j.hq != 0;
+        aj[i].q_dev = db.window_offset(j.q_read, j.q_start, j.q_end, j.q_rev != 0);
+        aj[i].t_dev = db.window_offset(j.t_read, j.t_start, j.t_end, j.t_rev != 0);
+    }
+    return align_batch_common(aj, h->dev_pool, flags, res, cigar, q_aln, t_aln, [&](size_t i, AlnBatchSrc &s) {
+        const ndgpu_aln_dbjob &j = jobs[i];
+        s.q_own = db.window(j.q_read, j.q_start, j.q_end, j.q_rev != 0), s.t_own = db.window(j.t_read, j.t_start, j.t_end, j.t_rev != 0);
+        s.q = s.q_own.data(), s.t = s.t_own.data();
+    });
+}
+
 void ndgpu_get_stats(ndgpu_stats *o) {
     RuntimeStats s = DeviceAligner::total_stats();
     o->tasks = s.tasks;
@@ -904,6 +1046,8 @@ void ndgpu_get_stats(ndgpu_stats *o) {
     o->poa_jobs = s.poa_jobs, o->poa_declined = s.poa_declined, o->poa_rounds = s.poa_rounds, o->poa_launches = s.poa_launches;
     o->poa_cells = s.poa_cells, o->poa_ms = s.poa_ms;
     o->rank_jobs = s.rank_jobs, o->rank_tail = s.rank_tail, o->rank_launches = s.rank_launches, o->rank_ms = s.rank_ms;
+    o->aln_batch_jobs = s.aln_batch_jobs, o->aln_batch_launches = s.aln_batch_launches, o->aln_batch_runs = s.aln_batch_runs;
+    o->aln_batch_ms = s.aln_batch_ms;
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }

@@ -313,6 +313,11 @@ enum class BufLevel { levelled, on_demand };
     X(TbSeg, d_tbseg, device, levelled)                                                                                                   \
     X(TbSegOut, d_tbout, device, levelled)                                                                                                \
     X(int32_t, d_ids, device, levelled)                                                                                                   \
+    /* K15 (align_batch_runs): per-task summaries, the bad-task bits, the runs' offsets, the runs (exact size, never n_cols a task) */     \
+    X(AlnRunSum, d_run_sums, device, levelled)                                                                                            \
+    X(uint32_t, d_run_skip, device, levelled)                                                                                             \
+    X(uint64_t, d_run_off, device, levelled)                                                                                              \
+    X(uint32_t, d_runs, device, levelled)                                                                                                 \
     /* main phase (alive from run_main to end_batch) */                                                                                   \
     X(ReadDev, d_reads, device, levelled)                                                                                                 \
     X(PileDev, d_piles, device, levelled)                                                                                                 \
@@ -600,6 +605,8 @@ RuntimeStats DeviceAligner::total_stats() {
         t.poa_jobs += s.poa_jobs; t.poa_declined += s.poa_declined; t.poa_rounds += s.poa_rounds; t.poa_launches += s.poa_launches;
         t.poa_cells += s.poa_cells; t.poa_ms += s.poa_ms;
         t.rank_jobs += s.rank_jobs; t.rank_tail += s.rank_tail; t.rank_launches += s.rank_launches; t.rank_ms += s.rank_ms;
+        t.aln_batch_jobs += s.aln_batch_jobs; t.aln_batch_launches += s.aln_batch_launches; t.aln_batch_runs += s.aln_batch_runs;
+        t.aln_batch_ms += s.aln_batch_ms;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -891,27 +898,47 @@ void DeviceAligner::State::tally_outs(size_t nt, std::vector<int32_t> *wide) {
     }
 }
 
+// How many of jobs[0, n) make the next chunk: as many as fit the trace budget -- one chunk of plan_chunks, which chunk_front relies on.
+// NDGPU_ALIGN_CHUNK_JOBS (test hook, read once): at most that many jobs a chunk.
+static size_t next_chunk(AlnJob *const *jobs, size_t n, uint64_t trace_budget_bytes) {
+    static const size_t max_jobs = getenv("NDGPU_ALIGN_CHUNK_JOBS") ? (size_t)std::max(1ll, atoll(getenv("NDGPU_ALIGN_CHUNK_JOBS"))) : ~(size_t)0;
+    size_t take = 0;
+    uint64_t bytes = 0;
+    while (take < n && take < max_jobs) {
+        const AlnJob &j = *jobs[take];
+        int md, bd;
+        limits_for(j.q_len + j.t_len, j.hq, &md, &bd);
+        const uint64_t b = task_trace_bytes(md);
+        if (take && bytes + b > trace_budget_bytes) break;
+        bytes += b;
+        take++;
+    }
+    return take;
+}
+
 void DeviceAligner::align_batch(AlnJob **jobs, size_t n) {
     if (n == 0) return;
     std::unique_lock<std::mutex> dbg_lock;
     if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
     std::lock_guard<std::mutex> lock(s_->mu);
     HIP_CHECK(hipSetDevice(s_->device));
-    size_t done = 0;
-    while (done < n) {
-        // take as many jobs as fit the trace budget: one chunk of plan_chunks, which run_chunk relies on
-        size_t take = 0;
-        uint64_t bytes = 0;
-        while (done + take < n) {
-            const AlnJob &j = *jobs[done + take];
-            int md, bd;
-            limits_for(j.q_len + j.t_len, j.hq, &md, &bd);
-            const uint64_t b = task_trace_bytes(md);
-            if (take && bytes + b > s_->trace_budget_bytes) break;
-            bytes += b;
-            take++;
-        }
+    for (size_t done = 0; done < n;) {
+        const size_t take = next_chunk(jobs + done, n - done, s_->trace_budget_bytes);
         run_chunk(jobs + done, take);
+        done += take;
+    }
+}
+
+void DeviceAligner::align_batch_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) {
+    runs.clear();
+    if (n == 0) return;
+    std::unique_lock<std::mutex> dbg_lock;
+    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
+    std::lock_guard<std::mutex> lock(s_->mu);
+    HIP_CHECK(hipSetDevice(s_->device));
+    for (size_t done = 0; done < n;) {
+        const size_t take = next_chunk(jobs + done, n - done, s_->trace_budget_bytes);
+        run_chunk_runs(jobs + done, take, res + done, runs);
         done += take;
     }
 }
@@ -962,13 +989,15 @@ bool pack_into(uint32_t *out, const char *s, size_t n) {
 
 void DeviceAligner::set_host_threads(int n) { s_->host_threads = n < 1 ? 1 : n; }
 
-void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
+// The front of a chunk, whatever becomes of its column streams: tasks laid out, sequences packed and uploaded, K7 / K8a launched, the
+// AlnOut records on the host (h_outs), the wide-band tasks run again.  ops_to_host: the ops come down with the records (h_ops).
+// bad[i]: job i has a byte the packer rejects; dev_ns: wall time from the first upload to the last record.  Returns the chunk's ops words.
+uint64_t DeviceAligner::chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t> &bad, bool ops_to_host, uint64_t *dev_ns) {
     State &S = *s_;
-    const uint64_t tc0 = wall_ns();
     std::vector<uint32_t> &pool = S.pool;
     std::vector<AlnTask> &tasks = S.tasks;
     tasks.assign(n, AlnTask());
-    std::vector<uint8_t> bad(n, 0);
+    bad.assign(n, 0);
     // pass 1 (serial, O(1) per job): offsets of every per-task region
     std::vector<uint64_t> qw(n + 1), tw(n + 1);
     uint64_t ops_words = 0, pool_words = 0;
@@ -990,9 +1019,11 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
         for (size_t i = a; i < b; i++) {
             AlnJob &j = *jobs[i];
             AlnTask &t = tasks[i];
-            j.status = ALN_NONE;
-            j.ops.clear();
-            j.q_used = j.t_used = 0;
+            if (ops_to_host) {
+                j.status = ALN_NONE;
+                j.ops.clear();
+                j.q_used = j.t_used = 0;
+            }
             if (j.q_dev >= 0) t.q_off = (uint64_t)j.q_dev | kOffDb;
             else {
                 t.q_off = qw[i] * 16;
@@ -1012,9 +1043,9 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     S.d_tasks.reserve(n);
     S.d_outs.reserve(n);
     const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), n);
-    assert(chunks.size() == 1);  // align_batch cut the jobs by the same rule (a task marked bad only shrinks the chunk)
+    assert(chunks.size() == 1);  // next_chunk cut the jobs by the same rule (a task marked bad only shrinks the chunk)
     S.d_ops.reserve(ops_words + 2);
-    S.h_ops.reserve(ops_words + 2);
+    if (ops_to_host) S.h_ops.reserve(ops_words + 2);
     S.h_outs.reserve(n);
 
     hipStream_t st = S.stream;
@@ -1026,7 +1057,7 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     S.launch_chunk(chunks[0], nullptr, nullptr, S.ev1, nullptr, "chunk");
     NDGPU_DBG(st, "chunk: done");
     HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, n * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(S.h_ops.p, S.d_ops.p, ops_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (ops_to_host) HIP_CHECK(hipMemcpyAsync(S.h_ops.p, S.d_ops.p, ops_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     S.sync_drain(st);
     HIP_CHECK(hipGetLastError());
     float ms = 0;
@@ -1039,8 +1070,8 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     std::vector<int32_t> wide;
     for (size_t i = 0; i < n; i++)
         if (S.h_outs.p[i].status == ST_NEED_WIDE) wide.push_back((int32_t)i);
-    if (!wide.empty()) run_wide(jobs, wide);
-    const uint64_t tc2 = wall_ns();
+    if (!wide.empty()) run_wide(ops_to_host ? jobs : nullptr, wide);
+    *dev_ns = wall_ns() - tc1;
 
     S.tally_outs(n, nullptr);  // (after run_wide: the wide tasks count with what the wide kernels reported)
     if (std::find(bad.begin(), bad.end(), 1) != bad.end()) {
@@ -1050,6 +1081,18 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
             warned = true;
         }
     }
+    return ops_words;
+}
+
+// The tail of run_align, the LQ host path and align(): the column kinds come down with the records and are unpacked, a byte a column.
+void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
+    State &S = *s_;
+    const uint64_t tc0 = wall_ns();
+    uint64_t dev_ns = 0;
+    std::vector<uint8_t> bad;
+    chunk_front(jobs, n, bad, true, &dev_ns);
+    const std::vector<AlnTask> &tasks = S.tasks;
+    const uint64_t tc2 = wall_ns();
     par_ranges(n, S.host_threads, [&](size_t a, size_t b) {
         for (size_t i = a; i < b; i++) {
             AlnJob &j = *jobs[i];
@@ -1083,7 +1126,78 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
             }
         }
     });
-    g_prof.c_pack += tc1 - tc0, g_prof.c_dev += tc2 - tc1, g_prof.c_decode += wall_ns() - tc2, g_prof.c_jobs += n;
+    // (host packing = the front less its device round trip)
+    g_prof.c_pack += tc2 - tc0 - dev_ns, g_prof.c_dev += dev_ns, g_prof.c_decode += wall_ns() - tc2, g_prof.c_jobs += n;
+}
+
+// The batched entry's tail: the column streams stay in HBM.  K15 counts every task's runs, the summaries come down (they are the
+// caller's anyway, and the host has to know the total to size the runs' buffer exactly -- so the exclusive scan of n_runs is done
+// here, on the n numbers at hand, and goes up as n offsets: a device scan would save that upload and nothing else, the
+// synchronisation in between stays), K15 emits, and exactly the runs come down behind what earlier chunks of the call left in `runs`.
+void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) {
+    State &S = *s_;
+    std::vector<uint8_t> bad;
+    uint64_t dev_ns = 0;
+    chunk_front(jobs, n, bad, false, &dev_ns);
+    hipStream_t st = S.stream;
+    const bool any_bad = std::find(bad.begin(), bad.end(), 1) != bad.end();
+    if (any_bad) {
+        std::vector<uint32_t> bits((n + 31) / 32, 0u);
+        for (size_t i = 0; i < n; i++)
+            if (bad[i]) bits[i >> 5] |= 1u << (i & 31);
+        S.d_run_skip.reserve(bits.size());
+        S.h2d(S.d_run_skip.p, bits.data(), bits.size() * sizeof(uint32_t), st);
+    }
+    S.d_run_sums.reserve(n);
+    std::vector<AlnRunSum> sums(n);
+    HIP_CHECK(hipEventRecord(S.evs[5], st));
+    NDGPU_DBG(st, "chunk: K15 count, %zu tasks", n);
+    launch_aln_runs_count(S.d_tasks.p, S.d_outs.p, S.d_ops.p, any_bad ? S.d_run_skip.p : nullptr, S.d_run_sums.p, (int)n, st);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(S.evs[6], st));
+    S.d2h(sums.data(), S.d_run_sums.p, n * sizeof(AlnRunSum), st);
+    S.sync_drain(st);
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
+    S.stats.aln_batch_ms += ms;
+
+    std::vector<uint64_t> off(n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = total;
+        total += sums[i].n_runs;
+    }
+    const size_t at = runs.size();
+    runs.resize(at + total);
+    if (total) {
+        S.d_run_off.reserve(n);
+        S.d_runs.reserve(total);
+        S.h2d(S.d_run_off.p, off.data(), n * sizeof(uint64_t), st);
+        HIP_CHECK(hipEventRecord(S.evs[5], st));
+        NDGPU_DBG(st, "chunk: K15 emit, %llu runs", (unsigned long long)total);
+        launch_aln_runs_emit(S.d_tasks.p, S.d_outs.p, S.d_ops.p, S.d_run_sums.p, S.d_run_off.p, S.d_runs.p, (int)n, st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(S.evs[6], st));
+        S.d2h(runs.data() + at, S.d_runs.p, total * sizeof(uint32_t), st);
+        S.sync_drain(st);
+        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
+        S.stats.aln_batch_ms += ms;
+        S.stats.aln_batch_launches++;
+    }
+    S.stats.aln_batch_jobs += n;
+    S.stats.aln_batch_runs += total;
+    for (size_t i = 0; i < n; i++) {
+        const AlnOut &o = S.h_outs.p[i];
+        const AlnRunSum &u = sums[i];
+        AlnRunsResult &r = res[i];
+        r = AlnRunsResult();
+        r.run_off = at + off[i];
+        if (bad[i] || (o.status != ST_ALIGNED && o.status != ST_GAP_ABORT)) continue;
+        r.status = o.status == ST_ALIGNED ? ALN_OK : ALN_GAP_ABORT;
+        r.q_used = (uint32_t)o.x_final, r.t_used = (uint32_t)o.y_final;
+        r.aln_len = u.aln_len, r.n_match = u.n_match, r.n_ins = u.n_ins, r.n_del = u.n_del, r.max_gap_run = u.max_gap_run;
+        r.n_runs = u.n_runs;
+    }
 }
 
 void DeviceAligner::run_wide(AlnJob **jobs, const std::vector<int32_t> &ids) {

@@ -372,4 +372,21 @@ void launch_ond_traceback(const AlnTask *tasks, AlnOut *outs, const uint32_t *po
                           const int32_t *trace_mink, uint32_t *ops, const int32_t *task_ids, int n, void *stream,
                           const int32_t *order = nullptr, const AlnTask *wtasks = nullptr);
 
+// ---- K15: the traceback's column stream as runs (aln_runs_kernel, ond_kernels.hip) ----
+// What a batch caller takes home instead of one byte per column: per task the counts of its columns by kind, its runs of equal kinds
+// and the longest gap run, and the runs themselves as BAM-numbered uint32 (length << 4 | op).
+struct AlnRunSum {
+    uint32_t n_runs;        // runs of equal column kinds (ST_ALIGNED: all n_cols columns; ST_GAP_ABORT: the last two; otherwise 0)
+    uint32_t n_match, n_ins, n_del;   // columns of OP_MATCH / OP_QONLY / OP_TONLY among them
+    uint32_t max_gap_run;   // the longest run of OP_QONLY or of OP_TONLY columns
+    uint32_t aln_len;       // the columns counted
+};
+constexpr uint32_t kCigarEq = 7, kCigarIns = 1, kCigarDel = 2;   // '=' for OP_MATCH (a diagonal step of O(ND) is an equal pair), 'I', 'D'
+// count pass: sums[i] of every task i of [0, n_tasks); skip (may be nullptr): bit i set = task i counts as not aligned
+void launch_aln_runs_count(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, const uint32_t *skip, AlnRunSum *sums, int n_tasks,
+                           void *stream);
+// emit pass: task i writes its sums[i].n_runs runs to runs[run_off[i] ...] (run_off: the exclusive scan of n_runs)
+void launch_aln_runs_emit(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, const AlnRunSum *sums, const uint64_t *run_off,
+                          uint32_t *runs, int n_tasks, void *stream);
+
 }  // namespace ndgpu

@@ -47,6 +47,37 @@ struct AlnJob {
     std::vector<uint8_t> ops;  // forward column kinds (empty unless ALN_OK)
 };
 
+// What the batched alignment entry reports per job (DeviceAligner::align_batch_runs): align()'s outcome, the counts of its columns
+// and its CIGAR as job.n_runs words from runs[job.run_off] on -- length << 4 | op in BAM numbering, 7 '=' / 1 'I' / 2 'D'.
+struct AlnRunsResult {
+    int status = ALN_NONE;
+    uint32_t aln_len = 0, q_used = 0, t_used = 0;
+    uint32_t n_match = 0, n_ins = 0, n_del = 0, max_gap_run = 0;
+    uint32_t n_runs = 0;
+    uint64_t run_off = 0;
+};
+// The same summary from one byte per column -- the host form of K15 (ond_kernels.hip), what the batched entry's host flag reports:
+// runs of equal kinds, appended to `runs`; status, q_used and t_used are the caller's.  (Inline: a stand-alone sanitizer program of
+// the tests includes this header and nothing else.)
+inline void aln_runs_host(const uint8_t *ops, size_t n_cols, AlnRunsResult &r, std::vector<uint32_t> &runs) {
+    r.aln_len = (uint32_t)n_cols;
+    r.n_match = r.n_ins = r.n_del = r.max_gap_run = r.n_runs = 0;
+    r.run_off = runs.size();
+    for (size_t a = 0; a < n_cols;) {
+        size_t b = a + 1;
+        while (b < n_cols && ops[b] == ops[a]) b++;
+        const uint32_t len = (uint32_t)(b - a);
+        if (ops[a] == OP_MATCH) r.n_match += len;
+        else {
+            (ops[a] == OP_QONLY ? r.n_ins : r.n_del) += len;
+            if (len > r.max_gap_run) r.max_gap_run = len;
+        }
+        runs.push_back(len << 4 | (ops[a] == OP_MATCH ? 7u : ops[a] == OP_QONLY ? 1u : 2u));
+        r.n_runs++;
+        a = b;
+    }
+}
+
 // One visited cell of the main MSA's best_pp walk, origin first (device: PathItem).
 struct PathStep {
     int32_t t_pos;

@@ -71,6 +71,11 @@ struct RuntimeStats {
     uint64_t rank_tail = 0;           // of which took the tail pass
     uint64_t rank_launches = 0;       // kernel launches
     double rank_ms = 0;               // HIP-event time of K14
+    // batched global alignment with the CIGARs built on the device (K15)
+    uint64_t aln_batch_jobs = 0;      // jobs through align_batch_runs
+    uint64_t aln_batch_launches = 0;  // launches of K15's emit pass (one per chunk that has a run)
+    uint64_t aln_batch_runs = 0;      // runs written
+    double aln_batch_ms = 0;          // HIP-event time of K15 (count + emit)
 };
 
 // Thrown when a device (or pinned host) allocation fails for lack of memory.  The C ABI catches it, releases the
@@ -93,6 +98,9 @@ class DeviceAligner {
     static void reserve_device_memory(uint64_t bytes);  // left free by every later plan (another stage's working set)
     static void reset_all_stats();
     void align_batch(AlnJob **jobs, size_t n);
+    // the same alignments, but what comes back is each job's summary and its runs (K15) instead of a byte per column: res[i] for
+    // jobs[i], runs = every job's CIGAR back to back (res[i].run_off); the jobs' own result fields stay untouched
+    void align_batch_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs);
     // device main phase / candidate extraction of a batch of piles (see Backend in nd_host.h);
     // begin_batch()/end_batch() bracket one batch and serialise batches of one process
     // order: who goes first when several callers wait for this context (lower first; equal: any) -- the calls of a process take a
@@ -132,6 +140,10 @@ class DeviceAligner {
     DeviceAligner();
     ~DeviceAligner();
     void run_chunk(AlnJob **jobs, size_t n);
+    void run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs);
+    // what both have in common: tasks built and uploaded, K7 / K8a launched, the AlnOut records (and the ops, if asked) on the host,
+    // the wide-band tasks run again; returns the chunk's ops words
+    uint64_t chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t> &bad, bool ops_to_host, uint64_t *dev_ns);
     void run_wide(AlnJob **jobs, const std::vector<int32_t> &ids);
     struct State;
     State *s_;
@@ -154,6 +166,7 @@ class HipBackend : public Backend {
     }
     void run_rank(RankReq *reqs, size_t n) { dev_.run_rank(reqs, n); }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
+    void run_align_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) { dev_.align_batch_runs(jobs, n, res, runs); }
     bool run_lq(LqRound **rounds, size_t n) override {
         static const bool host_lq = getenv("NDGPU_LQ_HOST") != nullptr;  // test hook: the host path of the rounds
         if (host_lq) return false;

@@ -18,6 +18,9 @@
 // K8a ond_traceback : one lane per alignment walks d -> 0 reading the move bits,
 //                     re-deriving match runs with clz over 64 bases a round, and emits
 //                     2-bit column kinds back to front.
+// K15 aln_runs      : one wavefront per alignment reads those column kinds 64 at a time and run-length-encodes them: a count pass
+//                     (runs, columns by kind, longest gap run) and an emit pass (the runs as a CIGAR), for the batched entry
+//                     (at the end of this file; DeviceAligner::align_batch_runs).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -959,7 +962,96 @@ __global__ __launch_bounds__(64) void tb_stitch_kernel(const AlnTask *__restrict
 }
 
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// K15: the column stream of an alignment as runs, one wavefront per task, 64 columns an iteration (lane l = column base + l of the
+// task's columns [ops_cap - n, ops_cap), which start anywhere inside a word).  A lane's predecessor kind is the lane below's (one
+// wave shift; lane 0 takes what lane 63 held in the iteration before), so the run starts of an iteration are one ballot; a run ends
+// in front of the next start or with the columns, and lane 63 -- whose successor belongs to the next iteration -- looks one column
+// ahead.  The lane that ENDS a run owns it: the run began at the highest start bit at or below the lane, or, without one, where the
+// run that was open when the iteration began did (a run may cross any number of iterations), and it is run number "runs ended
+// before this iteration + end bits below the lane" of the task.  EMIT = false counts (runs, columns by kind, the longest gap run);
+// EMIT = true writes the runs to the slots the count pass sized.  No LDS, no atomics: every word of the output has one writer.
+__device__ __forceinline__ uint32_t aln_col_kind(const uint32_t *__restrict__ W, uint32_t c) { return (W[c >> 4] >> ((c & 15u) * 2u)) & 3u; }
+
+template <bool EMIT>
+__global__ __launch_bounds__(64) void aln_runs_kernel(const AlnTask *__restrict__ tasks, const AlnOut *__restrict__ outs,
+                                                       const uint32_t *__restrict__ ops, const uint32_t *__restrict__ skip,
+                                                       AlnRunSum *__restrict__ sums, const uint64_t *__restrict__ run_off,
+                                                       uint32_t *__restrict__ runs) {
+    const uint32_t task = blockIdx.x, lane = threadIdx.x;
+    const uint32_t cap = tasks[task].ops_cap;
+    const int32_t status = outs[task].status;
+    // ST_GAP_ABORT: the last two columns, what align() reports (lib/align.c:542-556)
+    uint32_t n = status == ST_ALIGNED ? (uint32_t)outs[task].n_cols : status == ST_GAP_ABORT ? 2u : 0u;
+    if (n > cap) n = 0;
+    uint32_t n_runs = 0;
+    if (EMIT) {
+        n_runs = sums[task].n_runs;
+        if (n_runs == 0 || sums[task].aln_len != n) return;
+    } else if (skip && ((skip[task >> 5] >> (task & 31u)) & 1u)) {
+        n = 0;
+    }
+    const uint32_t *__restrict__ W = ops + tasks[task].ops_off;
+    uint32_t *__restrict__ out = EMIT ? runs + run_off[task] : nullptr;
+    const uint32_t c_end = cap;
+    uint32_t carry = 4u;             // kind of the column in front of this iteration's first (4: none)
+    uint32_t open_start = cap - n;   // first column of the last run that began before this iteration
+    uint32_t done = 0;               // runs that ended before this iteration
+    uint32_t n_match = 0, n_ins = 0, n_del = 0, longest = 0;
+    for (uint32_t base = cap - n; base < c_end; base += 64u) {
+        const uint32_t c = base + lane;
+        const bool valid = c < c_end;
+        const uint32_t kind = valid ? aln_col_kind(W, c) : 4u;
+        uint32_t prev = __shfl_up(kind, 1);
+        if (lane == 0) prev = carry;
+        const unsigned long long starts = __ballot(valid && kind != prev), live = __ballot(valid);
+        const bool last_of_wave = lane == 63u && valid && (c + 1u >= c_end || aln_col_kind(W, c + 1u) != kind);
+        const unsigned long long ends = (((starts | ~live) >> 1) & live) | __ballot(last_of_wave);
+        if (!EMIT) {
+            n_match += (uint32_t)__popcll(__ballot(kind == 0u));
+            n_ins += (uint32_t)__popcll(__ballot(kind == 1u));
+            n_del += (uint32_t)__popcll(__ballot(kind == 2u));
+        }
+        if ((ends >> lane) & 1ull) {
+            const unsigned long long below = starts & (~0ull >> (63u - lane));
+            const uint32_t first = below ? base + 63u - (uint32_t)__clzll((long long)below) : open_start;
+            const uint32_t len = c - first + 1u;
+            if (EMIT) {
+                const uint32_t slot = done + (uint32_t)__popcll(ends & ((1ull << lane) - 1ull));
+                if (slot < n_runs) out[slot] = len << 4 | (kind == 0u ? kCigarEq : kind == 1u ? kCigarIns : kCigarDel);
+            } else if (kind != 0u && len > longest) {
+                longest = len;
+            }
+        }
+        if (starts) open_start = base + 63u - (uint32_t)__clzll((long long)starts);
+        done += (uint32_t)__popcll(ends);
+        carry = __shfl(kind, 63);
+    }
+    if (!EMIT) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t o = __shfl_xor(longest, m);
+            longest = o > longest ? o : longest;
+        }
+        if (lane == 0) sums[task] = AlnRunSum{done, n_match, n_ins, n_del, longest, n};
+    }
+}
+
 }  // namespace
+
+void launch_aln_runs_count(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, const uint32_t *skip, AlnRunSum *sums, int n_tasks,
+                           void *stream) {
+    if (n_tasks <= 0) return;
+    hipLaunchKernelGGL(aln_runs_kernel<false>, dim3((unsigned)n_tasks), dim3(64), 0, (hipStream_t)stream, tasks, outs, ops, skip, sums,
+                       (const uint64_t *)nullptr, (uint32_t *)nullptr);
+}
+
+void launch_aln_runs_emit(const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops, const AlnRunSum *sums, const uint64_t *run_off,
+                          uint32_t *runs, int n_tasks, void *stream) {
+    if (n_tasks <= 0) return;
+    hipLaunchKernelGGL(aln_runs_kernel<true>, dim3((unsigned)n_tasks), dim3(64), 0, (hipStream_t)stream, tasks, outs, ops, (const uint32_t *)nullptr,
+                       (AlnRunSum *)sums, run_off, runs);
+}
 
 void launch_ond_forward(const AlnTask *tasks, AlnOut *outs, const uint32_t *pool, const uint32_t *db_pool, uint64_t *trace,
                         int n_tasks, void *stream, const int32_t *order) {
