@@ -1881,6 +1881,19 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
         if (attempt < 2 && getenv("NDGPU_TRACE"))
             fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", herr[1], herr[3], herr[2],
                     herr[4] ? ~herr[4] : 0u);
+        // NDGPU_K9_DIGEST (read once): a digest of the tables this attempt left, for comparing two builds or two paths of K9.  The
+        // stream is idle here; the kernel, its four words and their copy exist only under the switch.
+        static const bool k9_digest = getenv("NDGPU_K9_DIGEST") != nullptr && atoi(getenv("NDGPU_K9_DIGEST")) != 0;
+        if (k9_digest) {
+            unsigned long long *d_dig = nullptr, dig[4] = {};
+            HIP_CHECK(hipMalloc((void **)&d_dig, sizeof(dig)));
+            HIP_CHECK(hipMemsetAsync(d_dig, 0, sizeof(dig), st));
+            launch_k9_digest(S.d_piles.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p, S.d_ent_ppp.p, S.d_ent_cnt.p, d_dig, (int)np, st);
+            HIP_CHECK(hipMemcpyAsync(dig, d_dig, sizeof(dig), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            HIP_CHECK(hipFree(d_dig));
+            fprintf(stderr, "[ndgpu trace] K9 tables: digest=%016llx cells=%llu links=%llu max_cell_len=%llu\n", dig[0], dig[1], dig[2], dig[3]);
+        }
         static const bool force_retry = getenv("NDGPU_K9_FORCE_RETRY") != nullptr;  // test hook: take the overflow path
         if (attempt == 0 ? !herr[0] && !force_retry : !herr[0]) break;
         if (attempt == 2) break;  // (cannot happen: the lists hold one entry per accepted read)

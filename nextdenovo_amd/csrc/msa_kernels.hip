@@ -314,7 +314,7 @@ __global__ __launch_bounds__(64) void col_scan_kernel(PileDev *__restrict__ pile
 // once over the pile's accepted reads (rank = chunk * 64 + lane) and keeps those that can put a tag into the block
 // (t_s < t_end && t_e >= col0); ballot and prefix popcount give every kept read a slot, in rank order.  If the kept reads
 // number <= `compact_max` (at most 64), lane s takes the read in slot s and the block runs the compact path: ONE chunk, every
-// read with its 32-byte register window, no loop over chunks.  Otherwise the block runs the deep path: the loop over all
+// read with its 32-byte register window, no loop over chunks and no lists (k9_row elects a row's links in registers).  Otherwise the block runs the deep path: the loop over all
 // ceil(n_acc / 64) chunks (the first with windows, the second one load per row, the others through the column index).
 //
 // Why the tables are the same whichever path a block takes:
@@ -345,7 +345,7 @@ __device__ __forceinline__ void k9_collect(K9Lists<CAP> &L, uint32_t (&n_cell)[6
 #pragma unroll
     for (uint32_t bb = 0; bb < 6; bb++) {
         const bool mine = has && b == bb;
-        if (!__ballot(mine)) continue;
+        if (!wave_ballot(mine)) continue;
         uint32_t n0 = n_cell[bb];
         int found = -1;
         if (mine) {
@@ -356,13 +356,13 @@ __device__ __forceinline__ void k9_collect(K9Lists<CAP> &L, uint32_t (&n_cell)[6
                 }
             if (found >= 0) atomicAdd(&L.cnt[bb][found], 1u);
         }
-        unsigned long long rem = __ballot(mine && found < 0);
+        unsigned long long rem = wave_ballot(mine && found < 0);
         while (rem) {
             const int ld = __ffsll((long long)rem) - 1;  // earliest read that carries a new link
-            const uint32_t kp = (uint32_t)__shfl((int)pp, ld, 64);
-            const uint32_t kpp = (uint32_t)__shfl((int)ppp, ld, 64);
+            const uint32_t kp = (uint32_t)__builtin_amdgcn_readlane((int)pp, ld);  // (ld is the same in every lane: no LDS round trip)
+            const uint32_t kpp = (uint32_t)__builtin_amdgcn_readlane((int)ppp, ld);
             const bool in_rem = (rem >> lane) & 1ull;
-            const unsigned long long same = __ballot(in_rem && pp == kp && ppp == kpp);
+            const unsigned long long same = wave_ballot(in_rem && pp == kp && ppp == kpp);
             if (lane == ld) {
                 if (n0 < (uint32_t)CAP) {
                     L.pp[bb][n0] = pp;
@@ -401,6 +401,56 @@ __device__ __forceinline__ void k9_flush(const K9Lists<CAP> &L, const uint32_t (
         e += n;
     }
     __builtin_amdgcn_wave_barrier();
+}
+
+// The compact path's row: the tags `cur` (valid where `has`) of the block's covering reads in cell row (t, d), with their two
+// predecessors, straight from the lanes to the tables.  All the reads there are sit in this one chunk, so the lists of k9_collect
+// would be empty on entry and flushed right after: the election runs once over the whole row instead, and the leaders store.
+//
+// Why the tables are the same as k9_collect + k9_flush make them:
+//   * there, the links of a cell stand in first-seen order by lane (lowest bit of `rem` first, cell by cell).  One pass over all
+//     six cells in ascending lane order elects the leaders of any one cell in that same order, so a leader's rank among the
+//     leaders of its cell (`my_slot`: the cell's counter when it is elected) is its position there;
+//   * the cells of a row lie one behind the other in cell order 0..5: `excl`, the exclusive prefix sum of the six counters;
+//   * a link's count is the popcount of the same set of lanes (equal cell, pp and ppp);
+//   * a cell cannot overflow: at most 64 reads are at most 64 <= CAP links, so err[0] is never raised here -- as there.
+// The six counters are bytes of one 64-bit scalar (a row has at most 64 links: no byte carries into its neighbour, neither in
+// the counters nor in the prefix sums that one multiplication by 0x010101010101 makes of them).
+__device__ __forceinline__ void k9_row(bool has, uint32_t cur, uint32_t pp, uint32_t ppp, uint64_t cell0, uint64_t &e, uint64_t ent_off,
+                                       int lane, uint32_t *__restrict__ cell_start, uint32_t *__restrict__ cell_len,
+                                       uint32_t *__restrict__ ent_pp, uint32_t *__restrict__ ent_ppp, uint32_t *__restrict__ ent_cnt) {
+    const uint32_t b = cur & 7u;
+    has = has && b < 6u;  // (k9_collect looks at cells 0..5 only)
+    unsigned long long rem = wave_ballot(has);
+    unsigned long long n_pack = 0;      // links elected so far in cell c: byte c
+    uint32_t my_cnt = 0, my_slot = 0;   // a leader's count (0: this lane leads no link) and its rank among the leaders of its cell
+    while (rem) {
+        const int ld = __builtin_ctzll(rem);  // earliest read that carries a link not yet elected
+        const uint32_t kb = (uint32_t)__builtin_amdgcn_readlane((int)b, ld);
+        const uint32_t kp = (uint32_t)__builtin_amdgcn_readlane((int)pp, ld);
+        const uint32_t kpp = (uint32_t)__builtin_amdgcn_readlane((int)ppp, ld);
+        const unsigned long long same = wave_ballot(has && b == kb && pp == kp && ppp == kpp);  // (all of them still in `rem`)
+        if (lane == ld) {
+            my_cnt = (uint32_t)__popcll(same);
+            my_slot = (uint32_t)(n_pack >> (8u * kb)) & 0xffu;
+        }
+        n_pack += 1ull << (8u * kb);
+        rem &= ~same;
+    }
+    const unsigned long long incl = n_pack * 0x0000010101010101ull;
+    const unsigned long long excl = incl - n_pack;
+    const uint32_t total = (uint32_t)(incl >> 40) & 0xffu;
+    if (my_cnt) {
+        const uint64_t at = e + ((uint32_t)(excl >> (8u * b)) & 0xffu) + my_slot;
+        ent_pp[at] = pp;
+        ent_ppp[at] = ppp;
+        ent_cnt[at] = my_cnt;
+    }
+    if (lane < 6) {
+        cell_start[cell0 + (uint32_t)lane] = (uint32_t)(e - ent_off) + ((uint32_t)(excl >> (8u * (uint32_t)lane)) & 0xffu);
+        cell_len[cell0 + (uint32_t)lane] = (uint32_t)(n_pack >> (8u * (uint32_t)lane)) & 0xffu;
+    }
+    e += total;
 }
 
 // The deep path: every accepted read of the pile, 64 at a time.
@@ -617,7 +667,7 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
         m_cb = cb[B.col0 + (uint32_t)lane];
         m_eb = eb[B.col0 + (uint32_t)lane];
     }
-    __builtin_amdgcn_wave_barrier();  // the slot table has been read: the counters are the lists' again
+    __builtin_amdgcn_wave_barrier();  // the slot table has been read (the compact path uses no LDS from here on)
     const uint32_t *const tp = tags + g_tg;
 
     for (uint32_t t = B.col0; t < t_end; t++) {
@@ -626,7 +676,6 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
         const uint64_t cell_t = P.cell_off + (uint32_t)__builtin_amdgcn_readlane((int)m_cb, j);
         uint64_t e = P.ent_off + (uint32_t)__builtin_amdgcn_readlane((int)m_eb, j);
         for (uint32_t d = 0; d < width; d++) {
-            uint32_t n_cell[6] = {0, 0, 0, 0, 0, 0};  // links collected so far in the six cells of (t, d): the same in every lane
             bool has = false;
             uint32_t cur = 0, pp = kTagHead, ppp = kTagHead;
             const uint32_t key = ((t + 1u) << 8) | d;  // tag >> 3 of a tag of cell row (t, d)
@@ -642,9 +691,12 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
                     w_i = i;
                 }
                 const uint32_t k = i - w_i;
-                const uint4 w = k < 4u ? w_lo : w_hi;
-                const uint32_t k4 = k & 3u;
-                const uint32_t c = k4 == 0 ? w.x : k4 == 1 ? w.y : k4 == 2 ? w.z : w.w;
+                // word k of the window, picked bit by bit of k (seven selects; the chain `k4 == 0 ? w.x : k4 == 1 ? ...` compiled to
+                // a cascade of divergent branches)
+                const bool lo = k < 4u, odd = (k & 1u) != 0, up = (k & 2u) != 0;
+                const uint32_t c01 = odd ? (lo ? w_lo.y : w_hi.y) : (lo ? w_lo.x : w_hi.x);
+                const uint32_t c23 = odd ? (lo ? w_lo.w : w_hi.w) : (lo ? w_lo.z : w_hi.z);
+                const uint32_t c = up ? c23 : c01;
                 if ((c >> 3) == key) {  // the read's next tag sits in this cell row: consume it
                     cur = c;
                     pp = w_p1;
@@ -655,8 +707,7 @@ __global__ __launch_bounds__(64, CAP <= 64 ? 8 : 3) void count_links_kernel(cons
                     has = true;
                 }
             }
-            k9_collect<CAP>(L, n_cell, has, cur, pp, ppp, lane, err);
-            k9_flush<CAP>(L, n_cell, cell_t + (uint64_t)d * 6u, e, P.ent_off, lane, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt);
+            k9_row(has, cur, pp, ppp, cell_t + (uint64_t)d * 6u, e, P.ent_off, lane, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt);
         }
     }
 }
@@ -1853,6 +1904,46 @@ void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const
     hipLaunchKernelGGL(count_links_global_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, piles, reads, acc_list,
                        blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt, err,
                        lists, cap, n_blocks);
+}
+
+// The trace hook of NDGPU_K9_DIGEST (nd_device.h says what it sums).  One block per pile; never launched unless the switch is set.
+__device__ __forceinline__ unsigned long long k9_mix(unsigned long long x) {  // (the finaliser of splitmix64)
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+__global__ __launch_bounds__(256) void k9_digest_kernel(const PileDev *__restrict__ piles, const uint32_t *__restrict__ cell_start,
+                                                        const uint32_t *__restrict__ cell_len, const uint32_t *__restrict__ ent_pp,
+                                                        const uint32_t *__restrict__ ent_ppp, const uint32_t *__restrict__ ent_cnt,
+                                                        unsigned long long *__restrict__ out) {
+    const PileDev &P = piles[blockIdx.x];
+    unsigned long long h = 0, cells = 0, links = 0, longest = 0;
+    for (uint32_t c = threadIdx.x; c < P.n_cells; c += blockDim.x) {
+        const uint32_t start = cell_start[P.cell_off + c], len = cell_len[P.cell_off + c];
+        const unsigned long long where = k9_mix(((unsigned long long)blockIdx.x << 32) | c);
+        h += k9_mix(where ^ (((unsigned long long)start << 32) | len));
+        for (uint32_t j = 0; j < len; j++) {
+            const uint64_t at = P.ent_off + start + j;
+            const unsigned long long link = k9_mix(where + 0x9e3779b97f4a7c15ull * (j + 1u)) ^ (((unsigned long long)ent_pp[at] << 32) | ent_ppp[at]);
+            h += k9_mix(k9_mix(link) ^ ent_cnt[at]);
+        }
+        cells++;
+        links += len;
+        longest = len > longest ? len : longest;
+    }
+    atomicAdd(&out[0], h);
+    atomicAdd(&out[1], cells);
+    atomicAdd(&out[2], links);
+    atomicMax(&out[3], longest);
+}
+
+void launch_k9_digest(const PileDev *piles, const uint32_t *cell_start, const uint32_t *cell_len, const uint32_t *ent_pp,
+                      const uint32_t *ent_ppp, const uint32_t *ent_cnt, unsigned long long *out, int n_piles, void *stream) {
+    if (n_piles <= 0) return;
+    hipLaunchKernelGGL(k9_digest_kernel, dim3((unsigned)n_piles), dim3(256), 0, (hipStream_t)stream, piles, cell_start, cell_len,
+                       ent_pp, ent_ppp, ent_cnt, out);
 }
 
 void launch_score_backtrack(const K10Args &a, const SegItem *items_small, int n_small, const SegItem *items_large, int n_large,

@@ -100,6 +100,14 @@ __host__ __device__ inline int32_t tag_tpos(uint32_t g) { return (int32_t)(g >> 
 __host__ __device__ inline uint32_t tag_delta(uint32_t g) { return (g >> 3) & 0xffu; }
 __host__ __device__ inline uint32_t tag_base(uint32_t g) { return g & 7u; }
 
+// The lanes whose predicate holds, as a mask.  __ballot() goes through an int (v_cndmask 0/1, v_cmp_ne); the builtin is the
+// compare's own result.  The lane-by-lane interpreter of the kernel tests has __ballot only.
+#if defined(SIMT_EMULATION)
+inline unsigned long long wave_ballot(bool p) { return __ballot(p); }
+#elif defined(__HIPCC__)
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+#endif
+
 struct ReadDev {            // one per pile record (index 0 of a pile = the seed itself)
     int32_t task;           // index into the AlnTask/AlnOut tables, -1 for the seed
     uint32_t aln_start;     // inclusive seed window as handed to nextCorrect
@@ -315,6 +323,11 @@ void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const
                                const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
                                uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, uint32_t *lists, uint32_t cap,
                                int n_blocks, int grid, void *stream);
+// Trace hook (NDGPU_K9_DIGEST): what the link counter left in its tables, for piles [0, n_piles).  out[0] += a hash of every cell's
+// (pile, cell, start, len) and of every (pile, cell, position, pp, ppp, cnt) of its links [start, start + len) -- position-dependent,
+// summed, so the same whatever the order of the blocks; out[1] += cells, out[2] += links, out[3] = max(len).  out: zero before.
+void launch_k9_digest(const PileDev *piles, const uint32_t *cell_start, const uint32_t *cell_len, const uint32_t *ent_pp,
+                      const uint32_t *ent_ppp, const uint32_t *ent_cnt, unsigned long long *out, int n_piles, void *stream);
 // segment kernels of both table tiers (the large one on stream_large at the same time) -> stitch -> int64 kernel for
 // the piles they left (err == 2) -> best_pp walk
 // (ent_score == nullptr: the int64 kernel is not launched and leaves err == 2 piles for a second call with rescue = true,
