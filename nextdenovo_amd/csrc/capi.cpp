@@ -19,6 +19,7 @@
 #include "../../include/ndgpu_nextcorrect.h"
 #include "nd_host.h"
 #include "nd_runtime.h"
+#include "nd_subplan.h"
 
 using namespace ndgpu;
 
@@ -37,26 +38,6 @@ CorrectParams make_params(unsigned max_mem_len, unsigned min_len_aln, unsigned m
     p.fast = fast;
     p.read_type = read_type;
     return p;
-}
-
-template <typename F>
-void parallel_for(size_t n, int threads, F f) {
-    if (threads <= 1 || n <= 1) {
-        for (size_t i = 0; i < n; i++) f(i);
-        return;
-    }
-    std::atomic<size_t> next(0);
-    std::vector<std::thread> pool;
-    const int nt = (int)std::min<size_t>((size_t)threads, n);
-    for (int t = 0; t < nt; t++)
-        pool.emplace_back([&] {
-            for (;;) {
-                size_t i = next.fetch_add(1);
-                if (i >= n) break;
-                f(i);
-            }
-        });
-    for (auto &th : pool) th.join();
 }
 
 void run_single_alignment(char *q, int q_len, char *t, int t_len, alignment *a, int hq) {
@@ -113,6 +94,162 @@ void join_reapers() {
 struct ReaperAtExit {
     ~ReaperAtExit() { join_reapers(); }
 } g_reaper_at_exit;
+}  // namespace
+
+namespace {
+
+// Every record must name reads of this DB and windows inside them (a sorted.ovl written against other .idx files would otherwise
+// index the host tables and the device pool out of bounds): -2, nothing is computed
+int validate_records(const ReadDb &db, int n_piles, const uint32_t *recs, const uint64_t *pile_off) {
+    for (int i = 0; i < n_piles; i++) {
+        if (pile_off[i + 1] < pile_off[i]) return -2;
+        for (uint64_t r = pile_off[i]; r < pile_off[i + 1]; r++) {
+            const uint32_t *c = recs + r * 8;
+            if (c[0] >= db.n_reads() || c[4] >= db.n_reads() || c[5] > c[6] || c[6] >= db.length(c[4]) || c[2] > c[3] ||
+                c[3] >= db.length(c[0])) {
+                fprintf(stderr, "[ndgpu] ndgpu_correct_piles: record %llu of pile %d names read %u / %u or a window outside them "
+                                "(DB holds %u reads)\n", (unsigned long long)(r - pile_off[i]), i, c[0], c[4], db.n_reads());
+                return -2;
+            }
+        }
+    }
+    return 0;
+}
+
+uint64_t ns_since(std::chrono::steady_clock::time_point t0) {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// What the driver threads of one ndgpu_correct_piles_stream call share: the caller's arguments, the piles in launch order, the
+// sub-batches' cuts and the queue over them.
+struct PilesCall {
+    const ReadDb *db = nullptr;
+    const uint32_t *dev_pool = nullptr, *recs = nullptr;
+    const uint64_t *pile_off = nullptr;
+    unsigned min_len_aln = 0, max_cov_aln = 0, min_cov = 0, max_lq_length = 0, split = 0, fast = 0;
+    float ratio = 0;
+    int read_type = 0;
+    consensus_trimed **out = nullptr;
+    ndgpu_piles_done_fn done = nullptr;
+    void *user = nullptr;
+    std::vector<uint32_t> order;     // the piles, longest seed first
+    std::vector<size_t> sub_start;   // sub-batch j = order[sub_start[j], sub_start[j + 1])
+    uint64_t call_order = 0;         // (an older call in flight goes first on every context)
+    int threads_each = 1;
+    std::atomic<size_t> next_sub{0};
+    std::atomic<uint64_t> build_ns{0}, take_ns{0};
+    std::mutex done_mu;
+
+    PileEngine *build_engine(uint32_t pid) const {
+        const uint64_t r0 = pile_off[pid], r1 = pile_off[pid + 1];
+        const size_t n = (size_t)(r1 - r0);
+        std::vector<unsigned> st(n), en(n), len(n);
+        std::vector<int64_t> dev(n);
+        unsigned max_aln = n ? recs[r0 * 8 + 3] + 1 : 0;
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t *r = recs + (r0 + i) * 8;
+            dev[i] = db->window_offset(r[4], r[5], r[6], (int)r[1]);
+            len[i] = r[6] - r[5] + 1;
+            st[i] = r[2];
+            en[i] = r[3];
+            const unsigned v = r[3] - r[2] + r[6] - r[5] + 2;
+            if (v > max_aln && r[0] != r[4]) max_aln = v;
+        }
+        const unsigned lq = n ? std::min<unsigned>(en[0] / 2, max_lq_length) : max_lq_length;
+        std::string seed;  // only the HiFi consensus compares against the seed's own bases
+        if (read_type == 3 && n) seed = db->window(recs[r0 * 8 + 4], recs[r0 * 8 + 5], recs[r0 * 8 + 6], 0);
+        return new PileEngine(len.data(), dev.data(), st.data(), en.data(), (unsigned)n,
+                              make_params(max_aln, min_len_aln, max_cov_aln, min_cov, lq, ratio, split, fast, read_type),
+                              read_type == 3 ? seed.c_str() : nullptr);
+    }
+
+    void hand_over(size_t base, size_t cnt) {  // the caller's hand-over of these piles' records, while the other contexts work on
+        if (!done) return;
+        std::lock_guard<std::mutex> lock(done_mu);
+        done(user, &order[base], (int)cnt);
+    }
+
+    // One range of the length-sorted piles through one context; out of device memory -> the context's buffers are dropped and the
+    // range is halved, down to a single pile, which is then an out-of-memory seed (len 3)
+    void run_range(int ctx, size_t base, size_t cnt) {
+        std::vector<PileEngine *> eng(cnt, nullptr);
+        const auto t_b0 = std::chrono::steady_clock::now();
+        host_each(cnt, cnt <= 1, threads_each, cnt, false, [&](size_t k) { eng[k] = build_engine(order[base + k]); });
+        build_ns += ns_since(t_b0);
+        bool oom = false;
+        {
+            HipBackend be(ctx, threads_each, dev_pool, call_order, true);
+            try {
+                run_engines(eng.data(), cnt, be, threads_each);
+            } catch (const DeviceOom &e) {
+                oom = true;
+                if (getenv("NDGPU_TRACE"))
+                    fprintf(stderr, "[ndgpu trace] out of device memory (%zu bytes wanted) in a sub-batch of %zu piles: %s\n", e.bytes, cnt,
+                            cnt > 1 ? "halved" : "reported as an out-of-memory seed (len 3)");
+                // while `be` still holds the context: with two calls in flight the other call's waiting thread takes the context the
+                // moment the batch ends, and its run_main's buffers must not be the ones released here
+                DeviceAligner::context(ctx).release_memory();
+                DeviceAligner::forget_sizes();
+            }
+        }
+        if (oom) {
+            for (PileEngine *e : eng) delete e;
+            if (cnt == 1) {
+                out[order[base]] = (consensus_trimed *)make_error_seed(3);
+                hand_over(base, 1);
+            } else {
+                run_range(ctx, base, cnt / 2);
+                run_range(ctx, base + cnt / 2, cnt - cnt / 2);
+            }
+            return;
+        }
+        const auto t_t0 = std::chrono::steady_clock::now();
+        for (size_t k = 0; k < cnt; k++) out[order[base + k]] = (consensus_trimed *)eng[k]->take_result();
+        hand_over(base, cnt);
+        // tearing down the per-pile host state (thousands of small vectors per pile, ~0.3 ms each; parallel frees
+        // only fight over the allocator) is not on anybody's critical path: a reaper thread does it while the caller
+        // goes on, and the next call (or the library's unload) waits for it
+        {
+            std::lock_guard<std::mutex> lock(g_reap_mu);
+            g_reapers.emplace_back([v = std::move(eng)] {
+                for (PileEngine *e : v) delete e;
+            });
+        }
+        take_ns += ns_since(t_t0);
+    }
+
+    // A driver thread: sub-batches from the call's queue through context ctx.  (The context serves this call's sub-batches one
+    // behind the other before a newer call's: the place in its line is kept between them)
+    void drive(int ctx) {
+        DeviceAligner &dev = DeviceAligner::context(ctx);
+        dev.reserve_batches(call_order);
+        struct Unreserve { DeviceAligner &d; uint64_t o; ~Unreserve() { d.unreserve_batches(o); } } unreserve{dev, call_order};
+        for (size_t sb; (sb = next_sub.fetch_add(1)) + 1 < sub_start.size();) run_range(ctx, sub_start[sb], sub_start[sb + 1] - sub_start[sb]);
+    }
+};
+
+void print_prof(int drivers, int threads_each) {  // NDGPU_PROF: the host driver's wall-clock accounting since the last print
+    fprintf(stderr, "[ndgpu prof] drivers %d x %d threads | main %.3f s  extract %.3f s  align %.3f s (%llu jobs)  "
+                    "advance %.3f s  (driver-thread wall sums)\n",
+            drivers, threads_each, g_prof.main_ns * 1e-9, g_prof.extract_ns * 1e-9, g_prof.align_ns * 1e-9,
+            (unsigned long long)g_prof.jobs.load(), g_prof.advance_ns * 1e-9);
+    fprintf(stderr, "[ndgpu prof] run_main: prep %.3f  align(K7+K8a) %.3f  tags %.3f  msa(K9+K10) %.3f  post %.3f s\n",
+            g_prof.m_prep * 1e-9, g_prof.m_aln * 1e-9, g_prof.m_tags * 1e-9, g_prof.m_msa * 1e-9,
+            g_prof.m_post * 1e-9);
+    fprintf(stderr, "[ndgpu prof] advance, CPU seconds by phase: after main %.3f  after extract %.3f  after LQ round 1 %.3f  after round 2 + splice %.3f\n",
+            g_prof.adv_ns[0] * 1e-9, g_prof.adv_ns[1] * 1e-9, g_prof.adv_ns[2] * 1e-9, g_prof.adv_ns[3] * 1e-9);
+    fprintf(stderr, "[ndgpu prof] after extract: 8-mer ranking %.3f  POA %.3f  LQ round 1 layout %.3f s (CPU seconds)\n", g_prof.rank_ns * 1e-9,
+            g_prof.poa_ns * 1e-9, g_prof.lqstart_ns * 1e-9);
+    g_prof.rank_ns = g_prof.poa_ns = g_prof.lqstart_ns = 0;
+    fprintf(stderr, "[ndgpu prof] LQ-stage alignment batches (%llu jobs): host packing %.3f s, device round trip %.3f s, host decoding %.3f s "
+                    "(wall sums over contexts)\n", (unsigned long long)g_prof.c_jobs.load(), g_prof.c_pack * 1e-9, g_prof.c_dev * 1e-9,
+            g_prof.c_decode * 1e-9);
+    g_prof.c_pack = g_prof.c_dev = g_prof.c_decode = g_prof.c_jobs = 0;
+    for (auto &a : g_prof.adv_ns) a = 0;
+    g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
+    g_prof.m_prep = g_prof.m_aln = g_prof.m_tags = g_prof.m_msa = g_prof.m_post = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -224,7 +361,7 @@ int ndgpu_correct_batch(int n_piles, char ***seqs, unsigned int **aln_start, uns
     // gets the whole process throttled)
     if (host_threads <= 0 || (host_threads > effective_cpus() && !getenv("NDGPU_NO_CPU_CAP"))) host_threads = effective_cpus();
     std::vector<PileEngine *> eng((size_t)n_piles, nullptr);
-    parallel_for((size_t)n_piles, host_threads, [&](size_t i) {
+    host_each((size_t)n_piles, host_threads <= 1 || n_piles <= 1, host_threads, (size_t)n_piles, false, [&](size_t i) {
         eng[i] = new PileEngine(seqs[i], aln_start[i], aln_end[i], seq_count[i],
                                 make_params(max_mem_len[i], min_len_aln, max_cov_aln, min_cov, lqseq_max_length[i],
                                             min_error_corrected_ratio, split, fast, read_type));
@@ -384,31 +521,22 @@ int ndgpu_correct_piles_stream(ndgpu_db *h, int n_piles, const uint32_t *recs, c
     // (what the process can have, not what the machine has: a cgroup quota of 16 CPUs on a 256-thread host; asking for more only
     // gets the whole process throttled)
     if (host_threads <= 0 || (host_threads > effective_cpus() && !getenv("NDGPU_NO_CPU_CAP"))) host_threads = effective_cpus();
-    const ReadDb &db = *h->db;
-    // every record must name reads of this DB and windows inside them (a sorted.ovl written against other .idx files
-    // would otherwise index the host tables and the device pool out of bounds): -2, nothing is computed
-    for (int i = 0; i < n_piles; i++) {
-        if (pile_off[i + 1] < pile_off[i]) return -2;
-        for (uint64_t r = pile_off[i]; r < pile_off[i + 1]; r++) {
-            const uint32_t *c = recs + r * 8;
-            if (c[0] >= db.n_reads() || c[4] >= db.n_reads() || c[5] > c[6] || c[6] >= db.length(c[4]) || c[2] > c[3] ||
-                c[3] >= db.length(c[0])) {
-                fprintf(stderr, "[ndgpu] ndgpu_correct_piles: record %llu of pile %d names read %u / %u or a window outside them "
-                                "(DB holds %u reads)\n", (unsigned long long)(r - pile_off[i]), i, c[0], c[4], db.n_reads());
-                return -2;
-            }
-        }
-    }
+    if (const int rc = validate_records(*h->db, n_piles, recs, pile_off)) return rc;
     join_reapers();  // the previous call's teardown
-    const uint64_t call_order = DeviceAligner::next_order();  // (an older call in flight goes first on every context)
+    PilesCall call;
+    call.db = h->db, call.dev_pool = h->dev_pool, call.recs = recs, call.pile_off = pile_off;
+    call.min_len_aln = min_len_aln, call.max_cov_aln = max_cov_aln, call.min_cov = min_cov, call.max_lq_length = max_lq_length;
+    call.ratio = min_error_corrected_ratio, call.split = split, call.fast = fast, call.read_type = read_type;
+    call.out = out, call.done = done, call.user = user;
+    call.call_order = DeviceAligner::next_order();
     const auto t_call0 = std::chrono::steady_clock::now();
-    std::atomic<uint64_t> build_ns{0}, take_ns{0};
-    // piles per sub-batch at most (the cost target below normally cuts earlier)
+    // piles per sub-batch at most (the cost target normally cuts earlier)
     size_t sub = 384;
     if (const char *e = getenv("NDGPU_SUBBATCH")) sub = (size_t)std::max(1, atoi(e));
     // longest seeds first: the scoring DP is a sequential chain per seed, so similar lengths
     // share a launch and the long chains start early
-    std::vector<uint32_t> order((size_t)n_piles);
+    std::vector<uint32_t> &order = call.order;
+    order.resize((size_t)n_piles);
     for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
         return recs[pile_off[a] * 8 + 3] > recs[pile_off[b] * 8 + 3];
@@ -418,214 +546,36 @@ int ndgpu_correct_piles_stream(ndgpu_db *h, int n_piles, const uint32_t *recs, c
     // -- the contexts only take the CPUs from one another's host phases)
     drivers = std::min(drivers, std::max(2, host_threads));
     if (const char *e = getenv("NDGPU_CONTEXTS")) drivers = std::max(1, std::min(atoi(e), (int)DeviceAligner::kMaxContexts));
-    // sub-batches: at most `sub` piles and at most `tag_budget` estimated alignment columns each, so that the
-    // device buffers of a context (sized by the largest sub-batch it has seen) stay bounded whatever the seed lengths
+    // sub-batches (nd_subplan.h): at most `sub` piles and at most `tag_budget` estimated alignment columns each
     uint64_t tag_budget = 900000000ull;
     DeviceAligner::plan_memory(drivers, &tag_budget);  // what the device has free now decides it
     if (const char *e = getenv("NDGPU_SUBBATCH_TAGS")) tag_budget = std::max<uint64_t>(1000000ull, strtoull(e, nullptr, 10));
-    // Sub-batches = consecutive ranges of the length-sorted piles of (about) equal cost, two per context, pulled from one
-    // queue by whichever context is free.  Cost = estimated alignment columns (what every device phase and the host's
-    // low-quality-region stage scale with).  A context alternates device-heavy phases (alignment, MSA, scoring) with
-    // host-heavy ones (candidate ranking, POA, second MSA, splicing): with several sub-batches per context the phases of
-    // different contexts interleave instead of all contexts being on the host -- and the device idle -- at the end of a call.
-    // (Until round 2 the first sub-batches were small and held the longest seeds, because a seed's scoring chain bounded
-    // the call; the segment-parallel scoring DP removed that.)
-    std::vector<size_t> sub_start{0};
-    {
-        std::vector<uint64_t> est((size_t)n_piles);
-        uint64_t total = 0;
-        for (size_t k = 0; k < (size_t)n_piles; k++) {
-            const uint32_t pid = order[k];
-            uint64_t e = 0;
-            for (uint64_t r = pile_off[pid]; r < pile_off[pid + 1]; r++) e += (uint64_t)(recs[r * 8 + 3] - recs[r * 8 + 2] + 1);
-            est[k] = e + e / 6;
-            total += est[k];
-        }
-        // (measured on config 2, 1,666 piles: 1, 2, 3, 4, 6 per context = 1147, 1095, 1181, 1269, 1376 ms per step in round 2; 1 and 2
-        // within noise since.  A small call -- the share of one rank of 4 or 8 -- is a matter of latency, not of filling the device:
-        // every sub-batch of a context is another pass through the same dependent phases, and with one per context the 210 piles of a
-        // rank of 8 take 170 ms instead of 262, the 407 of a rank of 4 255 instead of 320: profiles/r04_rank_share_config2.txt)
-        int per_ctx = n_piles >= 1024 ? 2 : 1;
-        if (const char *e = getenv("NDGPU_SUBBATCHES_PER_CONTEXT")) per_ctx = std::max(1, atoi(e));
-        // exactly drivers x per_ctx pieces of equal cost where the caps allow it (a cut where the running cost passes the next multiple of
-        // total / pieces): with "cut before the piece would overflow" the pieces came out slightly small and a 17th, alone in a third round
-        // of the contexts, ended every config-2 call ~60 ms late.  The caps (piles per sub-batch, the memory plan's columns) still cut.
-        // Rounds may taper (NDGPU_TAPER=w1,w2,...: the share of the call's cost each round of the contexts takes; default: equal
-        // rounds): what the LAST round leaves for the host -- its piles' candidate ranking, POA, two more rounds -- ends the call with
-        // the device idle, and it is that round's share of the call's host work divided by the CPUs the process has.
-        std::vector<double> weights((size_t)per_ctx, 1.0 / per_ctx);
-        if (const char *e = getenv("NDGPU_TAPER")) {
-            std::vector<double> w;
-            for (const char *p = e; *p;) {
-                char *end = nullptr;
-                const double v = strtod(p, &end);
-                if (end == p) break;
-                if (v > 0) w.push_back(v);
-                p = *end ? end + 1 : end;
-            }
-            double sum = 0;
-            for (double v : w) sum += v;
-            if (!w.empty() && sum > 0) {
-                for (double &v : w) v /= sum;
-                weights = w;
-            }
-        }
-        std::vector<uint64_t> targets;   // cumulative cost at which piece k ends
-        {
-            double at = 0;
-            for (double w : weights)
-                for (int c = 0; c < drivers; c++) {
-                    at += w / drivers;
-                    targets.push_back((uint64_t)(at * (double)total));
-                }
-            if (!targets.empty()) targets.pop_back();  // (the last piece ends with the piles)
-        }
-        const uint64_t n_target = (uint64_t)targets.size() + 1;
-        const uint64_t piece = std::min<uint64_t>(tag_budget, std::max<uint64_t>(total / n_target + 1, 2000000ull));
-        const bool by_target = total / n_target + 1 <= tag_budget && total / n_target + 1 >= 2000000ull;  // (neither cap nor floor bites)
-        uint64_t acc = 0, run = 0;
-        size_t cnt = 0, next_cut = 0;
-        for (size_t k = 0; k < (size_t)n_piles; k++) {
-            bool cut = cnt && (cnt >= sub || acc + est[k] > tag_budget);
-            if (!cut && cnt) {
-                if (by_target) cut = next_cut < targets.size() && run + est[k] / 2 >= targets[next_cut];
-                else cut = acc + est[k] > piece;
-            }
-            if (cut) {
-                sub_start.push_back(k);
-                acc = 0, cnt = 0;
-                while (by_target && next_cut < targets.size() && run + est[k] / 2 >= targets[next_cut]) next_cut++;
-            }
-            acc += est[k], run += est[k], cnt++;
-        }
-        sub_start.push_back((size_t)n_piles);
+    std::vector<uint64_t> est((size_t)n_piles);  // cost of a pile = its estimated alignment columns
+    for (size_t k = 0; k < (size_t)n_piles; k++) {
+        const uint32_t pid = order[k];
+        uint64_t e = 0;
+        for (uint64_t r = pile_off[pid]; r < pile_off[pid + 1]; r++) e += (uint64_t)(recs[r * 8 + 3] - recs[r * 8 + 2] + 1);
+        est[k] = e + e / 6;
     }
-    const size_t n_sub = sub_start.size() - 1;
+    int per_ctx = n_piles >= 1024 ? 2 : 1;  // (a small call is a matter of latency: see plan_sub_batches)
+    if (const char *e = getenv("NDGPU_SUBBATCHES_PER_CONTEXT")) per_ctx = std::max(1, atoi(e));
+    call.sub_start = plan_sub_batches(est, drivers, round_weights(per_ctx, getenv("NDGPU_TAPER")), sub, tag_budget);
+    const size_t n_sub = call.sub_start.size() - 1;
     drivers = (int)std::min<size_t>((size_t)drivers, n_sub);
     int threads_each = std::max(1, host_threads / drivers);  // (measured: more threads per context is slower)
     if (const char *e = getenv("NDGPU_THREADS_PER_CONTEXT")) threads_each = std::max(1, atoi(e));
+    call.threads_each = threads_each;
     CoreGovernor::set_total(getenv("NDGPU_NO_BORROW") ? 0 : host_threads);
-    std::atomic<uint64_t> oom_seeds{0};
-    std::mutex done_mu;
-    // one range of the length-sorted piles through one context; out of device memory -> the context's buffers are
-    // dropped and the range is halved, down to a single pile, which is then an out-of-memory seed (len 3)
-    std::function<void(int, size_t, size_t)> run_range = [&](int ctx, size_t base, size_t cnt) {
-        std::vector<PileEngine *> eng(cnt, nullptr);
-        const auto t_b0 = std::chrono::steady_clock::now();
-        CoreLease *build_lease = new CoreLease(threads_each);
-        parallel_for(cnt, build_lease->n, [&](size_t k) {
-            const uint32_t pid = order[base + k];
-            const uint64_t r0 = pile_off[pid], r1 = pile_off[pid + 1];
-            const size_t n = (size_t)(r1 - r0);
-            std::vector<unsigned> st(n), en(n), len(n);
-            std::vector<int64_t> dev(n);
-            unsigned max_aln = n ? recs[r0 * 8 + 3] + 1 : 0;
-            for (size_t i = 0; i < n; i++) {
-                const uint32_t *r = recs + (r0 + i) * 8;
-                dev[i] = db.window_offset(r[4], r[5], r[6], (int)r[1]);
-                len[i] = r[6] - r[5] + 1;
-                st[i] = r[2];
-                en[i] = r[3];
-                const unsigned v = r[3] - r[2] + r[6] - r[5] + 2;
-                if (v > max_aln && r[0] != r[4]) max_aln = v;
-            }
-            const unsigned lq = n ? std::min<unsigned>(en[0] / 2, max_lq_length) : max_lq_length;
-            std::string seed;  // only the HiFi consensus compares against the seed's own bases
-            if (read_type == 3 && n) seed = db.window(recs[r0 * 8 + 4], recs[r0 * 8 + 5], recs[r0 * 8 + 6], 0);
-            eng[k] = new PileEngine(len.data(), dev.data(), st.data(), en.data(), (unsigned)n,
-                                    make_params(max_aln, min_len_aln, max_cov_aln, min_cov, lq,
-                                                min_error_corrected_ratio, split, fast, read_type),
-                                    read_type == 3 ? seed.c_str() : nullptr);
-        });
-        delete build_lease;
-        build_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_b0).count();
-        bool oom = false;
-        try {
-            HipBackend be(ctx, threads_each, h->dev_pool, call_order, true);
-            run_engines(eng.data(), cnt, be, threads_each);
-        } catch (const DeviceOom &e) {
-            oom = true;
-            if (getenv("NDGPU_TRACE"))
-                fprintf(stderr, "[ndgpu trace] out of device memory (%zu bytes wanted) in a sub-batch of %zu piles: %s\n", e.bytes, cnt,
-                        cnt > 1 ? "halved" : "reported as an out-of-memory seed (len 3)");
-        }
-        if (oom) {
-            DeviceAligner::context(ctx).release_memory();
-            DeviceAligner::forget_sizes();
-            for (PileEngine *e : eng) delete e;
-            if (cnt == 1) {
-                out[order[base]] = (consensus_trimed *)make_error_seed(3);
-                oom_seeds++;
-                if (done) {
-                    std::lock_guard<std::mutex> lock(done_mu);
-                    done(user, &order[base], 1);
-                }
-            } else {
-                run_range(ctx, base, cnt / 2);
-                run_range(ctx, base + cnt / 2, cnt - cnt / 2);
-            }
-            return;
-        }
-        const auto t_t0 = std::chrono::steady_clock::now();
-        for (size_t k = 0; k < cnt; k++) out[order[base + k]] = (consensus_trimed *)eng[k]->take_result();
-        if (done) {  // (the caller's hand-over of this sub-batch's records, while the other contexts work on)
-            std::lock_guard<std::mutex> lock(done_mu);
-            done(user, &order[base], (int)cnt);
-        }
-        // tearing down the per-pile host state (thousands of small vectors per pile, ~0.3 ms each; parallel frees
-        // only fight over the allocator) is not on anybody's critical path: a reaper thread does it while the caller
-        // goes on, and the next call (or the library's unload) waits for it
-        {
-            std::lock_guard<std::mutex> lock(g_reap_mu);
-            g_reapers.emplace_back([v = std::move(eng)] {
-                for (PileEngine *e : v) delete e;
-            });
-        }
-        take_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_t0).count();
-    };
-    std::atomic<size_t> next_sub{0};
-    auto drive = [&](int ctx) {
-        // (the context serves this call's sub-batches one behind the other before a newer call's: the place in its line is kept
-        // between them)
-        DeviceAligner &dev = DeviceAligner::context(ctx);
-        dev.reserve_batches(call_order);
-        struct Unreserve { DeviceAligner &d; uint64_t o; ~Unreserve() { d.unreserve_batches(o); } } unreserve{dev, call_order};
-        for (;;) {
-            const size_t sb = next_sub.fetch_add(1);
-            if (sb >= n_sub) break;
-            run_range(ctx, sub_start[sb], sub_start[sb + 1] - sub_start[sb]);
-        }
-    };
     std::vector<std::thread> th;
-    for (int c = 1; c < drivers; c++) th.emplace_back(drive, c);
-    drive(0);
+    for (int c = 1; c < drivers; c++) th.emplace_back([&call, c] { call.drive(c); });
+    call.drive(0);
     for (auto &t : th) t.join();
     DeviceAligner::level_buffers(drivers);  // (nothing in flight now) no context will have to grow a buffer in the middle of the next call
     if (getenv("NDGPU_TRACE"))
         fprintf(stderr, "[ndgpu trace] correct_piles %d piles in %zu sub-batches: %.1f ms wall | engine build %.1f ms, result take %.1f ms (summed over contexts)\n",
                 n_piles, n_sub, std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_call0).count() * 1e-3,
-                build_ns.load() * 1e-6, take_ns.load() * 1e-6);
-    if (getenv("NDGPU_PROF")) {
-        fprintf(stderr, "[ndgpu prof] drivers %d x %d threads | main %.3f s  extract %.3f s  align %.3f s (%llu jobs)  "
-                        "advance %.3f s  (driver-thread wall sums)\n",
-                drivers, threads_each, g_prof.main_ns * 1e-9, g_prof.extract_ns * 1e-9, g_prof.align_ns * 1e-9,
-                (unsigned long long)g_prof.jobs.load(), g_prof.advance_ns * 1e-9);
-        fprintf(stderr, "[ndgpu prof] run_main: prep %.3f  align(K7+K8a) %.3f  tags %.3f  msa(K9+K10) %.3f  post %.3f s\n",
-                g_prof.m_prep * 1e-9, g_prof.m_aln * 1e-9, g_prof.m_tags * 1e-9, g_prof.m_msa * 1e-9,
-                g_prof.m_post * 1e-9);
-        fprintf(stderr, "[ndgpu prof] advance, CPU seconds by phase: after main %.3f  after extract %.3f  after LQ round 1 %.3f  after round 2 + splice %.3f\n",
-                g_prof.adv_ns[0] * 1e-9, g_prof.adv_ns[1] * 1e-9, g_prof.adv_ns[2] * 1e-9, g_prof.adv_ns[3] * 1e-9);
-        fprintf(stderr, "[ndgpu prof] after extract: 8-mer ranking %.3f  POA %.3f  LQ round 1 layout %.3f s (CPU seconds)\n", g_prof.rank_ns * 1e-9,
-                g_prof.poa_ns * 1e-9, g_prof.lqstart_ns * 1e-9);
-        g_prof.rank_ns = g_prof.poa_ns = g_prof.lqstart_ns = 0;
-        fprintf(stderr, "[ndgpu prof] LQ-stage alignment batches (%llu jobs): host packing %.3f s, device round trip %.3f s, host decoding %.3f s "
-                        "(wall sums over contexts)\n", (unsigned long long)g_prof.c_jobs.load(), g_prof.c_pack * 1e-9, g_prof.c_dev * 1e-9,
-                g_prof.c_decode * 1e-9);
-        g_prof.c_pack = g_prof.c_dev = g_prof.c_decode = g_prof.c_jobs = 0;
-        for (auto &a : g_prof.adv_ns) a = 0;
-        g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
-        g_prof.m_prep = g_prof.m_aln = g_prof.m_tags = g_prof.m_msa = g_prof.m_post = 0;
-    }
+                call.build_ns.load() * 1e-6, call.take_ns.load() * 1e-6);
+    if (getenv("NDGPU_PROF")) print_prof(drivers, threads_each);
     return 0;
 }
 
@@ -799,7 +749,7 @@ int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) {
         }
     }
     int rc = 0;
-    parallel_for((size_t)n, threads, [&](size_t i) {
+    host_each((size_t)n, threads <= 1 || n <= 1, threads, (size_t)n, false, [&](size_t i) {
         PoaReq &rq = reqs[i];
         if (!rq.done && !rq.failed) {
             rq.out = poa_consensus(rq.seqs);
@@ -828,7 +778,7 @@ int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank
     std::vector<RankReq> reqs((size_t)n);
     for (int i = 0; i < n; i++) reqs[i].seqs = jobs[i].seqs, reqs[i].len = jobs[i].len, reqs[i].n = jobs[i].seq_count;
     if (flags & 1) {
-        parallel_for((size_t)n, effective_cpus(), [&](size_t i) {
+        host_each((size_t)n, effective_cpus() <= 1 || n <= 1, effective_cpus(), (size_t)n, false, [&](size_t i) {
             RankReq &rq = reqs[i];
             lq_rank_host(rq.seqs, rq.len, rq.n, rq.order, rq.kscore, &rq.tail);
         });
@@ -929,7 +879,7 @@ int align_batch_common(std::vector<AlnJob> &jobs, const uint32_t *db_pool, int f
             free(qs), free(ts);
             return -3;
         }
-        parallel_for(n, threads, [&](size_t i) {
+        host_each(n, threads <= 1 || n <= 1, threads, n, false, [&](size_t i) {
             const AlnRunsResult &r = sum[i];
             char *qa = qs + at[i], *ta = ts + at[i];
             size_t c = 0;

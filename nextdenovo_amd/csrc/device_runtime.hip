@@ -365,6 +365,30 @@ struct AlignChunk {
     uint64_t slots;  // walker slots of the launch (0 unless seg)
 };
 
+// The main phase's results, step by step (run_main).  What layout_piles makes of a sub-batch beside the context's pool, tasks, reads
+// and piles: the pile of every read, the piles with a byte outside [ACGT], and the slot totals the buffers are sized by.
+struct MainLayout {
+    std::vector<uint32_t> read_pile;
+    std::vector<uint8_t> bad_pile;
+    uint64_t ops_words = 0, tag_slots = 0, colidx_slots = 0, col_slots = 0, acc_slots = 0;
+};
+constexpr uint64_t kTagSlotLimit = 1ull << 32;  // count_links keeps a read's tag base (ReadDev::tag_off) in 32 bits
+struct CovPlanes {  // d_cov's three arrays of col_slots + 1 words: coverage, insertion count, longest insertion
+    uint32_t *cov, *inscnt, *insmax;
+};
+struct MsaPlan {  // plan_msa: K10's work lists by tier, K9's column blocks, the totals of cells / links / path items / segments
+    std::vector<SegItem> items_small, items_large, items_slow;  // (slow: piles of the int64 kernel; only the walk uses them)
+    std::vector<ColBlock> blocks;
+    uint64_t cells = 0, ents = 0, paths = 0;
+    uint32_t n_segs = 0;
+    size_t n_items() const { return items_small.size() + items_large.size() + items_slow.size(); }
+};
+struct MsaResult {  // count_and_score: the last attempt's error words, its piles, its paths (a view into the download arena)
+    uint32_t herr[kErrWords] = {};
+    const PathItem *hpath = nullptr;
+    std::vector<PileDev> piles;
+};
+
 }  // namespace
 
 
@@ -392,8 +416,9 @@ struct DeviceAligner::State {
         // a newer call's thread that is already waiting does not slip in while the older call's thread fetches its next sub-batch
         void lock(uint64_t order = 0, bool reserved = false) {
             std::unique_lock<std::mutex> l(m);
+            if (reserved && waiting.find(order) == waiting.end()) reserved = false;  // (no such reservation: waits like any other caller)
             auto it = reserved ? waiting.end() : waiting.insert(order);
-            cv.wait(l, [&] { return !held && *waiting.begin() == order; });
+            cv.wait(l, [&] { return !held && !waiting.empty() && *waiting.begin() == order; });
             if (!reserved) waiting.erase(it);
             held = true;
         }
@@ -433,7 +458,6 @@ struct DeviceAligner::State {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t trace_budget_bytes = (size_t)48 << 30;
     int host_threads = 1;
-    bool k9_full_capacity = getenv("NDGPU_K9_FULL") != nullptr;  // skip the small-capacity first attempt of K9
     uint64_t k9_retries = 0;
 
     // Host <-> device transfers go through two pinned arenas of the context (up, down).  An asynchronous copy from / to pageable
@@ -487,10 +511,34 @@ struct DeviceAligner::State {
         return at;
     }
 
+    // What every device phase of a context starts with, in this order: the lock of NDGPU_DEBUG_LAUNCH=2 (one phase at a time over
+    // all contexts), the context's own lock, the context's device.
+    struct Phase {
+        std::unique_lock<std::mutex> dbg;
+        std::lock_guard<std::mutex> lock;
+        explicit Phase(State &S) : dbg(g_debug_exclusive ? std::unique_lock<std::mutex>(g_dbg_mu) : std::unique_lock<std::mutex>()), lock(S.mu) {
+            HIP_CHECK(hipSetDevice(S.device));
+        }
+    };
+
     // The forward / traceback ("align") phase that run_chunk, run_lq and run_main share (defined with the traceback's set-up below)
     std::vector<AlignChunk> plan_chunks(AlnTask *t, size_t nt);
     void launch_chunk(const AlignChunk &c, const int32_t *order, const int32_t *tb_order, hipEvent_t ev_mid, hipEvent_t ev_end, const char *who);
     void tally_outs(size_t nt, std::vector<int32_t> *wide);
+    void run_wide(bool ops_to_host, const std::vector<int32_t> &ids);  // the tasks whose live band left the register path, again with V in HBM
+
+    // The steps of run_main, in its order (defined above it)
+    MainLayout layout_piles(MainPile **mp, size_t np);
+    void reserve_layout(const MainLayout &L, size_t np);
+    const int32_t *length_order(size_t a, size_t m);
+    void align_main(const std::vector<AlignChunk> &chunks, size_t np);
+    void launch_tags(const CovPlanes &cov, size_t np);
+    void upload_plan(const MsaPlan &plan);
+    MsaResult count_and_score(const MsaPlan &plan, const CovPlanes &cov);
+    void score_pass(const MsaPlan &plan, const K10Args &k10);
+    void rescue_pass(const MsaPlan &plan, const K10Args &k10);
+    void k9_digest_trace(const K9Args &k9, size_t np);
+    void tally_main(const MsaPlan &plan, const std::vector<uint8_t> &bad_pile, MainPile **mp, const uint64_t tp[5]);
 };
 
 static int g_ctx_creating = -1;  // index of the context under construction (guarded by g_ctx_mu)
@@ -742,6 +790,12 @@ static inline uint64_t wall_ns() {
         .count();
 }
 
+static inline double ms_between(hipEvent_t a, hipEvent_t b) {  // HIP-event time from a to b (both reached)
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+
 static void limits_for(int total, int hq, int *max_d, int *band) {
     // lib/align.c:567-568,575-576 -- double arithmetic on the host, exactly as the reference
     if (hq) {
@@ -777,6 +831,37 @@ struct TbConfig {
 static const TbConfig &tb_config() {
     static const TbConfig c;
     return c;
+}
+// Test hooks and A/B knobs of the main phase (run_main), read once per process at its first call.
+struct MainHooks {
+    uint32_t k10_seg_len = 1024;    // NDGPU_K10_SEG: columns of a K10 segment (the last one of a pile takes the remainder)
+    uint32_t k10_warm = 128;        // NDGPU_K10_WARM: warm-up columns of a speculative segment (< seg_len)
+    int32_t k10_guard = 1 << 30;    // NDGPU_K10_GUARD: raw scores beyond it send the pile to the int64 kernel
+    // NDGPU_K10_FORCE = large (every pile through the large tables) | slow (every pile through the int64 HBM-resident kernel) |
+    // seq (one segment per pile: no speculation) | repair (every second segment is scored again by the stitch kernel as if its
+    // check had failed)
+    bool k10_large = false, k10_slow = false;
+    uint32_t k10_force_repair = 0;
+    bool k7_order = !getenv("NDGPU_K7_NO_ORDER");                 // NDGPU_K7_NO_ORDER: K7 in table order, not longest first
+    bool k8_order = getenv("NDGPU_K8_ORDER") != nullptr;          // NDGPU_K8_ORDER: K8a in K7's order (see align_main)
+    bool k9_full = getenv("NDGPU_K9_FULL") != nullptr;            // NDGPU_K9_FULL: skip the small-capacity first attempt of K9
+    bool k9_force_retry = getenv("NDGPU_K9_FORCE_RETRY") != nullptr;  // NDGPU_K9_FORCE_RETRY: take the overflow path behind attempt 0
+    bool k9_digest = getenv("NDGPU_K9_DIGEST") != nullptr && atoi(getenv("NDGPU_K9_DIGEST")) != 0;  // NDGPU_K9_DIGEST: see k9_digest_trace
+    MainHooks() {
+        if (const char *e = getenv("NDGPU_K10_SEG")) k10_seg_len = (uint32_t)std::max(16, atoi(e));
+        if (const char *e = getenv("NDGPU_K10_WARM")) k10_warm = (uint32_t)std::max(1, atoi(e));
+        if (const char *e = getenv("NDGPU_K10_GUARD")) k10_guard = atoi(e);
+        if (const char *e = getenv("NDGPU_K10_FORCE")) {
+            k10_large = !strcmp(e, "large"), k10_slow = !strcmp(e, "slow");
+            if (!strcmp(e, "seq")) k10_seg_len = 0x7fffffffu;
+            if (!strcmp(e, "repair")) k10_force_repair = 2;
+        }
+        if (k10_warm >= k10_seg_len) k10_warm = k10_seg_len - 1;
+    }
+};
+static const MainHooks &main_hooks() {
+    static const MainHooks h;
+    return h;
 }
 static inline uint32_t tb_ck_slots(int max_d) { return max_d > 0 ? (uint32_t)(max_d - 1) >> tb_config().cshift : 0u; }
 // device bytes a task adds to its launch when the launch is walked in segments
@@ -918,10 +1003,7 @@ static size_t next_chunk(AlnJob *const *jobs, size_t n, uint64_t trace_budget_by
 
 void DeviceAligner::align_batch(AlnJob **jobs, size_t n) {
     if (n == 0) return;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(s_->mu);
-    HIP_CHECK(hipSetDevice(s_->device));
+    const State::Phase phase(*s_);
     for (size_t done = 0; done < n;) {
         const size_t take = next_chunk(jobs + done, n - done, s_->trace_budget_bytes);
         run_chunk(jobs + done, take);
@@ -932,10 +1014,7 @@ void DeviceAligner::align_batch(AlnJob **jobs, size_t n) {
 void DeviceAligner::align_batch_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) {
     runs.clear();
     if (n == 0) return;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(s_->mu);
-    HIP_CHECK(hipSetDevice(s_->device));
+    const State::Phase phase(*s_);
     for (size_t done = 0; done < n;) {
         const size_t take = next_chunk(jobs + done, n - done, s_->trace_budget_bytes);
         run_chunk_runs(jobs + done, take, res + done, runs);
@@ -945,20 +1024,8 @@ void DeviceAligner::align_batch_runs(AlnJob **jobs, size_t n, AlnRunsResult *res
 
 namespace {
 template <typename F>
-void par_ranges(size_t n, int base_threads, F f) {  // f(begin, end) over contiguous ranges
-    if (base_threads <= 1 || n < 4096) {
-        f((size_t)0, n);
-        return;
-    }
-    CoreLease lease(base_threads);
-    const int threads = lease.n;
-    const size_t nt = std::min<size_t>((size_t)threads, (n + 2047) / 2048);
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; t++) {
-        const size_t a = n * t / nt, b = n * (t + 1) / nt;
-        th.emplace_back([=] { f(a, b); });
-    }
-    for (auto &x : th) x.join();
+void par_ranges(size_t n, int base_threads, F f) {  // f(begin, end) over contiguous ranges: a chunk's jobs, packed / decoded
+    host_ranges(n, base_threads <= 1 || n < 4096, base_threads, (n + 2047) / 2048, f);
 }
 
 // ASCII -> 2-bit into a preallocated word range (same coding as pack_append)
@@ -1060,9 +1127,7 @@ uint64_t DeviceAligner::chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t
     if (ops_to_host) HIP_CHECK(hipMemcpyAsync(S.h_ops.p, S.d_ops.p, ops_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     S.sync_drain(st);
     HIP_CHECK(hipGetLastError());
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.ev0, S.ev1));
-    S.stats.forward_ms += ms;  // (this path brackets K7 alone: its K8a is in neither traceback_ms nor traceback_launches)
+    S.stats.forward_ms += ms_between(S.ev0, S.ev1);  // (this path brackets K7 alone: its K8a is in neither traceback_ms nor traceback_launches)
     S.stats.forward_launches++;
     S.stats.tasks += n;
 
@@ -1070,7 +1135,7 @@ uint64_t DeviceAligner::chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t
     std::vector<int32_t> wide;
     for (size_t i = 0; i < n; i++)
         if (S.h_outs.p[i].status == ST_NEED_WIDE) wide.push_back((int32_t)i);
-    if (!wide.empty()) run_wide(ops_to_host ? jobs : nullptr, wide);
+    if (!wide.empty()) S.run_wide(ops_to_host, wide);
     *dev_ns = wall_ns() - tc1;
 
     S.tally_outs(n, nullptr);  // (after run_wide: the wide tasks count with what the wide kernels reported)
@@ -1157,9 +1222,7 @@ void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, 
     HIP_CHECK(hipEventRecord(S.evs[6], st));
     S.d2h(sums.data(), S.d_run_sums.p, n * sizeof(AlnRunSum), st);
     S.sync_drain(st);
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
-    S.stats.aln_batch_ms += ms;
+    S.stats.aln_batch_ms += ms_between(S.evs[5], S.evs[6]);
 
     std::vector<uint64_t> off(n);
     uint64_t total = 0;
@@ -1180,8 +1243,7 @@ void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, 
         HIP_CHECK(hipEventRecord(S.evs[6], st));
         S.d2h(runs.data() + at, S.d_runs.p, total * sizeof(uint32_t), st);
         S.sync_drain(st);
-        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
-        S.stats.aln_batch_ms += ms;
+        S.stats.aln_batch_ms += ms_between(S.evs[5], S.evs[6]);
         S.stats.aln_batch_launches++;
     }
     S.stats.aln_batch_jobs += n;
@@ -1200,9 +1262,8 @@ void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, 
     }
 }
 
-void DeviceAligner::run_wide(AlnJob **jobs, const std::vector<int32_t> &ids) {
-    State &S = *s_;
-    const bool ops_to_host = jobs != nullptr;  // the device main phase keeps ops in HBM
+void DeviceAligner::State::run_wide(bool ops_to_host, const std::vector<int32_t> &ids) {  // (ops_to_host false: the main phase keeps ops in HBM)
+    State &S = *this;
     // process in groups bounded by the trace budget; wide rows are band-cap sized
     size_t at = 0;
     DevBuf<uint64_t> &trace = S.d_wtrace;
@@ -1268,7 +1329,7 @@ void DeviceAligner::run_wide(AlnJob **jobs, const std::vector<int32_t> &ids) {
 // Low-quality-region rounds of a batch of piles on the device: K7 / K8a over every (row, region) alignment, then K12 (lq_links + lq_score:
 // linked pseudo-seed, second MSA, DP, walk) -- the column streams stay in HBM, what comes back is each pile's walk string.
 // A round the kernel declines (r->ok stays false) is left to the caller's host path.
-constexpr uint32_t kLenClasses = 16384;  // 64-base length classes of the longest-first launch order (run_main); the last one holds >= 1 Mb
+constexpr uint32_t kLenClasses = 16384;  // 64-base length classes of the longest-first launch order (length_order); the last one holds >= 1 Mb
 constexpr uint64_t kLqJobColumns = 192;     // columns of a K12a job (a pile of 3,000 columns is ~15 wavefronts' worth of link building)
 constexpr uint64_t kLqMaxColumns = 400000;  // linked pseudo-seed columns K12 takes per pile (see run_lq)
 constexpr uint32_t kLqWarmColumns = 64;    // columns a K12b job starts before its own first one (speculative start, checked by the stitch)
@@ -1276,10 +1337,7 @@ constexpr uint32_t kLqWarmColumns = 64;    // columns a K12b job starts before i
 void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     if (n == 0) return;
     State &S = *s_;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(S.mu);
-    HIP_CHECK(hipSetDevice(S.device));
+    const State::Phase phase(S);
     hipStream_t st = S.stream;
     const uint64_t tc0 = wall_ns();
 
@@ -1481,17 +1539,13 @@ void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     if (out_bytes) S.d2h(out.data(), S.d_lq_out.p, out_bytes, st);
     S.sync_drain(st);
     HIP_CHECK(hipGetLastError());
-    float ms = 0;
     for (size_t c = 0; c < chunks.size(); c++) {
-        HIP_CHECK(hipEventElapsedTime(&ms, S.lq_evs[2 * c], S.lq_evs[2 * c + 1]));
-        S.stats.forward_ms += ms;
-        HIP_CHECK(hipEventElapsedTime(&ms, S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2]));
-        S.stats.traceback_ms += ms;
+        S.stats.forward_ms += ms_between(S.lq_evs[2 * c], S.lq_evs[2 * c + 1]);
+        S.stats.traceback_ms += ms_between(S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2]);
     }
     S.stats.forward_launches += chunks.size();
     S.stats.traceback_launches += chunks.size();
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[1], S.evs[2]));
-    S.stats.lq_ms += ms;
+    S.stats.lq_ms += ms_between(S.evs[1], S.evs[2]);
     S.stats.lq_launches++;
     S.stats.tasks += nt;
     const uint64_t tc2 = wall_ns();
@@ -1540,29 +1594,21 @@ uint64_t DeviceAligner::next_order() {
 }
 void DeviceAligner::end_batch() { s_->batch_mu.unlock(); }
 
-// Main phase of a batch of piles, entirely on the device:
-//   K7 forward -> K8a traceback -> K8s shift scan -> accept -> K8b tags -> column scan
-//   -> [one host sync: exact cell / link totals] -> K9 link counting -> K10 scoring + walk.
+// ---- the main phase of a batch of piles, entirely on the device.  run_main (below) is the sequence of these steps:
+//   layout (layout_piles) -> align: K7 forward, K8a traceback (align_main) -> tags: K8s shift scan, accept, K8b tags, column scan
+//   (launch_tags) -> [one host sync: exact cell / link totals] -> plan (plan_msa) -> links + scoring: K9, K10 + walk
+//   (count_and_score) -> stats (tally_main) -> unpack (unpack_paths).
+// A step reads what it is given and returns one result; pool, tasks, reads and piles are the context's own vectors (reads and
+// piles stay alive to end_batch: run_extract's kernels read their device copies).
 
-void DeviceAligner::run_main(MainPile **mp, size_t np) {
-    State &S = *s_;
-    uint64_t tp0 = wall_ns();
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(S.mu);
-    HIP_CHECK(hipSetDevice(S.device));
-    hipStream_t st = S.stream;
-    std::vector<uint32_t> &pool = S.pool;
-    std::vector<AlnTask> &tasks = S.tasks;
-    std::vector<ReadDev> &reads = S.reads;
-    std::vector<PileDev> &piles = S.piles;
+// Fills the context's pool, tasks, reads and piles from the callers' piles; returns the rest of the layout.
+MainLayout DeviceAligner::State::layout_piles(MainPile **mp, size_t np) {
+    MainLayout L;
     pool.clear();
     tasks.clear();
     reads.clear();
     piles.assign(np, PileDev());
-    std::vector<uint32_t> read_pile;
-    std::vector<uint8_t> bad_pile(np, 0);
-    uint64_t ops_words = 0, tag_slots = 0, colidx_slots = 0, col_slots = 0, acc_slots = 0;
+    L.bad_pile.assign(np, 0);
     for (size_t p = 0; p < np; p++) {
         MainPile &M = *mp[p];
         PileDev &P = piles[p];
@@ -1575,15 +1621,15 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
         P.min_len_aln = M.min_len_aln;
         P.max_cov_aln = M.max_cov_aln;
         P.factor = M.factor;
-        P.col_off = col_slots;
-        col_slots += (uint64_t)P.seed_len + 1;
-        P.acc_off = acc_slots;
-        acc_slots += M.n;
+        P.col_off = L.col_slots;
+        L.col_slots += (uint64_t)P.seed_len + 1;
+        P.acc_off = L.acc_slots;
+        L.acc_slots += M.n;
         if (M.dev_off) P.seed_off = (uint64_t)M.dev_off[0] | kOffDb;
         else {
             P.seed_off = (uint64_t)pool.size() * 16;
-            if (!pack_append(pool, M.seqs[0], M.seq_len[0])) bad_pile[p] = 1;
-            S.stats.pool_bases += M.seq_len[0];
+            if (!pack_append(pool, M.seqs[0], M.seq_len[0])) L.bad_pile[p] = 1;
+            stats.pool_bases += M.seq_len[0];
         }
         for (unsigned i = 0; i < M.n; i++) {
             ReadDev R;
@@ -1602,385 +1648,394 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
                 if (M.dev_off) t.q_off = (uint64_t)M.dev_off[i] | kOffDb;
                 else {
                     t.q_off = (uint64_t)pool.size() * 16;
-                    if (!pack_append(pool, M.seqs[i], M.seq_len[i])) bad_pile[p] = 1;
-                    S.stats.pool_bases += M.seq_len[i];
+                    if (!pack_append(pool, M.seqs[i], M.seq_len[i])) L.bad_pile[p] = 1;
+                    stats.pool_bases += M.seq_len[i];
                 }
                 t.t_off = P.seed_off + M.aln_start[i];
-                task_limits(t, M.hq, ops_words, S.stats);
+                task_limits(t, M.hq, L.ops_words, stats);
                 R.task = (int32_t)tasks.size();
                 tasks.push_back(t);
                 tag_cap = t.ops_cap;
                 ci_cap = (uint64_t)t.t_len;
             }
-            R.tag_off = tag_slots;
-            tag_slots += tag_cap;
-            R.colidx_off = colidx_slots;
-            colidx_slots += ci_cap + 1;
+            R.tag_off = L.tag_slots;
+            L.tag_slots += tag_cap;
+            R.colidx_off = L.colidx_slots;
+            L.colidx_slots += ci_cap + 1;
             reads.push_back(R);
-            read_pile.push_back((uint32_t)p);
+            L.read_pile.push_back((uint32_t)p);
         }
-        if (bad_pile[p]) {  // bytes outside [ACGT]: nothing of this pile is aligned
+        if (L.bad_pile[p]) {  // bytes outside [ACGT]: nothing of this pile is aligned
             fprintf(stderr, "[ndgpu] pile with bytes outside [ACGT]: reported as uncorrectable\n");
             for (uint32_t r = P.first_read + 1; r < reads.size(); r++) tasks[reads[r].task].max_d = 0;
             P.min_len_aln = 0xffffffffu;
         }
     }
     pool.insert(pool.end(), kPoolPadWords, 0u);
+    if (L.tag_slots + 9 >= kTagSlotLimit) throw DeviceOom{(size_t)L.tag_slots * sizeof(uint32_t)};  // (halved like a sub-batch that does not fit)
+    return L;
+}
+
+// The device (and pinned) buffers the layout sizes.
+void DeviceAligner::State::reserve_layout(const MainLayout &L, size_t np) {
     const size_t nt = tasks.size(), nr = reads.size();
+    d_pool.reserve(pool.size());
+    d_tasks.reserve(nt + 1);
+    d_outs.reserve(nt + 1);
+    h_outs.reserve(nt + 1);
+    d_ops.reserve(L.ops_words + 2);
+    d_reads.reserve(nr);
+    d_piles.reserve(np);
+    d_read_pile.reserve(nr);
+    d_acc.reserve(L.acc_slots + 1);
+    d_tags.reserve(L.tag_slots + 9);  // (K9 reads 32-byte windows: up to 7 tags past a read's last one)
+    d_colidx.reserve(L.colidx_slots + 1);
+    d_cov.reserve(3 * (L.col_slots + 1));  // per column: coverage, insertion count, longest insertion -- three arrays in one block
+    d_cellbase.reserve(L.col_slots + 1);
+    d_entbase.reserve(L.col_slots + 1);
+    d_err.reserve(kErrWords);
+}
 
-    // forward/traceback chunks bounded by the trace budget
-    const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), nt);
+// Tasks [a, a + m) longest alignments first (their chains bound the launch), as a device list of ids relative to a -- or nullptr
+// (table order) for a short chunk or under NDGPU_K7_NO_ORDER.  A counting sort over 64-base length classes: a sub-batch holds up
+// to a million tasks and this runs on the context's critical path.
+const int32_t *DeviceAligner::State::length_order(size_t a, size_t m) {
+    if (!main_hooks().k7_order || m <= 64) return nullptr;
+    order.resize(m);
+    order_cls.assign(kLenClasses + 1, 0);
+    auto cls_of = [&](size_t i) {
+        const uint32_t c = ((uint32_t)tasks[a + i].q_len + (uint32_t)tasks[a + i].t_len) >> 6;
+        return (kLenClasses - 1) - std::min<uint32_t>(c, kLenClasses - 1);  // class 0 = the longest
+    };
+    for (size_t i = 0; i < m; i++) order_cls[cls_of(i) + 1]++;
+    for (uint32_t c = 0; c < kLenClasses; c++) order_cls[c + 1] += order_cls[c];
+    for (size_t i = 0; i < m; i++) order[order_cls[cls_of(i)]++] = (int32_t)i;
+    d_ids.reserve(m);
+    h2d(d_ids.p, order.data(), m * sizeof(int32_t), stream);
+    return d_ids.p;
+}
 
-    S.d_pool.reserve(pool.size());
-    S.d_tasks.reserve(nt + 1);
-    S.d_outs.reserve(nt + 1);
-    S.h_outs.reserve(nt + 1);
-    S.d_ops.reserve(ops_words + 2);
-    S.d_reads.reserve(nr);
-    S.d_piles.reserve(np);
-    S.d_read_pile.reserve(nr);
-    S.d_acc.reserve(acc_slots + 1);
-    S.d_tags.reserve(tag_slots + 9);  // (K9 reads 32-byte windows: up to 7 tags past a read's last one)
-    S.d_colidx.reserve(colidx_slots + 1);
-    S.d_cov.reserve(3 * (col_slots + 1));  // per column: coverage, insertion count, longest insertion -- three arrays in one block
-    S.d_cellbase.reserve(col_slots + 1);
-    S.d_entbase.reserve(col_slots + 1);
-    S.d_err.reserve(kErrWords);
-
-    uint64_t tp1 = wall_ns();
-    g_prof.m_prep += tp1 - tp0;
-    S.h2d(S.d_pool.p, pool.data(), pool.size() * sizeof(uint32_t), st);
-    if (nt) S.h2d(S.d_tasks.p, tasks.data(), nt * sizeof(AlnTask), st);
-    S.h2d(S.d_reads.p, reads.data(), nr * sizeof(ReadDev), st);
-    S.h2d(S.d_piles.p, piles.data(), np * sizeof(PileDev), st);
-    S.h2d(S.d_read_pile.p, read_pile.data(), nr * sizeof(uint32_t), st);
-    uint32_t *const d_cov = S.d_cov.p, *const d_inscnt = d_cov + (col_slots + 1), *const d_insmax = d_inscnt + (col_slots + 1);
-    HIP_CHECK(hipMemsetAsync(d_cov, 0, 3 * (col_slots + 1) * sizeof(uint32_t), st));  // (one fill for the three)
-    HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, kErrWords * sizeof(uint32_t), st));
-
+// K7 / K8a chunk by chunk, the AlnOut records to the host, the wide-band tasks run again.
+void DeviceAligner::State::align_main(const std::vector<AlignChunk> &chunks, size_t np) {
+    hipStream_t st = stream;
+    const size_t nt = tasks.size();
     for (const AlignChunk &ch : chunks) {
-        const size_t a = ch.begin, m = ch.end - ch.begin;
-        NDGPU_DBG(st, "main: forward %zu..%zu of %zu tasks, %zu piles", a, ch.end, nt, np);
-        const int32_t *order = nullptr;
-        static const bool lpt = !getenv("NDGPU_K7_NO_ORDER");
-        if (lpt && m > 64) {
-            // longest alignments first (their chains bound the launch): a counting sort over 64-base length classes
-            // -- a sub-batch holds up to a million tasks and this runs on the context's critical path
-            std::vector<int32_t> &ord = S.order;
-            std::vector<uint32_t> &cls = S.order_cls;
-            ord.resize(m);
-            cls.assign(kLenClasses + 1, 0);
-            auto cls_of = [&](size_t i) {
-                const uint32_t c = ((uint32_t)tasks[a + i].q_len + (uint32_t)tasks[a + i].t_len) >> 6;
-                return (kLenClasses - 1) - std::min<uint32_t>(c, kLenClasses - 1);  // class 0 = the longest
-            };
-            for (size_t i = 0; i < m; i++) cls[cls_of(i) + 1]++;
-            for (uint32_t c = 0; c < kLenClasses; c++) cls[c + 1] += cls[c];
-            for (size_t i = 0; i < m; i++) ord[cls[cls_of(i)]++] = (int32_t)i;
-            S.d_ids.reserve(m);
-            S.h2d(S.d_ids.p, ord.data(), m * sizeof(int32_t), st);
-            order = S.d_ids.p;
-        }
+        NDGPU_DBG(st, "main: forward %zu..%zu of %zu tasks, %zu piles", ch.begin, ch.end, nt, np);
+        const int32_t *ids = length_order(ch.begin, ch.end - ch.begin);
         // (K8a stays in table order: measured in round 5, the 64 walks of a wavefront ordered longest first like K7's --
         // equal lengths, long walks first -- cost 605 ms of traceback per step against 496: the lanes of a wavefront in pile
         // order walk neighbouring windows of one seed and share its cache lines; NDGPU_K8_ORDER=1 switches the order on)
-        static const bool k8_order = getenv("NDGPU_K8_ORDER") != nullptr;
-        HIP_CHECK(hipEventRecord(S.evs[0], st));
-        S.launch_chunk(ch, order, k8_order ? order : nullptr, S.evs[1], S.evs[2], "main");
+        HIP_CHECK(hipEventRecord(evs[0], st));
+        launch_chunk(ch, ids, main_hooks().k8_order ? ids : nullptr, evs[1], evs[2], "main");
         NDGPU_DBG(st, "main: traceback done");
-        HIP_CHECK(hipEventSynchronize(S.evs[2]));  // (chunk by chunk: the next one records the same three events)
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[0], S.evs[1]));
-        S.stats.forward_ms += ms;
-        S.stats.forward_launches++;
-        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[1], S.evs[2]));
-        S.stats.traceback_ms += ms;
-        S.stats.traceback_launches++;
+        HIP_CHECK(hipEventSynchronize(evs[2]));  // (chunk by chunk: the next one records the same three events)
+        stats.forward_ms += ms_between(evs[0], evs[1]);
+        stats.forward_launches++;
+        stats.traceback_ms += ms_between(evs[1], evs[2]);
+        stats.traceback_launches++;
     }
-    if (nt) {
-        HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, nt * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
-        S.sync_drain(st);
-        std::vector<int32_t> wide;
-        S.tally_outs(nt, &wide);  // (before run_wide: a wide task counts with what the register path reported)
-        if (!wide.empty()) run_wide(nullptr, wide);
-        S.stats.tasks += nt;
-    }
+    if (!nt) return;
+    HIP_CHECK(hipMemcpyAsync(h_outs.p, d_outs.p, nt * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
+    sync_drain(st);
+    std::vector<int32_t> wide;
+    tally_outs(nt, &wide);  // (before run_wide: a wide task counts with what the register path reported)
+    if (!wide.empty()) run_wide(false, wide);
+    stats.tasks += nt;
+}
 
-    uint64_t tp2 = wall_ns();
-    g_prof.m_aln += tp2 - tp1;
-    HIP_CHECK(hipEventRecord(S.evs[0], st));
+// The four launches between events 0 and 1: shift scan, accept, tags, column scan.
+void DeviceAligner::State::launch_tags(const CovPlanes &cov, size_t np) {
+    hipStream_t st = stream;
+    const int nr = (int)reads.size();
+    HIP_CHECK(hipEventRecord(evs[0], st));
     NDGPU_DBG(st, "main: shift_scan");
-    launch_shift_scan(S.d_tasks.p, S.d_outs.p, S.d_ops.p, S.d_reads.p, (int)nr, st);
+    launch_shift_scan(d_tasks.p, d_outs.p, d_ops.p, d_reads.p, nr, st);
     NDGPU_DBG(st, "main: pile_accept");
-    launch_pile_accept(S.d_piles.p, S.d_reads.p, S.d_acc.p, d_cov, (int)np, st);
+    launch_pile_accept(d_piles.p, d_reads.p, d_acc.p, cov.cov, (int)np, st);
     NDGPU_DBG(st, "main: make_tags");
-    launch_make_tags(S.d_piles.p, S.d_reads.p, S.d_tasks.p, S.d_ops.p, S.d_pool.p, S.db_pool, S.d_read_pile.p,
-                     S.d_tags.p, S.d_colidx.p, d_inscnt, d_insmax, (int)nr, st);
+    launch_make_tags(d_piles.p, d_reads.p, d_tasks.p, d_ops.p, d_pool.p, db_pool, d_read_pile.p, d_tags.p, d_colidx.p, cov.inscnt,
+                     cov.insmax, nr, st);
     NDGPU_DBG(st, "main: col_scan");
-    launch_col_scan(S.d_piles.p, d_cov, d_inscnt, d_insmax, S.d_cellbase.p, S.d_entbase.p, (int)np, st);
+    launch_col_scan(d_piles.p, cov.cov, cov.inscnt, cov.insmax, d_cellbase.p, d_entbase.p, (int)np, st);
     NDGPU_DBG(st, "main: col_scan done");
-    HIP_CHECK(hipEventRecord(S.evs[1], st));
-    S.d2h(piles.data(), S.d_piles.p, np * sizeof(PileDev), st);
-    S.sync_drain(st);
+    HIP_CHECK(hipEventRecord(evs[1], st));
+}
 
-    uint64_t tp3 = wall_ns();
-    g_prof.m_tags += tp3 - tp2;
-    uint64_t cells = 0, ents = 0, paths = 0;
-    std::vector<ColBlock> blocks;
-    // scoring segments (K10): `seg_len` columns each, the last one takes the remainder; the two table tiers get a work
-    // list each.  Test hooks: NDGPU_K10_FORCE = large (every pile through the large tables) | slow (every pile through the
-    // int64 HBM-resident kernel) | seq (one segment per pile: no speculation) | repair (every second segment is scored
-    // again by the stitch kernel as if its check had failed); NDGPU_K10_SEG / NDGPU_K10_WARM / NDGPU_K10_GUARD set the
-    // segment length, the warm-up length and the raw-score guard.
-    struct K10Cfg {
-        uint32_t seg_len = 1024, warm = 128, force_repair = 0;
-        int32_t guard = 1 << 30;
-        bool large = false, slow = false;
-        K10Cfg() {
-            if (const char *e = getenv("NDGPU_K10_SEG")) seg_len = (uint32_t)std::max(16, atoi(e));
-            if (const char *e = getenv("NDGPU_K10_WARM")) warm = (uint32_t)std::max(1, atoi(e));
-            if (const char *e = getenv("NDGPU_K10_GUARD")) guard = atoi(e);
-            if (const char *e = getenv("NDGPU_K10_FORCE")) {
-                large = !strcmp(e, "large"), slow = !strcmp(e, "slow");
-                if (!strcmp(e, "seq")) seg_len = 0x7fffffffu;
-                if (!strcmp(e, "repair")) force_repair = 2;
-            }
-            if (warm >= seg_len) warm = seg_len - 1;
-        }
-    };
-    static const K10Cfg k10;
-    std::vector<SegItem> items_small, items_large, items_slow;  // (slow: piles of the int64 kernel; only the walk uses them)
-    uint32_t n_segs = 0;
-    for (size_t p = 0; p < np; p++) {
+// From the piles as the column scan left them (n_cells, n_tags, err): every pile's K10 segments -- `seg_len` columns each, the
+// last one takes the remainder -- on the work list of its tier, its offsets into the cell / link / path tables, K9's column
+// blocks.  Pure host arithmetic; writes the piles' n_seg, seg_off, n_repair, tier and the three offsets.
+static MsaPlan plan_msa(std::vector<PileDev> &piles) {
+    const MainHooks &k = main_hooks();
+    MsaPlan M;
+    for (size_t p = 0; p < piles.size(); p++) {
         PileDev &P = piles[p];
-        if (k10.large) P.err = 3;
-        if (k10.slow) P.err = 2;
-        P.n_seg = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)P.seed_len + k10.seg_len / 2) / k10.seg_len));
-        P.seg_off = n_segs;
-        n_segs += P.n_seg;
+        if (k.k10_large) P.err = 3;
+        if (k.k10_slow) P.err = 2;
+        P.n_seg = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)P.seed_len + k.k10_seg_len / 2) / k.k10_seg_len));
+        P.seg_off = M.n_segs;
+        M.n_segs += P.n_seg;
         P.n_repair = 0;
         P.tier = P.err == 3 ? 1u : 0u;
-        std::vector<SegItem> &dst = P.err == 2 ? items_slow : P.err == 3 ? items_large : items_small;
+        std::vector<SegItem> &dst = P.err == 2 ? M.items_slow : P.err == 3 ? M.items_large : M.items_small;
         for (uint32_t g = 0; g < P.n_seg; g++) dst.push_back(SegItem{(uint32_t)p, g});
     }
-    for (size_t p = 0; p < np; p++) {
+    for (size_t p = 0; p < piles.size(); p++) {
         PileDev &P = piles[p];
-        P.cell_off = cells;
-        P.ent_off = ents;
-        P.path_off = paths;
-        cells += P.n_cells;
-        ents += P.n_tags;
-        paths += P.n_cells / 6 + 1;
-        for (uint32_t c = 0; c < P.seed_len; c += kColBlock) blocks.push_back(ColBlock{(uint32_t)p, c});
-        S.stats.tags += P.n_tags;
-        S.stats.cells_msa += P.n_cells;
+        P.cell_off = M.cells;
+        P.ent_off = M.ents;
+        P.path_off = M.paths;
+        M.cells += P.n_cells;
+        M.ents += P.n_tags;
+        M.paths += P.n_cells / 6 + 1;
+        for (uint32_t c = 0; c < P.seed_len; c += kColBlock) M.blocks.push_back(ColBlock{(uint32_t)p, c});
     }
-    S.stats.piles += np;
-    S.d_cell_start.reserve(cells + 1);
-    S.d_cell_len.reserve(cells + 1);
-    S.d_cell_bpp.reserve(cells + 1);
-    S.d_cell_blink.reserve(cells + 1);
-    S.d_ent_pp.reserve(ents + 1);
-    S.d_ent_ppp.reserve(ents + 1);
-    S.d_ent_cnt.reserve(ents + 1);
+    return M;
+}
+
+// The tables K9 / K10 fill, sized by the plan; its column blocks and the three item lists (small | large | slow) go up.
+void DeviceAligner::State::upload_plan(const MsaPlan &plan) {
+    hipStream_t st = stream;
+    d_cell_start.reserve(plan.cells + 1);
+    d_cell_len.reserve(plan.cells + 1);
+    d_cell_bpp.reserve(plan.cells + 1);
+    d_cell_blink.reserve(plan.cells + 1);
+    d_ent_pp.reserve(plan.ents + 1);
+    d_ent_ppp.reserve(plan.ents + 1);
+    d_ent_cnt.reserve(plan.ents + 1);
     // (d_ent_score, 8 bytes per link, belongs to the int64 kernel: allocated only when a pile needs it -- see the rescue pass)
-    S.d_path.reserve(paths + 1);
-    S.d_blocks.reserve(blocks.size() + 1);
-    S.d_cell_best.reserve(cells + 1);
-    S.d_sums.reserve(n_segs + 1);
-    S.d_spec.reserve((size_t)n_segs * kSegEnts + 1);
-    S.d_fin.reserve((size_t)n_segs * kSegEnts + 1);
-    const size_t n_items_all = items_small.size() + items_large.size() + items_slow.size();
-    S.d_items.reserve(n_items_all + 1);
-    S.d_bt_exit.reserve((size_t)n_segs * kBtSlots + 1);
-    S.d_bt_steps.reserve((size_t)n_segs * kBtSlots + 1);
-    S.d_bt_entry.reserve(n_segs + 1);
-    S.d_bt_off.reserve(n_segs + 1);
-    S.h2d(S.d_blocks.p, blocks.data(), blocks.size() * sizeof(ColBlock), st);
-    S.h2d(S.d_items.p, items_small.data(), items_small.size() * sizeof(SegItem), st);
-    S.h2d(S.d_items.p + items_small.size(), items_large.data(), items_large.size() * sizeof(SegItem), st);
-    S.h2d(S.d_items.p + items_small.size() + items_large.size(), items_slow.data(), items_slow.size() * sizeof(SegItem), st);
-    const PathItem *hpath = nullptr;  // view into the download arena
-    std::vector<PileDev> piles_out(np);
-    uint32_t herr[kErrWords] = {};
-    // attempt 0 counts links with the small LDS lists; a cell with more distinct links than they hold raises err[0] and the
-    // sub-batch is counted and scored again with the full capacity (everything the kernels write is rewritten), and if that
-    // overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap)
-    K10Args ka;
-    ka.piles = S.d_piles.p;
-    ka.coverage = d_cov, ka.max_size = d_insmax, ka.cell_base = S.d_cellbase.p, ka.ent_base = S.d_entbase.p;
-    ka.cell_start = S.d_cell_start.p, ka.cell_len = S.d_cell_len.p;
-    ka.ent_pp = S.d_ent_pp.p, ka.ent_ppp = S.d_ent_ppp.p, ka.ent_cnt = S.d_ent_cnt.p;
-    ka.cell_best_pp = S.d_cell_bpp.p, ka.cell_best_link = S.d_cell_blink.p, ka.cell_best = S.d_cell_best.p;
-    ka.sums = S.d_sums.p, ka.spec = S.d_spec.p, ka.fin = S.d_fin.p;
-    ka.seg_len = k10.seg_len, ka.warm = k10.warm, ka.guard = k10.guard, ka.force_repair = k10.force_repair;
-    for (int attempt = S.k9_full_capacity ? 1 : 0, first = 1; attempt < 3; attempt++, first = 0) {
-        S.reserve_down(np * sizeof(PileDev) + paths * sizeof(PathItem) + 1024, st);
-        S.h2d(S.d_piles.p, piles.data(), np * sizeof(PileDev), st);
-        if (!first) HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, kErrWords * sizeof(uint32_t), st));
-        HIP_CHECK(hipEventRecord(S.evs[2], st));
-        NDGPU_DBG(st, "main: count_links %zu blocks, cells %llu ents %llu segs %u", blocks.size(), (unsigned long long)cells,
-                  (unsigned long long)ents, n_segs);
+    d_path.reserve(plan.paths + 1);
+    d_blocks.reserve(plan.blocks.size() + 1);
+    d_cell_best.reserve(plan.cells + 1);
+    d_sums.reserve(plan.n_segs + 1);
+    d_spec.reserve((size_t)plan.n_segs * kSegEnts + 1);
+    d_fin.reserve((size_t)plan.n_segs * kSegEnts + 1);
+    d_items.reserve(plan.n_items() + 1);
+    d_bt_exit.reserve((size_t)plan.n_segs * kBtSlots + 1);
+    d_bt_steps.reserve((size_t)plan.n_segs * kBtSlots + 1);
+    d_bt_entry.reserve(plan.n_segs + 1);
+    d_bt_off.reserve(plan.n_segs + 1);
+    h2d(d_blocks.p, plan.blocks.data(), plan.blocks.size() * sizeof(ColBlock), st);
+    h2d(d_items.p, plan.items_small.data(), plan.items_small.size() * sizeof(SegItem), st);
+    h2d(d_items.p + plan.items_small.size(), plan.items_large.data(), plan.items_large.size() * sizeof(SegItem), st);
+    h2d(d_items.p + plan.items_small.size() + plan.items_large.size(), plan.items_slow.data(), plan.items_slow.size() * sizeof(SegItem), st);
+}
+
+// K10 + the best_pp walk behind one attempt of K9 (events 3 .. 7 .. 4).  A sub-batch small enough for the reserved compute units
+// (4 two-wave blocks each) scores there: fork from the context's stream before, join behind.
+void DeviceAligner::State::score_pass(const MsaPlan &plan, const K10Args &k10) {
+    hipStream_t st = stream;
+    const size_t np = piles.size();
+    const bool on_reserved = lat_stream && np <= (size_t)reserved_cus * 2;
+    hipStream_t sst = on_reserved ? lat_stream : st;
+    if (on_reserved) {
+        HIP_CHECK(hipEventRecord(ev_lat0, st));
+        HIP_CHECK(hipStreamWaitEvent(sst, ev_lat0, 0));
+        HIP_CHECK(hipEventRecord(evs[3], sst));
+    }
+    launch_score_backtrack(k10, d_items.p, (int)plan.items_small.size(), d_items.p + plan.items_small.size(), (int)plan.items_large.size(),
+                           d_items.p, (int)plan.n_items(), d_ent_score.cap >= plan.ents + 1 ? d_ent_score.p : nullptr, false, d_path.p,
+                           d_bt_exit.p, d_bt_steps.p, d_bt_entry.p, d_bt_off.p, (int)np, sst, evs[7], on_reserved ? nullptr : stream2,
+                           ev_fork, ev_join);
+    HIP_CHECK(hipEventRecord(evs[4], sst));
+    NDGPU_DBG(st, "main: score + walk done");
+    if (on_reserved) {
+        HIP_CHECK(hipEventRecord(ev_lat1, sst));
+        HIP_CHECK(hipStreamWaitEvent(st, ev_lat1, 0));
+    }
+}
+
+// The piles the segment kernels handed to the int64 HBM-resident kernel (err == 2: a column wider than the LDS tables, raw scores
+// out of the int32 working range) when its 8-byte-per-link score array was not there yet: that kernel and the walk, once more.
+void DeviceAligner::State::rescue_pass(const MsaPlan &plan, const K10Args &k10) {
+    d_ent_score.reserve(plan.ents + 1);
+    launch_score_backtrack(k10, nullptr, 0, nullptr, 0, d_items.p, (int)plan.n_items(), d_ent_score.p, true, d_path.p, d_bt_exit.p,
+                           d_bt_steps.p, d_bt_entry.p, d_bt_off.p, (int)piles.size(), stream, nullptr, nullptr, nullptr, nullptr);
+}
+
+// NDGPU_K9_DIGEST: a digest of the tables an attempt of K9 left, for comparing two builds or two paths of K9.  The stream is idle
+// here; the kernel, its four words and their copy exist only under the switch.
+void DeviceAligner::State::k9_digest_trace(const K9Args &k9, size_t np) {
+    hipStream_t st = stream;
+    unsigned long long *d_dig = nullptr, dig[4] = {};
+    HIP_CHECK(hipMalloc((void **)&d_dig, sizeof(dig)));
+    HIP_CHECK(hipMemsetAsync(d_dig, 0, sizeof(dig), st));
+    launch_k9_digest(k9, d_dig, (int)np, st);
+    HIP_CHECK(hipMemcpyAsync(dig, d_dig, sizeof(dig), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipFree(d_dig));
+    fprintf(stderr, "[ndgpu trace] K9 tables: digest=%016llx cells=%llu links=%llu max_cell_len=%llu\n", dig[0], dig[1], dig[2], dig[3]);
+}
+
+// Links and scores, up to three times: attempt 0 counts links with the small LDS lists; a cell with more distinct links than they
+// hold raises err[0] and the sub-batch is counted and scored again with the full capacity (everything the kernels write is
+// rewritten), and if that overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap).
+// Returns the last attempt's error words, its piles and a view of its paths in the download arena.
+MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPlanes &cov) {
+    const MainHooks &hooks = main_hooks();
+    hipStream_t st = stream;
+    const K9Args k9{d_piles.p,   d_reads.p,      d_acc.p,      d_blocks.p, d_tags.p,    d_colidx.p,  cov.insmax, d_cellbase.p,
+                    d_entbase.p, d_cell_start.p, d_cell_len.p, d_ent_pp.p, d_ent_ppp.p, d_ent_cnt.p, d_err.p};
+    K10Args k10 = k10_args_from(k9);
+    k10.coverage = cov.cov;
+    k10.cell_best_pp = d_cell_bpp.p, k10.cell_best_link = d_cell_blink.p, k10.cell_best = d_cell_best.p;
+    k10.sums = d_sums.p, k10.spec = d_spec.p, k10.fin = d_fin.p;
+    k10.seg_len = hooks.k10_seg_len, k10.warm = hooks.k10_warm, k10.guard = hooks.k10_guard, k10.force_repair = hooks.k10_force_repair;
+    const size_t np = piles.size();
+    const size_t down_bytes = np * sizeof(PileDev) + plan.paths * sizeof(PathItem) + 1024;
+    MsaResult R;
+    R.piles.resize(np);
+    for (int attempt = hooks.k9_full ? 1 : 0, first = 1; attempt < 3; attempt++, first = 0) {
+        reserve_down(down_bytes, st);
+        h2d(d_piles.p, piles.data(), np * sizeof(PileDev), st);
+        if (!first) HIP_CHECK(hipMemsetAsync(d_err.p, 0, kErrWords * sizeof(uint32_t), st));
+        HIP_CHECK(hipEventRecord(evs[2], st));
+        NDGPU_DBG(st, "main: count_links %zu blocks, cells %llu ents %llu segs %u", plan.blocks.size(), (unsigned long long)plan.cells,
+                  (unsigned long long)plan.ents, plan.n_segs);
         if (attempt < 2) {
-            launch_count_links(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_blocks.p, S.d_tags.p, S.d_colidx.p, d_insmax,
-                               S.d_cellbase.p, S.d_entbase.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p, S.d_ent_ppp.p,
-                               S.d_ent_cnt.p, S.d_err.p, (int)blocks.size(), attempt != 0, st);
+            launch_count_links(k9, (int)plan.blocks.size(), attempt != 0, st);
         } else {  // (the stream is idle here: the attempt before was waited for)
             uint32_t cap = 1;
             for (size_t p = 0; p < np; p++) cap = std::max(cap, piles[p].n_acc);
-            const int grid = (int)std::min<size_t>(blocks.size(), (size_t)kLinkGlobalGrid);
-            S.d_link_lists.reserve((size_t)grid * 18u * cap + 1);
-            launch_count_links_global(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_blocks.p, S.d_tags.p, S.d_colidx.p, d_insmax,
-                                      S.d_cellbase.p, S.d_entbase.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p,
-                                      S.d_ent_ppp.p, S.d_ent_cnt.p, S.d_err.p, S.d_link_lists.p, cap, (int)blocks.size(), grid, st);
+            const int grid = (int)std::min<size_t>(plan.blocks.size(), (size_t)kLinkGlobalGrid);
+            d_link_lists.reserve((size_t)grid * 18u * cap + 1);
+            launch_count_links_global(k9, d_link_lists.p, cap, (int)plan.blocks.size(), grid, st);
         }
-        HIP_CHECK(hipEventRecord(S.evs[3], st));
+        HIP_CHECK(hipEventRecord(evs[3], st));
         NDGPU_DBG(st, "main: score + walk");
-        // a sub-batch small enough for the reserved compute units (4 two-wave blocks each) scores there
-        const bool on_reserved = S.lat_stream && np <= (size_t)S.reserved_cus * 2;
-        hipStream_t sst = on_reserved ? S.lat_stream : st;
-        if (on_reserved) {
-            HIP_CHECK(hipEventRecord(S.ev_lat0, st));
-            HIP_CHECK(hipStreamWaitEvent(sst, S.ev_lat0, 0));
-            HIP_CHECK(hipEventRecord(S.evs[3], sst));
-        }
-        launch_score_backtrack(ka, S.d_items.p, (int)items_small.size(), S.d_items.p + items_small.size(), (int)items_large.size(),
-                               S.d_items.p, (int)n_items_all, S.d_ent_score.cap >= ents + 1 ? S.d_ent_score.p : nullptr, false,
-                               S.d_path.p, S.d_bt_exit.p, S.d_bt_steps.p,
-                               S.d_bt_entry.p, S.d_bt_off.p, (int)np, sst, S.evs[7], on_reserved ? nullptr : S.stream2, S.ev_fork,
-                               S.ev_join);
-        HIP_CHECK(hipEventRecord(S.evs[4], sst));
-        NDGPU_DBG(st, "main: score + walk done");
-        if (on_reserved) {
-            HIP_CHECK(hipEventRecord(S.ev_lat1, sst));
-            HIP_CHECK(hipStreamWaitEvent(st, S.ev_lat1, 0));
-        }
-        const void *v_piles = S.d2h(nullptr, S.d_piles.p, np * sizeof(PileDev), st);  // (re-taken by the rescue pass)
-        hpath = (const PathItem *)S.d2h(nullptr, S.d_path.p, paths * sizeof(PathItem), st);
-        const void *v_err = S.d2h(nullptr, S.d_err.p, sizeof(herr), st);
+        score_pass(plan, k10);
+        const void *v_piles = d2h(nullptr, d_piles.p, np * sizeof(PileDev), st);  // (re-taken by the rescue pass)
+        R.hpath = (const PathItem *)d2h(nullptr, d_path.p, plan.paths * sizeof(PathItem), st);
+        const void *v_err = d2h(nullptr, d_err.p, sizeof(R.herr), st);
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
-        memcpy(piles_out.data(), v_piles, np * sizeof(PileDev));
-        memcpy(herr, v_err, sizeof(herr));
-        // rescue pass: piles the segment kernels handed to the int64 HBM-resident kernel (err == 2: a column wider than the
-        // LDS tables, raw scores out of the int32 working range) when its 8-byte-per-link score array was not there yet
+        memcpy(R.piles.data(), v_piles, np * sizeof(PileDev));
+        memcpy(R.herr, v_err, sizeof(R.herr));
         bool rescue = false;
-        for (size_t p = 0; p < np; p++) rescue = rescue || piles_out[p].err == 2;
+        for (size_t p = 0; p < np; p++) rescue = rescue || R.piles[p].err == 2;
         if (rescue) {
-            S.d_ent_score.reserve(ents + 1);
-            launch_score_backtrack(ka, nullptr, 0, nullptr, 0, S.d_items.p, (int)n_items_all, S.d_ent_score.p, true, S.d_path.p,
-                                   S.d_bt_exit.p, S.d_bt_steps.p, S.d_bt_entry.p, S.d_bt_off.p, (int)np, st, nullptr, nullptr, nullptr,
-                                   nullptr);
-            S.reserve_down(np * sizeof(PileDev) + paths * sizeof(PathItem) + 1024, st);
-            v_piles = S.d2h(nullptr, S.d_piles.p, np * sizeof(PileDev), st);
-            hpath = (const PathItem *)S.d2h(nullptr, S.d_path.p, paths * sizeof(PathItem), st);
+            rescue_pass(plan, k10);
+            reserve_down(down_bytes, st);
+            v_piles = d2h(nullptr, d_piles.p, np * sizeof(PileDev), st);
+            R.hpath = (const PathItem *)d2h(nullptr, d_path.p, plan.paths * sizeof(PathItem), st);
             HIP_CHECK(hipStreamSynchronize(st));
             HIP_CHECK(hipGetLastError());
-            memcpy(piles_out.data(), v_piles, np * sizeof(PileDev));
+            memcpy(R.piles.data(), v_piles, np * sizeof(PileDev));
         }
         if (attempt < 2 && getenv("NDGPU_TRACE"))
-            fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", herr[1], herr[3], herr[2],
-                    herr[4] ? ~herr[4] : 0u);
-        // NDGPU_K9_DIGEST (read once): a digest of the tables this attempt left, for comparing two builds or two paths of K9.  The
-        // stream is idle here; the kernel, its four words and their copy exist only under the switch.
-        static const bool k9_digest = getenv("NDGPU_K9_DIGEST") != nullptr && atoi(getenv("NDGPU_K9_DIGEST")) != 0;
-        if (k9_digest) {
-            unsigned long long *d_dig = nullptr, dig[4] = {};
-            HIP_CHECK(hipMalloc((void **)&d_dig, sizeof(dig)));
-            HIP_CHECK(hipMemsetAsync(d_dig, 0, sizeof(dig), st));
-            launch_k9_digest(S.d_piles.p, S.d_cell_start.p, S.d_cell_len.p, S.d_ent_pp.p, S.d_ent_ppp.p, S.d_ent_cnt.p, d_dig, (int)np, st);
-            HIP_CHECK(hipMemcpyAsync(dig, d_dig, sizeof(dig), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            HIP_CHECK(hipFree(d_dig));
-            fprintf(stderr, "[ndgpu trace] K9 tables: digest=%016llx cells=%llu links=%llu max_cell_len=%llu\n", dig[0], dig[1], dig[2], dig[3]);
-        }
-        static const bool force_retry = getenv("NDGPU_K9_FORCE_RETRY") != nullptr;  // test hook: take the overflow path
-        if (attempt == 0 ? !herr[0] && !force_retry : !herr[0]) break;
+            fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", R.herr[1], R.herr[3], R.herr[2],
+                    R.herr[4] ? ~R.herr[4] : 0u);
+        if (hooks.k9_digest) k9_digest_trace(k9, np);
+        if (attempt == 0 ? !R.herr[0] && !hooks.k9_force_retry : !R.herr[0]) break;
         if (attempt == 2) break;  // (cannot happen: the lists hold one entry per accepted read)
-        S.k9_retries++;
+        k9_retries++;
         if (getenv("NDGPU_TRACE")) {
             if (attempt == 0) fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with %d\n", kLinkCapSmall, kLinkCap);
             else fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with the lists in device memory\n", kLinkCap);
         }
     }
-    piles.swap(piles_out);
-    uint64_t tp4 = wall_ns();
-    g_prof.m_msa += tp4 - tp3;
-    if (herr[0]) {
-        fprintf(stderr, "[ndgpu] FATAL: a cell of the MSA holds more links than its pile has reads\n");
-        abort();
-    }
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[0], S.evs[1]));
-    S.stats.tags_ms += ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[2], S.evs[3]));
-    S.stats.links_ms += ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[3], S.evs[7]));
-    S.stats.score_ms += ms;
-    S.stats.score_launches++;
-    HIP_CHECK(hipEventElapsedTime(&ms, S.evs[7], S.evs[4]));
-    S.stats.backtrack_ms += ms;
-    {
-        static const bool trace = getenv("NDGPU_TRACE") != nullptr;
-        if (trace) {
-            float t_links = 0, t_score = 0, t_back = 0;
-            (void)hipEventElapsedTime(&t_links, S.evs[2], S.evs[3]);
-            (void)hipEventElapsedTime(&t_score, S.evs[3], S.evs[7]);
-            (void)hipEventElapsedTime(&t_back, S.evs[7], S.evs[4]);
-            uint32_t longest = 0;
-            for (size_t p = 0; p < np; p++) longest = std::max(longest, piles[p].seed_len);
-            uint32_t rep = 0, slow = 0;
-            for (size_t p = 0; p < np; p++) {
-                if (piles[p].n_repair == 0xffffffffu) slow++;
-                else rep += piles[p].n_repair;
-            }
-            fprintf(stderr, "[ndgpu trace] run_main %zu piles longest %u | host prep %.1f align %.1f tags %.1f msa %.1f ms | K9 %.1f K10 %.1f backtrack %.1f ms | %u segments, %u repaired, %u piles through the int64 kernel\n",
-                    np, longest, (tp1 - tp0) * 1e-6, (tp2 - tp1) * 1e-6, (tp3 - tp2) * 1e-6, (tp4 - tp3) * 1e-6, t_links, t_score, t_back, n_segs, rep, slow);
+    return R;
+}
+
+// The main phase's counters and the NDGPU_TRACE line, both from one reading of each event pair.  piles: as the last attempt left
+// them; tp: wall clock at the start of run_main and behind its prep, align, tags and msa parts.
+void DeviceAligner::State::tally_main(const MsaPlan &plan, const std::vector<uint8_t> &bad_pile, MainPile **mp, const uint64_t tp[5]) {
+    const size_t np = piles.size();
+    const double t_tags = ms_between(evs[0], evs[1]), t_links = ms_between(evs[2], evs[3]), t_score = ms_between(evs[3], evs[7]),
+                 t_back = ms_between(evs[7], evs[4]);
+    stats.tags_ms += t_tags;
+    stats.links_ms += t_links;
+    stats.score_ms += t_score;
+    stats.score_launches++;
+    stats.backtrack_ms += t_back;
+    static const bool trace = getenv("NDGPU_TRACE") != nullptr;
+    if (trace) {
+        uint32_t longest = 0, rep = 0, slow = 0;
+        for (size_t p = 0; p < np; p++) {
+            longest = std::max(longest, piles[p].seed_len);
+            if (piles[p].n_repair == 0xffffffffu) slow++;
+            else rep += piles[p].n_repair;
         }
+        fprintf(stderr, "[ndgpu trace] run_main %zu piles longest %u | host prep %.1f align %.1f tags %.1f msa %.1f ms | K9 %.1f K10 %.1f backtrack %.1f ms | %u segments, %u repaired, %u piles through the int64 kernel\n",
+                np, longest, (tp[1] - tp[0]) * 1e-6, (tp[2] - tp[1]) * 1e-6, (tp[3] - tp[2]) * 1e-6, (tp[4] - tp[3]) * 1e-6, t_links, t_score, t_back,
+                plan.n_segs, rep, slow);
     }
     for (size_t p = 0; p < np; p++) {
         const PileDev &P = piles[p];
         mp[p]->n_aligned = P.n_acc;
         if (bad_pile[p]) continue;
-        S.stats.path_items += P.path_len;
-        S.stats.links += P.n_links;
-        S.stats.score_segments += P.n_seg;
-        if (P.n_repair == 0xffffffffu) S.stats.score_slow_piles++;  // marker left by the int64 kernel
-        else S.stats.score_repairs += P.n_repair;
+        stats.path_items += P.path_len;
+        stats.links += P.n_links;
+        stats.score_segments += P.n_seg;
+        if (P.n_repair == 0xffffffffu) stats.score_slow_piles++;  // marker left by the int64 kernel
+        else stats.score_repairs += P.n_repair;
     }
-    {  // unpack the walk of every pile (one step per consensus position): piles dealt to the context's host threads
-        std::atomic<size_t> next(0);
-        auto work = [&] {
-            for (;;) {
-                const size_t p = next.fetch_add(1);
-                if (p >= np) break;
-                if (bad_pile[p]) continue;
-                const PileDev &P = piles[p];
-                MainPile &M = *mp[p];
-                M.path.resize(P.path_len);
-                const PathItem *src = hpath + P.path_off;
-                for (uint32_t k = 0; k < P.path_len; k++) {
-                    PathStep &d = M.path[k];
-                    d.t_pos = tag_tpos(src[k].tag);
-                    d.delta = (uint16_t)tag_delta(src[k].tag);
-                    d.base = (uint8_t)tag_base(src[k].tag);
-                    d.link = src[k].link;
-                    d.cov = src[k].cov;
-                }
-            }
-        };
-        if (S.host_threads <= 1 || np < 4) {
-            work();
-        } else {
-            CoreLease lease(S.host_threads);
-            const size_t nth = std::min<size_t>((size_t)lease.n, np);
-            std::vector<std::thread> th;
-            for (size_t t = 1; t < nth; t++) th.emplace_back(work);
-            work();
-            for (auto &x : th) x.join();
+}
+
+// The walk of every pile (one step per consensus position) into its MainPile: piles dealt to the context's host threads.
+static void unpack_paths(const std::vector<PileDev> &piles, const PathItem *hpath, const std::vector<uint8_t> &bad_pile, MainPile **mp,
+                         int host_threads) {
+    const size_t np = piles.size();
+    host_each(np, host_threads <= 1 || np < 4, host_threads, np, true, [&](size_t p) {
+        if (bad_pile[p]) return;
+        const PileDev &P = piles[p];
+        MainPile &M = *mp[p];
+        M.path.resize(P.path_len);
+        const PathItem *src = hpath + P.path_off;
+        for (uint32_t k = 0; k < P.path_len; k++) {
+            PathStep &d = M.path[k];
+            d.t_pos = tag_tpos(src[k].tag);
+            d.delta = (uint16_t)tag_delta(src[k].tag);
+            d.base = (uint8_t)tag_base(src[k].tag);
+            d.link = src[k].link;
+            d.cov = src[k].cov;
         }
+    });
+}
+
+void DeviceAligner::run_main(MainPile **mp, size_t np) {
+    State &S = *s_;
+    uint64_t tp[5] = {wall_ns()};
+    const State::Phase phase(S);
+    hipStream_t st = S.stream;
+    const MainLayout L = S.layout_piles(mp, np);
+    std::vector<PileDev> &piles = S.piles;
+    const size_t nt = S.tasks.size(), nr = S.reads.size();
+    // forward/traceback chunks bounded by the trace budget
+    const std::vector<AlignChunk> chunks = S.plan_chunks(S.tasks.data(), nt);
+    S.reserve_layout(L, np);
+    g_prof.m_prep += (tp[1] = wall_ns()) - tp[0];
+
+    S.h2d(S.d_pool.p, S.pool.data(), S.pool.size() * sizeof(uint32_t), st);
+    if (nt) S.h2d(S.d_tasks.p, S.tasks.data(), nt * sizeof(AlnTask), st);
+    S.h2d(S.d_reads.p, S.reads.data(), nr * sizeof(ReadDev), st);
+    S.h2d(S.d_piles.p, piles.data(), np * sizeof(PileDev), st);
+    S.h2d(S.d_read_pile.p, L.read_pile.data(), nr * sizeof(uint32_t), st);
+    const CovPlanes cov{S.d_cov.p, S.d_cov.p + (L.col_slots + 1), S.d_cov.p + 2 * (L.col_slots + 1)};
+    HIP_CHECK(hipMemsetAsync(cov.cov, 0, 3 * (L.col_slots + 1) * sizeof(uint32_t), st));  // (one fill for the three)
+    HIP_CHECK(hipMemsetAsync(S.d_err.p, 0, kErrWords * sizeof(uint32_t), st));
+    S.align_main(chunks, np);
+    g_prof.m_aln += (tp[2] = wall_ns()) - tp[1];
+
+    S.launch_tags(cov, np);
+    S.d2h(piles.data(), S.d_piles.p, np * sizeof(PileDev), st);
+    S.sync_drain(st);
+    g_prof.m_tags += (tp[3] = wall_ns()) - tp[2];
+
+    const MsaPlan plan = plan_msa(piles);
+    S.stats.tags += plan.ents;
+    S.stats.cells_msa += plan.cells;
+    S.stats.piles += np;
+    S.upload_plan(plan);
+    MsaResult res = S.count_and_score(plan, cov);
+    piles.swap(res.piles);
+    g_prof.m_msa += (tp[4] = wall_ns()) - tp[3];
+    if (res.herr[0]) {
+        fprintf(stderr, "[ndgpu] FATAL: a cell of the MSA holds more links than its pile has reads\n");
+        abort();
     }
-    g_prof.m_post += wall_ns() - tp4;
+    S.tally_main(plan, L.bad_pile, mp, tp);
+    unpack_paths(piles, res.hpath, L.bad_pile, mp, S.host_threads);
+    g_prof.m_post += wall_ns() - tp[4];
 }
 
 // ---- POA problems as a batch (K13): lockstep rounds -- round r aligns sequence r of every problem that has one against the
@@ -1991,10 +2046,7 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
 void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
     if (n == 0) return;
     State &S = *s_;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(S.mu);
-    HIP_CHECK(hipSetDevice(S.device));
+    const State::Phase phase(S);
     hipStream_t st = S.stream;
     // test hooks, read once: the cell budget of a launch (0: every problem is declined), the kernel form every job takes, the row
     // length from which the workgroup form takes over
@@ -2030,20 +2082,7 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
     }
 
     auto host_for = [&](const std::vector<size_t> &ids, auto f) {  // f(problem) over the context's host threads
-        if (ids.size() < 8 || S.host_threads <= 1) {
-            for (size_t i : ids) f(i);
-            return;
-        }
-        CoreLease lease(S.host_threads);
-        const size_t nt = std::min<size_t>((size_t)lease.n, ids.size() / 4);
-        std::atomic<size_t> next(0);
-        auto work = [&] {
-            for (size_t k; (k = next.fetch_add(1)) < ids.size();) f(ids[k]);
-        };
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-        work();
-        for (auto &x : th) x.join();
+        host_each(ids.size(), ids.size() < 8 || S.host_threads <= 1, S.host_threads, ids.size() / 4, true, [&](size_t k) { f(ids[k]); });
     };
 
     std::vector<size_t> round_ids, slice;
@@ -2124,9 +2163,7 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
             S.d2h(jobs.data(), S.d_poa_jobs.p, jobs.size() * sizeof(PoaJobDev), st);
             S.d2h(routes.data(), S.d_poa_route.p, route_at * sizeof(uint32_t), st);
             S.sync_drain(st);
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
-            S.stats.poa_ms += ms;
+            S.stats.poa_ms += ms_between(S.evs[5], S.evs[6]);
             S.stats.poa_launches += (ids_wave.empty() ? 0 : 1) + (ids_group.empty() ? 0 : 1);
             S.stats.poa_cells += cell_at;
             // ---- graph growth and the new order, on the host
@@ -2159,10 +2196,7 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
 void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
     if (n == 0) return;
     State &S = *s_;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(S.mu);
-    HIP_CHECK(hipSetDevice(S.device));
+    const State::Phase phase(S);
     hipStream_t st = S.stream;
     constexpr size_t kRankSliceBytes = (size_t)256 << 20, kRankSliceJobs = 1 << 20;
     std::vector<RegionDev> regs;
@@ -2197,9 +2231,7 @@ void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
         HIP_CHECK(hipEventRecord(S.evs[6], st));
         S.d2h(regs.data(), S.d_regions.p, regs.size() * sizeof(RegionDev), st);
         S.sync_drain(st);
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
-        S.stats.rank_ms += ms;
+        S.stats.rank_ms += ms_between(S.evs[5], S.evs[6]);
         S.stats.rank_launches++;
         for (size_t i = a; i < b; i++) {
             const RegionDev &g = regs[i - a];
@@ -2220,10 +2252,7 @@ void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
 
 void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
     State &S = *s_;
-    std::unique_lock<std::mutex> dbg_lock;
-    if (g_debug_exclusive) dbg_lock = std::unique_lock<std::mutex>(g_dbg_mu);
-    std::lock_guard<std::mutex> lock(S.mu);
-    HIP_CHECK(hipSetDevice(S.device));
+    const State::Phase phase(S);
     hipStream_t st = S.stream;
     std::vector<RegionDev> regs;
     bool rank = false;   // K14 behind K11: some pile of this launch takes a ranking
@@ -2269,12 +2298,9 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
         unsigned long long used = 0;
         S.d2h(&used, S.d_cursor.p, sizeof(used), st);
         S.sync_drain(st);
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, S.evs[5], S.evs[6]));
-        S.stats.extract_ms += ms;
+        S.stats.extract_ms += ms_between(S.evs[5], S.evs[6]);
         if (rank) {
-            HIP_CHECK(hipEventElapsedTime(&ms, S.evs[6], S.evs[7]));
-            S.stats.rank_ms += ms;
+            S.stats.rank_ms += ms_between(S.evs[6], S.evs[7]);
             S.stats.rank_launches++;
         }
         if (used <= cap) {
@@ -2318,15 +2344,7 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
             }
         }
     };
-    if (n < 32 || S.host_threads <= 1) {
-        fill(0, n);
-    } else {
-        CoreLease lease(S.host_threads);
-        const size_t nt = std::min<size_t>((size_t)lease.n, n / 8);
-        std::vector<std::thread> th;
-        for (size_t t = 0; t < nt; t++) th.emplace_back(fill, n * t / nt, n * (t + 1) / nt);
-        for (auto &x : th) x.join();
-    }
+    host_ranges(n, n < 32 || S.host_threads <= 1, S.host_threads, n / 8, fill);
 }
 
 }  // namespace ndgpu

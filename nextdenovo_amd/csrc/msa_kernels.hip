@@ -1873,11 +1873,7 @@ void launch_col_scan(PileDev *piles, uint32_t *cov_diff, const uint32_t *ins_cou
                        ins_count, ins_max, cell_base, ent_base);
 }
 
-void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
-                        const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
-                        const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
-                        uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, int n_blocks,
-                        bool full_capacity, void *stream) {
+void launch_count_links(const K9Args &a, int n_blocks, bool full_capacity, void *stream) {
     if (n_blocks <= 0) return;
     // NDGPU_K9_COMPACT=<T>: a column block that at most T reads reach takes the compact path (0..64, default 64; 0: none does)
     static const uint32_t compact_max = [] {
@@ -1886,24 +1882,20 @@ void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32
         return (uint32_t)(t < 0 ? 0 : t > 64 ? 64 : t);
     }();
     if (full_capacity)
-        hipLaunchKernelGGL(count_links_kernel<kLinkCap>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, piles, reads,
-                           acc_list, blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp,
-                           ent_ppp, ent_cnt, err, compact_max);
+        hipLaunchKernelGGL(count_links_kernel<kLinkCap>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, a.piles, a.reads,
+                           a.acc, a.blocks, a.tags, a.colidx, a.max_size, a.cell_base, a.ent_base, a.cell_start, a.cell_len, a.ent_pp,
+                           a.ent_ppp, a.ent_cnt, a.err, compact_max);
     else
-        hipLaunchKernelGGL(count_links_kernel<kLinkCapSmall>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, piles,
-                           reads, acc_list, blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp,
-                           ent_ppp, ent_cnt, err, compact_max);
+        hipLaunchKernelGGL(count_links_kernel<kLinkCapSmall>, dim3((unsigned)n_blocks), dim3(64), 0, (hipStream_t)stream, a.piles,
+                           a.reads, a.acc, a.blocks, a.tags, a.colidx, a.max_size, a.cell_base, a.ent_base, a.cell_start, a.cell_len,
+                           a.ent_pp, a.ent_ppp, a.ent_cnt, a.err, compact_max);
 }
 
-void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
-                               const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
-                               const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
-                               uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, uint32_t *lists, uint32_t cap,
-                               int n_blocks, int grid, void *stream) {
+void launch_count_links_global(const K9Args &a, uint32_t *lists, uint32_t cap, int n_blocks, int grid, void *stream) {
     if (n_blocks <= 0) return;
-    hipLaunchKernelGGL(count_links_global_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, piles, reads, acc_list,
-                       blocks, tags, colidx, max_size, cell_base, ent_base, cell_start, cell_len, ent_pp, ent_ppp, ent_cnt, err,
-                       lists, cap, n_blocks);
+    hipLaunchKernelGGL(count_links_global_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, a.piles, a.reads, a.acc,
+                       a.blocks, a.tags, a.colidx, a.max_size, a.cell_base, a.ent_base, a.cell_start, a.cell_len, a.ent_pp, a.ent_ppp,
+                       a.ent_cnt, a.err, lists, cap, n_blocks);
 }
 
 // The trace hook of NDGPU_K9_DIGEST (nd_device.h says what it sums).  One block per pile; never launched unless the switch is set.
@@ -1939,11 +1931,10 @@ __global__ __launch_bounds__(256) void k9_digest_kernel(const PileDev *__restric
     atomicMax(&out[3], longest);
 }
 
-void launch_k9_digest(const PileDev *piles, const uint32_t *cell_start, const uint32_t *cell_len, const uint32_t *ent_pp,
-                      const uint32_t *ent_ppp, const uint32_t *ent_cnt, unsigned long long *out, int n_piles, void *stream) {
+void launch_k9_digest(const K9Args &a, unsigned long long *out, int n_piles, void *stream) {
     if (n_piles <= 0) return;
-    hipLaunchKernelGGL(k9_digest_kernel, dim3((unsigned)n_piles), dim3(256), 0, (hipStream_t)stream, piles, cell_start, cell_len,
-                       ent_pp, ent_ppp, ent_cnt, out);
+    hipLaunchKernelGGL(k9_digest_kernel, dim3((unsigned)n_piles), dim3(256), 0, (hipStream_t)stream, a.piles, a.cell_start, a.cell_len,
+                       a.ent_pp, a.ent_ppp, a.ent_cnt, out);
 }
 
 void launch_score_backtrack(const K10Args &a, const SegItem *items_small, int n_small, const SegItem *items_large, int n_large,

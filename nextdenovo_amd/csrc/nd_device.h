@@ -311,23 +311,31 @@ void launch_make_tags(const PileDev *piles, const ReadDev *reads, const AlnTask 
 // in: cov_diff (difference array), ins_max; out (in place): coverage, max_size; plus offsets
 void launch_col_scan(PileDev *piles, uint32_t *cov_diff, const uint32_t *ins_count, uint32_t *ins_max,
                      uint32_t *cell_base, uint32_t *ent_base, int n_piles, void *stream);
-// err: kErrWords words, zero before the launch.  A column block that at most NDGPU_K9_COMPACT (0..64, default 64; read once) accepted
-// reads reach is counted on the compact path -- one lane per covering read --, any other by the loop over all accepted reads.
-void launch_count_links(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
-                        const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
-                        const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
-                        uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, int n_blocks, bool full_capacity,
-                        void *stream);
-void launch_count_links_global(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const ColBlock *blocks,
-                               const uint32_t *tags, const uint32_t *colidx, const uint32_t *max_size,
-                               const uint32_t *cell_base, const uint32_t *ent_base, uint32_t *cell_start, uint32_t *cell_len,
-                               uint32_t *ent_pp, uint32_t *ent_ppp, uint32_t *ent_cnt, uint32_t *err, uint32_t *lists, uint32_t cap,
-                               int n_blocks, int grid, void *stream);
+// What the link counter (K9) reads and the five tables it writes: one record for its two launches, the digest hook and the fields
+// K10Args shares with them (k10_args_from).  The kernels keep their flat parameter lists; the wrappers unpack the record.
+struct K9Args {
+    PileDev *piles;
+    const ReadDev *reads;
+    const uint32_t *acc;          // accepted reads of every pile
+    const ColBlock *blocks;
+    const uint32_t *tags, *colidx, *max_size, *cell_base, *ent_base;
+    uint32_t *cell_start, *cell_len, *ent_pp, *ent_ppp, *ent_cnt;   // the tables
+    uint32_t *err;                // kErrWords words, zero before the launch
+};
+inline K10Args k10_args_from(const K9Args &k) {   // (coverage, the cell bests, the segment buffers and the knobs are the caller's)
+    K10Args a{};
+    a.piles = k.piles, a.max_size = k.max_size, a.cell_base = k.cell_base, a.ent_base = k.ent_base;
+    a.cell_start = k.cell_start, a.cell_len = k.cell_len, a.ent_pp = k.ent_pp, a.ent_ppp = k.ent_ppp, a.ent_cnt = k.ent_cnt;
+    return a;
+}
+// A column block that at most NDGPU_K9_COMPACT (0..64, default 64; read once) accepted reads reach is counted on the compact path
+// -- one lane per covering read --, any other by the loop over all accepted reads.
+void launch_count_links(const K9Args &a, int n_blocks, bool full_capacity, void *stream);
+void launch_count_links_global(const K9Args &a, uint32_t *lists, uint32_t cap, int n_blocks, int grid, void *stream);
 // Trace hook (NDGPU_K9_DIGEST): what the link counter left in its tables, for piles [0, n_piles).  out[0] += a hash of every cell's
 // (pile, cell, start, len) and of every (pile, cell, position, pp, ppp, cnt) of its links [start, start + len) -- position-dependent,
 // summed, so the same whatever the order of the blocks; out[1] += cells, out[2] += links, out[3] = max(len).  out: zero before.
-void launch_k9_digest(const PileDev *piles, const uint32_t *cell_start, const uint32_t *cell_len, const uint32_t *ent_pp,
-                      const uint32_t *ent_ppp, const uint32_t *ent_cnt, unsigned long long *out, int n_piles, void *stream);
+void launch_k9_digest(const K9Args &a, unsigned long long *out, int n_piles, void *stream);
 // segment kernels of both table tiers (the large one on stream_large at the same time) -> stitch -> int64 kernel for
 // the piles they left (err == 2) -> best_pp walk
 // (ent_score == nullptr: the int64 kernel is not launched and leaves err == 2 piles for a second call with rescue = true,

@@ -2,9 +2,11 @@
 // public C ABI is include/ndgpu_nextcorrect.h).
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace ndgpu {
@@ -300,6 +302,41 @@ struct CoreLease {
     CoreLease(const CoreLease &) = delete;
     CoreLease &operator=(const CoreLease &) = delete;
 };
+
+// The two host pools, both on a CoreLease of `base` threads held for the loop.  small: not worth a thread -- the caller's thread
+// does everything and no lease is taken; max_threads: what the amount of work justifies; every call site passes its own thresholds.
+// f(begin, end) over contiguous ranges of [0, n): one range a thread, the caller's thread waits.
+template <typename F>
+void host_ranges(size_t n, bool small, int base, size_t max_threads, F f) {
+    if (small) {
+        f((size_t)0, n);
+        return;
+    }
+    CoreLease lease(base);
+    const size_t nt = std::max<size_t>(1, std::min<size_t>((size_t)lease.n, max_threads));
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; t++) th.emplace_back(f, n * t / nt, n * (t + 1) / nt);
+    for (auto &x : th) x.join();
+}
+// f(i) for every i of [0, n): a thread claims the next index when it is done with the last.  caller_works: the caller's thread is
+// one of the threads, else it waits.
+template <typename F>
+void host_each(size_t n, bool small, int base, size_t max_threads, bool caller_works, F f) {
+    if (small) {
+        for (size_t i = 0; i < n; i++) f(i);
+        return;
+    }
+    CoreLease lease(base);
+    const size_t nt = std::max<size_t>(1, std::min<size_t>((size_t)lease.n, max_threads));
+    std::atomic<size_t> next(0);
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
+    };
+    std::vector<std::thread> th;
+    for (size_t t = caller_works ? 1 : 0; t < nt; t++) th.emplace_back(work);
+    if (caller_works) work();
+    for (auto &x : th) x.join();
+}
 
 // Drives a set of engines to completion over one backend (host phases on `threads`).
 void run_engines(PileEngine **eng, size_t n, Backend &be, int threads);

@@ -144,7 +144,6 @@ class DeviceAligner {
     // what both have in common: tasks built and uploaded, K7 / K8a launched, the AlnOut records (and the ops, if asked) on the host,
     // the wide-band tasks run again; returns the chunk's ops words
     uint64_t chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t> &bad, bool ops_to_host, uint64_t *dev_ns);
-    void run_wide(AlnJob **jobs, const std::vector<int32_t> &ids);
     struct State;
     State *s_;
 };
