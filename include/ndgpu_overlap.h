@@ -177,6 +177,44 @@ int64_t ndgpu_assemble_piles(const ndgpu_ovl_rec *sorted, int64_t n, uint32_t n_
                              uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, uint32_t **recs8,
                              uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles);
 
+/* ---- the same admission on the device (K16, one wavefront per seed group; csrc/ovlsort_kernels.hip) ----
+ * On a well-formed stream -- every group of records with one seed id starts with a record the loop admits or with one that rejects
+ * the whole group -- the loop's verdicts are a per-group rule with one prefix sum, and the device applies it.  A group where the
+ * loop's last_seed / '+' state would split the group again is "irregular": a valid seed whose first record is shorter than
+ * min_len_aln, a rejected seed with a later record that passes as a seed, t_e < t_s, a query id >= n_ids.  One such group and the
+ * whole call is answered by ndgpu_assemble_piles (groups_declined says so); ndgpu_ovl_sort's output is regular at nextDenovo's
+ * thresholds.  The result is ndgpu_assemble_piles's either way.
+ *   sorted_records    records the admission saw;  groups = seed groups among them
+ *   groups_declined   irregular groups found before the call turned to the host routine (0: the device's answer)
+ *   groups_wide       groups whose table of seen query reads did not fit LDS (more than 1024 records, or more than half of
+ *                     NDGPU_ADMIT_TABLE=<slots>, which forces a smaller table) and lived in global memory
+ *   admitted, piles   records and piles handed out
+ *   k16_ms            HIP-event time of the admission tail: the two kernel passes, the scans between them, the downloads
+ *   bytes_downloaded  bytes copied from the device for the call's outputs (rows, offsets, seeds, `.bl` lists, sorted records if any) */
+typedef struct ndgpu_ovl_admit_stats {
+	double k16_ms;
+	uint64_t sorted_records, groups, groups_declined, groups_wide, admitted, piles, bytes_downloaded;
+} ndgpu_ovl_admit_stats;
+/* array-level view: the arguments and the three blocks of ndgpu_assemble_piles; the records are uploaded, K16 runs, only what was
+ * admitted comes back.  flags bit 0: the host routine instead (a cross-check); bit 1 reserved (0).  stats may be NULL.
+ * n = 0 and "every seed rejected" give pile_off = {0}.  Returns the number of admitted records; -1 no device, -2 a device operation
+ * failed (ndgpu_ovl_last_error), -3 more than 2^30 records. */
+int64_t ndgpu_admit_piles(const ndgpu_ovl_rec *sorted, int64_t n, uint32_t n_ids, uint32_t min_len_seed, uint32_t min_len_aln,
+                          uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, int32_t flags,
+                          uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles, ndgpu_ovl_admit_stats *stats);
+/* ndgpu_ovl_sort (hq != 0: ndgpu_ovl_sort_hq) with the admission as its tail: the sorted records, their group offsets and the
+ * `.bl` verdicts are admitted where the sort left them, range by range in the out-of-core form.  The skip set is skip_ids plus,
+ * with use_bl != 0, the seeds of this sort's own `.bl` verdicts.  Only recs8 / pile_off / seeds and the `.bl` lists are downloaded;
+ * the sorted records too when `sorted` is not NULL (*sorted malloc'd, *n_sorted records) -- or when a group declined, for the host
+ * routine.  flags as above.  Everything handed out is malloc'd (ndgpu_ovl_free).  Returns the number of admitted records, or
+ * ndgpu_ovl_sort's error codes. */
+int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
+                             uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq,
+                             uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                             const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                             int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                             ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats);
+
 /* ---- read ingestion: the 2-bit packing of `seq_dump` (seq2bit, lib/bseq.c:114-139; called from util/seq_dump.c:36-41) ----
  * Read i is the lens[i] ASCII bytes at ascii + ascii_off[i]; its ceil(lens[i]/16) words go to words + word_off[i] (word_off ascending,
  * reads back to back).  Bytes other than ACGTU (either case) are coded 4 and OR-ed in as the reference does, so they disturb the low

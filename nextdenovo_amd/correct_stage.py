@@ -186,8 +186,14 @@ def run(argv) -> int:
         seed_len = np.zeros(int(lens.size), dtype=np.uint32)
         seed_len[s.ids] = s.lens
         files = [r for _, r in sorted(per_seed_files[i], key=lambda kr: kr[0])]
-        srt, bl, _ = overlap.sort_overlaps(files, seed_len, int(s.lens.min()) if len(s) else 0, a.sort_k, a.flank)
         tag = os.path.basename(seed_paths[i])[len("input.seed."):-len(".2bit")]
+        fused = os.environ.get("NDGPU_ADMIT_DEVICE") == "1"   # the pile admission as the sort's tail on the device (ndgpu_ovl_sort_piles)
+        if fused:
+            dec, off, names, bl, srt, _ = overlap.sort_piles(files, seed_len, int(s.lens.min()) if len(s) else 0, a.sort_k, a.flank,
+                                                             min_len_seed=a.min_len_seed, min_len_aln=a.min_len_aln, max_cov_aln=a.max_cov_aln,
+                                                             min_cov_seed=a.min_cov_seed, use_bl=bool(a.blacklist), want_sorted=bool(a.keep))
+        else:
+            srt, bl, _ = overlap.sort_overlaps(files, seed_len, int(s.lens.min()) if len(s) else 0, a.sort_k, a.flank)
         if a.keep:
             so = os.path.join(a.keep, "input.seed.%s.sorted.ovl" % tag)
             with open(so, "wb") as f:
@@ -195,8 +201,9 @@ def run(argv) -> int:
             with open(so + ".bl", "w") as f:
                 for rid, kind in bl:
                     f.write("%d %s\n" % (rid, kind))
-        skip = [rid for rid, _ in bl] if a.blacklist else []
-        dec, off, names = overlap.assemble_piles(srt, int(lens.size), a.min_len_seed, a.min_len_aln, a.max_cov_aln, a.min_cov_seed, skip)
+        if not fused:
+            skip = [rid for rid, _ in bl] if a.blacklist else []
+            dec, off, names = overlap.assemble_piles(srt, int(lens.size), a.min_len_seed, a.min_len_aln, a.max_cov_aln, a.min_cov_seed, skip)
         return tag, dec, off, names
 
     def correct(i, made):

@@ -38,6 +38,18 @@ void launch_seed_filter(const OvlRec *cand, const uint32_t *perm, const uint64_t
                         uint32_t *n_out, uint32_t *bl_id, uint8_t *bl_kind, bool hq, hipStream_t s);
 void launch_compact_seed_recs(const uint64_t *seed_start, uint32_t n_seeds, const OvlRec *out, const uint32_t *n_out, const uint64_t *off,
                               OvlRec *dense, hipStream_t s);
+// K16, the pile admission (csrc/ovlsort_kernels.hip)
+void launch_group_flag(const OvlRec *recs, uint64_t n, uint32_t *flag, hipStream_t s);
+void launch_skip_bits(const uint32_t *ids, const uint8_t *kind, uint64_t n, uint32_t n_ids, uint32_t *bits, hipStream_t s);
+uint32_t admit_lds_slots();
+void launch_admit_plan(const uint64_t *off, uint32_t n_groups, uint32_t lds_slots, uint32_t *slots, uint32_t *counters, hipStream_t s);
+void launch_admit_count(const OvlRec *recs, const uint64_t *off, uint32_t n_groups, const uint32_t *skip_bits, uint32_t n_ids,
+                        uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, uint32_t lds_slots,
+                        const uint32_t *wide_slots, const uint64_t *tab_off, uint64_t *scratch, uint8_t *adm, uint32_t *n_adm, uint32_t *kept,
+                        uint32_t *counters, hipStream_t s);
+void launch_admit_emit(const OvlRec *recs, const uint64_t *off, uint32_t n_groups, const uint8_t *adm, const uint32_t *n_adm,
+                       const uint32_t *kept, const uint64_t *rec_off, const uint64_t *pile_idx, uint32_t *recs8, uint64_t *pile_off,
+                       uint32_t *seeds, hipStream_t s);
 
 struct SortRun {
 	hipStream_t st = nullptr;
@@ -87,14 +99,115 @@ struct SortOut {
 	RecOut recs;
 	std::vector<uint32_t> bl_id;
 	std::vector<uint8_t> bl_kind;
-	uint64_t seeds = 0;
+	uint64_t seeds = 0, n_recs = 0;   // n_recs: sorted records, downloaded or not
 };
+
+// The admission tail of a call (K16): the thresholds, the skip set as a bitmap on the device, and what was admitted so far -- the
+// seed ranges of the out-of-core sort are independent, their piles are appended in order.  A row of recs8 is as wide as a record,
+// so the rows grow in a RecOut too.
+struct Admission {
+	uint32_t n_ids = 0, min_len_seed = 0, min_len_aln = 0, max_cov_aln = 0, min_cov_seed = 0, lds_slots = 0;
+	bool use_bl = false, want_sorted = false, declined = false;
+	DevBuf<uint32_t> skip_bits;
+	RecOut rows;
+	std::vector<uint64_t> pile_off{0};
+	std::vector<uint32_t> seeds;
+	ndgpu_ovl_admit_stats st{};
+
+	Admission(uint32_t ids, uint32_t mls, uint32_t mla, uint32_t mca, uint32_t mcs)
+		: n_ids(ids), min_len_seed(mls), min_len_aln(mla), max_cov_aln(mca), min_cov_seed(mcs) {}
+	void begin(const uint32_t *skip_ids, int64_t n_skip, hipStream_t s)
+	{
+		// the LDS table's capacity, a power of two; NDGPU_ADMIT_TABLE=<slots> forces a smaller one (groups of more than half of it
+		// take the table in global memory: the wide path on small inputs)
+		lds_slots = admit_lds_slots();
+		if (const char *e = getenv("NDGPU_ADMIT_TABLE")) {
+			const uint64_t v = strtoull(e, nullptr, 10);
+			uint32_t p = 2;
+			while ((uint64_t)p * 2 <= v && p * 2 <= lds_slots) p *= 2;
+			lds_slots = p;
+		}
+		skip_bits.alloc((size_t)(n_ids >> 5) + 2);
+		skip_bits.zero(s);
+		if (n_skip > 0) {
+			DevBuf<uint32_t> ids_d((size_t)n_skip);
+			ids_d.upload(skip_ids, (size_t)n_skip, s);
+			launch_skip_bits(ids_d.p, nullptr, (uint64_t)n_skip, n_ids, skip_bits.p, s);
+			HIP_OK(hipStreamSynchronize(s));   // (ids_d goes back to the pool)
+		}
+	}
+	void hand_out(uint32_t **recs8, uint64_t **poff, uint32_t **sd, int64_t *n_piles)
+	{
+		*poff = malloc_copy<uint64_t>(pile_off);
+		*sd = malloc_copy<uint32_t>(seeds);
+		*n_piles = (int64_t)seeds.size();
+		*recs8 = (uint32_t*)rows.release();
+		if (!*recs8) throw std::runtime_error("malloc");
+	}
+};
+
+// K16 over `n` dense sorted records in `n_groups` groups (group g = dense[off[g] .. off[g + 1]); off has n_groups + 1 entries):
+// count, two scans, emit; the piles are appended to A.  An irregular group turns the call over to the host routine (A.declined).
+static void admit_tail(SortRun &R, const OvlRec *dense, const uint64_t *off, uint64_t n_groups, uint64_t n, Admission &A)
+{
+	A.st.sorted_records += n, A.st.groups += n_groups;
+	if (A.declined || n_groups == 0 || n == 0) return;
+	if (n >= (1ull << 30) || n_groups >= 0x7fffffffull) throw std::runtime_error("too many records for one admission call");
+	const uint32_t G = (uint32_t)n_groups;
+	EvTimer tm(R.st);
+	tm.start();
+	DevBuf<uint8_t> adm(n + 1);
+	DevBuf<uint32_t> n_adm(G + 1), kept(G + 1), slots(G + 1), counters(4);
+	DevBuf<uint64_t> rec_off(G + 1), pile_idx(G + 1), tab_off(G + 1);
+	// a wide group of c records takes pow2ceil(2 c) < 4 c slots, and no group is wide when all records together are not
+	DevBuf<uint64_t> scratch(2 * n > A.lds_slots ? 4 * n + 1 : 1);
+	adm.zero(R.st), n_adm.zero(R.st), kept.zero(R.st), slots.zero(R.st), counters.zero(R.st);
+	launch_admit_plan(off, G, A.lds_slots, slots.p, counters.p, R.st);
+	R.exscan(slots.p, tab_off.p, (size_t)G + 1);
+	launch_admit_count(dense, off, G, A.skip_bits.p, A.n_ids, A.min_len_seed, A.min_len_aln, A.max_cov_aln, A.min_cov_seed, A.lds_slots, slots.p,
+	                   tab_off.p, scratch.p, adm.p, n_adm.p, kept.p, counters.p, R.st);
+	R.exscan(n_adm.p, rec_off.p, (size_t)G + 1);
+	R.exscan(kept.p, pile_idx.p, (size_t)G + 1);
+	uint64_t n_rows = 0, n_piles = 0;
+	uint32_t h_counters[4] = {0, 0, 0, 0};
+	rec_off.download(&n_rows, 1, R.st, G);
+	pile_idx.download(&n_piles, 1, R.st, G);
+	counters.download(h_counters, 4, R.st);
+	HIP_OK(hipStreamSynchronize(R.st));
+	HIP_OK(hipGetLastError());
+	A.st.groups_declined += h_counters[0], A.st.groups_wide += h_counters[1];
+	A.st.bytes_downloaded += 32;
+	if (h_counters[0]) {
+		A.declined = true;
+		A.st.k16_ms += tm.stop();
+		return;
+	}
+	if (n_rows > n || n_piles > n_groups) throw std::runtime_error("admission counts out of range");
+	DevBuf<uint32_t> r8(n_rows * 8 + 8), sd(n_piles + 1);
+	DevBuf<uint64_t> poff(n_piles + 1);
+	launch_admit_emit(dense, off, G, adm.p, n_adm.p, kept.p, rec_off.p, pile_idx.p, r8.p, poff.p, sd.p, R.st);
+	const uint64_t row_base = A.pile_off.back();
+	const size_t pile_base = A.seeds.size();
+	A.pile_off.pop_back();
+	A.pile_off.resize(pile_base + n_piles + 1);
+	A.seeds.resize(pile_base + n_piles);
+	uint32_t *const dst = (uint32_t*)A.rows.grow(n_rows);
+	r8.download(dst, n_rows * 8, R.st);
+	poff.download(A.pile_off.data() + pile_base, n_piles, R.st);
+	sd.download(A.seeds.data() + pile_base, n_piles, R.st);
+	A.st.k16_ms += tm.stop();   // (waits for the stream: the downloads above are in)
+	HIP_OK(hipGetLastError());
+	for (uint64_t p = 0; p < n_piles; ++p) A.pile_off[pile_base + p] += row_base;
+	A.pile_off[pile_base + n_piles] = row_base + n_rows;
+	A.st.admitted += n_rows, A.st.piles += n_piles;
+	A.st.bytes_downloaded += n_rows * 32 + n_piles * 12;
+}
 
 // S2 + S3 over one set of candidates (all of a call, or those of one seed range): the sorted, filtered records and the `.bl`
 // verdicts are appended to `o`
 static void sort_and_filter(SortRun &R, const OvlRec *cand_p, const uint32_t *k_span_p, const uint32_t *k_match_p, const uint32_t *k_seed_p,
                             uint64_t nc, const uint32_t *d_seed_p, const uint32_t *seed_len, uint32_t n_ids, int32_t min_seed_len,
-                            int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, SortOut &o)
+                            int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, SortOut &o, Admission *A = nullptr)
 {
 	DevBuf<uint32_t> perm(nc), perm2(nc), k1(nc), k2(nc);
 	// S2: (seed asc, match desc, span asc), stable
@@ -135,8 +248,11 @@ static void sort_and_filter(SortRun &R, const OvlRec *cand_p, const uint32_t *k_
 	launch_compact_seed_recs(sstart.p, (uint32_t)n_seeds, outrec.p, n_out.p, off.p, dense.p, R.st);
 	std::vector<uint32_t> h_id(n_seeds);
 	std::vector<uint8_t> h_kind(n_seeds);
-	OvlRec *const dst = o.recs.grow(total);
-	dense.download(dst, total, R.st);
+	if (!A || A->want_sorted) {
+		OvlRec *const dst = o.recs.grow(total);
+		dense.download(dst, total, R.st);
+	}
+	o.n_recs += total;
 	d_bl_id.download(h_id.data(), n_seeds, R.st);
 	d_bl_kind.download(h_kind.data(), n_seeds, R.st);
 	HIP_OK(hipStreamSynchronize(R.st));
@@ -144,6 +260,11 @@ static void sort_and_filter(SortRun &R, const OvlRec *cand_p, const uint32_t *k_
 	for (uint64_t i = 0; i < n_seeds; ++i)
 		if (h_kind[i]) o.bl_id.push_back(h_id[i]), o.bl_kind.push_back(h_kind[i]);
 	o.seeds += n_seeds;
+	if (A) {   // the admission on dense / off / the verdicts while they are on the device
+		A->st.bytes_downloaded += n_seeds * 5 + (A->want_sorted ? total * sizeof(OvlRec) : 0);
+		if (A->use_bl) launch_skip_bits(d_bl_id.p, d_bl_kind.p, n_seeds, A->n_ids, A->skip_bits.p, R.st);
+		admit_tail(R, dense.p, off.p, n_seeds, total, *A);
+	}
 }
 
 static void hand_out(SortOut &so, ndgpu_ovl_rec **out, uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl)
@@ -168,7 +289,7 @@ static void hand_out(SortOut &so, ndgpu_ovl_rec **out, uint32_t **bl_id, uint8_t
 // are the output of the whole sort; equal (seed, match, span) keys keep input order in either form.
 static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
                              uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, uint64_t piece_cap,
-                             uint64_t range_cap, SortOut &so, uint64_t *nc_total, uint64_t *n_ranges)
+                             uint64_t range_cap, SortOut &so, uint64_t *nc_total, uint64_t *n_ranges, Admission *A)
 {
 	DevBuf<uint32_t> d_seed(n_ids + 1), hist(n_ids + 1);
 	d_seed.upload(seed_len, n_ids, R.st);
@@ -234,7 +355,7 @@ static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, cons
 			}
 		}
 		if (base != nc) throw std::runtime_error("candidate count changed between the passes");
-		sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so);
+		sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A);
 		*nc_total += nc, ++*n_ranges;
 		lo = hi;
 	}
@@ -242,7 +363,8 @@ static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, cons
 
 static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
                          uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, ndgpu_ovl_rec **out,
-                         uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats, bool hq_mode)
+                         uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats, bool hq_mode, Admission *A = nullptr,
+                         const uint32_t *skip_ids = nullptr, int64_t n_skip = 0)
 {
 	*out = nullptr, *bl_id = nullptr, *bl_kind = nullptr, *n_bl = 0;
 	if (stats) memset(stats, 0, sizeof(*stats));
@@ -264,6 +386,7 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 		h_fstart[n_files] = n;
 		SortOut so;
 		if (n == 0) { hand_out(so, out, bl_id, bl_kind, n_bl); return 0; }   // (nothing in: an empty result, the stats stay zero)
+		if (A) A->begin(skip_ids, n_skip, R.st);
 		// in one piece when the device holds the raw records, their flags and up to two candidates per record (~360 bytes per record
 		// with the sort's scratch); otherwise -- or when told to -- in seed ranges (sort_out_of_core)
 		uint64_t piece_cap = 0, range_cap = 0;
@@ -278,7 +401,7 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			if (!piece_cap) piece_cap = std::max<uint64_t>(1u << 20, std::min<uint64_t>(n, avail / 8 / 96));
 			if (!range_cap) range_cap = std::max<uint64_t>(1u << 20, std::min<uint64_t>(0x7ffffff0ull, avail / 2 / 180));
 			sort_out_of_core(R, files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, piece_cap, range_cap, so,
-			                 &nc, &n_ranges);
+			                 &nc, &n_ranges, A);
 		} else {
 			std::vector<uint32_t> h_file_of(n);
 			DevBuf<OvlRec> raw(n);
@@ -311,10 +434,10 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			DevBuf<OvlRec> cand(nc);
 			DevBuf<uint32_t> k_span(nc), k_match(nc), k_seed(nc);
 			launch_expand_write(raw.p, n, sel.p, pos.p, cand.p, k_span.p, k_match.p, k_seed.p, R.st);
-			sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so);
+			sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A);
 		}
 		const double gpu_ms = tm.stop();
-		const uint64_t kept = so.recs.size(), n_seeds = so.seeds;
+		const uint64_t kept = so.n_recs, n_seeds = so.seeds;
 		const double t_dev = since();
 		hand_out(so, out, bl_id, bl_kind, n_bl);
 		if (prof && in_core)
@@ -404,4 +527,122 @@ extern "C" int64_t ndgpu_assemble_piles(const ndgpu_ovl_rec *sorted, int64_t n, 
 	if (np) memcpy(*seeds, names.data(), sizeof(uint32_t) * np);
 	*n_piles = (int64_t)np;
 	return (int64_t)nr;
+}
+
+
+// the answer of the host routine in the place of the device's (an irregular group, or flags bit 0)
+static int64_t admit_on_host(const ndgpu_ovl_rec *sorted, int64_t n, const Admission &A, const uint32_t *skip_ids, int64_t n_skip,
+                             const std::vector<uint32_t> *bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                             ndgpu_ovl_admit_stats *st)
+{
+	std::vector<uint32_t> skip(skip_ids, skip_ids + (n_skip > 0 ? n_skip : 0));
+	if (bl) skip.insert(skip.end(), bl->begin(), bl->end());
+	const int64_t nr = ndgpu_assemble_piles(sorted, n, A.n_ids, A.min_len_seed, A.min_len_aln, A.max_cov_aln, A.min_cov_seed, skip.data(),
+	                                        (int64_t)skip.size(), recs8, pile_off, seeds, n_piles);
+	st->admitted = (uint64_t)nr, st->piles = (uint64_t)*n_piles;
+	return nr;
+}
+
+extern "C" int64_t ndgpu_admit_piles(const ndgpu_ovl_rec *sorted, int64_t n, uint32_t n_ids, uint32_t min_len_seed, uint32_t min_len_aln,
+                                     uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, int32_t flags,
+                                     uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles, ndgpu_ovl_admit_stats *stats)
+{
+	*recs8 = nullptr, *pile_off = nullptr, *seeds = nullptr, *n_piles = 0;
+	ndgpu_ovl_admit_stats st_local;
+	if (!stats) stats = &st_local;
+	memset(stats, 0, sizeof(*stats));
+	try {
+		Admission A(n_ids, min_len_seed, min_len_aln, max_cov_aln, min_cov_seed);
+		if (n <= 0 || (flags & 1)) {   // nothing to admit, or the host routine asked for (the cross-check)
+			A.st.sorted_records = n > 0 ? (uint64_t)n : 0;
+			*stats = A.st;
+			return admit_on_host(sorted, n > 0 ? n : 0, A, skip_ids, n_skip, nullptr, recs8, pile_off, seeds, n_piles, stats);
+		}
+		if ((uint64_t)n >= (1ull << 30)) { fprintf(stderr, "[ndgpu_overlap] too many records for one admission call\n"); return -3; }
+		if (select_device(true) < 0) return -1;
+		{
+			SortRun R;
+			HIP_OK(ndovl::create_stage_stream(&R.st));
+			const StreamGuard guard{R.st};
+			A.begin(skip_ids, n_skip, R.st);
+			// the groups: runs of one seed id
+			const uint64_t un = (uint64_t)n;
+			DevBuf<OvlRec> recs(un);
+			recs.upload((const OvlRec*)sorted, un, R.st);
+			DevBuf<uint32_t> flag(un + 1);
+			DevBuf<uint64_t> rank(un + 1);
+			flag.zero(R.st);
+			launch_group_flag(recs.p, un, flag.p, R.st);
+			R.exscan(flag.p, rank.p, un + 1);
+			uint64_t n_groups = 0;
+			rank.download(&n_groups, 1, R.st, un);
+			HIP_OK(hipStreamSynchronize(R.st));
+			DevBuf<uint64_t> off(n_groups + 1);
+			launch_seed_start(flag.p, rank.p, un, off.p, R.st);
+			HIP_OK(hipMemcpyAsync(off.p + n_groups, &un, sizeof(un), hipMemcpyHostToDevice, R.st));
+			admit_tail(R, recs.p, off.p, n_groups, un, A);
+		}
+		*stats = A.st;
+		if (A.declined) return admit_on_host(sorted, n, A, skip_ids, n_skip, nullptr, recs8, pile_off, seeds, n_piles, stats);
+		const int64_t nr = (int64_t)A.rows.size();
+		A.hand_out(recs8, pile_off, seeds, n_piles);
+		return nr;
+	} catch (...) {
+		return -2;
+	}
+}
+
+extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
+                                        uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq,
+                                        uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                                        const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                                        int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                        ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats)
+{
+	*recs8 = nullptr, *pile_off = nullptr, *seeds = nullptr, *n_piles = 0;
+	if (sorted) *sorted = nullptr;
+	if (n_sorted) *n_sorted = 0;
+	ndgpu_ovl_admit_stats st_local;
+	if (!astats) astats = &st_local;
+	memset(astats, 0, sizeof(*astats));
+	ndgpu_ovl_rec *srt = nullptr;
+	auto drop = [&] { free(srt), free(*bl_id), free(*bl_kind); srt = nullptr, *bl_id = nullptr, *bl_kind = nullptr, *n_bl = 0; };
+	try {
+		Admission A(n_ids, min_len_seed, min_len_aln, max_cov_aln, min_cov_seed);
+		A.use_bl = use_bl != 0;
+		const bool host_only = flags & 1;
+		A.want_sorted = sorted != nullptr || host_only;
+		int64_t ns = sort_impl(files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, bl_id, bl_kind, n_bl, stats,
+		                       hq != 0, host_only ? nullptr : &A, skip_ids, n_skip);
+		if (ns < 0) return ns;
+		*astats = A.st;
+		if (A.declined && !A.want_sorted) {   // the sorted records were left on the device: once more, for the host routine
+			drop();
+			ns = sort_impl(files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, bl_id, bl_kind, n_bl, stats,
+			               hq != 0);
+			if (ns < 0) return ns;
+		}
+		int64_t nr;
+		if (A.declined || host_only) {
+			astats->sorted_records = (uint64_t)ns;
+			const std::vector<uint32_t> bl(*bl_id, *bl_id + *n_bl);
+			nr = admit_on_host(srt, ns, A, skip_ids, n_skip, use_bl ? &bl : nullptr, recs8, pile_off, seeds, n_piles, astats);
+			astats->bytes_downloaded += (uint64_t)ns * sizeof(OvlRec);
+		} else {
+			nr = (int64_t)A.rows.size();
+			A.hand_out(recs8, pile_off, seeds, n_piles);
+		}
+		if (getenv("NDGPU_PROF"))
+			fprintf(stderr, "[ndgpu_ovl_sort_piles] %llu sorted records in %llu groups (%llu declined, %llu wide): %llu rows in %llu piles, K16 %.3f ms, "
+			        "%llu bytes downloaded\n", (unsigned long long)astats->sorted_records, (unsigned long long)astats->groups,
+			        (unsigned long long)astats->groups_declined, (unsigned long long)astats->groups_wide, (unsigned long long)astats->admitted,
+			        (unsigned long long)astats->piles, astats->k16_ms, (unsigned long long)astats->bytes_downloaded);
+		if (sorted) *sorted = srt, srt = nullptr;
+		if (n_sorted) *n_sorted = ns;
+		free(srt);
+		return nr;
+	} catch (...) {
+		drop();
+		return -2;
+	}
 }

@@ -589,4 +589,229 @@ void launch_compact_seed_recs(const uint64_t *seed_start, uint32_t n_seeds, cons
 	if (n_seeds) ND_LAUNCH(compact_seed_recs_kernel, dim3(n_seeds), dim3(64), 0, s, seed_start, n_seeds, out, n_out, off, dense);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K16: pile admission (read_seq_data, lib/nextcorrect.py:92-143) on the dense sorted records, one wavefront per group (a run of
+// records with one seed id in field 0; group g = recs[off[g] .. off[g + 1])).  The reference loop carries state from record to
+// record; on a well-formed stream that state is, per group, one prefix sum:
+//   seed_len = t_e + 1 of the group's first record; the seed is valid iff seed_len >= min_len_seed and it is not in the skip set;
+//   a record is a candidate iff t_e - t_s >= min_len_aln; only the first candidate of a query read counts; `before` = the spans
+//   (t_e - t_s + 1) of the counting records in front of it; it is admitted iff !(before / seed_len > 1.5 * max_cov_aln);
+//   the pile is kept iff total / seed_len >= min_cov_seed.
+// `before` only grows, so the first counting record that fails the depth test ends the group (in the loop nothing is admitted and
+// nothing marked behind it, so "counting" and "admitted" are the same records in front of it).
+// The two comparisons are the host's own: both sums converted to double (round to nearest, as on the host), one IEEE division
+// (correctly rounded in device code built without fast-math), compared with a limit that is exact in a double (1.5 x a 32-bit
+// integer).  Operation for operation ndgpu_assemble_piles's arithmetic, so the verdicts are equal for every total, with no
+// 64-bit product (3 * max_cov_aln * seed_len does not fit 64 bits when both are large) and no bound on the totals to argue.
+// Where the loop's last_seed / '+' state would split a group again -- a valid seed whose first record is not admitted, a rejected seed
+// one of whose later records passes as a seed, t_e < t_s, a query id >= n_ids (the host does not de-duplicate those) -- the group is
+// irregular: lane 0 counts it in counters[0] (one atomic per such group; any non-zero value is the flag) and the host side
+// answers the whole call with ndgpu_assemble_piles.
+// The query reads seen so far are an open-addressing table of 64-bit slots, (query id + 1) << 32 | number of the record in its
+// group, 0 = empty: a slot is claimed with a compare-and-swap and lowered with an atomic minimum, so the first occurrence owns it
+// whatever order lanes and probes run in; a chunk of 64 records inserts, then every lane reads its slot back.  Groups of up to
+// half of kAdmitLdsSlots records (or of the forced capacity, NDGPU_ADMIT_TABLE) keep the table in LDS, larger ones ("wide") in
+// their slice of a global scratch region, pow2ceil(2 x records) slots: never more than half full either way.
+
+constexpr uint32_t kAdmitLdsSlots = 2048;   // 16 KB of LDS: groups of up to 1024 records
+constexpr uint32_t kNoSlot = 0xffffffffu;
+
+__device__ __forceinline__ uint32_t pow2ceil_u32(uint32_t v) { uint32_t p = 2; while (p < v) p <<= 1; return p; }
+
+__global__ void group_flag_kernel(const OvlRec *__restrict__ recs, uint64_t n, uint32_t *__restrict__ flag)
+{
+	uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) flag[i] = i == 0 || recs[i].qname != recs[i - 1].qname;
+}
+
+// skip set as a bitmap over the read ids: ids[i] joins when kind == nullptr (the caller's list) or kind[i] != 0 (a `.bl` verdict)
+__global__ void skip_bits_kernel(const uint32_t *__restrict__ ids, const uint8_t *__restrict__ kind, uint64_t n, uint32_t n_ids,
+                                 uint32_t *__restrict__ bits)
+{
+	uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || (kind && !kind[i])) return;
+	const uint32_t id = ids[i];
+	if (id < n_ids) atomicOr(bits + (id >> 5), 1u << (id & 31));
+}
+
+// slots of the global table of every group that does not fit the LDS one (0: it does); counters[1] = such groups
+__global__ void admit_plan_kernel(const uint64_t *__restrict__ off, uint32_t n_groups, uint32_t lds_slots, uint32_t *__restrict__ slots,
+                                  uint32_t *__restrict__ counters)
+{
+	uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_groups) return;
+	const uint64_t cnt = off[g + 1] - off[g];   // (< 2^30: the host side refuses longer streams)
+	const bool wide = 2 * cnt > lds_slots;
+	slots[g] = wide ? pow2ceil_u32((uint32_t)(2 * cnt)) : 0;
+	if (wide) atomicAdd(counters + 1, 1u);
+}
+
+// the slot that record `idx` of the group holds for query read q, or kNoSlot when an earlier record already holds it
+__device__ __forceinline__ uint32_t seen_insert(unsigned long long *tab, uint32_t mask, uint32_t shift, uint32_t q, uint32_t idx)
+{
+	const unsigned long long mine = ((unsigned long long)q + 1) << 32 | idx;
+	uint32_t h = (q * 2654435761u) >> shift;
+	for (;;) {
+		const unsigned long long old = atomicCAS(tab + h, 0ull, mine);
+		if (old == 0) return h;
+		if ((old >> 32) == (mine >> 32)) return atomicMin(tab + h, mine) < mine ? kNoSlot : h;   // (the value found decides: the atomic has finished)
+		h = (h + 1) & mask;
+	}
+}
+
+__device__ __forceinline__ unsigned long long wave_excl_sum_u64(unsigned long long v, int lane, unsigned long long *total)
+{
+	unsigned long long s = v;
+	for (int d = 1; d < 64; d <<= 1) {
+		const unsigned long long o = __shfl_up(s, d, 64);
+		if (lane >= d) s += o;
+	}
+	*total = __shfl(s, 63, 64);
+	return s - v;
+}
+
+struct AdmitArgs {
+	const OvlRec *recs;
+	const uint64_t *off;
+	const uint32_t *skip_bits;
+	uint32_t n_groups, n_ids, min_len_seed, min_len_aln, max_cov_aln, min_cov_seed;
+	uint8_t *adm;         // per record: admitted (zeroed by the caller)
+	uint32_t *n_adm;      // per group: records of its pile (0: no pile)
+	uint32_t *kept;       // per group: 1 = a pile
+	uint32_t *counters;   // [0] irregular groups
+};
+
+// tab: `slots` zeroed-by-us slots of this group (a power of two >= 2 x its records); global: tab is device memory
+__device__ __forceinline__ void admit_group(const AdmitArgs &A, uint32_t g, unsigned long long *tab, uint32_t slots, bool global)
+{
+	const int lane = threadIdx.x;
+	const uint64_t c0 = A.off[g], c1 = A.off[g + 1];
+	if (c0 == c1) return;   // (a seed the sort left nothing of: n_adm / kept stay 0)
+	const OvlRec first = A.recs[c0];
+	const uint32_t seed = first.qname;
+	const unsigned long long seed_len = (unsigned long long)first.qe + 1;
+	const bool skipped = seed < A.n_ids && (A.skip_bits[seed >> 5] >> (seed & 31) & 1);
+	const bool valid = seed_len >= A.min_len_seed && !skipped;
+	bool irregular = valid && first.qe - first.qs < A.min_len_aln;
+	const uint32_t mask = slots - 1, shift = 32 - (uint32_t)(__ffs((int)slots) - 1);
+	if (valid) {
+		for (uint32_t i = lane; i < slots; i += 64) tab[i] = 0;
+		if (global) __threadfence();   // the zeroes are in place before another lane's atomic finds the slot
+		ND_LOCKSTEP();
+	}
+	const double lim = (double)A.max_cov_aln * 1.5;
+	unsigned long long before = 0;
+	uint32_t n = 0;
+	for (uint64_t base = c0; base < c1; base += 64) {
+		const uint64_t k = base + lane;
+		const bool live = k < c1;
+		OvlRec r = first;
+		if (live) r = A.recs[k];
+		bool bad = live && (r.qe < r.qs || r.tname >= A.n_ids);
+		if (!valid) bad = bad || (live && !skipped && (unsigned long long)r.qe + 1 >= A.min_len_seed);   // the loop would start a pile here
+		if (__ballot(bad)) irregular = true;
+		if (!valid) continue;
+		if (irregular) break;
+		const uint32_t idx = (uint32_t)(k - c0);
+		uint32_t slot = kNoSlot;
+		if (live && r.qe - r.qs >= A.min_len_aln) slot = seen_insert(tab, mask, shift, r.tname, idx);
+		ND_LOCKSTEP();   // every insert of the chunk before any read-back
+		bool counting = false;
+		if (slot != kNoSlot) counting = (uint32_t)__hip_atomic_load(tab + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == idx;
+		const unsigned long long span = counting ? (unsigned long long)(r.qe - r.qs) + 1 : 0;
+		unsigned long long chunk_total;
+		const unsigned long long mine_before = before + wave_excl_sum_u64(span, lane, &chunk_total);
+		const bool admitted = counting && !((double)mine_before / (double)seed_len > lim);
+		const unsigned long long am = __ballot(admitted), fm = __ballot(counting && !admitted);
+		if (admitted) A.adm[k] = 1;
+		n += (uint32_t)__popcll(am);
+		if (fm) {   // the depth limit: nothing behind this record is admitted
+			before = __shfl(mine_before, __ffsll((long long)fm) - 1, 64);
+			break;
+		}
+		before += chunk_total;
+	}
+	if (lane == 0) {
+		const bool keep = valid && !irregular && (double)before / (double)seed_len >= (double)A.min_cov_seed;
+		A.n_adm[g] = keep ? n : 0;
+		A.kept[g] = keep;
+		if (irregular) atomicAdd(A.counters, 1u);
+	}
+}
+
+__global__ void __launch_bounds__(64) admit_count_kernel(AdmitArgs A, uint32_t lds_slots, const uint32_t *__restrict__ wide_slots,
+                                                          const uint64_t *__restrict__ tab_off, unsigned long long *__restrict__ scratch)
+{
+	__shared__ unsigned long long lds_tab[kAdmitLdsSlots];
+	const uint32_t g = blockIdx.x;
+	if (g >= A.n_groups) return;
+	const uint32_t ws = wide_slots[g];
+	if (ws) {
+		admit_group(A, g, scratch + tab_off[g], ws, true);
+	} else {
+		const uint64_t cnt = A.off[g + 1] - A.off[g];   // 2 * cnt <= lds_slots <= kAdmitLdsSlots (admit_plan_kernel)
+		admit_group(A, g, lds_tab, pow2ceil_u32((uint32_t)(2 * cnt)), false);
+	}
+}
+
+// second pass: the admitted records of every kept group as rows (seed, rev, seed start, seed end, read, read start, read end,
+// match) from rec_off[g] on, and the pile's entry
+__global__ void __launch_bounds__(64) admit_emit_kernel(const OvlRec *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n_groups,
+                                                         const uint8_t *__restrict__ adm, const uint32_t *__restrict__ n_adm,
+                                                         const uint32_t *__restrict__ kept, const uint64_t *__restrict__ rec_off,
+                                                         const uint64_t *__restrict__ pile_idx, uint32_t *__restrict__ recs8,
+                                                         uint64_t *__restrict__ pile_off, uint32_t *__restrict__ seeds)
+{
+	const uint32_t g = blockIdx.x;
+	if (g >= n_groups || !kept[g]) return;
+	const int lane = threadIdx.x;
+	const uint64_t c0 = off[g], c1 = off[g + 1], o = rec_off[g];
+	const uint32_t want = n_adm[g];
+	if (lane == 0) pile_off[pile_idx[g]] = o, seeds[pile_idx[g]] = recs[c0].qname;
+	uint32_t done = 0;
+	for (uint64_t base = c0; base < c1 && done < want; base += 64) {
+		const uint64_t k = base + lane;
+		const bool a = k < c1 && adm[k];
+		const unsigned long long m = __ballot(a);
+		if (a) {
+			const OvlRec r = recs[k];
+			uint32_t *row = recs8 + (o + done + (uint32_t)__popcll(m & ((1ull << lane) - 1))) * 8;
+			row[0] = r.qname, row[1] = r.rev, row[2] = r.qs, row[3] = r.qe, row[4] = r.tname, row[5] = r.ts, row[6] = r.te, row[7] = r.match;
+		}
+		done += (uint32_t)__popcll(m);
+	}
+}
+
+void launch_group_flag(const OvlRec *recs, uint64_t n, uint32_t *flag, hipStream_t s)
+{
+	if (n) ND_LAUNCH(group_flag_kernel, GRID1(n), 0, s, recs, n, flag);
+}
+void launch_skip_bits(const uint32_t *ids, const uint8_t *kind, uint64_t n, uint32_t n_ids, uint32_t *bits, hipStream_t s)
+{
+	if (n) ND_LAUNCH(skip_bits_kernel, GRID1(n), 0, s, ids, kind, n, n_ids, bits);
+}
+uint32_t admit_lds_slots() { return kAdmitLdsSlots; }
+void launch_admit_plan(const uint64_t *off, uint32_t n_groups, uint32_t lds_slots, uint32_t *slots, uint32_t *counters, hipStream_t s)
+{
+	if (n_groups) ND_LAUNCH(admit_plan_kernel, GRID1(n_groups), 0, s, off, n_groups, lds_slots, slots, counters);
+}
+void launch_admit_count(const OvlRec *recs, const uint64_t *off, uint32_t n_groups, const uint32_t *skip_bits, uint32_t n_ids,
+                        uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, uint32_t lds_slots,
+                        const uint32_t *wide_slots, const uint64_t *tab_off, uint64_t *scratch, uint8_t *adm, uint32_t *n_adm, uint32_t *kept,
+                        uint32_t *counters, hipStream_t s)
+{
+	AdmitArgs A;
+	A.recs = recs, A.off = off, A.skip_bits = skip_bits, A.n_groups = n_groups, A.n_ids = n_ids, A.min_len_seed = min_len_seed;
+	A.min_len_aln = min_len_aln, A.max_cov_aln = max_cov_aln, A.min_cov_seed = min_cov_seed, A.adm = adm, A.n_adm = n_adm, A.kept = kept;
+	A.counters = counters;
+	if (n_groups) ND_LAUNCH(admit_count_kernel, dim3(n_groups), dim3(64), 0, s, A, lds_slots, wide_slots, tab_off, (unsigned long long*)scratch);
+}
+void launch_admit_emit(const OvlRec *recs, const uint64_t *off, uint32_t n_groups, const uint8_t *adm, const uint32_t *n_adm,
+                       const uint32_t *kept, const uint64_t *rec_off, const uint64_t *pile_idx, uint32_t *recs8, uint64_t *pile_off,
+                       uint32_t *seeds, hipStream_t s)
+{
+	if (n_groups) ND_LAUNCH(admit_emit_kernel, dim3(n_groups), dim3(64), 0, s, recs, off, n_groups, adm, n_adm, kept, rec_off, pile_idx, recs8,
+	                        pile_off, seeds);
+}
+
 } // namespace ndovl

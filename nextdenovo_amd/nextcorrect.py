@@ -187,8 +187,12 @@ def main(args):
     # record; `assemble_piles` above is the line-by-line restatement the tests hold it against
     from nextdenovo_amd import overlap
     n_ids = max(int(lens.size), int(recs[:, [0, 4]].max()) + 1 if recs.size else 0)
-    recs, off, names = overlap.assemble_piles(overlap.from_decoded(recs), n_ids, args.min_len_seed, args.min_len_aln, args.max_cov_aln,
-                                              args.min_cov_seed, sorted(skip))
+    if os.environ.get("NDGPU_ADMIT_DEVICE") == "1":   # the same admission on the device (ndgpu_admit_piles, K16)
+        recs, off, names, _ = overlap.admit_piles(overlap.from_decoded(recs), n_ids, args.min_len_seed, args.min_len_aln, args.max_cov_aln,
+                                                  args.min_cov_seed, sorted(skip))
+    else:
+        recs, off, names = overlap.assemble_piles(overlap.from_decoded(recs), n_ids, args.min_len_seed, args.min_len_aln, args.max_cov_aln,
+                                                  args.min_cov_seed, sorted(skip))
     piles = [(int(names[p]), np.arange(int(off[p]), int(off[p + 1]))) for p in range(names.size)]
 
     fail_seed = correct_and_write(db, recs, piles, args, OUT, IDX)

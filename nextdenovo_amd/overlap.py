@@ -371,13 +371,51 @@ def assemble_piles(srt: np.ndarray, n_ids: int, min_len_seed: int, min_len_aln: 
         lib.ndgpu_assemble_piles.restype = C.c_int64
         lib.ndgpu_assemble_piles._bound = True
     srt = np.ascontiguousarray(srt, dtype=REC)
-    sk = np.ascontiguousarray(np.fromiter(skip, dtype=np.uint32, count=len(skip)) if len(skip) else np.zeros(0, dtype=np.uint32))
+    sk = _skip_array(skip)
     r8, off, seeds = C.c_void_p(), C.c_void_p(), C.c_void_p()
     npiles = C.c_int64(0)
     n = lib.ndgpu_assemble_piles(_ptr(srt), srt.size, int(n_ids), int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed),
                                  _ptr(sk), sk.size, C.byref(r8), C.byref(off), C.byref(seeds), C.byref(npiles))
     recs = _take(lib, r8, n * 8, np.uint32).reshape(-1, 8)
     return recs, _take(lib, off, npiles.value + 1, np.uint64), _take(lib, seeds, npiles.value, np.uint32)
+
+
+class AdmitStats(C.Structure):
+    _fields_ = [("k16_ms", C.c_double)] + [(n, C.c_uint64) for n in ("sorted_records", "groups", "groups_declined", "groups_wide", "admitted",
+                                                                    "piles", "bytes_downloaded")]
+
+
+def _skip_array(skip) -> np.ndarray:
+    return np.ascontiguousarray(np.fromiter(skip, dtype=np.uint32, count=len(skip)) if len(skip) else np.zeros(0, dtype=np.uint32))
+
+
+def admit_piles(srt: np.ndarray, n_ids: int, min_len_seed: int, min_len_aln: int = 500, max_cov_aln: int = 130, min_cov_seed: int = 10,
+                skip=(), flags: int = 0):
+    """assemble_piles on the device (ndgpu_admit_piles: the records are uploaded, K16 admits them, only the admitted rows come back).
+    flags bit 0: the host routine instead.  Returns (recs uint32[n,8], pile_off uint64[p+1], seeds uint32[p], stats dict);
+    stats["groups_declined"] > 0: a group the device form does not cover was found and the host routine answered."""
+    lib = load()
+    if not hasattr(lib.ndgpu_admit_piles, "_bound"):
+        P = C.c_void_p
+        lib.ndgpu_admit_piles.argtypes = [P, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_int64, C.c_int32,
+                                          C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int64), C.POINTER(AdmitStats)]
+        lib.ndgpu_admit_piles.restype = C.c_int64
+        lib.ndgpu_admit_piles._bound = True
+    srt = np.ascontiguousarray(srt, dtype=REC)
+    sk = _skip_array(skip)
+    r8, off, seeds = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    npiles = C.c_int64(0)
+    st = AdmitStats()
+    n = lib.ndgpu_admit_piles(_ptr(srt), srt.size, int(n_ids), int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed),
+                              _ptr(sk), sk.size, int(flags), C.byref(r8), C.byref(off), C.byref(seeds), C.byref(npiles), C.byref(st))
+    if n == -2:
+        raise _fail(lib, "ndgpu_admit_piles failed")
+    if n < 0:
+        raise RuntimeError({-1: "ndgpu_admit_piles: no usable HIP device", -3: "ndgpu_admit_piles: more than 2^30 records in one call"}
+                           .get(int(n), "ndgpu_admit_piles failed (%d)" % n))
+    recs = _take(lib, r8, n * 8, np.uint32).reshape(-1, 8)
+    return (recs, _take(lib, off, npiles.value + 1, np.uint64), _take(lib, seeds, npiles.value, np.uint32),
+            {n_: getattr(st, n_) for n_, _ in AdmitStats._fields_})
 
 
 def pack_2bit(ascii_buf: np.ndarray, ascii_off: np.ndarray, lens: np.ndarray):
@@ -501,3 +539,45 @@ def sort_overlaps(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: i
               file=sys.stderr)
     return recs, bl, {n_: getattr(st, n_) for n_, _ in SortStats._fields_}
 
+
+
+def sort_piles(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int = 40, max_flank_len: int = 300, hq: bool = False,
+               min_len_seed: int = 0, min_len_aln: int = 500, max_cov_aln: int = 130, min_cov_seed: int = 10, use_bl: bool = True, skip=(),
+               flags: int = 0, want_sorted: bool = False):
+    """sort_overlaps followed by assemble_piles in one call (ndgpu_ovl_sort_piles): the sorted records are admitted on the device
+    (K16) and only the piles come back.  The skip set is `skip` plus, with use_bl, the seeds of this sort's `.bl` verdicts; n_ids =
+    seed_len.size.  Returns (recs uint32[n,8], pile_off, seeds, bl list, sorted records or None, {"sort": ..., "admit": ...})."""
+    lib = load()
+    if not hasattr(lib.ndgpu_ovl_sort_piles, "_bound"):
+        P, PP, u32 = C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32
+        lib.ndgpu_ovl_sort_piles.argtypes = [PP, C.POINTER(C.c_int64), C.c_int32, P, u32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             u32, u32, u32, u32, C.c_int32, P, C.c_int64, C.c_int32, PP, PP, C.POINTER(C.c_int64), PP, PP, PP,
+                                             C.POINTER(C.c_int64), PP, C.POINTER(C.c_int64), C.POINTER(SortStats), C.POINTER(AdmitStats)]
+        lib.ndgpu_ovl_sort_piles.restype = C.c_int64
+        lib.ndgpu_ovl_sort_piles._bound = True
+    files = [np.ascontiguousarray(f, dtype=REC) for f in files]
+    nf = len(files)
+    ptrs = (C.c_void_p * max(1, nf))(*[f.ctypes.data for f in files])
+    cnts = (C.c_int64 * max(1, nf))(*[f.size for f in files])
+    seed_len = np.ascontiguousarray(seed_len, dtype=np.uint32)
+    sk = _skip_array(skip)
+    bid, bkind, r8, off, seeds, srt = (C.c_void_p() for _ in range(6))
+    nbl, npiles, nsrt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    st, ast = SortStats(), AdmitStats()
+    n = lib.ndgpu_ovl_sort_piles(ptrs, cnts, nf, _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len), int(bool(hq)),
+                                 int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed), int(bool(use_bl)), _ptr(sk), sk.size,
+                                 int(flags), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(r8), C.byref(off), C.byref(seeds),
+                                 C.byref(npiles), C.byref(srt) if want_sorted else None, C.byref(nsrt), C.byref(st), C.byref(ast))
+    if n == -2:
+        raise _fail(lib, "ndgpu_ovl_sort_piles failed (about 150 bytes of device memory per candidate overlap are needed; use more seed "
+                         "files: seed_cutfiles)")
+    if n < 0:
+        raise RuntimeError({-1: "ndgpu_ovl_sort_piles: no usable HIP device", -3: "ndgpu_ovl_sort_piles: more than 2^31 candidate overlaps in "
+                            "one call (use more seed files: seed_cutfiles)"}.get(int(n), "ndgpu_ovl_sort_piles failed (%d)" % n))
+    recs = _take(lib, r8, n * 8, np.uint32).reshape(-1, 8)
+    ids = _take(lib, bid, nbl.value, np.uint32)
+    kinds = _take(lib, bkind, nbl.value, np.uint8)
+    bl = list(zip(ids.tolist(), [chr(k) for k in kinds.tolist()]))
+    sorted_recs = _take(lib, srt, nsrt.value, REC) if want_sorted else None
+    return (recs, _take(lib, off, npiles.value + 1, np.uint64), _take(lib, seeds, npiles.value, np.uint32), bl, sorted_recs,
+            {"sort": {n_: getattr(st, n_) for n_, _ in SortStats._fields_}, "admit": {n_: getattr(ast, n_) for n_, _ in AdmitStats._fields_}})

@@ -56,6 +56,13 @@ class DeviceBackend:
     def sort(self, files, seed_len, min_seed_len, k, flank):
         return overlap.sort_overlaps(files, seed_len, min_seed_len, k, flank)
 
+    def sort_piles(self, files, seed_len, min_seed_len, k, flank, min_len_seed, min_len_aln, max_cov_aln, min_cov_seed, use_bl):
+        """The sort with the pile admission as its tail on the device (ndgpu_ovl_sort_piles): (rows, pile_off, seeds, bl, stats)."""
+        sub, off, seeds, bl, _srt, st = overlap.sort_piles(files, seed_len, min_seed_len, k, flank, min_len_seed=min_len_seed,
+                                                           min_len_aln=min_len_aln, max_cov_aln=max_cov_aln, min_cov_seed=min_cov_seed,
+                                                           use_bl=use_bl)
+        return sub, off, seeds, bl, st
+
 
 def deal(lens: np.ndarray, read_cutoff: int, seed_cutoff: int, n_seed_files: int, block_size: int = 0):
     """Read ids (dense, in input order over the reads >= read_cutoff) of every seed file and part file, as seq_dump
@@ -499,13 +506,22 @@ class Shard:
         seed_len = np.zeros(self.lens.size, dtype=np.uint32)
         sid = self.seed_ids[i]
         seed_len[sid] = self.lens[sid]
-        srt, bl, sst = self.backend.sort(files, seed_len, int(self.lens[sid].min()) if sid.size else 0, self.sort_k, self.flank)
-        t1 = time.perf_counter()
-        skip = [rid for rid, _ in bl] if self.blacklist else []
-        sub, off, seeds = overlap.assemble_piles(srt, int(self.lens.size), self.min_len_seed, self.min_len_aln, self.max_cov_aln,
-                                                 self.min_cov_seed, skip)
+        if os.environ.get("NDGPU_ADMIT_DEVICE") == "1" and hasattr(self.backend, "sort_piles"):
+            # the admission as the sort's tail on the device (K16): the sorted records never reach the host.  sort_s is the fused call;
+            # assemble_s holds only what is left on the host -- nothing
+            sub, off, seeds, bl, fst = self.backend.sort_piles(files, seed_len, int(self.lens[sid].min()) if sid.size else 0, self.sort_k,
+                                                               self.flank, self.min_len_seed, self.min_len_aln, self.max_cov_aln,
+                                                               self.min_cov_seed, bool(self.blacklist))
+            t1 = time.perf_counter()
+            sst, self.admit_stats = fst["sort"], fst["admit"]
+        else:
+            srt, bl, sst = self.backend.sort(files, seed_len, int(self.lens[sid].min()) if sid.size else 0, self.sort_k, self.flank)
+            t1 = time.perf_counter()
+            skip = [rid for rid, _ in bl] if self.blacklist else []
+            sub, off, seeds = overlap.assemble_piles(srt, int(self.lens.size), self.min_len_seed, self.min_len_aln, self.max_cov_aln,
+                                                     self.min_cov_seed, skip)
         self.stats["sort_s"] += t1 - t0
-        self.stats["assemble_s"] += time.perf_counter() - t1
+        self.stats["assemble_s"] += time.perf_counter() - t1   # the host's part of the pile admission (none of it with NDGPU_ADMIT_DEVICE=1)
         self.sort_stats = sst
         if isinstance(self.backend, DeviceBackend):
             # the consensus contexts size their (grow-only) buffers from what is free when they are called: leave the overlap stage
