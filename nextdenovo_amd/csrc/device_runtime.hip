@@ -26,6 +26,7 @@
 
 #include "nd_device.h"
 #include "nd_host.h"
+#include "nd_lqplan.h"
 #include "nd_runtime.h"
 
 namespace ndgpu {
@@ -57,15 +58,19 @@ static const bool g_debug_launch = getenv("NDGPU_DEBUG_LAUNCH") != nullptr;  // 
 static std::mutex g_dbg_mu;  // NDGPU_DEBUG_LAUNCH=2: one device phase at a time over all contexts
 static const bool g_debug_exclusive = getenv("NDGPU_DEBUG_LAUNCH") && atoi(getenv("NDGPU_DEBUG_LAUNCH")) >= 2;
 static const bool g_debug_nofree = getenv("NDGPU_DEBUG_NOFREE") != nullptr;  // triage: outgrown buffers are leaked, not freed
+// NDGPU_TRACE, read once per process: the "[ndgpu trace]" lines and run_extract's summary
+static bool trace_on() { static const bool on = getenv("NDGPU_TRACE") != nullptr; return on; }
+static uint64_t env_u64(const char *name, uint64_t unset) { return getenv(name) ? strtoull(getenv(name), nullptr, 10) : unset; }
+static bool env_is(const char *name, const char *value) { return getenv(name) && !strcmp(getenv(name), value); }
 
 // Test hook: NDGPU_OOM_ABOVE=bytes makes every device allocation larger than that fail as if the memory were exhausted.
 static inline bool oom_injected(size_t bytes) {
-    static const size_t lim = getenv("NDGPU_OOM_ABOVE") ? (size_t)strtoull(getenv("NDGPU_OOM_ABOVE"), nullptr, 10) : 0;
+    static const size_t lim = (size_t)env_u64("NDGPU_OOM_ABOVE", 0);
     return lim && bytes > lim;
 }
 // The same for the pinned host arenas: NDGPU_PINNED_OOM_ABOVE=bytes.
 static inline bool oom_injected_pinned(size_t bytes) {
-    static const size_t lim = getenv("NDGPU_PINNED_OOM_ABOVE") ? (size_t)strtoull(getenv("NDGPU_PINNED_OOM_ABOVE"), nullptr, 10) : 0;
+    static const size_t lim = (size_t)env_u64("NDGPU_PINNED_OOM_ABOVE", 0);
     return lim && bytes > lim;
 }
 
@@ -169,16 +174,7 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
-    void level() {  // (while the device is idle) up to what any context has asked of the buffer of this name
-        const size_t want = high_water(name) / sizeof(T);
-        if (want > cap) reserve(want);
-    }
-    ~DevBuf() {
-        if (p) {
-            (void)hipFree(p);
-            g_dev_bytes -= (long long)(cap * sizeof(T));
-        }
-    }
+    ~DevBuf() { release(); }
 };
 
 template <typename T>
@@ -216,13 +212,7 @@ struct PinBuf {
         p = nullptr;
         cap = 0;
     }
-    void level() {
-        const size_t want = high_water(name) / sizeof(T);
-        if (want > cap) reserve(want);
-    }
-    ~PinBuf() {
-        if (p) (void)hipHostFree(p);
-    }
+    ~PinBuf() { release(); }
 };
 
 struct CodeLut {
@@ -237,16 +227,12 @@ struct CodeLut {
 };
 const CodeLut kCode;
 
-// ASCII [ACGT]* -> 2-bit, LSB-first, appended at a word boundary.  Returns false on
-// any other byte (the reference compares raw bytes; we only accept what lib/bseq.c
-// can emit from a .2bit DB).
-bool pack_append(std::vector<uint32_t> &pool, const char *s, size_t n) {
-    const size_t w0 = pool.size();
-    pool.resize(w0 + (n + 15) / 16);
-    uint32_t *out = pool.data() + w0;
-    size_t i = 0;
+// ASCII [ACGT]* -> 2-bit, LSB-first, into a preallocated word range.  Returns false on any other byte (the reference compares raw
+// bytes; we only accept what lib/bseq.c can emit from a .2bit DB).
+bool pack_into(uint32_t *out, const char *s, size_t n) {
     unsigned bad = 0;
-    for (size_t w = 0; i + 16 <= n; w++, i += 16) {
+    size_t i = 0, w = 0;
+    for (; i + 16 <= n; w++, i += 16) {
         uint32_t acc = 0;
         for (int b = 0; b < 16; b++) {
             const uint8_t c = kCode.v[(unsigned char)s[i + b]];
@@ -262,9 +248,15 @@ bool pack_append(std::vector<uint32_t> &pool, const char *s, size_t n) {
             bad |= c;
             acc |= (uint32_t)(c & 3u) << (2 * b);
         }
-        out[(n + 15) / 16 - 1] = acc;
+        out[w] = acc;
     }
     return (bad & 0x80u) == 0;
+}
+// The same, appended to a pool at a word boundary.
+bool pack_append(std::vector<uint32_t> &pool, const char *s, size_t n) {
+    const size_t w0 = pool.size();
+    pool.resize(w0 + (n + 15) / 16);
+    return pack_into(pool.data() + w0, s, n);
 }
 
 // Every grow-only buffer of a context, once: X(element type, member, device | pinned, levelled | on_demand).  The members of State, their
@@ -389,8 +381,46 @@ struct MsaResult {  // count_and_score: the last attempt's error words, its pile
     std::vector<PileDev> piles;
 };
 
+struct LqSrc {  // a sequence of an LQ call's pool: packed already (words), or ASCII
+    const uint32_t *words;
+    const char *ascii;
+    uint32_t len;
+    uint64_t word_off;
+};
+struct LqLayout {  // layout_lq: per round its device record and whether K12 takes it; the pieces, jobs and sequences of all rounds; the totals
+    std::vector<LqPileDev> piles;
+    std::vector<uint8_t> usable;
+    std::vector<LqPieceDev> pieces;
+    std::vector<LqJobDev> jobs;
+    std::vector<LqSrc> srcs;
+    uint64_t pool_words = 0, ops_words = 0, cell_rows = 0, out_bytes = 0, hdr_words = 0, lnk_words = 0;
+};
+struct PoaProb {
+    PoaGraph g;
+    PoaRows rows;
+    bool live = false;   // still on the device path
+    uint64_t cells = 0;  // of the round in progress
+    uint32_t job = 0;    // its job of the launch in progress
+};
+struct PoaBatch {  // run_poa: the problems, and the launch in progress -- its five staged tables, what it sizes, what comes back
+    std::vector<PoaProb> probs;
+    std::vector<PoaJobDev> jobs;
+    std::vector<PoaRowDev> rows;
+    std::vector<uint16_t> preds;
+    std::vector<char> qpool;
+    std::vector<uint32_t> ids, routes;  // ids: the wave form's jobs [0, n_wave), then the workgroup form's
+    size_t n_wave = 0;
+    uint64_t cells = 0, route_words = 0;
+    explicit PoaBatch(size_t n) : probs(n) {}
+};
+
 }  // namespace
 
+static inline double ms_between(hipEvent_t a, hipEvent_t b) {  // HIP-event time from a to b (both reached)
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
 
 struct DeviceAligner::State {
     int device = 0;
@@ -450,12 +480,23 @@ struct DeviceAligner::State {
     } batch_mu;
     std::vector<ReadDev> reads;  // main-phase state (alive from run_main to end_batch)
     std::vector<PileDev> piles;
-    hipEvent_t evs[8] = {nullptr};
-    std::vector<hipEvent_t> lq_evs;  // run_lq: K7 / K8a brackets per chunk
+    // The context's timing events, each named by the one step that records it; read with ms() behind a synchronisation.
+    enum Ev {
+        kEvFrontK7, kEvFrontK8a,                                 // chunk_front: before K7 | between K7 and K8a
+        kEvMainK7, kEvMainK8a, kEvMainAligned,                   // align_main, chunk by chunk: before K7 | K8a | behind it
+        kEvTagsBegin, kEvTagsEnd,                                // launch_tags: around its four launches
+        kEvLinksBegin, kEvScoreBegin, kEvWalkBegin, kEvWalkEnd,  // count_and_score, score_pass: before K9 | K10 | the walk | behind it
+        kEvLqMsaBegin, kEvLqMsaEnd,                              // launch_lq: around K12 (its K7 / K8a: lq_evs)
+        kEvTailBegin, kEvTailEnd, kEvExtractRanked,  // K11, K13, K14, K15: around the launch in flight | behind K14 where it follows K11
+        kEvCount
+    };
+    hipEvent_t evs[kEvCount] = {nullptr};
+    std::vector<hipEvent_t> lq_evs;  // launch_lq: K7 / K8a brackets per chunk (a chunk count is not bounded)
+    void mark(Ev e, hipStream_t st) { HIP_CHECK(hipEventRecord(evs[e], st)); }
+    double ms(Ev a, Ev b) const { return ms_between(evs[a], evs[b]); }
     std::vector<uint32_t> pool;
     std::vector<AlnTask> tasks;
     RuntimeStats stats;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t trace_budget_bytes = (size_t)48 << 30;
     int host_threads = 1;
     uint64_t k9_retries = 0;
@@ -539,6 +580,25 @@ struct DeviceAligner::State {
     void rescue_pass(const MsaPlan &plan, const K10Args &k10);
     void k9_digest_trace(const K9Args &k9, size_t np);
     void tally_main(const MsaPlan &plan, const std::vector<uint8_t> &bad_pile, MainPile **mp, const uint64_t tp[5]);
+
+    // The steps of run_lq, run_poa and run_extract, in their order (defined above each)
+    LqLayout layout_lq(LqRound **rounds, size_t n);
+    void layout_lq_round(LqRound &R, size_t r, LqLayout &L);
+    bool pack_lq_pool(const LqLayout &L);
+    std::vector<AlignChunk> reserve_lq(const LqLayout &L);
+    std::vector<char> launch_lq(LqLayout &L, const std::vector<AlignChunk> &chunks);
+    void tally_lq(LqRound **rounds, const LqLayout &L, size_t n_chunks, const std::vector<char> &out);
+    void grow_lq_evs(size_t n) { for (hipEvent_t e; lq_evs.size() < n; lq_evs.push_back(e)) HIP_CHECK(hipEventCreate(&e)); }
+    size_t admit_poa(PoaReq **reqs, size_t n, uint64_t budget, PoaBatch &B);
+    void export_rows(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &ids, size_t r, std::vector<PoaLoad> &load);
+    void stage_poa_slice(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r);
+    void launch_poa_slice(PoaBatch &B, size_t r);
+    void thread_routes(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r);
+    template <typename F>
+    void poa_each(const std::vector<size_t> &ids, F f) {  // f(problem) over the context's host threads
+        host_each(ids.size(), ids.size() < 8 || host_threads <= 1, host_threads, ids.size() / 4, true, [&](size_t k) { f(ids[k]); });
+    }
+    unsigned extract_into_pool(std::vector<RegionDev> &regs, bool rank, std::vector<char> &hstr);
 };
 
 static int g_ctx_creating = -1;  // index of the context under construction (guarded by g_ctx_mu)
@@ -598,8 +658,6 @@ DeviceAligner::DeviceAligner() : s_(new State) {
     NDGPU_BUFFERS(NDGPU_NAME)
 #undef NDGPU_NAME
     const unsigned ev_flags = getenv("NDGPU_SPIN_SYNC") ? hipEventDefault : hipEventBlockingSync;  // (hipEventSynchronize sleeps, see above)
-    HIP_CHECK(hipEventCreateWithFlags(&s_->ev0, ev_flags));
-    HIP_CHECK(hipEventCreateWithFlags(&s_->ev1, ev_flags));
     for (auto &e : s_->evs) HIP_CHECK(hipEventCreateWithFlags(&e, ev_flags));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > ((size_t)8 << 30))
@@ -733,7 +791,7 @@ void DeviceAligner::level_buffers(int drivers) {
                 if (growth > budget) return;
                 budget -= growth;
             }
-            buf.level();
+            buf.reserve(want);  // (while the device is idle: up to what any context has asked of the buffer of this name)
         };
         try {
 #define NDGPU_LVL(T, x, place, level) \
@@ -775,7 +833,7 @@ void DeviceAligner::plan_memory(int drivers, uint64_t *tag_budget) {
     const long long cols = (per_ctx - (long long)trace - ((long long)1 << 30)) / 40;
     *tag_budget = (uint64_t)std::min<long long>(900000000ll, std::max<long long>(20000000ll, cols));
     for (int i = 0; i < drivers && i < kMaxContexts; i++) context(i).s_->trace_budget_bytes = trace;
-    if (getenv("NDGPU_TRACE"))
+    if (trace_on())
         fprintf(stderr, "[ndgpu trace] memory plan: %.1f GB free + %.1f GB held by the contexts -> %d contexts x (%.1f GB trace + %llu M columns)\n",
                 free_b / 1073741824.0, held / 1073741824.0, drivers, trace / 1073741824.0, (unsigned long long)(*tag_budget / 1000000));
 }
@@ -790,11 +848,6 @@ static inline uint64_t wall_ns() {
         .count();
 }
 
-static inline double ms_between(hipEvent_t a, hipEvent_t b) {  // HIP-event time from a to b (both reached)
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-    return ms;
-}
 
 static void limits_for(int total, int hq, int *max_d, int *band) {
     // lib/align.c:567-568,575-576 -- double arithmetic on the host, exactly as the reference
@@ -806,6 +859,10 @@ static void limits_for(int total, int hq, int *max_d, int *band) {
         *band = (int)((total > 5000 ? 0.1 : 1) * total);
     }
 }
+
+// Test hooks and A/B knobs, a struct per phase, each read once per process at the first call of its phase.
+template <typename H>
+static const H &hooks_of() { static const H h; return h; }
 
 // ---- the traceback in segments (ond_kernels.hip: tb_chase / tb_walk / tb_stitch) ----
 // NDGPU_K8_SEG = rows per walker (a power of two; 0: the one-lane kernel everywhere), NDGPU_K8_WARM = rows a walker walks before the rows
@@ -828,12 +885,7 @@ struct TbConfig {
         if (const char *e = getenv("NDGPU_K8_MINLEN")) minlen = (uint32_t)atoll(e);
     }
 };
-static const TbConfig &tb_config() {
-    static const TbConfig c;
-    return c;
-}
-// Test hooks and A/B knobs of the main phase (run_main), read once per process at its first call.
-struct MainHooks {
+struct MainHooks {  // the main phase (run_main)
     uint32_t k10_seg_len = 1024;    // NDGPU_K10_SEG: columns of a K10 segment (the last one of a pile takes the remainder)
     uint32_t k10_warm = 128;        // NDGPU_K10_WARM: warm-up columns of a speculative segment (< seg_len)
     int32_t k10_guard = 1 << 30;    // NDGPU_K10_GUARD: raw scores beyond it send the pile to the int64 kernel
@@ -859,20 +911,39 @@ struct MainHooks {
         if (k10_warm >= k10_seg_len) k10_warm = k10_seg_len - 1;
     }
 };
-static const MainHooks &main_hooks() {
-    static const MainHooks h;
-    return h;
-}
-static inline uint32_t tb_ck_slots(int max_d) { return max_d > 0 ? (uint32_t)(max_d - 1) >> tb_config().cshift : 0u; }
+struct LqHooks {
+    // NDGPU_K12_MAX_COLUMNS: a pile whose linked pseudo-seed is longer is left to the host path.  (12,000 until round 4, when K12b was one
+    // wavefront per pile; scored job by job the chain is as long as a job, and the bound is what the packed records can address.)
+    uint64_t max_cols = env_u64("NDGPU_K12_MAX_COLUMNS", 400000);
+    // NDGPU_K12_JOB_COLUMNS: columns of a K12a job (a pile of 3,000 columns is ~15 wavefronts' worth of link building; 1 = every region a job)
+    uint64_t job_cols = env_u64("NDGPU_K12_JOB_COLUMNS", 192);
+    // NDGPU_K12_WARM: columns a K12b job starts before its own first one (speculative start, checked by the stitch)
+    uint32_t warm = (uint32_t)std::max(1, getenv("NDGPU_K12_WARM") ? atoi(getenv("NDGPU_K12_WARM")) : 64);
+    // NDGPU_K12_FORCE=repair: every second job is scored again by the stitch kernel as if its boundary check had failed
+    uint32_t force_repair = env_is("NDGPU_K12_FORCE", "repair") ? 2u : 0u;
+};
+struct PoaHooks {
+    bool budget_set = getenv("NDGPU_POA_BUDGET") != nullptr;  // NDGPU_POA_BUDGET: the cell budget of a launch, in place of a sixth
+    uint64_t budget = env_u64("NDGPU_POA_BUDGET", 0);         // of the trace budget's bytes (0: every problem is declined)
+    int form = env_is("NDGPU_POA_FORM", "wave") ? 1 : env_is("NDGPU_POA_FORM", "group") ? 2 : 0;  // the kernel form every job takes
+    uint32_t group_min = (uint32_t)env_u64("NDGPU_POA_GROUP_MIN", kPoaGroupMinLen);  // the query length the workgroup form takes over from
+};
+struct ExtractHooks {
+    // NDGPU_EXTRACT_POOL=bytes: the first guess of K11's string pool (extract_into_pool) -- a small one makes the first call of a
+    // process retake the pool, a path no fixture reaches otherwise
+    bool pool_set = getenv("NDGPU_EXTRACT_POOL") != nullptr;
+    size_t pool = (size_t)env_u64("NDGPU_EXTRACT_POOL", 0);
+};
+static inline uint32_t tb_ck_slots(int max_d) { return max_d > 0 ? (uint32_t)(max_d - 1) >> hooks_of<TbConfig>().cshift : 0u; }
 // device bytes a task adds to its launch when the launch is walked in segments
 static inline uint64_t tb_bytes(int max_d) {
-    if (!tb_config().on) return 0;
+    if (!hooks_of<TbConfig>().on) return 0;
     const uint64_t k = tb_ck_slots(max_d);
     return k * (kCkptCells * sizeof(uint32_t) + sizeof(uint2)) + (k + 1) * (sizeof(TbSeg) + sizeof(TbSegOut));
 }
 // tasks [a, b) of one launch: their checkpoint / walker slots (AlnTask::mink_off, seg_off); false: the launch keeps the one-lane kernel
 static bool tb_assign(AlnTask *tasks, size_t a, size_t b, uint64_t *ck_slots, uint64_t *seg_slots) {
-    const TbConfig &c = tb_config();
+    const TbConfig &c = hooks_of<TbConfig>();
     *ck_slots = *seg_slots = 0;
     if (!c.on) return false;
     uint32_t longest = 0;
@@ -952,7 +1023,7 @@ void DeviceAligner::State::launch_chunk(const AlignChunk &c, const int32_t *orde
     const AlnTask *tk = d_tasks.p + c.begin;
     AlnOut *out = d_outs.p + c.begin;
     const int n = (int)(c.end - c.begin);
-    const TbArgs tb{d_ck_cells.p, d_ck_hdr.p, d_tbseg.p, d_tbout.p, (int)c.slots, tb_config().cshift, tb_config().warm};
+    const TbArgs tb{d_ck_cells.p, d_ck_hdr.p, d_tbseg.p, d_tbout.p, (int)c.slots, hooks_of<TbConfig>().cshift, hooks_of<TbConfig>().warm};
     if (c.seg) launch_ond_forward_ckpt(tk, out, d_pool.p, db_pool, d_trace.p, d_ops.p, tb, n, stream, order);
     else launch_ond_forward(tk, out, d_pool.p, db_pool, d_trace.p, n, stream, order);
     HIP_CHECK(hipEventRecord(ev_mid, stream));
@@ -971,7 +1042,7 @@ void DeviceAligner::State::tally_outs(size_t nt, std::vector<int32_t> *wide) {
         stats.trace_words += (uint64_t)o.trace_end;
         if (o.fin_idx & kTbSeen) {
             stats.tb_tasks++;
-            stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> tb_config().cshift : 0) + 1;
+            stats.tb_walkers += (uint64_t)(o.d_final > 0 ? (o.d_final - 1) >> hooks_of<TbConfig>().cshift : 0) + 1;
             if (o.fin_idx & kTbRefused) stats.tb_fallbacks++;
         }
         if ((uint32_t)o.max_band > stats.max_band) stats.max_band = (uint32_t)o.max_band;
@@ -1028,30 +1099,6 @@ void par_ranges(size_t n, int base_threads, F f) {  // f(begin, end) over contig
     host_ranges(n, base_threads <= 1 || n < 4096, base_threads, (n + 2047) / 2048, f);
 }
 
-// ASCII -> 2-bit into a preallocated word range (same coding as pack_append)
-bool pack_into(uint32_t *out, const char *s, size_t n) {
-    unsigned bad = 0;
-    size_t i = 0, w = 0;
-    for (; i + 16 <= n; w++, i += 16) {
-        uint32_t acc = 0;
-        for (int b = 0; b < 16; b++) {
-            const uint8_t c = kCode.v[(unsigned char)s[i + b]];
-            bad |= c;
-            acc |= (uint32_t)(c & 3u) << (2 * b);
-        }
-        out[w] = acc;
-    }
-    if (i < n) {
-        uint32_t acc = 0;
-        for (int b = 0; i + b < n; b++) {
-            const uint8_t c = kCode.v[(unsigned char)s[i + b]];
-            bad |= c;
-            acc |= (uint32_t)(c & 3u) << (2 * b);
-        }
-        out[w] = acc;
-    }
-    return (bad & 0x80u) == 0;
-}
 }  // namespace
 
 void DeviceAligner::set_host_threads(int n) { s_->host_threads = n < 1 ? 1 : n; }
@@ -1119,15 +1166,15 @@ uint64_t DeviceAligner::chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t
     const uint64_t tc1 = wall_ns();
     S.h2d(S.d_pool.p, pool.data(), pool.size() * sizeof(uint32_t), st);
     S.h2d(S.d_tasks.p, tasks.data(), n * sizeof(AlnTask), st);
-    HIP_CHECK(hipEventRecord(S.ev0, st));
+    S.mark(State::kEvFrontK7, st);
     NDGPU_DBG(st, "chunk: forward %zu tasks", n);
-    S.launch_chunk(chunks[0], nullptr, nullptr, S.ev1, nullptr, "chunk");
+    S.launch_chunk(chunks[0], nullptr, nullptr, S.evs[State::kEvFrontK8a], nullptr, "chunk");
     NDGPU_DBG(st, "chunk: done");
     HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, n * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
     if (ops_to_host) HIP_CHECK(hipMemcpyAsync(S.h_ops.p, S.d_ops.p, ops_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     S.sync_drain(st);
     HIP_CHECK(hipGetLastError());
-    S.stats.forward_ms += ms_between(S.ev0, S.ev1);  // (this path brackets K7 alone: its K8a is in neither traceback_ms nor traceback_launches)
+    S.stats.forward_ms += S.ms(State::kEvFrontK7, State::kEvFrontK8a);  // (this path brackets K7 alone: its K8a is in neither traceback_ms nor traceback_launches)
     S.stats.forward_launches++;
     S.stats.tasks += n;
 
@@ -1149,6 +1196,12 @@ uint64_t DeviceAligner::chunk_front(AlnJob **jobs, size_t n, std::vector<uint8_t
     return ops_words;
 }
 
+// Columns [first_col, first_col + n) of a task's 2-bit column kinds, a byte a column.
+static void unpack_cols(const uint32_t *W, uint32_t first_col, uint32_t n, std::vector<uint8_t> &out) {
+    out.resize(n);
+    for (uint32_t c = 0, cc = first_col; c < n; c++, cc++) out[c] = (uint8_t)((W[cc >> 4] >> ((cc & 15u) * 2u)) & 3u);
+}
+
 // The tail of run_align, the LQ host path and align(): the column kinds come down with the records and are unpacked, a byte a column.
 void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
     State &S = *s_;
@@ -1168,24 +1221,12 @@ void DeviceAligner::run_chunk(AlnJob **jobs, size_t n) {
                 j.status = ALN_OK;
                 j.q_used = o.x_final;
                 j.t_used = o.y_final;
-                const uint32_t nc = (uint32_t)o.n_cols, c0 = t.ops_cap - nc;
-                const uint32_t *W = S.h_ops.p + t.ops_off;
-                j.ops.resize(nc);
-                for (uint32_t c = 0; c < nc; c++) {
-                    const uint32_t cc = c0 + c;
-                    j.ops[c] = (uint8_t)((W[cc >> 4] >> ((cc & 15u) * 2u)) & 3u);
-                }
+                unpack_cols(S.h_ops.p + t.ops_off, t.ops_cap - (uint32_t)o.n_cols, (uint32_t)o.n_cols, j.ops);
             } else if (o.status == ST_GAP_ABORT) {
                 j.status = ALN_GAP_ABORT;
                 j.q_used = o.x_final;
                 j.t_used = o.y_final;
-                // the reference reports aln_len = 2: keep the last two alignment columns
-                const uint32_t *W = S.h_ops.p + t.ops_off;
-                j.ops.resize(2);
-                for (uint32_t c = 0; c < 2; c++) {
-                    const uint32_t cc = t.ops_cap - 2 + c;
-                    j.ops[c] = (uint8_t)((W[cc >> 4] >> ((cc & 15u) * 2u)) & 3u);
-                }
+                unpack_cols(S.h_ops.p + t.ops_off, t.ops_cap - 2, 2, j.ops);  // the reference reports aln_len = 2: the last two alignment columns
             } else {
                 j.status = ALN_NONE;
             }
@@ -1215,14 +1256,14 @@ void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, 
     }
     S.d_run_sums.reserve(n);
     std::vector<AlnRunSum> sums(n);
-    HIP_CHECK(hipEventRecord(S.evs[5], st));
+    S.mark(State::kEvTailBegin, st);
     NDGPU_DBG(st, "chunk: K15 count, %zu tasks", n);
     launch_aln_runs_count(S.d_tasks.p, S.d_outs.p, S.d_ops.p, any_bad ? S.d_run_skip.p : nullptr, S.d_run_sums.p, (int)n, st);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(S.evs[6], st));
+    S.mark(State::kEvTailEnd, st);
     S.d2h(sums.data(), S.d_run_sums.p, n * sizeof(AlnRunSum), st);
     S.sync_drain(st);
-    S.stats.aln_batch_ms += ms_between(S.evs[5], S.evs[6]);
+    S.stats.aln_batch_ms += S.ms(State::kEvTailBegin, State::kEvTailEnd);
 
     std::vector<uint64_t> off(n);
     uint64_t total = 0;
@@ -1236,14 +1277,14 @@ void DeviceAligner::run_chunk_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, 
         S.d_run_off.reserve(n);
         S.d_runs.reserve(total);
         S.h2d(S.d_run_off.p, off.data(), n * sizeof(uint64_t), st);
-        HIP_CHECK(hipEventRecord(S.evs[5], st));
+        S.mark(State::kEvTailBegin, st);
         NDGPU_DBG(st, "chunk: K15 emit, %llu runs", (unsigned long long)total);
         launch_aln_runs_emit(S.d_tasks.p, S.d_outs.p, S.d_ops.p, S.d_run_sums.p, S.d_run_off.p, S.d_runs.p, (int)n, st);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(S.evs[6], st));
+        S.mark(State::kEvTailEnd, st);
         S.d2h(runs.data() + at, S.d_runs.p, total * sizeof(uint32_t), st);
         S.sync_drain(st);
-        S.stats.aln_batch_ms += ms_between(S.evs[5], S.evs[6]);
+        S.stats.aln_batch_ms += S.ms(State::kEvTailBegin, State::kEvTailEnd);
         S.stats.aln_batch_launches++;
     }
     S.stats.aln_batch_jobs += n;
@@ -1326,262 +1367,203 @@ void DeviceAligner::State::run_wide(bool ops_to_host, const std::vector<int32_t>
     }
 }
 
-// Low-quality-region rounds of a batch of piles on the device: K7 / K8a over every (row, region) alignment, then K12 (lq_links + lq_score:
-// linked pseudo-seed, second MSA, DP, walk) -- the column streams stay in HBM, what comes back is each pile's walk string.
-// A round the kernel declines (r->ok stays false) is left to the caller's host path.
 constexpr uint32_t kLenClasses = 16384;  // 64-base length classes of the longest-first launch order (length_order); the last one holds >= 1 Mb
-constexpr uint64_t kLqJobColumns = 192;     // columns of a K12a job (a pile of 3,000 columns is ~15 wavefronts' worth of link building)
-constexpr uint64_t kLqMaxColumns = 400000;  // linked pseudo-seed columns K12 takes per pile (see run_lq)
-constexpr uint32_t kLqWarmColumns = 64;    // columns a K12b job starts before its own first one (speculative start, checked by the stitch)
+
+// ---- low-quality-region rounds of a batch of piles on the device: K7 / K8a over every (row, region) alignment, then K12 (lq_links +
+// lq_score: linked pseudo-seed, second MSA, DP, walk) -- the column streams stay in HBM, what comes back is each pile's walk string.
+// A round the kernel declines (r->ok stays false) is left to the caller's host path.  run_lq (below) is the sequence of these steps:
+//   layout_lq (a round at a time, its jobs cut by cut_lq_jobs of nd_lqplan.h) -> pack_lq_pool -> reserve_lq (buffers, align chunks) ->
+//   launch_lq (uploads, K7 / K8a chunk by chunk, K12, downloads, the one synchronisation) -> tally_lq (events, verdicts, stats).
+
+// One round: its pieces, tasks (one per piece with a job), sequence words (candidates once each, pseudo-seeds once per region), jobs
+// and output regions, appended to the layout.  L.usable[r] stays 0 where the round is left to the host path.
+void DeviceAligner::State::layout_lq_round(LqRound &R, size_t r, LqLayout &L) {
+    R.ok = false;
+    R.lqc.clear();
+    LqPileDev &P = L.piles[r];
+    memset(&P, 0, sizeof(P));
+    const uint32_t nr = R.n_regions;
+    if (nr == 0 || R.pieces.size() != (size_t)nr * kLqRoundRows) return;
+    uint64_t link_len = 1, ins_cap = 0;
+    for (uint32_t g = 0; g < nr; g++) link_len += (uint64_t)R.pieces[g].sl + 1;
+    if (link_len > hooks_of<LqHooks>().max_cols) return;
+    P.first_piece = (uint32_t)L.pieces.size(), P.n_regions = nr, P.factor = R.factor, P.qv_factor = R.qv_factor;
+    std::vector<uint64_t> t_off(nr, ~0ull);  // word offset of every region's pseudo-seed, packed on first use
+    std::vector<LqRegionLoad> load(nr);      // what cut_lq_jobs sizes the jobs' streams by
+    for (uint32_t g = 0; g < nr; g++) load[g] = LqRegionLoad{R.pieces[g].sl, 0, 0, 0};
+    for (size_t k = 0; k < R.pieces.size(); k++) {
+        const LqRound::Piece &pc = R.pieces[k];
+        const uint32_t g = (uint32_t)(k % nr);
+        LqPieceDev d{-1, pc.sl};
+        if (pc.job >= 0) {
+            const AlnJob &j = (*R.jobs)[(size_t)pc.job];
+            AlnTask t;
+            memset(&t, 0, sizeof(t));
+            t.q_len = j.q_len, t.t_len = j.t_len;
+            L.srcs.push_back(LqSrc{j.q_words, j.q, (uint32_t)j.q_len, L.pool_words});
+            t.q_off = L.pool_words * 16;
+            L.pool_words += ((uint64_t)j.q_len + 15) / 16;
+            if (t_off[g] == ~0ull) {
+                t_off[g] = L.pool_words;
+                L.srcs.push_back(LqSrc{nullptr, j.t, (uint32_t)j.t_len, L.pool_words});
+                L.pool_words += ((uint64_t)j.t_len + 15) / 16;
+            }
+            t.t_off = t_off[g] * 16;
+            task_limits(t, j.hq, L.ops_words, stats);
+            ins_cap += (uint64_t)j.q_len;
+            load[g].q_bases += (uint64_t)j.q_len, load[g].qt_bases += (uint64_t)j.q_len + (uint64_t)j.t_len;
+            d.task = (int32_t)tasks.size();
+            tasks.push_back(t);
+            stats.pool_bases += (uint64_t)j.q_len;
+        } else load[g].empty_rows++;
+        L.pieces.push_back(d);
+    }
+    if (link_len + ins_cap >= (1ull << 27) || link_len >= (1ull << 20)) return;  // beyond the packed tag's column field / the record's row field
+    P.link_len = (uint32_t)link_len;
+    P.out_cap = (uint32_t)(2 * link_len + 64);
+    P.cell_off = L.cell_rows * 6, P.out_off = L.out_bytes;
+    L.out_bytes += P.out_cap;
+    P.first_job = (uint32_t)L.jobs.size();
+    std::vector<LqJobCut> cuts;
+    cut_lq_jobs(load, hooks_of<LqHooks>().job_cols, kLqRoundRows, L.hdr_words, L.lnk_words, cuts);
+    for (const LqJobCut &c : cuts) {
+        LqJobDev jb;
+        memset(&jb, 0, sizeof(jb));
+        jb.pile = (uint32_t)r, jb.g_a = c.g_a, jb.g_b = c.g_b, jb.t0 = c.t0, jb.t1 = c.t1;
+        jb.row_cap = c.row_cap, jb.lnk_cap = c.lnk_cap, jb.hdr_off = c.hdr_off, jb.lnk_off = c.lnk_off;
+        P.row_cap += c.row_cap;
+        L.jobs.push_back(jb);
+    }
+    P.n_jobs = (uint32_t)cuts.size();
+    L.cell_rows += P.row_cap;
+    L.usable[r] = 1;
+}
+
+// Every round of the call; the tasks are the context's own vector.
+LqLayout DeviceAligner::State::layout_lq(LqRound **rounds, size_t n) {
+    LqLayout L;
+    L.piles.resize(n), L.usable.assign(n, 0);
+    tasks.clear();
+    size_t n_pieces = 0;
+    for (size_t r = 0; r < n; r++) n_pieces += rounds[r]->pieces.size();
+    L.pieces.reserve(n_pieces);
+    for (size_t r = 0; r < n; r++) layout_lq_round(*rounds[r], r, L);
+    return L;
+}
+
+// The sequence words (parallel): memcpy of what is packed already, packing of the rest.  false: a byte outside [ACGT].
+bool DeviceAligner::State::pack_lq_pool(const LqLayout &L) {
+    pool.assign(L.pool_words + kPoolPadWords, 0);  // (the kernels fetch up to five words from a sequence's last base on)
+    std::atomic<int> bad_any{0};
+    par_ranges(L.srcs.size(), host_threads, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) {
+            const LqSrc &x = L.srcs[i];
+            if (x.words) memcpy(pool.data() + x.word_off, x.words, (((size_t)x.len + 15) / 16) * sizeof(uint32_t));
+            else if (!pack_into(pool.data() + x.word_off, x.ascii, x.len)) bad_any = 1;
+        }
+    });
+    return !bad_any.load();
+}
+
+// The buffers the layout sizes, then the forward / traceback chunks bounded by the trace budget (the column streams of every chunk
+// stay resident; the traceback runs in segments where a launch holds long pairs -- regions of several kb).
+std::vector<AlignChunk> DeviceAligner::State::reserve_lq(const LqLayout &L) {
+    const size_t nt = tasks.size();
+    d_pool.reserve(pool.size()), d_tasks.reserve(nt), d_outs.reserve(nt), d_ops.reserve(L.ops_words + 2);
+    d_lq_piles.reserve(L.piles.size()), d_lq_pieces.reserve(L.pieces.size()), d_lq_rec.reserve(L.cell_rows * 6 + 6);
+    d_lq_jobs.reserve(L.jobs.size() + 1), d_lq_hdr.reserve(L.hdr_words + 1);
+    d_lq_lnk.reserve(L.lnk_words + 64);  // (K12b fetches a row's 64 link slots ahead)
+    d_lq_out.reserve(L.out_bytes + 1), d_lq_tmp.reserve(L.cell_rows + 1), d_lq_bnd.reserve((L.jobs.size() + 1) * 4 * (size_t)kLqLinkCap);
+    return plan_chunks(tasks.data(), nt);
+}
+
+// Five uploads, K7 / K8a chunk by chunk (an event bracket per kernel, read behind the one synchronisation), K12, the records, the
+// piles as K12 left them (into L.piles) and their characters (returned) down.
+std::vector<char> DeviceAligner::State::launch_lq(LqLayout &L, const std::vector<AlignChunk> &chunks) {
+    hipStream_t st = stream;
+    const size_t n = L.piles.size(), nt = tasks.size();
+    h2d(d_pool.p, pool.data(), pool.size() * sizeof(uint32_t), st);
+    h2d(d_tasks.p, tasks.data(), nt * sizeof(AlnTask), st);
+    h2d(d_lq_piles.p, L.piles.data(), n * sizeof(LqPileDev), st);
+    h2d(d_lq_pieces.p, L.pieces.data(), L.pieces.size() * sizeof(LqPieceDev), st);
+    if (!L.jobs.empty()) h2d(d_lq_jobs.p, L.jobs.data(), L.jobs.size() * sizeof(LqJobDev), st);
+    grow_lq_evs(2 * chunks.size() + 1);
+    HIP_CHECK(hipEventRecord(lq_evs[0], st));
+    for (size_t c = 0; c < chunks.size(); c++) {
+        NDGPU_DBG(st, "lq: forward / traceback %zu..%zu of %zu tasks", chunks[c].begin, chunks[c].end, nt);
+        launch_chunk(chunks[c], nullptr, nullptr, lq_evs[2 * c + 1], lq_evs[2 * c + 2], nullptr);
+    }
+    mark(kEvLqMsaBegin, st);
+    NDGPU_DBG(st, "lq: msa of %zu piles", n);
+    launch_lq_msa(d_lq_piles.p, d_lq_jobs.p, d_lq_pieces.p, d_tasks.p, d_outs.p, d_ops.p, d_pool.p, d_lq_hdr.p, d_lq_lnk.p, d_lq_rec.p,
+                  d_lq_bnd.p, d_lq_tmp.p, d_lq_out.p, (int)n, (int)L.jobs.size(), hooks_of<LqHooks>().warm, hooks_of<LqHooks>().force_repair, st);
+    mark(kEvLqMsaEnd, st);
+    h_outs.reserve(nt + 1);
+    HIP_CHECK(hipMemcpyAsync(h_outs.p, d_outs.p, nt * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
+    std::vector<char> out(L.out_bytes + 1);
+    d2h(L.piles.data(), d_lq_piles.p, n * sizeof(LqPileDev), st);
+    if (L.out_bytes) d2h(out.data(), d_lq_out.p, L.out_bytes, st);
+    sync_drain(st);
+    HIP_CHECK(hipGetLastError());
+    return out;
+}
+
+// The kernels' times and counters, then round by round: taken (its walk string and its stats) or declined.
+void DeviceAligner::State::tally_lq(LqRound **rounds, const LqLayout &L, size_t n_chunks, const std::vector<char> &out) {
+    const size_t nt = tasks.size();
+    for (size_t c = 0; c < n_chunks; c++) {
+        stats.forward_ms += ms_between(lq_evs[2 * c], lq_evs[2 * c + 1]);
+        stats.traceback_ms += ms_between(lq_evs[2 * c + 1], lq_evs[2 * c + 2]);
+    }
+    stats.forward_launches += n_chunks, stats.traceback_launches += n_chunks;
+    stats.lq_ms += ms(kEvLqMsaBegin, kEvLqMsaEnd);
+    stats.lq_launches++, stats.tasks += nt;
+    tally_outs(nt, nullptr);  // (ST_NEED_WIDE is looked for piece by piece below)
+    for (size_t r = 0; r < L.piles.size(); r++) {
+        stats.lq_rounds++;
+        const LqPileDev &P = L.piles[r];
+        const LqPieceDev *pc = L.pieces.data() + P.first_piece;
+        const uint32_t n_pc = L.usable[r] ? kLqRoundRows * P.n_regions : 0u;
+        // (an alignment whose live band left the register path: K12 saw it as unaligned, so its pile goes the host way, where
+        // run_chunk reruns it in the wide kernel)
+        bool need_wide = false;
+        for (uint32_t k = 0; k < n_pc && !need_wide; k++) need_wide = pc[k].task >= 0 && h_outs.p[pc[k].task].status == ST_NEED_WIDE;
+        if (!L.usable[r] || need_wide || P.err != 0) {
+            stats.lq_declined++;
+            if (trace_on()) fprintf(stderr, "[ndgpu trace] K12 declined a pile (code %u): host path\n", L.usable[r] ? (need_wide ? 1u : P.err) : 9u);
+            continue;
+        }
+        rounds[r]->lqc.assign(out.data() + P.out_off, P.out_len);
+        rounds[r]->ok = true;
+        stats.lq_repairs += P.n_repair, stats.lq_jobs += P.n_jobs, stats.lq_columns += P.link_len, stats.lq_out += P.out_len;
+        for (uint32_t k = 0; k < n_pc; k++) {
+            const int32_t t = pc[k].task;
+            if (t < 0) continue;
+            stats.lq_bases += (uint64_t)tasks[(size_t)t].q_len;
+            if (h_outs.p[t].status == ST_ALIGNED) stats.lq_aln_columns += (uint64_t)h_outs.p[t].n_cols;
+        }
+    }
+}
 
 void DeviceAligner::run_lq(LqRound **rounds, size_t n) {
     if (n == 0) return;
     State &S = *s_;
     const State::Phase phase(S);
-    hipStream_t st = S.stream;
     const uint64_t tc0 = wall_ns();
-
-    // ---- layout: per round its pieces, tasks (one per piece with a job), sequence words (candidates once each, pseudo-seeds once
-    //      per region) and output regions
-    std::vector<LqPileDev> piles(n);
-    std::vector<LqPieceDev> pieces;
-    std::vector<AlnTask> &tasks = S.tasks;
-    tasks.clear();
-    struct Src {
-        const uint32_t *words;  // packed already, or
-        const char *ascii;
-        uint32_t len;
-        uint64_t word_off;
-    };
-    std::vector<Src> srcs;
-    std::vector<uint8_t> usable(n, 1);
-    uint64_t pool_words = 0, ops_words = 0, cell_rows = 0, out_bytes = 0, hdr_words = 0, lnk_words = 0;
-    std::vector<LqJobDev> jobs;
-    size_t n_piece_total = 0;
-    for (size_t r = 0; r < n; r++) n_piece_total += rounds[r]->pieces.size();
-    pieces.reserve(n_piece_total);
-    for (size_t r = 0; r < n; r++) {
-        LqRound &R = *rounds[r];
-        R.ok = false;
-        R.lqc.clear();
-        LqPileDev &P = piles[r];
-        memset(&P, 0, sizeof(P));
-        const uint32_t nr = R.n_regions;
-        if (nr == 0 || R.pieces.size() != (size_t)nr * 30u) {
-            usable[r] = 0;
-            continue;
-        }
-        uint64_t link_len = 1, ins_cap = 0;
-        for (uint32_t g = 0; g < nr; g++) link_len += (uint64_t)R.pieces[g].sl + 1;
-        // Until round 4 K12b was one wavefront per pile (~1 us per cell row; config 3 had K12 launches of 250 ms) and a pile whose
-        // low-quality regions added up to more than 12,000 columns was left to the host path.  Scored job by job (lq_kernels.hip) the
-        // chain is as long as a job, not as the pile: the bound is what the packed records can address (below), well above this.
-        static const uint64_t max_cols = getenv("NDGPU_K12_MAX_COLUMNS") ? strtoull(getenv("NDGPU_K12_MAX_COLUMNS"), nullptr, 10) : kLqMaxColumns;  // (test hook)
-        if (link_len > max_cols) {
-            usable[r] = 0;
-            continue;
-        }
-        P.first_piece = (uint32_t)pieces.size();
-        P.n_regions = nr;
-        P.factor = R.factor;
-        P.qv_factor = R.qv_factor;
-        std::vector<uint64_t> t_off(nr, ~0ull);  // word offset of every region's pseudo-seed, packed on first use
-        for (size_t k = 0; k < R.pieces.size(); k++) {
-            const LqRound::Piece &pc = R.pieces[k];
-            LqPieceDev d;
-            d.task = -1;
-            d.sl = pc.sl;
-            if (pc.job >= 0) {
-                const AlnJob &j = (*R.jobs)[(size_t)pc.job];
-                const uint32_t g = (uint32_t)(k % nr);
-                AlnTask t;
-                memset(&t, 0, sizeof(t));
-                t.q_len = j.q_len;
-                t.t_len = j.t_len;
-                srcs.push_back(Src{j.q_words, j.q, (uint32_t)j.q_len, pool_words});
-                t.q_off = pool_words * 16;
-                pool_words += ((uint64_t)j.q_len + 15) / 16;
-                if (t_off[g] == ~0ull) {
-                    t_off[g] = pool_words;
-                    srcs.push_back(Src{nullptr, j.t, (uint32_t)j.t_len, pool_words});
-                    pool_words += ((uint64_t)j.t_len + 15) / 16;
-                }
-                t.t_off = t_off[g] * 16;
-                task_limits(t, j.hq, ops_words, S.stats);
-                ins_cap += (uint64_t)j.q_len;
-                d.task = (int32_t)tasks.size();
-                tasks.push_back(t);
-                S.stats.pool_bases += (uint64_t)j.q_len;
-            }
-            pieces.push_back(d);
-        }
-        if (link_len + ins_cap >= (1ull << 27) || link_len >= (1ull << 20)) {  // beyond the packed tag's column field / the record's row field
-            usable[r] = 0;
-            continue;
-        }
-        P.link_len = (uint32_t)link_len;
-        P.out_cap = (uint32_t)(2 * link_len + 64);
-        P.cell_off = cell_rows * 6;
-        P.out_off = out_bytes;
-        out_bytes += P.out_cap;
-        // K12a's jobs: runs of regions of about kLqJobColumns columns (each region with the 'N' column in front of it); a job
-        // starts only behind a region that has columns (its rows' first tags come from the tail of that region's alignments).
-        // Capacities: cell rows = columns + the longest insertion run after every column -- bounded by the candidates' bases, in
-        // practice a fraction of the columns: three times the columns are laid out, a job that needs more declines the pile (host
-        // path); links <= tags = the alignments' columns (<= q_len + t_len each) + a tag per row of an unaligned region's columns
-        // + 30 per 'N'.
-        static const uint64_t job_cols = getenv("NDGPU_K12_JOB_COLUMNS") ? strtoull(getenv("NDGPU_K12_JOB_COLUMNS"), nullptr, 10) : kLqJobColumns;  // (test hook: 1 = every region a job)
-        P.first_job = (uint32_t)jobs.size();
-        {
-            uint32_t g = 0, t = 0;
-            while (g < nr) {
-                LqJobDev jb;
-                memset(&jb, 0, sizeof(jb));
-                jb.pile = (uint32_t)r, jb.g_a = g, jb.t0 = t;
-                uint64_t cols = 0, ins = 0, tags = 0;
-                do {
-                    const uint32_t sl = R.pieces[g].sl;
-                    cols += (uint64_t)sl + 1;
-                    tags += 30;
-                    for (uint32_t row = 0; row < 30u; row++) {
-                        const LqRound::Piece &pc = R.pieces[(size_t)row * nr + g];
-                        if (pc.job >= 0) {
-                            const AlnJob &j = (*R.jobs)[(size_t)pc.job];
-                            ins += (uint64_t)j.q_len;
-                            tags += (uint64_t)j.q_len + (uint64_t)j.t_len;
-                        } else tags += sl;
-                    }
-                    t += sl + 1;
-                    g++;
-                } while (g < nr && (cols < job_cols || R.pieces[g - 1].sl == 0));
-                jb.g_b = g;
-                if (g == nr) cols += 1, tags += 30, t += 1;  // the closing 'N'
-                jb.t1 = t;
-                jb.row_cap = (uint32_t)std::min<uint64_t>(cols + ins, 3 * cols + 256);
-                jb.lnk_cap = (uint32_t)std::min<uint64_t>(tags, (uint64_t)jb.row_cap * 30u);
-                jb.hdr_off = hdr_words, jb.lnk_off = lnk_words;
-                hdr_words += jb.row_cap;
-                lnk_words += jb.lnk_cap;
-                P.row_cap += jb.row_cap;
-                jobs.push_back(jb);
-            }
-        }
-        P.n_jobs = (uint32_t)jobs.size() - P.first_job;
-        cell_rows += P.row_cap;
-    }
-    const size_t nt = tasks.size();
+    LqLayout L = S.layout_lq(rounds, n);
+    const size_t nt = S.tasks.size();
     if (nt == 0) {  // nothing K12 takes in this call: every pile goes the host way
         S.stats.lq_rounds += n, S.stats.lq_declined += n;
         return;
     }
-
-    // ---- sequence words (parallel): memcpy of what is packed already, packing of the rest
-    std::vector<uint32_t> &pool = S.pool;
-    pool.assign(pool_words + kPoolPadWords, 0);  // (the kernels fetch up to five words from a sequence's last base on)
-    std::atomic<int> bad_any{0};
-    par_ranges(srcs.size(), S.host_threads, [&](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) {
-            const Src &x = srcs[i];
-            if (x.words) memcpy(pool.data() + x.word_off, x.words, (((size_t)x.len + 15) / 16) * sizeof(uint32_t));
-            else if (!pack_into(pool.data() + x.word_off, x.ascii, x.len)) bad_any = 1;
-        }
-    });
-    if (bad_any.load()) return;  // bytes outside [ACGT]: the host path reports them
-
-    S.d_pool.reserve(pool.size());
-    S.d_tasks.reserve(nt);
-    S.d_outs.reserve(nt);
-    S.d_ops.reserve(ops_words + 2);
-    S.d_lq_piles.reserve(n);
-    S.d_lq_pieces.reserve(pieces.size());
-    S.d_lq_rec.reserve(cell_rows * 6 + 6);
-    S.d_lq_jobs.reserve(jobs.size() + 1);
-    S.d_lq_hdr.reserve(hdr_words + 1);
-    S.d_lq_lnk.reserve(lnk_words + 64);   // (K12b fetches a row's 64 link slots ahead)
-    S.d_lq_out.reserve(out_bytes + 1);
-    S.d_lq_tmp.reserve(cell_rows + 1);
-    S.d_lq_bnd.reserve((jobs.size() + 1) * 4 * (size_t)kLqLinkCap);
-
-    // forward / traceback chunks bounded by the trace budget (the column streams of every chunk stay resident); the traceback runs in
-    // segments where a launch holds long pairs (regions of several kb)
-    const std::vector<AlignChunk> chunks = S.plan_chunks(tasks.data(), nt);
-
+    // bytes outside [ACGT]: the host path reports them.  (This exit counts neither lq_rounds nor lq_declined, unlike the one above
+    // and unlike a round that is not usable: kept as it is, the counters do not move in a change of the code's shape.)
+    if (!S.pack_lq_pool(L)) return;
+    const std::vector<AlignChunk> chunks = S.reserve_lq(L);
     const uint64_t tc1 = wall_ns();
-    S.h2d(S.d_pool.p, pool.data(), pool.size() * sizeof(uint32_t), st);
-    S.h2d(S.d_tasks.p, tasks.data(), nt * sizeof(AlnTask), st);
-    S.h2d(S.d_lq_piles.p, piles.data(), n * sizeof(LqPileDev), st);
-    S.h2d(S.d_lq_pieces.p, pieces.data(), pieces.size() * sizeof(LqPieceDev), st);
-    if (!jobs.empty()) S.h2d(S.d_lq_jobs.p, jobs.data(), jobs.size() * sizeof(LqJobDev), st);
-    // (HIP-event brackets per kernel: K7, K8a per chunk -- read after the round's one synchronisation)
-    while (S.lq_evs.size() < 2 * chunks.size() + 1) {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
-        S.lq_evs.push_back(e);
-    }
-    HIP_CHECK(hipEventRecord(S.lq_evs[0], st));
-    for (size_t c = 0; c < chunks.size(); c++) {
-        NDGPU_DBG(st, "lq: forward / traceback %zu..%zu of %zu tasks", chunks[c].begin, chunks[c].end, nt);
-        S.launch_chunk(chunks[c], nullptr, nullptr, S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2], nullptr);
-    }
-    HIP_CHECK(hipEventRecord(S.evs[1], st));
-    NDGPU_DBG(st, "lq: msa of %zu piles", n);
-    // test hooks: NDGPU_K12_WARM = warm-up columns of a job's speculative start; NDGPU_K12_FORCE=repair: every second job is scored again
-    // by the stitch kernel as if its boundary check had failed
-    static const uint32_t k12_warm = getenv("NDGPU_K12_WARM") ? (uint32_t)std::max(1, atoi(getenv("NDGPU_K12_WARM"))) : kLqWarmColumns;
-    static const uint32_t k12_force = (getenv("NDGPU_K12_FORCE") && !strcmp(getenv("NDGPU_K12_FORCE"), "repair")) ? 2u : 0u;
-    launch_lq_msa(S.d_lq_piles.p, S.d_lq_jobs.p, S.d_lq_pieces.p, S.d_tasks.p, S.d_outs.p, S.d_ops.p, S.d_pool.p, S.d_lq_hdr.p, S.d_lq_lnk.p,
-                  S.d_lq_rec.p, S.d_lq_bnd.p, S.d_lq_tmp.p, S.d_lq_out.p, (int)n, (int)jobs.size(), k12_warm, k12_force, st);
-    HIP_CHECK(hipEventRecord(S.evs[2], st));
-    S.h_outs.reserve(nt + 1);
-    HIP_CHECK(hipMemcpyAsync(S.h_outs.p, S.d_outs.p, nt * sizeof(AlnOut), hipMemcpyDeviceToHost, st));
-    std::vector<char> out(out_bytes + 1);
-    S.d2h(piles.data(), S.d_lq_piles.p, n * sizeof(LqPileDev), st);
-    if (out_bytes) S.d2h(out.data(), S.d_lq_out.p, out_bytes, st);
-    S.sync_drain(st);
-    HIP_CHECK(hipGetLastError());
-    for (size_t c = 0; c < chunks.size(); c++) {
-        S.stats.forward_ms += ms_between(S.lq_evs[2 * c], S.lq_evs[2 * c + 1]);
-        S.stats.traceback_ms += ms_between(S.lq_evs[2 * c + 1], S.lq_evs[2 * c + 2]);
-    }
-    S.stats.forward_launches += chunks.size();
-    S.stats.traceback_launches += chunks.size();
-    S.stats.lq_ms += ms_between(S.evs[1], S.evs[2]);
-    S.stats.lq_launches++;
-    S.stats.tasks += nt;
+    const std::vector<char> out = S.launch_lq(L, chunks);
     const uint64_t tc2 = wall_ns();
-
-    S.tally_outs(nt, nullptr);  // (ST_NEED_WIDE is looked for piece by piece below)
-    for (size_t r = 0; r < n; r++) {
-        LqRound &R = *rounds[r];
-        S.stats.lq_rounds++;
-        const LqPileDev &P = piles[r];
-        // (an alignment whose live band left the register path: K12 saw it as unaligned, so its pile goes the host way, where
-        // run_chunk reruns it in the wide kernel)
-        bool need_wide = false;
-        if (usable[r])
-            for (uint32_t k = 0; k < 30u * P.n_regions && !need_wide; k++) {
-                const int32_t t = pieces[P.first_piece + k].task;
-                need_wide = t >= 0 && S.h_outs.p[t].status == ST_NEED_WIDE;
-            }
-        if (!usable[r] || need_wide || P.err != 0) {
-            S.stats.lq_declined++;
-            static const bool trace = getenv("NDGPU_TRACE") != nullptr;
-            if (trace) fprintf(stderr, "[ndgpu trace] K12 declined a pile (code %u): host path\n", usable[r] ? (need_wide ? 1u : P.err) : 9u);
-            continue;
-        }
-        R.lqc.assign(out.data() + P.out_off, P.out_len);
-        R.ok = true;
-        S.stats.lq_repairs += P.n_repair;
-        S.stats.lq_jobs += P.n_jobs;
-        S.stats.lq_columns += P.link_len;
-        S.stats.lq_out += P.out_len;
-        for (uint32_t k = 0; k < 30u * P.n_regions; k++) {
-            const int32_t t = pieces[P.first_piece + k].task;
-            if (t < 0) continue;
-            S.stats.lq_bases += (uint64_t)tasks[(size_t)t].q_len;
-            if (S.h_outs.p[t].status == ST_ALIGNED) S.stats.lq_aln_columns += (uint64_t)S.h_outs.p[t].n_cols;
-        }
-    }
+    S.tally_lq(rounds, L, chunks.size(), out);
     g_prof.c_pack += tc1 - tc0, g_prof.c_dev += tc2 - tc1, g_prof.c_decode += wall_ns() - tc2, g_prof.c_jobs += nt;
 }
 
@@ -1700,7 +1682,7 @@ void DeviceAligner::State::reserve_layout(const MainLayout &L, size_t np) {
 // (table order) for a short chunk or under NDGPU_K7_NO_ORDER.  A counting sort over 64-base length classes: a sub-batch holds up
 // to a million tasks and this runs on the context's critical path.
 const int32_t *DeviceAligner::State::length_order(size_t a, size_t m) {
-    if (!main_hooks().k7_order || m <= 64) return nullptr;
+    if (!hooks_of<MainHooks>().k7_order || m <= 64) return nullptr;
     order.resize(m);
     order_cls.assign(kLenClasses + 1, 0);
     auto cls_of = [&](size_t i) {
@@ -1725,13 +1707,13 @@ void DeviceAligner::State::align_main(const std::vector<AlignChunk> &chunks, siz
         // (K8a stays in table order: measured in round 5, the 64 walks of a wavefront ordered longest first like K7's --
         // equal lengths, long walks first -- cost 605 ms of traceback per step against 496: the lanes of a wavefront in pile
         // order walk neighbouring windows of one seed and share its cache lines; NDGPU_K8_ORDER=1 switches the order on)
-        HIP_CHECK(hipEventRecord(evs[0], st));
-        launch_chunk(ch, ids, main_hooks().k8_order ? ids : nullptr, evs[1], evs[2], "main");
+        mark(kEvMainK7, st);
+        launch_chunk(ch, ids, hooks_of<MainHooks>().k8_order ? ids : nullptr, evs[kEvMainK8a], evs[kEvMainAligned], "main");
         NDGPU_DBG(st, "main: traceback done");
-        HIP_CHECK(hipEventSynchronize(evs[2]));  // (chunk by chunk: the next one records the same three events)
-        stats.forward_ms += ms_between(evs[0], evs[1]);
+        HIP_CHECK(hipEventSynchronize(evs[kEvMainAligned]));  // (chunk by chunk: the next one records the same three events)
+        stats.forward_ms += ms(kEvMainK7, kEvMainK8a);
         stats.forward_launches++;
-        stats.traceback_ms += ms_between(evs[1], evs[2]);
+        stats.traceback_ms += ms(kEvMainK8a, kEvMainAligned);
         stats.traceback_launches++;
     }
     if (!nt) return;
@@ -1743,11 +1725,11 @@ void DeviceAligner::State::align_main(const std::vector<AlignChunk> &chunks, siz
     stats.tasks += nt;
 }
 
-// The four launches between events 0 and 1: shift scan, accept, tags, column scan.
+// The four launches between the events kEvTagsBegin and kEvTagsEnd: shift scan, accept, tags, column scan.
 void DeviceAligner::State::launch_tags(const CovPlanes &cov, size_t np) {
     hipStream_t st = stream;
     const int nr = (int)reads.size();
-    HIP_CHECK(hipEventRecord(evs[0], st));
+    mark(kEvTagsBegin, st);
     NDGPU_DBG(st, "main: shift_scan");
     launch_shift_scan(d_tasks.p, d_outs.p, d_ops.p, d_reads.p, nr, st);
     NDGPU_DBG(st, "main: pile_accept");
@@ -1758,14 +1740,14 @@ void DeviceAligner::State::launch_tags(const CovPlanes &cov, size_t np) {
     NDGPU_DBG(st, "main: col_scan");
     launch_col_scan(d_piles.p, cov.cov, cov.inscnt, cov.insmax, d_cellbase.p, d_entbase.p, (int)np, st);
     NDGPU_DBG(st, "main: col_scan done");
-    HIP_CHECK(hipEventRecord(evs[1], st));
+    mark(kEvTagsEnd, st);
 }
 
 // From the piles as the column scan left them (n_cells, n_tags, err): every pile's K10 segments -- `seg_len` columns each, the
 // last one takes the remainder -- on the work list of its tier, its offsets into the cell / link / path tables, K9's column
 // blocks.  Pure host arithmetic; writes the piles' n_seg, seg_off, n_repair, tier and the three offsets.
 static MsaPlan plan_msa(std::vector<PileDev> &piles) {
-    const MainHooks &k = main_hooks();
+    const MainHooks &k = hooks_of<MainHooks>();
     MsaPlan M;
     for (size_t p = 0; p < piles.size(); p++) {
         PileDev &P = piles[p];
@@ -1820,7 +1802,7 @@ void DeviceAligner::State::upload_plan(const MsaPlan &plan) {
     h2d(d_items.p + plan.items_small.size() + plan.items_large.size(), plan.items_slow.data(), plan.items_slow.size() * sizeof(SegItem), st);
 }
 
-// K10 + the best_pp walk behind one attempt of K9 (events 3 .. 7 .. 4).  A sub-batch small enough for the reserved compute units
+// K10 + the best_pp walk behind one attempt of K9 (events kEvScoreBegin .. kEvWalkBegin .. kEvWalkEnd).  A sub-batch small enough for the reserved compute units
 // (4 two-wave blocks each) scores there: fork from the context's stream before, join behind.
 void DeviceAligner::State::score_pass(const MsaPlan &plan, const K10Args &k10) {
     hipStream_t st = stream;
@@ -1830,13 +1812,13 @@ void DeviceAligner::State::score_pass(const MsaPlan &plan, const K10Args &k10) {
     if (on_reserved) {
         HIP_CHECK(hipEventRecord(ev_lat0, st));
         HIP_CHECK(hipStreamWaitEvent(sst, ev_lat0, 0));
-        HIP_CHECK(hipEventRecord(evs[3], sst));
+        mark(kEvScoreBegin, sst);
     }
     launch_score_backtrack(k10, d_items.p, (int)plan.items_small.size(), d_items.p + plan.items_small.size(), (int)plan.items_large.size(),
                            d_items.p, (int)plan.n_items(), d_ent_score.cap >= plan.ents + 1 ? d_ent_score.p : nullptr, false, d_path.p,
-                           d_bt_exit.p, d_bt_steps.p, d_bt_entry.p, d_bt_off.p, (int)np, sst, evs[7], on_reserved ? nullptr : stream2,
+                           d_bt_exit.p, d_bt_steps.p, d_bt_entry.p, d_bt_off.p, (int)np, sst, evs[kEvWalkBegin], on_reserved ? nullptr : stream2,
                            ev_fork, ev_join);
-    HIP_CHECK(hipEventRecord(evs[4], sst));
+    mark(kEvWalkEnd, sst);
     NDGPU_DBG(st, "main: score + walk done");
     if (on_reserved) {
         HIP_CHECK(hipEventRecord(ev_lat1, sst));
@@ -1871,7 +1853,7 @@ void DeviceAligner::State::k9_digest_trace(const K9Args &k9, size_t np) {
 // rewritten), and if that overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap).
 // Returns the last attempt's error words, its piles and a view of its paths in the download arena.
 MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPlanes &cov) {
-    const MainHooks &hooks = main_hooks();
+    const MainHooks &hooks = hooks_of<MainHooks>();
     hipStream_t st = stream;
     const K9Args k9{d_piles.p,   d_reads.p,      d_acc.p,      d_blocks.p, d_tags.p,    d_colidx.p,  cov.insmax, d_cellbase.p,
                     d_entbase.p, d_cell_start.p, d_cell_len.p, d_ent_pp.p, d_ent_ppp.p, d_ent_cnt.p, d_err.p};
@@ -1888,7 +1870,7 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
         reserve_down(down_bytes, st);
         h2d(d_piles.p, piles.data(), np * sizeof(PileDev), st);
         if (!first) HIP_CHECK(hipMemsetAsync(d_err.p, 0, kErrWords * sizeof(uint32_t), st));
-        HIP_CHECK(hipEventRecord(evs[2], st));
+        mark(kEvLinksBegin, st);
         NDGPU_DBG(st, "main: count_links %zu blocks, cells %llu ents %llu segs %u", plan.blocks.size(), (unsigned long long)plan.cells,
                   (unsigned long long)plan.ents, plan.n_segs);
         if (attempt < 2) {
@@ -1900,7 +1882,7 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
             d_link_lists.reserve((size_t)grid * 18u * cap + 1);
             launch_count_links_global(k9, d_link_lists.p, cap, (int)plan.blocks.size(), grid, st);
         }
-        HIP_CHECK(hipEventRecord(evs[3], st));
+        mark(kEvScoreBegin, st);
         NDGPU_DBG(st, "main: score + walk");
         score_pass(plan, k10);
         const void *v_piles = d2h(nullptr, d_piles.p, np * sizeof(PileDev), st);  // (re-taken by the rescue pass)
@@ -1921,14 +1903,14 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
             HIP_CHECK(hipGetLastError());
             memcpy(R.piles.data(), v_piles, np * sizeof(PileDev));
         }
-        if (attempt < 2 && getenv("NDGPU_TRACE"))
+        if (attempt < 2 && trace_on())
             fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", R.herr[1], R.herr[3], R.herr[2],
                     R.herr[4] ? ~R.herr[4] : 0u);
         if (hooks.k9_digest) k9_digest_trace(k9, np);
         if (attempt == 0 ? !R.herr[0] && !hooks.k9_force_retry : !R.herr[0]) break;
         if (attempt == 2) break;  // (cannot happen: the lists hold one entry per accepted read)
         k9_retries++;
-        if (getenv("NDGPU_TRACE")) {
+        if (trace_on()) {
             if (attempt == 0) fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with %d\n", kLinkCapSmall, kLinkCap);
             else fprintf(stderr, "[ndgpu trace] K9: a cell holds more than %d distinct links, sub-batch repeated with the lists in device memory\n", kLinkCap);
         }
@@ -1940,15 +1922,14 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
 // them; tp: wall clock at the start of run_main and behind its prep, align, tags and msa parts.
 void DeviceAligner::State::tally_main(const MsaPlan &plan, const std::vector<uint8_t> &bad_pile, MainPile **mp, const uint64_t tp[5]) {
     const size_t np = piles.size();
-    const double t_tags = ms_between(evs[0], evs[1]), t_links = ms_between(evs[2], evs[3]), t_score = ms_between(evs[3], evs[7]),
-                 t_back = ms_between(evs[7], evs[4]);
+    const double t_tags = ms(kEvTagsBegin, kEvTagsEnd), t_links = ms(kEvLinksBegin, kEvScoreBegin), t_score = ms(kEvScoreBegin, kEvWalkBegin),
+                 t_back = ms(kEvWalkBegin, kEvWalkEnd);
     stats.tags_ms += t_tags;
     stats.links_ms += t_links;
     stats.score_ms += t_score;
     stats.score_launches++;
     stats.backtrack_ms += t_back;
-    static const bool trace = getenv("NDGPU_TRACE") != nullptr;
-    if (trace) {
+    if (trace_on()) {
         uint32_t longest = 0, rep = 0, slow = 0;
         for (size_t p = 0; p < np; p++) {
             longest = std::max(longest, piles[p].seed_len);
@@ -2043,29 +2024,13 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
 // context's host threads thread the routes through the graphs and sort them (poa.cpp).  The workspace -- 6 bytes per cell of
 // (X + 1)(Y + 1) -- is charged to the trace budget of the memory plan.  A problem outside the device's limits (a sequence of 0 or
 // more than 9,999 bases) or whose round alone exceeds the budget is declined: req.done stays false and the caller takes the host path.
-void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
-    if (n == 0) return;
-    State &S = *s_;
-    const State::Phase phase(S);
-    hipStream_t st = S.stream;
-    // test hooks, read once: the cell budget of a launch (0: every problem is declined), the kernel form every job takes, the row
-    // length from which the workgroup form takes over
-    static const char *e_budget = getenv("NDGPU_POA_BUDGET");
-    static const char *e_form = getenv("NDGPU_POA_FORM");
-    static const uint32_t group_min = getenv("NDGPU_POA_GROUP_MIN") ? (uint32_t)atoll(getenv("NDGPU_POA_GROUP_MIN")) : kPoaGroupMinLen;
-    static const int form = !e_form ? 0 : !strcmp(e_form, "wave") ? 1 : !strcmp(e_form, "group") ? 2 : 0;
-    const uint64_t budget = e_budget ? strtoull(e_budget, nullptr, 10) : (uint64_t)(S.trace_budget_bytes / 6);
+// run_poa (below) is: admit (admit_poa) -> per round: export_rows -> per slice: the budget cut (next_poa_slice of nd_lqplan.h) ->
+// stage_poa_slice -> launch_poa_slice -> thread_routes -> the consensus of the problems still live.
 
-    struct Prob {
-        PoaGraph g;
-        PoaRows rows;
-        bool live = false;       // still on the device path
-        uint64_t cells = 0;      // of the round in progress
-        uint32_t job = 0;        // its job of the launch in progress
-    };
-    std::vector<Prob> probs(n);
+// Which problems take the device path (PoaProb::live), each with its first sequence as a chain; returns the most sequences of one.
+size_t DeviceAligner::State::admit_poa(PoaReq **reqs, size_t n, uint64_t budget, PoaBatch &B) {
     size_t max_seqs = 0;
-    S.stats.poa_jobs += n;
+    stats.poa_jobs += n;
     for (size_t i = 0; i < n; i++) {
         PoaReq &rq = *reqs[i];
         rq.done = false, rq.failed = false;
@@ -2075,120 +2040,144 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
         }
         bool ok = !rq.seqs.empty() && budget > 0;
         for (const std::string &q : rq.seqs) ok = ok && !q.empty() && q.size() <= (size_t)kPoaMaxSeqLen;
-        probs[i].live = ok;
+        B.probs[i].live = ok;
         if (!ok) continue;
-        probs[i].g.start(rq.seqs[0].c_str(), rq.seqs[0].size());
+        B.probs[i].g.start(rq.seqs[0].c_str(), rq.seqs[0].size());
         max_seqs = std::max(max_seqs, rq.seqs.size());
     }
+    return max_seqs;
+}
 
-    auto host_for = [&](const std::vector<size_t> &ids, auto f) {  // f(problem) over the context's host threads
-        host_each(ids.size(), ids.size() < 8 || S.host_threads <= 1, S.host_threads, ids.size() / 4, true, [&](size_t k) { f(ids[k]); });
-    };
+// Round r of problems ids: every graph as rows, and what the budget cut goes by (load[k] for ids[k]).
+void DeviceAligner::State::export_rows(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &ids, size_t r, std::vector<PoaLoad> &load) {
+    poa_each(ids, [&](size_t i) {
+        PoaProb &p = B.probs[i];
+        p.g.export_rows(p.rows);
+        p.cells = (uint64_t)(p.g.rows() + 1) * (uint64_t)(reqs[i]->seqs[r].size() + 1);
+    });
+    load.resize(ids.size());
+    for (size_t k = 0; k < ids.size(); k++) load[k] = PoaLoad{B.probs[ids[k]].cells, (uint64_t)B.probs[ids[k]].g.rows()};
+}
 
-    std::vector<size_t> round_ids, slice;
-    std::vector<PoaJobDev> jobs;
-    std::vector<PoaRowDev> rows;
-    std::vector<uint16_t> preds;
-    std::vector<char> qpool;
-    std::vector<uint32_t> ids, routes;
+// The slice's five tables: jobs, rows, predecessor rows, query bytes, and the ids each kernel form takes (wave jobs, then group jobs).
+void DeviceAligner::State::stage_poa_slice(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r) {
+    const PoaHooks &hk = hooks_of<PoaHooks>();
+    B.jobs.clear(), B.rows.clear(), B.preds.clear(), B.qpool.clear(), B.ids.clear();
+    B.cells = B.route_words = 0;
+    std::vector<uint32_t> ids_group;
+    for (size_t i : slice) {
+        PoaProb &p = B.probs[i];
+        const std::string &q = reqs[i]->seqs[r];
+        PoaJobDev J;
+        memset(&J, 0, sizeof(J));
+        J.X = (uint32_t)p.g.rows(), J.Y = (uint32_t)q.size();
+        J.q_off = B.qpool.size(), J.row_off = B.rows.size(), J.pred_off = B.preds.size();
+        J.cell_off = B.cells, J.route_off = B.route_words;
+        B.cells += p.cells, B.route_words += (uint64_t)J.X + J.Y;
+        B.qpool.insert(B.qpool.end(), q.begin(), q.end());
+        for (uint32_t x = 0; x < J.X; x++) {
+            PoaRowDev rw;
+            rw.pred_off = p.rows.pred_off[x];
+            rw.n_pred = (uint16_t)(p.rows.pred_off[x + 1] - p.rows.pred_off[x]);
+            rw.base = p.rows.base[x], rw.sink = p.rows.sink[x];
+            B.rows.push_back(rw);
+        }
+        B.preds.insert(B.preds.end(), p.rows.preds.begin(), p.rows.preds.end());
+        p.job = (uint32_t)B.jobs.size();
+        const bool group = hk.form ? hk.form == 2 : J.Y >= hk.group_min;
+        (group ? ids_group : B.ids).push_back(p.job);
+        B.jobs.push_back(J);
+    }
+    B.n_wave = B.ids.size();
+    B.ids.insert(B.ids.end(), ids_group.begin(), ids_group.end());
+}
+
+// Buffers, five uploads, the launch pair in one event bracket, the jobs (their route lengths) and the routes down, one synchronisation.
+void DeviceAligner::State::launch_poa_slice(PoaBatch &B, size_t r) {
+    hipStream_t st = stream;
+    const size_t n_group = B.ids.size() - B.n_wave;
+    d_poa_jobs.reserve(B.jobs.size()), d_poa_ids.reserve(B.ids.size()), d_poa_q.reserve(B.qpool.size());
+    d_poa_rows.reserve(B.rows.size()), d_poa_preds.reserve(B.preds.size());
+    d_poa_s.reserve(B.cells), d_poa_f.reserve(B.cells), d_poa_route.reserve(B.route_words);
+    h2d(d_poa_jobs.p, B.jobs.data(), B.jobs.size() * sizeof(PoaJobDev), st);
+    h2d(d_poa_ids.p, B.ids.data(), B.ids.size() * sizeof(uint32_t), st);
+    h2d(d_poa_q.p, B.qpool.data(), B.qpool.size(), st);
+    h2d(d_poa_rows.p, B.rows.data(), B.rows.size() * sizeof(PoaRowDev), st);
+    h2d(d_poa_preds.p, B.preds.data(), B.preds.size() * sizeof(uint16_t), st);
+    mark(kEvTailBegin, st);
+    NDGPU_DBG(st, "poa: round %zu, %zu + %zu jobs, %llu cells", r, B.n_wave, n_group, (unsigned long long)B.cells);
+    launch_poa_align(d_poa_jobs.p, d_poa_ids.p, (int)B.n_wave, d_poa_ids.p + B.n_wave, (int)n_group, d_poa_q.p, d_poa_rows.p, d_poa_preds.p,
+                     d_poa_s.p, d_poa_f.p, d_poa_route.p, st);
+    HIP_CHECK(hipGetLastError());
+    mark(kEvTailEnd, st);
+    B.routes.resize(B.route_words);
+    d2h(B.jobs.data(), d_poa_jobs.p, B.jobs.size() * sizeof(PoaJobDev), st);
+    d2h(B.routes.data(), d_poa_route.p, B.route_words * sizeof(uint32_t), st);
+    sync_drain(st);
+    stats.poa_ms += ms(kEvTailBegin, kEvTailEnd);
+    stats.poa_launches += (B.n_wave ? 1 : 0) + (n_group ? 1 : 0);
+    stats.poa_cells += B.cells;
+}
+
+// Graph growth and the new order, on the host: the slice's routes threaded through their graphs.
+void DeviceAligner::State::thread_routes(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r) {
+    poa_each(slice, [&](size_t i) {
+        PoaProb &p = B.probs[i];
+        const PoaJobDev &J = B.jobs[p.job];
+        const std::string &q = reqs[i]->seqs[r];
+        if (J.route_len > J.X + J.Y) {  // (the walk did not reach the origin: cannot happen)
+            fprintf(stderr, "[ndgpu] FATAL: POA route of a %u x %u problem did not end\n", J.X, J.Y);
+            abort();
+        }
+        p.g.set_route(B.routes.data() + J.route_off, J.route_len);
+        if (!p.g.thread((int)r, q.c_str(), (int)q.size())) p.live = false, reqs[i]->failed = true;
+    });
+}
+
+void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    const State::Phase phase(S);
+    const PoaHooks &hk = hooks_of<PoaHooks>();
+    const uint64_t budget = hk.budget_set ? hk.budget : (uint64_t)(S.trace_budget_bytes / 6);
+    PoaBatch B(n);
+    const size_t max_seqs = S.admit_poa(reqs, n, budget, B);
+    std::vector<size_t> round_ids, slice, dropped;
+    std::vector<PoaLoad> load;
     for (size_t r = 1; r < max_seqs; r++) {
         round_ids.clear();
         for (size_t i = 0; i < n; i++)
-            if (probs[i].live && reqs[i]->seqs.size() > r) round_ids.push_back(i);
+            if (B.probs[i].live && reqs[i]->seqs.size() > r) round_ids.push_back(i);
         if (round_ids.empty()) break;
         S.stats.poa_rounds++;
-        host_for(round_ids, [&](size_t i) {
-            Prob &p = probs[i];
-            p.g.export_rows(p.rows);
-            p.cells = (uint64_t)(p.g.rows() + 1) * (uint64_t)(reqs[i]->seqs[r].size() + 1);
-        });
+        S.export_rows(B, reqs, round_ids, r, load);
         for (size_t a = 0; a < round_ids.size();) {
-            // ---- a slice of the round: as many jobs as fit the budget; a job over the budget on its own is declined
-            slice.clear();
-            uint64_t cells = 0;
-            for (; a < round_ids.size(); a++) {
-                Prob &p = probs[round_ids[a]];
-                if (p.cells > budget || p.g.rows() > 65535) {
-                    p.live = false;
-                    continue;
-                }
-                if (!slice.empty() && cells + p.cells > budget) break;
-                cells += p.cells;
-                slice.push_back(round_ids[a]);
-            }
+            a = next_poa_slice(load, a, budget, slice, dropped);
+            for (size_t k : dropped) B.probs[round_ids[k]].live = false;  // (over the budget or the row limit on its own: declined)
+            for (size_t &k : slice) k = round_ids[k];
             if (slice.empty()) continue;
-            jobs.clear(), rows.clear(), preds.clear(), qpool.clear();
-            std::vector<uint32_t> ids_wave, ids_group;
-            uint64_t cell_at = 0, route_at = 0;
-            for (size_t i : slice) {
-                Prob &p = probs[i];
-                const std::string &q = reqs[i]->seqs[r];
-                PoaJobDev J;
-                memset(&J, 0, sizeof(J));
-                J.X = (uint32_t)p.g.rows(), J.Y = (uint32_t)q.size();
-                J.q_off = qpool.size(), J.row_off = rows.size(), J.pred_off = preds.size();
-                J.cell_off = cell_at, J.route_off = route_at;
-                cell_at += p.cells, route_at += (uint64_t)J.X + J.Y;
-                qpool.insert(qpool.end(), q.begin(), q.end());
-                for (uint32_t x = 0; x < J.X; x++) {
-                    PoaRowDev rw;
-                    rw.pred_off = p.rows.pred_off[x];
-                    rw.n_pred = (uint16_t)(p.rows.pred_off[x + 1] - p.rows.pred_off[x]);
-                    rw.base = p.rows.base[x], rw.sink = p.rows.sink[x];
-                    rows.push_back(rw);
-                }
-                preds.insert(preds.end(), p.rows.preds.begin(), p.rows.preds.end());
-                p.job = (uint32_t)jobs.size();
-                const bool group = form ? form == 2 : J.Y >= group_min;
-                (group ? ids_group : ids_wave).push_back(p.job);
-                jobs.push_back(J);
-            }
-            ids = ids_wave;
-            ids.insert(ids.end(), ids_group.begin(), ids_group.end());
-            S.d_poa_jobs.reserve(jobs.size()), S.d_poa_ids.reserve(ids.size()), S.d_poa_q.reserve(qpool.size());
-            S.d_poa_rows.reserve(rows.size()), S.d_poa_preds.reserve(preds.size());
-            S.d_poa_s.reserve(cell_at), S.d_poa_f.reserve(cell_at), S.d_poa_route.reserve(route_at);
-            S.h2d(S.d_poa_jobs.p, jobs.data(), jobs.size() * sizeof(PoaJobDev), st);
-            S.h2d(S.d_poa_ids.p, ids.data(), ids.size() * sizeof(uint32_t), st);
-            S.h2d(S.d_poa_q.p, qpool.data(), qpool.size(), st);
-            S.h2d(S.d_poa_rows.p, rows.data(), rows.size() * sizeof(PoaRowDev), st);
-            S.h2d(S.d_poa_preds.p, preds.data(), preds.size() * sizeof(uint16_t), st);
-            HIP_CHECK(hipEventRecord(S.evs[5], st));
-            NDGPU_DBG(st, "poa: round %zu, %zu + %zu jobs, %llu cells", r, ids_wave.size(), ids_group.size(), (unsigned long long)cell_at);
-            launch_poa_align(S.d_poa_jobs.p, S.d_poa_ids.p, (int)ids_wave.size(), S.d_poa_ids.p + ids_wave.size(), (int)ids_group.size(),
-                             S.d_poa_q.p, S.d_poa_rows.p, S.d_poa_preds.p, S.d_poa_s.p, S.d_poa_f.p, S.d_poa_route.p, st);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(S.evs[6], st));
-            routes.resize(route_at);
-            S.d2h(jobs.data(), S.d_poa_jobs.p, jobs.size() * sizeof(PoaJobDev), st);
-            S.d2h(routes.data(), S.d_poa_route.p, route_at * sizeof(uint32_t), st);
-            S.sync_drain(st);
-            S.stats.poa_ms += ms_between(S.evs[5], S.evs[6]);
-            S.stats.poa_launches += (ids_wave.empty() ? 0 : 1) + (ids_group.empty() ? 0 : 1);
-            S.stats.poa_cells += cell_at;
-            // ---- graph growth and the new order, on the host
-            host_for(slice, [&](size_t i) {
-                Prob &p = probs[i];
-                const PoaJobDev &J = jobs[p.job];
-                const std::string &q = reqs[i]->seqs[r];
-                if (J.route_len > J.X + J.Y) {  // (the walk did not reach the origin: cannot happen)
-                    fprintf(stderr, "[ndgpu] FATAL: POA route of a %u x %u problem did not end\n", J.X, J.Y);
-                    abort();
-                }
-                p.g.set_route(routes.data() + J.route_off, J.route_len);
-                if (!p.g.thread((int)r, q.c_str(), (int)q.size())) p.live = false, reqs[i]->failed = true;
-            });
+            S.stage_poa_slice(B, reqs, slice, r);
+            S.launch_poa_slice(B, r);
+            S.thread_routes(B, reqs, slice, r);
         }
     }
     round_ids.clear();
     for (size_t i = 0; i < n; i++)
-        if (probs[i].live) round_ids.push_back(i);
-    host_for(round_ids, [&](size_t i) {
-        reqs[i]->out = probs[i].g.consensus((int)reqs[i]->seqs.size());
+        if (B.probs[i].live) round_ids.push_back(i);
+    S.poa_each(round_ids, [&](size_t i) {
+        reqs[i]->out = B.probs[i].g.consensus((int)reqs[i]->seqs.size());
         reqs[i]->done = true;
     });
     for (size_t i = 0; i < n; i++)
         if (!reqs[i]->done && !reqs[i]->failed) S.stats.poa_declined++;
+}
+
+// The ranking K14 left in a region's record (ranked != 0), for whoever asked: run_rank's problems, run_extract's regions.
+template <typename Tail>
+static void read_ranking(const RegionDev &g, uint8_t (&order)[40], uint16_t (&kscore)[40], Tail &tail) {
+    memcpy(order, g.rank_order, sizeof(order));
+    memcpy(kscore, g.rank_kscore, sizeof(kscore));
+    tail = g.rank_tail;
 }
 
 // ---- the 8-mer ranking as a batch (K14): the problems' sequences go up as one pool, laid out as K11 leaves a region's candidates
@@ -2224,25 +2213,22 @@ void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
         S.d_strpool.reserve(pool.size() + 1);
         S.h2d(S.d_regions.p, regs.data(), regs.size() * sizeof(RegionDev), st);
         S.h2d(S.d_strpool.p, pool.data(), pool.size(), st);
-        HIP_CHECK(hipEventRecord(S.evs[5], st));
+        S.mark(State::kEvTailBegin, st);
         NDGPU_DBG(st, "rank: %zu problems, %zu bytes", regs.size(), pool.size());
         launch_lq_rank(S.d_regions.p, S.d_strpool.p, (unsigned long long)pool.size(), 1u, (int)regs.size(), st);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(S.evs[6], st));
+        S.mark(State::kEvTailEnd, st);
         S.d2h(regs.data(), S.d_regions.p, regs.size() * sizeof(RegionDev), st);
         S.sync_drain(st);
-        S.stats.rank_ms += ms_between(S.evs[5], S.evs[6]);
+        S.stats.rank_ms += S.ms(State::kEvTailBegin, State::kEvTailEnd);
         S.stats.rank_launches++;
         for (size_t i = a; i < b; i++) {
             const RegionDev &g = regs[i - a];
-            RankReq &rq = reqs[i];
             if (!g.ranked) {  // (cannot happen: every problem has 1..40 sequences inside the pool)
-                fprintf(stderr, "[ndgpu] FATAL: the ranking kernel left a problem of %d sequences\n", rq.n);
+                fprintf(stderr, "[ndgpu] FATAL: the ranking kernel left a problem of %d sequences\n", reqs[i].n);
                 abort();
             }
-            memcpy(rq.order, g.rank_order, sizeof(rq.order));
-            memcpy(rq.kscore, g.rank_kscore, sizeof(rq.kscore));
-            rq.tail = g.rank_tail;
+            read_ranking(g, reqs[i].order, reqs[i].kscore, reqs[i].tail);
             S.stats.rank_jobs++;
             S.stats.rank_tail += g.rank_tail;
         }
@@ -2250,91 +2236,85 @@ void DeviceAligner::run_rank(RankReq *reqs, size_t n) {
     }
 }
 
-void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
-    State &S = *s_;
-    const State::Phase phase(S);
-    hipStream_t st = S.stream;
+// ---- candidate extraction (K11) of the piles run_main left on the device, with the ranking of their regions (K14) behind it where
+// a pile asks for it.  run_extract (below) is: regions_of -> extract_into_pool -> the NDGPU_TRACE line -> fill_regions.
+
+// Every region of every pile as a device record, in the piles' order.
+static std::vector<RegionDev> regions_of(ExtractPile **ep, size_t n, bool offer_rank) {
     std::vector<RegionDev> regs;
-    bool rank = false;   // K14 behind K11: some pile of this launch takes a ranking
     for (size_t i = 0; i < n; i++)
         for (RegionReq &r : ep[i]->regions) {
             RegionDev g;
             memset(&g, 0, sizeof(g));
             g.pile = (uint32_t)ep[i]->slot;
-            g.start = r.start;
-            g.end = r.end;
-            g.max_len = r.max_len;
+            g.start = r.start, g.end = r.end, g.max_len = r.max_len;
             g.max_len0 = r.max_len0 ? r.max_len0 : r.max_len;
             g.want_rank = offer_rank && ep[i]->rank ? 1 : 0;
-            rank = rank || g.want_rank;
             r.ranked = false;
             regs.push_back(g);
         }
-    if (regs.empty()) return;
-    S.d_regions.reserve(regs.size());
-    S.d_cursor.reserve(2);
-    // first guess of the string pool: 64 MB, or less when the regions cannot produce that much (<= 40 candidates of <= max_len
-    // characters each); the kernel reports what it needed and a pool that was too small is retaken at the exact size
+    return regs;
+}
+
+// K11 (and K14 behind it, if rank) until the string pool held everything: leaves the records in regs and the strings in hstr, returns
+// the number of launches that came back short.  First guess of the pool: 64 MB, or less when the regions cannot
+// produce that much (<= 40 candidates of <= max_len characters each) -- or NDGPU_EXTRACT_POOL; what the context holds already wins if
+// larger.  The kernel reports what it needed and a pool that was too small is retaken at the exact size.
+unsigned DeviceAligner::State::extract_into_pool(std::vector<RegionDev> &regs, bool rank, std::vector<char> &hstr) {
+    hipStream_t st = stream;
+    d_regions.reserve(regs.size());
+    d_cursor.reserve(2);
     size_t bound = (size_t)1 << 20;
     for (const RegionDev &g : regs) bound += (size_t)40 * ((size_t)g.max_len + 64);
-    size_t cap = std::max<size_t>(S.d_strpool.cap, std::min<size_t>((size_t)64 << 20, bound));
-    std::vector<char> hstr;
-    for (;;) {
-        S.d_strpool.reserve(cap);
-        cap = S.d_strpool.cap;
-        S.h2d(S.d_regions.p, regs.data(), regs.size() * sizeof(RegionDev), st);
-        HIP_CHECK(hipMemsetAsync(S.d_cursor.p, 0, sizeof(unsigned long long), st));
-        HIP_CHECK(hipEventRecord(S.evs[5], st));
+    const ExtractHooks &hk = hooks_of<ExtractHooks>();
+    size_t cap = std::max<size_t>(d_strpool.cap, hk.pool_set ? hk.pool : std::min<size_t>((size_t)64 << 20, bound));
+    for (unsigned retaken = 0;; retaken++) {
+        d_strpool.reserve(cap);
+        cap = d_strpool.cap;
+        h2d(d_regions.p, regs.data(), regs.size() * sizeof(RegionDev), st);
+        HIP_CHECK(hipMemsetAsync(d_cursor.p, 0, sizeof(unsigned long long), st));
+        mark(kEvTailBegin, st);
         NDGPU_DBG(st, "extract: %zu regions", regs.size());
-        launch_extract(S.d_piles.p, S.d_reads.p, S.d_acc.p, S.d_tags.p, S.d_colidx.p, S.d_regions.p, S.d_strpool.p,
-                       S.d_cursor.p, (unsigned long long)cap, (int)regs.size(), st);
-        HIP_CHECK(hipEventRecord(S.evs[6], st));
+        launch_extract(d_piles.p, d_reads.p, d_acc.p, d_tags.p, d_colidx.p, d_regions.p, d_strpool.p, d_cursor.p, (unsigned long long)cap,
+                       (int)regs.size(), st);
+        mark(kEvTailEnd, st);
         // the ranking of the regions with five or more candidates (fewer: the engine drops the region), on the strings where K11
         // left them; with a pool that was too small K14 leaves the regions it cannot read and runs again with K11
         if (rank) {
-            launch_lq_rank(S.d_regions.p, S.d_strpool.p, (unsigned long long)cap, 5u, (int)regs.size(), st);
-            HIP_CHECK(hipEventRecord(S.evs[7], st));
+            launch_lq_rank(d_regions.p, d_strpool.p, (unsigned long long)cap, 5u, (int)regs.size(), st);
+            mark(kEvExtractRanked, st);
         }
         unsigned long long used = 0;
-        S.d2h(&used, S.d_cursor.p, sizeof(used), st);
-        S.sync_drain(st);
-        S.stats.extract_ms += ms_between(S.evs[5], S.evs[6]);
+        d2h(&used, d_cursor.p, sizeof(used), st);
+        sync_drain(st);
+        stats.extract_ms += ms(kEvTailBegin, kEvTailEnd);
         if (rank) {
-            S.stats.rank_ms += ms_between(S.evs[6], S.evs[7]);
-            S.stats.rank_launches++;
+            stats.rank_ms += ms(kEvTailEnd, kEvExtractRanked);
+            stats.rank_launches++;
         }
         if (used <= cap) {
             hstr.resize((size_t)used + 1);
-            S.d2h(regs.data(), S.d_regions.p, regs.size() * sizeof(RegionDev), st);
-            if (used) S.d2h(hstr.data(), S.d_strpool.p, (size_t)used, st);
-            S.sync_drain(st);
-            break;
+            d2h(regs.data(), d_regions.p, regs.size() * sizeof(RegionDev), st);
+            if (used) d2h(hstr.data(), d_strpool.p, (size_t)used, st);
+            sync_drain(st);
+            return retaken;
         }
         cap = (size_t)used + ((size_t)16 << 20);  // pool too small: rerun with the exact size
     }
-    {
-        uint64_t n_ranked = 0, n_tail = 0;
-        for (const RegionDev &g : regs) n_ranked += g.ranked ? 1 : 0, n_tail += g.ranked ? g.rank_tail : 0;
-        S.stats.rank_jobs += n_ranked, S.stats.rank_tail += n_tail;
-        static const bool trace = getenv("NDGPU_TRACE") != nullptr;
-        if (trace)
-            fprintf(stderr, "[ndgpu] extract: %zu regions, %llu ranked on the device, %llu tail passes\n", regs.size(),
-                    (unsigned long long)n_ranked, (unsigned long long)n_tail);
-    }
+}
+
+// The records and their strings into the callers' regions: piles dealt to the context's host threads.
+static void fill_regions(ExtractPile **ep, size_t n, const std::vector<RegionDev> &regs, const std::vector<char> &hstr, int host_threads) {
     std::vector<size_t> first(n + 1, 0);
     for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + ep[i]->regions.size();
-    auto fill = [&](size_t a, size_t b) {
+    host_ranges(n, n < 32 || host_threads <= 1, host_threads, n / 8, [&](size_t a, size_t b) {
         for (size_t i = a; i < b; i++) {
             size_t k = first[i];
             for (RegionReq &r : ep[i]->regions) {
                 const RegionDev &g = regs[k++];
                 r.n_large = g.n_large;
                 r.ranked = g.ranked != 0;
-                if (r.ranked) {
-                    r.rank_tail = g.rank_tail;
-                    memcpy(r.rank_order, g.rank_order, sizeof(r.rank_order));
-                    memcpy(r.rank_kscore, g.rank_kscore, sizeof(r.rank_kscore));
-                }
+                if (r.ranked) read_ranking(g, r.rank_order, r.rank_kscore, r.rank_tail);
                 r.cands.resize(g.n_ok);
                 r.cand_rank.resize(g.n_ok);
                 for (uint32_t c = 0; c < g.n_ok; c++) {
@@ -2343,8 +2323,28 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
                 }
             }
         }
-    };
-    host_ranges(n, n < 32 || S.host_threads <= 1, S.host_threads, n / 8, fill);
+    });
+}
+
+void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
+    State &S = *s_;
+    const State::Phase phase(S);
+    std::vector<RegionDev> regs = regions_of(ep, n, offer_rank);
+    if (regs.empty()) return;
+    // K14 behind K11: some pile of this launch takes a ranking
+    const bool rank = std::any_of(regs.begin(), regs.end(), [](const RegionDev &g) { return g.want_rank != 0; });
+    std::vector<char> hstr;
+    const unsigned retaken = S.extract_into_pool(regs, rank, hstr);
+    uint64_t n_ranked = 0, n_tail = 0;
+    for (const RegionDev &g : regs) n_ranked += g.ranked ? 1 : 0, n_tail += g.ranked ? g.rank_tail : 0;
+    S.stats.rank_jobs += n_ranked, S.stats.rank_tail += n_tail;
+    if (trace_on()) {
+        char again[48] = "";  // (only a pool that was retaken says so: NDGPU_EXTRACT_POOL, or a bound beyond 64 MB)
+        if (retaken) snprintf(again, sizeof(again), ", pool retaken %u", retaken);
+        fprintf(stderr, "[ndgpu] extract: %zu regions, %llu ranked on the device, %llu tail passes%s\n", regs.size(),
+                (unsigned long long)n_ranked, (unsigned long long)n_tail, again);
+    }
+    fill_regions(ep, n, regs, hstr, S.host_threads);
 }
 
 }  // namespace ndgpu

@@ -154,7 +154,8 @@ struct PileDev {
 };
 
 // ---- low-quality-region rounds (K12, lq_kernels.hip) ----
-struct LqPieceDev {          // one (row, region) slot of a pile's round, row-major (30 rows x n_regions)
+constexpr uint32_t kLqRoundRows = 30;  // rows of a round: the candidates the second MSA takes per region
+struct LqPieceDev {          // one (row, region) slot of a pile's round, row-major (kLqRoundRows rows x n_regions)
     int32_t task;            // index into the round's AlnTask / AlnOut tables, -1: nothing aligned ('M' row)
     uint32_t sl;             // length of the region's pseudo-seed
 };

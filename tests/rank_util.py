@@ -283,7 +283,7 @@ elif what == "piles":           # fixtures through correct_batch, grouped by the
 
 
 def child(lib, what, *args, timeout=1500, **env):
-    e = {k: v for k, v in os.environ.items() if not k.startswith(("NDGPU_RANK", "NDGPU_POA", "NDGPU_TRACE"))}   # no switch of the caller's reaches the child
+    e = {k: v for k, v in os.environ.items() if not k.startswith(("NDGPU_RANK", "NDGPU_POA", "NDGPU_TRACE", "NDGPU_EXTRACT"))}   # no switch of the caller's reaches the child
     e.update(env)
     if lib == "simt":
         e.setdefault("NDGPU_CONTEXTS", "1")
@@ -291,5 +291,20 @@ def child(lib, what, *args, timeout=1500, **env):
                          env=e, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads(out.stdout.strip().splitlines()[-1])
-    r["extract_launches"] = sum(1 for ln in out.stderr.splitlines() if ln.startswith("[ndgpu] extract: "))   # (NDGPU_TRACE)
+    lines = [ln for ln in out.stderr.splitlines() if ln.startswith("[ndgpu] extract: ")]   # (NDGPU_TRACE)
+    r["extract_launches"] = len(lines)
+    r["pool_retaken"] = sum(int(ln.rsplit(", pool retaken ", 1)[1]) for ln in lines if ", pool retaken " in ln)   # K11 launches that came back short
     return r
+
+
+def check_pool_retake(short, plain):
+    """Two runs of the same piles with the ranking behind K11, `short` under NDGPU_EXTRACT_POOL=1 (the first guess of K11's string
+    pool is one byte: K11 writes nothing beyond it, K14 leaves the regions it cannot read, and DeviceAligner::run_extract takes both
+    again with the size K11 reported), `plain` without: the same records and the same regions ranked, and only `short` retook."""
+    assert short["n"] == plain["n"] >= 12 and short["bad"] == [] and plain["bad"] == [], (short["bad"], plain["bad"])
+    assert short["rec"] == plain["rec"]    # length, float32 identity bits, bases
+    assert short["pool_retaken"] >= 1 and plain["pool_retaken"] == 0, (short["pool_retaken"], plain["pool_retaken"])
+    assert short["extract_launches"] == plain["extract_launches"] > 0
+    for k in ("rank_jobs", "rank_tail"):
+        assert short["stats"][k] == plain["stats"][k] > 0, (k, short["stats"], plain["stats"])
+    assert short["stats"]["rank_launches"] == plain["stats"]["rank_launches"] + short["pool_retaken"]    # K14 runs again with K11

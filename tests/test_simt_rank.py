@@ -37,14 +37,15 @@ def test_rank_batch_on_the_interpreter(env):
 @pytest.fixture(scope="module")
 def pile_runs():
     """The golden piles and the rank_piles cases of nine or fewer reads through correct_batch: with the device ranking, without the
-    switch, and with the switch while the backend offers nothing."""
-    envs = [dict(NDGPU_RANK_DEVICE="1", NDGPU_TRACE="1"), {}, dict(NDGPU_RANK_DEVICE="1", NDGPU_RANK_HOST="1")]
-    with ThreadPoolExecutor(3) as ex:
+    switch, with the switch while the backend offers nothing, and like the first with a string pool of one byte to start with."""
+    envs = [dict(NDGPU_RANK_DEVICE="1", NDGPU_TRACE="1"), {}, dict(NDGPU_RANK_DEVICE="1", NDGPU_RANK_HOST="1"),
+            dict(NDGPU_RANK_DEVICE="1", NDGPU_TRACE="1", NDGPU_EXTRACT_POOL="1")]
+    with ThreadPoolExecutor(4) as ex:
         return list(ex.map(lambda e: rank_util.child("simt", "piles", "golden,rank", 9, **e), envs))
 
 
 def test_engine_with_its_ranking_on_the_device_and_on_the_host(pile_runs):
-    dev, plain, host = pile_runs
+    dev, plain, host = pile_runs[:3]
     assert dev["n"] == plain["n"] == host["n"] >= 30
     assert dev["bad"] == [] and plain["bad"] == [] and host["bad"] == [], (dev["bad"], plain["bad"], host["bad"])   # the reference's answers
     assert dev["rec"] == plain["rec"] == host["rec"]    # length, float32 identity bits, bases
@@ -52,6 +53,11 @@ def test_engine_with_its_ranking_on_the_device_and_on_the_host(pile_runs):
     assert st["rank_jobs"] > 0 and st["rank_tail"] > 0 and 0 < st["rank_launches"] <= dev["extract_launches"], (st, dev["extract_launches"])
     assert plain["stats"]["rank_jobs"] == 0 and plain["stats"]["rank_launches"] == 0, plain["stats"]
     assert host["stats"]["rank_jobs"] == 0 and host["stats"]["rank_launches"] == 0, host["stats"]
+
+
+def test_extract_retakes_a_string_pool_that_was_too_small(pile_runs):
+    """NDGPU_EXTRACT_POOL=1 (one context, as every interpreted run): the retake path of DeviceAligner::run_extract."""
+    rank_util.check_pool_retake(pile_runs[3], pile_runs[0])
 
 
 def test_a_job_of_41_sequences_and_an_empty_batch(native_lib):

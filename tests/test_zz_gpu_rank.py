@@ -87,3 +87,11 @@ def test_rank_piles_fixture_on_the_device():
     assert whole["bad"] == [] and small["bad"] == []
     assert whole["stats"]["rank_jobs"] >= 100 and whole["stats"]["rank_tail"] >= 6, whole["stats"]
     assert small["stats"]["rank_tail"] >= 1 and small["n"] < whole["n"], small["stats"]
+
+
+def test_extract_retakes_a_string_pool_that_was_too_small():
+    """The piles of nine or fewer reads of rank_piles.npz on one context, each run a process of its own (the pool only grows, so only
+    a process's first calls can find it short): NDGPU_EXTRACT_POOL=1 takes the retake path of DeviceAligner::run_extract."""
+    env = dict(NDGPU_RANK_DEVICE="1", NDGPU_CONTEXTS="1", NDGPU_TRACE="1")
+    short = rank_util.child("native", "piles", "rank", 9, NDGPU_EXTRACT_POOL="1", **env)
+    rank_util.check_pool_retake(short, rank_util.child("native", "piles", "rank", 9, **env))
