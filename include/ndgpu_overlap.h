@@ -215,6 +215,50 @@ int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const int64_t *n
                              int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
                              ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats);
 
+/* ---- the `.ovl` codec on the device (K17; csrc/ovlsort_kernels.hip): what ndgpu_ovl_encode / ndgpu_ovl_decode do, as scans ----
+ * A value of the host loop, v = (v << 7) | (c & 127) in 32 bits, depends on its terminator and the 4 bytes in front of it only, so
+ * the device form equals the loop on every byte string: nothing declines.  Decode: terminators counted per 16 bytes, a prefix gives
+ * every value its index, value j of a file = field j % 8 of record j / 8, the names are prefix sums of the signed deltas modulo 2^32,
+ * restarted per file.  Encode: one lane per record, sizes, a prefix, the bytes staged per wavefront and stored once.
+ *   decode_ms, encode_ms             HIP-event time of the decode (image upload -- with the page faults of a memory-mapped file --, kernels, scans)
+ *                                    and of the encode (kernels, scan)
+ *   records                          records decoded / encoded
+ *   bytes_in, bytes_out              size of what the call was given and of what it made (images or 32-byte records)
+ *   bytes_uploaded, bytes_downloaded `.ovl` images and records copied to / from the device (not the few control words)
+ *   host_decodes                     files the host loop decoded (flags bit 0, a sort in seed ranges, a declined admission) */
+typedef struct ndgpu_ovl_codec_stats {
+	double decode_ms, encode_ms;
+	uint64_t records, bytes_in, bytes_out, bytes_uploaded, bytes_downloaded, host_decodes;
+} ndgpu_ovl_codec_stats;
+/* n_files images (bufs[f], n_bytes[f]) -> all their records in one malloc'd block (ndgpu_ovl_free), file after file; every file
+ * starts from prev = {0, 0}.  n_per_file[f] = its whole records, consumed[f] (may be NULL) = the offset behind the last of them (a
+ * trailing partial record is left alone, as by ndgpu_ovl_decode).  flags bit 0: the host loop per file.  stats may be NULL.
+ * Returns the number of records; -1 no device, -2 a device operation failed (ndgpu_ovl_last_error), -4 a bad argument.  On an
+ * error *recs stays NULL and nothing else is written. */
+int64_t ndgpu_ovl_decode_batch(const uint8_t *const *bufs, const uint64_t *n_bytes, int32_t n_files, int32_t flags, ndgpu_ovl_rec **recs,
+                               int64_t *n_per_file, uint64_t *consumed, ndgpu_ovl_codec_stats *stats);
+/* ndgpu_ovl_encode with the output allocated: *out = the bytes, malloc'd at their exact size (ndgpu_ovl_free); prev[2] is read and
+ * updated as there.  flags bit 0: the host loop.  Returns the byte count, or an error code as above (prev untouched, *out NULL). */
+int64_t ndgpu_ovl_encode_batch(const ndgpu_ovl_rec *recs, int64_t n, uint32_t prev[2], int32_t flags, uint8_t **out,
+                               ndgpu_ovl_codec_stats *stats);
+/* The `ovl_sort` command in one device pass: the step-1 files as images in, the image of `sorted.ovl` and the `.bl` verdicts out
+ * (hq != 0: the -H filter).  The images are decoded into the sort's own buffer and every seed range's sorted records are encoded
+ * where they lie, `prev` carried from range to range: no 32-byte record crosses the bus.  A sort in seed ranges (see ndgpu_ovl_sort)
+ * reads its files from host memory: they are decoded by the host loop (codec_stats->host_decodes), the ranges still encoded on the
+ * device.  flags bit 0: host decode, ndgpu_ovl_sort, host encode.  Everything handed out is malloc'd (ndgpu_ovl_free).  Returns the
+ * number of sorted records, ndgpu_ovl_sort's error codes, or -4 for a bad argument. */
+int64_t ndgpu_ovl_sort_images(const uint8_t *const *bufs, const uint64_t *n_bytes, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                              int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, int32_t flags, uint8_t **image,
+                              uint64_t *image_bytes, uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *sort_stats,
+                              ndgpu_ovl_codec_stats *codec_stats);
+/* ndgpu_admit_piles on the image of a sorted.ovl: the bytes are uploaded and decoded on the device, K16 admits the records.  A stream
+ * with an irregular group (admit_stats->groups_declined) is decoded by the host loop and answered by ndgpu_assemble_piles, as is
+ * flags bit 0.  Returns the number of admitted records, or the error codes of ndgpu_admit_piles, -4 for a bad argument. */
+int64_t ndgpu_admit_piles_image(const uint8_t *buf, uint64_t n_bytes, uint32_t n_ids, uint32_t min_len_seed, uint32_t min_len_aln,
+                                uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, int32_t flags,
+                                uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                ndgpu_ovl_admit_stats *admit_stats, ndgpu_ovl_codec_stats *codec_stats);
+
 /* ---- read ingestion: the 2-bit packing of `seq_dump` (seq2bit, lib/bseq.c:114-139; called from util/seq_dump.c:36-41) ----
  * Read i is the lens[i] ASCII bytes at ascii + ascii_off[i]; its ceil(lens[i]/16) words go to words + word_off[i] (word_off ascending,
  * reads back to back).  Bytes other than ACGTU (either case) are coded 4 and OR-ed in as the reference does, so they disturb the low

@@ -96,6 +96,12 @@ def read_db_from_sets(sets):
     return np.concatenate(chunks), word_off, lens
 
 
+def _keep_encode(recs) -> bytes:
+    """The `.ovl` bytes of a --keep file: the host encoder, or under NDGPU_CODEC_DEVICE=1 the device's (ndgpu_ovl_encode_batch)."""
+    prev = np.zeros(2, dtype=np.uint32)
+    return overlap.encode_device(recs, prev) if overlap.codec_device() else overlap.encode(recs, prev)
+
+
 def run(argv) -> int:
     ap = argparse.ArgumentParser(prog="correct_stage", description=__doc__.split("\n")[0])
     ap.add_argument("-d", dest="dir", required=True, help="seq_dump output directory (input.seed.*.2bit, input.part.*.2bit)")
@@ -167,7 +173,7 @@ def run(argv) -> int:
             os.makedirs(a.keep, exist_ok=True)
             name = "%s.%d.ovl" % (os.path.basename(seed_paths[i]), k)
             with open(os.path.join(a.keep, name), "wb") as f:
-                f.write(overlap.encode(recs, np.zeros(2, dtype=np.uint32)))
+                f.write(_keep_encode(recs))
         if kind == "seed" and j == len(seeds) - 1:
             caches.pop(i).close()                         # seed file i is not a target again
     for c in caches.values():
@@ -197,7 +203,7 @@ def run(argv) -> int:
         if a.keep:
             so = os.path.join(a.keep, "input.seed.%s.sorted.ovl" % tag)
             with open(so, "wb") as f:
-                f.write(overlap.encode(srt, np.zeros(2, dtype=np.uint32)))
+                f.write(_keep_encode(srt))
             with open(so + ".bl", "w") as f:
                 for rid, kind in bl:
                     f.write("%d %s\n" % (rid, kind))

@@ -51,6 +51,20 @@ void launch_admit_emit(const OvlRec *recs, const uint64_t *off, uint32_t n_group
                        const uint32_t *kept, const uint64_t *rec_off, const uint64_t *pile_idx, uint32_t *recs8, uint64_t *pile_off,
                        uint32_t *seeds, hipStream_t s);
 
+// K17, the `.ovl` codec (csrc/ovlsort_kernels.hip)
+uint32_t codec_tile_bytes();
+void launch_codec_count(const uint8_t *img, const uint64_t *start, const uint64_t *bytes, const uint64_t *tile0, const uint32_t *tile_file,
+                        uint64_t n_tiles, uint32_t *tile_cnt, hipStream_t s);
+void launch_codec_file_plan(const uint64_t *tile0, const uint64_t *tile_first, uint32_t n_files, uint64_t *n_rec, hipStream_t s);
+void launch_codec_emit(const uint8_t *img, const uint64_t *start, const uint64_t *bytes, const uint64_t *tile0, const uint32_t *tile_file,
+                       uint64_t n_tiles, const uint64_t *tile_first, const uint64_t *n_rec, const uint64_t *rec_base, OvlRec *recs,
+                       uint64_t *consumed, hipStream_t s);
+void launch_codec_delta(const OvlRec *recs, uint64_t n, uint32_t *dq, uint32_t *dt, hipStream_t s);
+void launch_codec_records(OvlRec *recs, uint64_t n, const uint32_t *dq, const uint32_t *dt, const uint64_t *sq, const uint64_t *st,
+                          const uint64_t *rec_base, uint32_t n_files, hipStream_t s);
+void launch_codec_size(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, uint32_t *len, hipStream_t s);
+void launch_codec_write(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, const uint64_t *off, uint8_t *out, hipStream_t s);
+
 struct SortRun {
 	hipStream_t st = nullptr;
 	Scratch tmp{256};
@@ -146,6 +160,164 @@ struct Admission {
 	}
 };
 
+// ---- K17, the `.ovl` codec on the device: the host side ----
+// the byte images of a call's files, as the caller holds them
+struct ImageSet {
+	const uint8_t *const *bufs;
+	const uint64_t *n_bytes;
+	int32_t n_files;
+	uint64_t total() const { uint64_t t = 0; for (int f = 0; f < n_files; ++f) t += n_bytes[f]; return t; }
+};
+
+// the host loop over every file (the cross-check, and the decode of a call that sorts out of core): records in file order
+static void decode_on_host(const ImageSet &I, RecOut &out, std::vector<int64_t> &n_per_file, uint64_t *consumed)
+{
+	n_per_file.assign((size_t)I.n_files, 0);
+	for (int f = 0; f < I.n_files; ++f) {
+		const uint64_t cap = I.n_bytes[f] / 8;   // a record is 8 bytes at least
+		OvlRec *const at = out.grow(cap);
+		uint32_t prev[2] = {0, 0};
+		uint64_t used = 0;
+		const int64_t n = cap ? ndgpu_ovl_decode(I.bufs[f], I.n_bytes[f], prev, (uint32_t*)at, (int64_t)cap, &used) : 0;
+		for (int64_t i = 0; i < n; ++i) {   // decode_ovl's field order -> the record's
+			const uint32_t *o = (const uint32_t*)(at + i);
+			const OvlRec r = {o[1], o[0], o[2], o[3], o[4], o[5], o[6], o[7]};
+			at[i] = r;
+		}
+		out.n -= cap - (uint64_t)n;
+		n_per_file[(size_t)f] = n;
+		if (consumed) consumed[f] = used;
+	}
+}
+
+// Decode in two steps, so that a caller can size its buffers (or turn to another path) between them: count() uploads the images
+// and finds every file's whole records, emit() writes them to device memory the caller names.
+struct DecodeRun {
+	DevBuf<uint8_t> img;
+	DevBuf<uint64_t> start, bytes, tile0, tile_first, n_rec_d;
+	DevBuf<uint32_t> tile_file;
+	uint64_t n_tiles = 0, total = 0;
+	uint32_t n_files = 0;
+	std::vector<uint64_t> n_rec, base;   // per file: whole records, first record (n_files + 1 entries)
+
+	void count(SortRun &R, const ImageSet &I)
+	{
+		const uint64_t tile = codec_tile_bytes();
+		n_files = (uint32_t)I.n_files;
+		std::vector<uint64_t> h_start(n_files + 1), h_bytes(n_files + 1, 0), h_tile0(n_files + 1);
+		for (uint32_t f = 0; f < n_files; ++f) {
+			h_start[f] = n_tiles * tile, h_tile0[f] = n_tiles, h_bytes[f] = I.n_bytes[f];
+			n_tiles += (I.n_bytes[f] + tile - 1) / tile;
+		}
+		h_start[n_files] = n_tiles * tile, h_tile0[n_files] = n_tiles;
+		if (n_tiles >= 0x7fffffffull) throw std::runtime_error("too many bytes for one decode call");
+		std::vector<uint32_t> h_tile_file(n_tiles);
+		for (uint32_t f = 0; f < n_files; ++f) std::fill(h_tile_file.begin() + h_tile0[f], h_tile_file.begin() + h_tile0[f + 1], f);
+		n_rec.assign(n_files, 0), base.assign((size_t)n_files + 1, 0);
+		if (n_tiles == 0) return;
+		img.alloc(n_tiles * tile);
+		for (uint32_t f = 0; f < n_files; ++f)
+			if (h_bytes[f]) HIP_OK(hipMemcpyAsync(img.p + h_start[f], I.bufs[f], h_bytes[f], hipMemcpyHostToDevice, R.st));
+		start.alloc(n_files + 1), bytes.alloc(n_files + 1), tile0.alloc(n_files + 1), tile_file.alloc(n_tiles);
+		start.upload(h_start.data(), n_files + 1, R.st), bytes.upload(h_bytes.data(), n_files + 1, R.st);
+		tile0.upload(h_tile0.data(), n_files + 1, R.st), tile_file.upload(h_tile_file.data(), n_tiles, R.st);
+		DevBuf<uint32_t> tile_cnt(n_tiles + 1);
+		tile_cnt.zero(R.st);
+		tile_first.alloc(n_tiles + 1), n_rec_d.alloc(n_files);
+		launch_codec_count(img.p, start.p, bytes.p, tile0.p, tile_file.p, n_tiles, tile_cnt.p, R.st);
+		R.exscan(tile_cnt.p, tile_first.p, n_tiles + 1);
+		launch_codec_file_plan(tile0.p, tile_first.p, n_files, n_rec_d.p, R.st);
+		n_rec_d.download(n_rec.data(), n_files, R.st);
+		HIP_OK(hipStreamSynchronize(R.st));   // (the host vectors of the uploads above live until here)
+		HIP_OK(hipGetLastError());
+		for (uint32_t f = 0; f < n_files; ++f) base[f + 1] = base[f] + n_rec[f];
+		total = base[n_files];
+	}
+	// the records to out[0 .. total); consumed (n_files entries) may be null
+	void emit(SortRun &R, OvlRec *out, uint64_t *consumed)
+	{
+		if (consumed) std::fill(consumed, consumed + n_files, 0);
+		if (total == 0) return;
+		DevBuf<uint64_t> rec_base((size_t)n_files + 1), used(n_files), sq(total), st(total);
+		DevBuf<uint32_t> dq(total), dt(total);
+		rec_base.upload(base.data(), (size_t)n_files + 1, R.st);
+		used.zero(R.st);
+		launch_codec_emit(img.p, start.p, bytes.p, tile0.p, tile_file.p, n_tiles, tile_first.p, n_rec_d.p, rec_base.p, out, used.p, R.st);
+		launch_codec_delta(out, total, dq.p, dt.p, R.st);
+		R.exscan(dq.p, sq.p, total);
+		R.exscan(dt.p, st.p, total);
+		launch_codec_records(out, total, dq.p, dt.p, sq.p, st.p, rec_base.p, n_files, R.st);
+		if (consumed) used.download(consumed, n_files, R.st);
+		HIP_OK(hipStreamSynchronize(R.st));   // (the scratch buffers of this call go back to the pool)
+		HIP_OK(hipGetLastError());
+	}
+	void release() { img.release(), tile_first.release(), tile_file.release(); }
+};
+
+// bytes handed to the caller in one malloc'd block that grows as the seed ranges of a call are encoded
+struct ByteOut {
+	uint8_t *p = nullptr;
+	size_t n = 0, cap = 0;
+	~ByteOut() { free(p); }
+	ByteOut() = default;
+	ByteOut(const ByteOut &) = delete;
+	ByteOut &operator=(const ByteOut &) = delete;
+	uint8_t *grow(size_t more)
+	{
+		if (n + more + 1 > cap) {
+			const size_t want = std::max(n + more + 1, cap + cap / 2);
+			uint8_t *q = (uint8_t*)realloc(p, want);
+			if (!q) throw std::runtime_error("malloc");
+			p = q, cap = want;
+		}
+		uint8_t *at = p + n;
+		n += more;
+		return at;
+	}
+	uint8_t *release()   // at exact size (one byte when there is none), never null
+	{
+		uint8_t *q = (uint8_t*)realloc(p, n ? n : 1);
+		if (!q) throw std::runtime_error("malloc");
+		p = nullptr, n = cap = 0;
+		return q;
+	}
+};
+
+// The encode tail of a call: device records in, their bytes appended to the image, `prev` carried from one append to the next
+// (the seed ranges of the out-of-core sort are one file).
+struct EncodeTail {
+	uint32_t prev[2] = {0, 0};
+	ByteOut image;
+	ndgpu_ovl_codec_stats st{};
+	void append(SortRun &R, const OvlRec *recs, uint64_t n)
+	{
+		if (n == 0) return;
+		EvTimer tm(R.st);
+		tm.start();
+		DevBuf<uint32_t> len(n + 1);
+		DevBuf<uint64_t> off(n + 1);
+		HIP_OK(hipMemsetAsync(len.p + n, 0, sizeof(uint32_t), R.st));
+		launch_codec_size(recs, n, prev[0], prev[1], len.p, R.st);
+		R.exscan(len.p, off.p, n + 1);
+		uint64_t nb = 0;
+		OvlRec last;
+		off.download(&nb, 1, R.st, n);
+		HIP_OK(hipMemcpyAsync(&last, recs + (n - 1), sizeof(OvlRec), hipMemcpyDeviceToHost, R.st));
+		HIP_OK(hipStreamSynchronize(R.st));
+		HIP_OK(hipGetLastError());
+		if (nb < 8 * n || nb > 40 * n) throw std::runtime_error("encoded size out of range");
+		DevBuf<uint8_t> out(nb + 4);
+		launch_codec_write(recs, n, prev[0], prev[1], off.p, out.p, R.st);
+		st.encode_ms += tm.stop();
+		uint8_t *const dst = image.grow(nb);
+		out.download(dst, nb, R.st);
+		HIP_OK(hipStreamSynchronize(R.st));
+		HIP_OK(hipGetLastError());
+		prev[0] = last.qname, prev[1] = last.tname;
+		st.bytes_out += nb, st.bytes_downloaded += nb;
+	}
+};
+
 // K16 over `n` dense sorted records in `n_groups` groups (group g = dense[off[g] .. off[g + 1]); off has n_groups + 1 entries):
 // count, two scans, emit; the piles are appended to A.  An irregular group turns the call over to the host routine (A.declined).
 static void admit_tail(SortRun &R, const OvlRec *dense, const uint64_t *off, uint64_t n_groups, uint64_t n, Admission &A)
@@ -207,7 +379,8 @@ static void admit_tail(SortRun &R, const OvlRec *dense, const uint64_t *off, uin
 // verdicts are appended to `o`
 static void sort_and_filter(SortRun &R, const OvlRec *cand_p, const uint32_t *k_span_p, const uint32_t *k_match_p, const uint32_t *k_seed_p,
                             uint64_t nc, const uint32_t *d_seed_p, const uint32_t *seed_len, uint32_t n_ids, int32_t min_seed_len,
-                            int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, SortOut &o, Admission *A = nullptr)
+                            int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, SortOut &o, Admission *A = nullptr,
+                            EncodeTail *E = nullptr)
 {
 	DevBuf<uint32_t> perm(nc), perm2(nc), k1(nc), k2(nc);
 	// S2: (seed asc, match desc, span asc), stable
@@ -248,7 +421,9 @@ static void sort_and_filter(SortRun &R, const OvlRec *cand_p, const uint32_t *k_
 	launch_compact_seed_recs(sstart.p, (uint32_t)n_seeds, outrec.p, n_out.p, off.p, dense.p, R.st);
 	std::vector<uint32_t> h_id(n_seeds);
 	std::vector<uint8_t> h_kind(n_seeds);
-	if (!A || A->want_sorted) {
+	if (E) {   // the sorted records leave as their `.ovl` bytes (K17): encoded where they lie
+		E->append(R, dense.p, total);
+	} else if (!A || A->want_sorted) {
 		OvlRec *const dst = o.recs.grow(total);
 		dense.download(dst, total, R.st);
 	}
@@ -289,7 +464,7 @@ static void hand_out(SortOut &so, ndgpu_ovl_rec **out, uint32_t **bl_id, uint8_t
 // are the output of the whole sort; equal (seed, match, span) keys keep input order in either form.
 static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
                              uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, bool hq_mode, uint64_t piece_cap,
-                             uint64_t range_cap, SortOut &so, uint64_t *nc_total, uint64_t *n_ranges, Admission *A)
+                             uint64_t range_cap, SortOut &so, uint64_t *nc_total, uint64_t *n_ranges, Admission *A, EncodeTail *E)
 {
 	DevBuf<uint32_t> d_seed(n_ids + 1), hist(n_ids + 1);
 	d_seed.upload(seed_len, n_ids, R.st);
@@ -355,7 +530,7 @@ static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, cons
 			}
 		}
 		if (base != nc) throw std::runtime_error("candidate count changed between the passes");
-		sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A);
+		sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A, E);
 		*nc_total += nc, ++*n_ranges;
 		lo = hi;
 	}
@@ -364,7 +539,7 @@ static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, cons
 static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
                          uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, ndgpu_ovl_rec **out,
                          uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats, bool hq_mode, Admission *A = nullptr,
-                         const uint32_t *skip_ids = nullptr, int64_t n_skip = 0)
+                         const uint32_t *skip_ids = nullptr, int64_t n_skip = 0, const ImageSet *images = nullptr, EncodeTail *E = nullptr)
 {
 	*out = nullptr, *bl_id = nullptr, *bl_kind = nullptr, *n_bl = 0;
 	if (stats) memset(stats, 0, sizeof(*stats));
@@ -380,6 +555,59 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 		tm.start();
 		const double t_setup = since();
 
+		// in one piece when the device holds the raw records, their flags and up to two candidates per record (~360 bytes per record
+		// with the sort's scratch); otherwise -- or when told to -- in seed ranges (sort_out_of_core)
+		uint64_t piece_cap = 0, range_cap = 0;
+		if (const char *e = getenv("NDGPU_OVLSORT_PIECE_RECORDS")) piece_cap = strtoull(e, nullptr, 10);
+		if (const char *e = getenv("NDGPU_OVLSORT_RANGE_CANDIDATES")) range_cap = strtoull(e, nullptr, 10);
+		uint64_t avail = 0;
+		auto fits = [&](uint64_t recs) { return !(piece_cap || range_cap || recs * 360ull > avail || 2 * recs >= 0x7fffffffull); };
+		auto look_at_memory = [&] {
+			size_t mem_free = 0, mem_total = 0;
+			HIP_OK(hipMemGetInfo(&mem_free, &mem_total));
+			avail = (uint64_t)mem_free + (uint64_t)pool_cached_bytes();
+			// NDGPU_OVLSORT_AVAIL_BYTES=<bytes>: the figure to decide on instead (a test hook, like the two knobs above)
+			if (const char *e = getenv("NDGPU_OVLSORT_AVAIL_BYTES")) avail = strtoull(e, nullptr, 10);
+		};
+
+		// the files as `.ovl` images (K17): counted on the device, and decoded straight into `raw` below when the sort is in one
+		// piece; a sort in seed ranges reads its files from host memory, piece by piece and twice, so it gets them decoded on the host.
+		// The form of the sort is decided HERE for a call with images, once, on the memory seen before the images went up: deciding
+		// again below, with the images resident, could turn an in-core verdict around when no host records exist.
+		DecodeRun D;
+		RecOut host_recs;
+		std::vector<const ndgpu_ovl_rec*> host_files;
+		std::vector<int64_t> host_counts;
+		bool raw_on_device = false;
+		if (images) {
+			n_files = images->n_files;
+			const uint64_t img_bytes = images->total();
+			look_at_memory();
+			bool on_device = img_bytes > 0 && fits(img_bytes / 40);   // (a record is 40 bytes at most)
+			if (on_device) {
+				EvTimer dtm(R.st);
+				dtm.start();
+				D.count(R, *images);
+				if (E) E->st.decode_ms += dtm.stop();
+				on_device = fits(D.total);
+			}
+			uint64_t at = 0;
+			if (on_device) {   // no host records: `files` stays null
+				raw_on_device = true;
+				host_counts.assign(D.n_rec.begin(), D.n_rec.end());
+				at = D.total;
+				if (E) E->st.bytes_uploaded += img_bytes;
+			} else {
+				D.release();
+				decode_on_host(*images, host_recs, host_counts, nullptr);
+				if (E && img_bytes) E->st.host_decodes += (uint64_t)n_files;
+				for (int f = 0; f < n_files; ++f) host_files.push_back((const ndgpu_ovl_rec*)host_recs.p + at), at += (uint64_t)host_counts[(size_t)f];
+				files = host_files.data();
+			}
+			n_per_file = host_counts.data();
+			if (E) E->st.bytes_in += img_bytes, E->st.records += at;
+		}
+
 		uint64_t n = 0;
 		std::vector<uint64_t> h_fstart((size_t)n_files + 1);
 		for (int f = 0; f < n_files; ++f) { h_fstart[f] = n; n += (uint64_t)n_per_file[f]; }
@@ -387,27 +615,29 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 		SortOut so;
 		if (n == 0) { hand_out(so, out, bl_id, bl_kind, n_bl); return 0; }   // (nothing in: an empty result, the stats stay zero)
 		if (A) A->begin(skip_ids, n_skip, R.st);
-		// in one piece when the device holds the raw records, their flags and up to two candidates per record (~360 bytes per record
-		// with the sort's scratch); otherwise -- or when told to -- in seed ranges (sort_out_of_core)
-		uint64_t piece_cap = 0, range_cap = 0;
-		if (const char *e = getenv("NDGPU_OVLSORT_PIECE_RECORDS")) piece_cap = strtoull(e, nullptr, 10);
-		if (const char *e = getenv("NDGPU_OVLSORT_RANGE_CANDIDATES")) range_cap = strtoull(e, nullptr, 10);
-		size_t mem_free = 0, mem_total = 0;
-		HIP_OK(hipMemGetInfo(&mem_free, &mem_total));
-		const uint64_t avail = (uint64_t)mem_free + (uint64_t)pool_cached_bytes();
-		const bool in_core = !(piece_cap || range_cap || n * 360ull > avail || 2 * n >= 0x7fffffffull);
+		if (!images) look_at_memory();
+		const bool in_core = images ? raw_on_device : fits(n);
 		uint64_t nc = 0, n_ranges = 1;
 		if (!in_core) {
+			if (raw_on_device || !files) throw std::runtime_error("a sort in seed ranges needs its records in host memory");
 			if (!piece_cap) piece_cap = std::max<uint64_t>(1u << 20, std::min<uint64_t>(n, avail / 8 / 96));
 			if (!range_cap) range_cap = std::max<uint64_t>(1u << 20, std::min<uint64_t>(0x7ffffff0ull, avail / 2 / 180));
 			sort_out_of_core(R, files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, piece_cap, range_cap, so,
-			                 &nc, &n_ranges, A);
+			                 &nc, &n_ranges, A, E);
 		} else {
 			std::vector<uint32_t> h_file_of(n);
 			DevBuf<OvlRec> raw(n);
 			for (int f = 0; f < n_files; ++f) {
 				std::fill(h_file_of.begin() + h_fstart[f], h_file_of.begin() + h_fstart[f + 1], (uint32_t)f);
-				if (n_per_file[f]) HIP_OK(hipMemcpyAsync(raw.p + h_fstart[f], files[f], (size_t)n_per_file[f] * sizeof(OvlRec), hipMemcpyHostToDevice, R.st));
+				if (n_per_file[f] && !raw_on_device)
+					HIP_OK(hipMemcpyAsync(raw.p + h_fstart[f], files[f], (size_t)n_per_file[f] * sizeof(OvlRec), hipMemcpyHostToDevice, R.st));
+			}
+			if (raw_on_device) {   // the records come out of the images the device already holds
+				EvTimer dtm(R.st);
+				dtm.start();
+				D.emit(R, raw.p, nullptr);
+				if (E) E->st.decode_ms += dtm.stop();
+				D.release();
 			}
 			DevBuf<uint32_t> file_of(n), d_seed(n_ids + 1);
 			DevBuf<uint64_t> fstart((size_t)n_files + 1);
@@ -434,7 +664,7 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			DevBuf<OvlRec> cand(nc);
 			DevBuf<uint32_t> k_span(nc), k_match(nc), k_seed(nc);
 			launch_expand_write(raw.p, n, sel.p, pos.p, cand.p, k_span.p, k_match.p, k_seed.p, R.st);
-			sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A);
+			sort_and_filter(R, cand.p, k_span.p, k_match.p, k_seed.p, nc, d_seed.p, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, so, A, E);
 		}
 		const double gpu_ms = tm.stop();
 		const uint64_t kept = so.n_recs, n_seeds = so.seeds;
@@ -543,6 +773,23 @@ static int64_t admit_on_host(const ndgpu_ovl_rec *sorted, int64_t n, const Admis
 	return nr;
 }
 
+// the admission of `un` sorted records that lie on the device: the groups (runs of one seed id), then K16
+static void admit_records(SortRun &R, const OvlRec *recs, uint64_t un, Admission &A)
+{
+	DevBuf<uint32_t> flag(un + 1);
+	DevBuf<uint64_t> rank(un + 1);
+	flag.zero(R.st);
+	launch_group_flag(recs, un, flag.p, R.st);
+	R.exscan(flag.p, rank.p, un + 1);
+	uint64_t n_groups = 0;
+	rank.download(&n_groups, 1, R.st, un);
+	HIP_OK(hipStreamSynchronize(R.st));
+	DevBuf<uint64_t> off(n_groups + 1);
+	launch_seed_start(flag.p, rank.p, un, off.p, R.st);
+	HIP_OK(hipMemcpyAsync(off.p + n_groups, &un, sizeof(un), hipMemcpyHostToDevice, R.st));
+	admit_tail(R, recs, off.p, n_groups, un, A);
+}
+
 extern "C" int64_t ndgpu_admit_piles(const ndgpu_ovl_rec *sorted, int64_t n, uint32_t n_ids, uint32_t min_len_seed, uint32_t min_len_aln,
                                      uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, int32_t flags,
                                      uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles, ndgpu_ovl_admit_stats *stats)
@@ -565,22 +812,10 @@ extern "C" int64_t ndgpu_admit_piles(const ndgpu_ovl_rec *sorted, int64_t n, uin
 			HIP_OK(ndovl::create_stage_stream(&R.st));
 			const StreamGuard guard{R.st};
 			A.begin(skip_ids, n_skip, R.st);
-			// the groups: runs of one seed id
 			const uint64_t un = (uint64_t)n;
 			DevBuf<OvlRec> recs(un);
 			recs.upload((const OvlRec*)sorted, un, R.st);
-			DevBuf<uint32_t> flag(un + 1);
-			DevBuf<uint64_t> rank(un + 1);
-			flag.zero(R.st);
-			launch_group_flag(recs.p, un, flag.p, R.st);
-			R.exscan(flag.p, rank.p, un + 1);
-			uint64_t n_groups = 0;
-			rank.download(&n_groups, 1, R.st, un);
-			HIP_OK(hipStreamSynchronize(R.st));
-			DevBuf<uint64_t> off(n_groups + 1);
-			launch_seed_start(flag.p, rank.p, un, off.p, R.st);
-			HIP_OK(hipMemcpyAsync(off.p + n_groups, &un, sizeof(un), hipMemcpyHostToDevice, R.st));
-			admit_tail(R, recs.p, off.p, n_groups, un, A);
+			admit_records(R, recs.p, un, A);
 		}
 		*stats = A.st;
 		if (A.declined) return admit_on_host(sorted, n, A, skip_ids, n_skip, nullptr, recs8, pile_off, seeds, n_piles, stats);
@@ -643,6 +878,223 @@ extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const
 		return nr;
 	} catch (...) {
 		drop();
+		return -2;
+	}
+}
+
+
+// ---- K17: the `.ovl` codec on the device (csrc/ovlsort_kernels.hip) ----
+static bool bad_images(const uint8_t *const *bufs, const uint64_t *n_bytes, int32_t n_files)
+{
+	if (n_files < 0 || (n_files > 0 && (!bufs || !n_bytes))) return true;
+	for (int f = 0; f < n_files; ++f) if (n_bytes[f] && !bufs[f]) return true;
+	return false;
+}
+
+extern "C" int64_t ndgpu_ovl_decode_batch(const uint8_t *const *bufs, const uint64_t *n_bytes, int32_t n_files, int32_t flags, ndgpu_ovl_rec **recs,
+                                          int64_t *n_per_file, uint64_t *consumed, ndgpu_ovl_codec_stats *stats)
+{
+	if (!recs) return -4;
+	*recs = nullptr;
+	if (stats) memset(stats, 0, sizeof(*stats));
+	if (bad_images(bufs, n_bytes, n_files) || (n_files > 0 && !n_per_file)) return -4;
+	try {
+		const ImageSet I{bufs, n_bytes, n_files};
+		ndgpu_ovl_codec_stats st{};
+		RecOut out;
+		std::vector<int64_t> counts((size_t)n_files, 0);
+		std::vector<uint64_t> used((size_t)n_files, 0);
+		const uint64_t img_bytes = I.total();
+		bool on_host = (flags & 1) || img_bytes == 0 || img_bytes / 8 >= 0x7fffffffull;
+		if (!on_host) {
+			if (select_device(true) < 0) return -1;
+			SortRun R;
+			HIP_OK(ndovl::create_stage_stream(&R.st));
+			const StreamGuard guard{R.st};
+			EvTimer tm(R.st);
+			tm.start();
+			DecodeRun D;
+			D.count(R, I);
+			if (D.total >= 0x7fffffffull) {   // (as the sort: beyond 2^31 records the call is not the device's)
+				on_host = true;
+				(void)tm.stop();
+			} else {
+				DevBuf<OvlRec> d(D.total + 1);
+				D.emit(R, d.p, used.data());
+				st.decode_ms = tm.stop();
+				OvlRec *const dst = out.grow(D.total);
+				d.download(dst, D.total, R.st);
+				HIP_OK(hipStreamSynchronize(R.st));
+				HIP_OK(hipGetLastError());
+				counts.assign(D.n_rec.begin(), D.n_rec.end());
+				st.bytes_uploaded = img_bytes, st.bytes_downloaded = D.total * sizeof(OvlRec);
+			}
+		}
+		if (on_host) {
+			decode_on_host(I, out, counts, used.data());
+			if (img_bytes) st.host_decodes = (uint64_t)n_files;
+		}
+		st.records = out.size(), st.bytes_in = img_bytes, st.bytes_out = out.size() * sizeof(OvlRec);
+		const int64_t n = (int64_t)out.size();
+		*recs = (ndgpu_ovl_rec*)out.release();
+		if (!*recs) throw std::runtime_error("malloc");
+		for (int f = 0; f < n_files; ++f) {
+			n_per_file[f] = counts[(size_t)f];
+			if (consumed) consumed[f] = used[(size_t)f];
+		}
+		if (stats) *stats = st;
+		return n;
+	} catch (...) {
+		return -2;
+	}
+}
+
+extern "C" int64_t ndgpu_ovl_encode_batch(const ndgpu_ovl_rec *recs, int64_t n, uint32_t prev[2], int32_t flags, uint8_t **out,
+                                          ndgpu_ovl_codec_stats *stats)
+{
+	if (!out) return -4;
+	*out = nullptr;
+	if (stats) memset(stats, 0, sizeof(*stats));
+	if (n < 0 || !prev || (n > 0 && !recs)) return -4;
+	try {
+		EncodeTail E;
+		E.prev[0] = prev[0], E.prev[1] = prev[1];
+		if (n == 0) {
+		} else if ((flags & 1) || (uint64_t)n >= 0x7fffffffull) {   // the host loop: the cross-check, and beyond 2^31 records
+			uint8_t *const dst = E.image.grow((size_t)n * 40);
+			const int64_t nb = ndgpu_ovl_encode(recs, n, E.prev, dst);
+			E.image.n = (size_t)nb;
+			E.st.bytes_out = (uint64_t)nb;
+		} else {
+			if (select_device(true) < 0) return -1;
+			SortRun R;
+			HIP_OK(ndovl::create_stage_stream(&R.st));
+			const StreamGuard guard{R.st};
+			DevBuf<OvlRec> d((size_t)n);
+			d.upload((const OvlRec*)recs, (size_t)n, R.st);
+			E.append(R, d.p, (uint64_t)n);
+			E.st.bytes_uploaded = (uint64_t)n * sizeof(OvlRec);
+		}
+		E.st.records = (uint64_t)n, E.st.bytes_in = (uint64_t)n * sizeof(OvlRec);
+		const int64_t nb = (int64_t)E.image.n;
+		*out = E.image.release();
+		prev[0] = E.prev[0], prev[1] = E.prev[1];
+		if (stats) *stats = E.st;
+		return nb;
+	} catch (...) {
+		return -2;
+	}
+}
+
+extern "C" int64_t ndgpu_ovl_sort_images(const uint8_t *const *bufs, const uint64_t *n_bytes, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                                         int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, int32_t flags, uint8_t **image,
+                                         uint64_t *image_bytes, uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *sort_stats,
+                                         ndgpu_ovl_codec_stats *codec_stats)
+{
+	if (!image || !image_bytes || !bl_id || !bl_kind || !n_bl) return -4;
+	*image = nullptr, *image_bytes = 0, *bl_id = nullptr, *bl_kind = nullptr, *n_bl = 0;
+	if (sort_stats) memset(sort_stats, 0, sizeof(*sort_stats));
+	if (codec_stats) memset(codec_stats, 0, sizeof(*codec_stats));
+	if (bad_images(bufs, n_bytes, n_files) || (n_ids > 0 && !seed_len)) return -4;
+	ndgpu_ovl_rec *srt = nullptr;
+	uint32_t *b_id = nullptr;
+	uint8_t *b_kind = nullptr;
+	int64_t nb = 0;
+	try {
+		const ImageSet I{bufs, n_bytes, n_files};
+		EncodeTail E;
+		int64_t ns;
+		if (flags & 1) {   // the cross-check: the host loops around the sort as it was
+			RecOut recs;
+			std::vector<int64_t> counts;
+			decode_on_host(I, recs, counts, nullptr);
+			std::vector<const ndgpu_ovl_rec*> files;
+			uint64_t at = 0;
+			for (int f = 0; f < n_files; ++f) files.push_back((const ndgpu_ovl_rec*)recs.p + at), at += (uint64_t)counts[(size_t)f];
+			ns = sort_impl(files.data(), counts.data(), n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, &b_id, &b_kind, &nb,
+			               sort_stats, hq != 0);
+			if (ns >= 0) {
+				uint8_t *const dst = E.image.grow((size_t)ns * 40);
+				E.image.n = (size_t)ndgpu_ovl_encode(srt, ns, E.prev, dst);
+				E.st.bytes_in = I.total(), E.st.records = at, E.st.bytes_out = E.image.n, E.st.host_decodes = I.total() ? (uint64_t)n_files : 0;
+			}
+		} else {
+			ns = sort_impl(nullptr, nullptr, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, &b_id, &b_kind, &nb, sort_stats,
+			               hq != 0, nullptr, nullptr, 0, &I, &E);
+		}
+		free(srt), srt = nullptr;
+		if (ns < 0) { free(b_id), free(b_kind); return ns; }
+		const uint64_t bytes = E.image.n;
+		*image = E.image.release();
+		*image_bytes = bytes, *bl_id = b_id, *bl_kind = b_kind, *n_bl = nb;
+		if (codec_stats) *codec_stats = E.st;
+		return ns;
+	} catch (...) {
+		free(srt), free(b_id), free(b_kind);
+		return -2;
+	}
+}
+
+extern "C" int64_t ndgpu_admit_piles_image(const uint8_t *buf, uint64_t n_bytes, uint32_t n_ids, uint32_t min_len_seed, uint32_t min_len_aln,
+                                           uint32_t max_cov_aln, uint32_t min_cov_seed, const uint32_t *skip_ids, int64_t n_skip, int32_t flags,
+                                           uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                           ndgpu_ovl_admit_stats *admit_stats, ndgpu_ovl_codec_stats *codec_stats)
+{
+	if (!recs8 || !pile_off || !seeds || !n_piles) return -4;
+	*recs8 = nullptr, *pile_off = nullptr, *seeds = nullptr, *n_piles = 0;
+	ndgpu_ovl_admit_stats st_local;
+	if (!admit_stats) admit_stats = &st_local;
+	memset(admit_stats, 0, sizeof(*admit_stats));
+	if (codec_stats) memset(codec_stats, 0, sizeof(*codec_stats));
+	if ((n_bytes && !buf) || n_skip < 0 || (n_skip > 0 && !skip_ids)) return -4;
+	try {
+		Admission A(n_ids, min_len_seed, min_len_aln, max_cov_aln, min_cov_seed);
+		ndgpu_ovl_codec_stats cs{};
+		const uint8_t *const bufs[1] = {buf};
+		const ImageSet I{bufs, &n_bytes, 1};
+		cs.bytes_in = n_bytes;
+		bool on_host = (flags & 1) || n_bytes < 8 || n_bytes / 8 >= (1ull << 30);
+		if (!on_host) {
+			if (select_device(true) < 0) return -1;
+			SortRun R;
+			HIP_OK(ndovl::create_stage_stream(&R.st));
+			const StreamGuard guard{R.st};
+			EvTimer tm(R.st);
+			tm.start();
+			DecodeRun D;
+			D.count(R, I);
+			const uint64_t un = D.total;
+			cs.bytes_uploaded = n_bytes;
+			if (un >= (1ull << 30)) { fprintf(stderr, "[ndgpu_overlap] too many records for one admission call\n"); return -3; }
+			if (un) {
+				DevBuf<OvlRec> recs(un);
+				D.emit(R, recs.p, nullptr);
+				cs.decode_ms = tm.stop();
+				D.release();
+				A.begin(skip_ids, n_skip, R.st);
+				admit_records(R, recs.p, un, A);
+			}
+			cs.records = un;
+			on_host = A.declined;
+		}
+		int64_t nr;
+		if (on_host) {   // flags bit 0, or a group the device form does not cover: the host loop and the host routine
+			RecOut recs;
+			std::vector<int64_t> counts;
+			decode_on_host(I, recs, counts, nullptr);
+			cs.records = recs.size(), cs.host_decodes = n_bytes ? 1 : 0;
+			A.st.sorted_records = recs.size();
+			*admit_stats = A.st;
+			nr = admit_on_host((const ndgpu_ovl_rec*)recs.p, (int64_t)recs.size(), A, skip_ids, n_skip, nullptr, recs8, pile_off, seeds, n_piles, admit_stats);
+		} else {
+			*admit_stats = A.st;
+			nr = (int64_t)A.rows.size();
+			A.hand_out(recs8, pile_off, seeds, n_piles);
+		}
+		cs.bytes_out = (uint64_t)nr * 32;
+		if (codec_stats) *codec_stats = cs;
+		return nr;
+	} catch (...) {
 		return -2;
 	}
 }

@@ -814,4 +814,292 @@ void launch_admit_emit(const OvlRec *recs, const uint64_t *off, uint32_t n_group
 	                        pile_off, seeds);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K17: the `.ovl` codec (encode_ovl / decode_ovl, lib/ovl.c:105-203; the host loops are ndgpu_ovl_encode / ndgpu_ovl_decode).
+// A record is 8 big-endian base-128 varints (a byte < 128 ends a value), the two read names delta-coded against the record in front.
+//
+// Decode.  The images of a call's files lie in one device buffer, every file at a multiple of kCodecTile bytes; a tile (one wavefront,
+// kCodecIters x 64 lanes x 16 bytes) belongs to one file.  The host loop's value is v = (v << 7) | (c & 127) in uint32_t over the
+// bytes since the last terminator: whatever lies more than 4 bytes in front of the terminator has been shifted out of the 32 bits,
+// and the 5th-from-last byte keeps its low 4 bits.  So a value is a function of its terminator and of at most the 4 bytes in front of
+// it, for EVERY byte string -- over-long values, runs of continuation bytes, anything -- and every terminator is found by looking at
+// its own byte alone.  That is why this path has no "malformed input" decline: there is no input on which it differs from the loop.
+// Value j of a file is field j % 8 of record j / 8 (a file's values beyond its last whole record are dropped), and j is a prefix
+// count of terminators: per lane a popcount, per wavefront a prefix, per tile a total the host side scans.
+// The names are running sums of +-delta in wrapping 32-bit arithmetic: addition modulo 2^32 is associative, so an exclusive scan of
+// the two's-complement deltas (summed in 64 bits, truncated) is the loop's `prev`; a file's own sum starts at its first record.
+//
+// Encode.  One lane per record; the predecessor's names come from the lane below.  Sizes, a scan, then each wavefront stages the
+// bytes of its 64 records in LDS at the alignment they have in the output and stores the span with dword stores (byte stores for
+// the up to 3 bytes in front of the first and behind the last whole dword): every output byte has one writer, no atomics.
+
+constexpr uint32_t kCodecIters = 4;
+constexpr uint32_t kCodecTile = kCodecIters * 64 * 16;   // bytes of a decode tile
+
+// what a decode launch knows of the files: file f = img[start[f] .. start[f] + bytes[f]), its tiles tile0[f] .. tile0[f + 1]
+struct CodecFiles {
+	const uint8_t *img;
+	const uint64_t *start, *bytes, *tile0;
+	const uint32_t *tile_file;
+};
+
+// the 16-bit terminator mask of 16 bytes (bit i: byte i < 128), the first `valid` bytes of them
+__device__ __forceinline__ uint32_t term_mask16(const uint4 w, uint32_t valid)
+{
+	// per word: bit 0, 8, 16, 24 = the byte is a terminator; the multiply gathers them into bits 24..27 (all partial products land on
+	// distinct bits, so there is no carry)
+	const uint32_t a = ((~w.x >> 7 & 0x01010101u) * 0x01020408u) >> 24 & 15u, b = ((~w.y >> 7 & 0x01010101u) * 0x01020408u) >> 24 & 15u;
+	const uint32_t c = ((~w.z >> 7 & 0x01010101u) * 0x01020408u) >> 24 & 15u, d = ((~w.w >> 7 & 0x01010101u) * 0x01020408u) >> 24 & 15u;
+	const uint32_t m = a | b << 4 | c << 8 | d << 12;
+	return valid >= 16 ? m : m & ((1u << valid) - 1u);
+}
+
+__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v, int lane)
+{
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t o = __shfl_up(v, d, 64);
+		if (lane >= d) v += o;
+	}
+	return v;
+}
+
+// the lane's 16 bytes of iteration `it` of tile `t` (file-relative offset *at), and how many of them are the file's
+__device__ __forceinline__ uint4 codec_load(const CodecFiles &F, uint32_t f, uint64_t t, uint32_t it, int lane, uint64_t *at, uint32_t *valid)
+{
+	const uint64_t o = (t - F.tile0[f]) * kCodecTile + (uint64_t)it * 1024 + (uint64_t)lane * 16, nb = F.bytes[f];
+	*at = o;
+	*valid = o >= nb ? 0u : (nb - o >= 16 ? 16u : (uint32_t)(nb - o));
+	// (the buffer is whole tiles: the load is inside it wherever the file ends; start[f] is a multiple of the tile)
+	return *reinterpret_cast<const uint4*>(F.img + F.start[f] + o);
+}
+
+__global__ void __launch_bounds__(64) codec_count_kernel(CodecFiles F, uint64_t n_tiles, uint32_t *__restrict__ tile_cnt)
+{
+	const uint64_t t = blockIdx.x;
+	if (t >= n_tiles) return;
+	const int lane = threadIdx.x;
+	const uint32_t f = F.tile_file[t];
+	uint32_t cnt = 0;
+	for (uint32_t it = 0; it < kCodecIters; ++it) {
+		uint64_t at;
+		uint32_t valid;
+		const uint4 w = codec_load(F, f, t, it, lane, &at, &valid);
+		cnt += (uint32_t)__popc(term_mask16(w, valid));
+	}
+	cnt = wave_incl_sum_u32(cnt, lane);
+	if (lane == 63) tile_cnt[t] = cnt;
+}
+
+// whole records of every file (tile_first = the exclusive scan of tile_cnt, n_tiles + 1 entries)
+__global__ void codec_file_plan_kernel(const uint64_t *__restrict__ tile0, const uint64_t *__restrict__ tile_first, uint32_t n_files,
+                                       uint64_t *__restrict__ n_rec)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f < n_files) n_rec[f] = (tile_first[tile0[f + 1]] - tile_first[tile0[f]]) >> 3;
+}
+
+// fields[8 * (rec_base[f] + j / 8) + j % 8] = value j of file f; consumed[f] = the offset behind the last byte of its last whole
+// record (zeroed by the caller: a file without a whole record consumes nothing)
+__global__ void __launch_bounds__(64) codec_emit_kernel(CodecFiles F, uint64_t n_tiles, const uint64_t *__restrict__ tile_first,
+                                                         const uint64_t *__restrict__ n_rec, const uint64_t *__restrict__ rec_base,
+                                                         uint32_t *__restrict__ fields, uint64_t *__restrict__ consumed)
+{
+	const uint64_t t = blockIdx.x;
+	if (t >= n_tiles) return;
+	const int lane = threadIdx.x;
+	const uint32_t f = F.tile_file[t];
+	const uint64_t want = n_rec[f] * 8;                               // values of the file that belong to whole records
+	uint64_t j0 = tile_first[t] - tile_first[F.tile0[f]];             // file-relative index of the tile's first value
+	if (j0 >= want) return;                                           // (the whole wavefront: nothing but the partial tail)
+	uint32_t *const out = fields + rec_base[f] * 8;
+	const uint8_t *const file = F.img + F.start[f];
+	for (uint32_t it = 0; it < kCodecIters; ++it) {
+		uint64_t at;
+		uint32_t valid;
+		const uint4 w = codec_load(F, f, t, it, lane, &at, &valid);
+		uint32_t m = term_mask16(w, valid);
+		const uint32_t mine = (uint32_t)__popc(m), incl = wave_incl_sum_u32(mine, lane);
+		uint64_t j = j0 + (incl - mine);
+		j0 += __shfl(incl, 63, 64);
+		const unsigned long long lo = (unsigned long long)w.y << 32 | w.x, hi = (unsigned long long)w.w << 32 | w.z;
+		while (m) {
+			const int i = __ffs((int)m) - 1;
+			m &= m - 1;
+			if (j >= want) break;
+			uint32_t v = (uint32_t)((i < 8 ? lo >> (8 * i) : hi >> (8 * (i - 8))) & 0xffu);
+			const uint64_t p = at + (uint32_t)i;                      // the terminator's offset in the file
+#pragma unroll
+			for (int k = 1; k <= 4; ++k) {
+				if (p < (uint64_t)k) break;                            // the start of the file: nothing in front
+				const int q = i - k;
+				// in front of the lane's 16 bytes (another lane's, another iteration's, another tile's): a plain load
+				const uint32_t b = q >= 0 ? (uint32_t)((q < 8 ? lo >> (8 * q) : hi >> (8 * (q - 8))) & 0xffu) : (uint32_t)file[p - k];
+				if (b < 128) break;
+				v |= (b & 127u) << (7 * k);                            // (k = 4: the low 4 bits stay, as in the loop's uint32_t)
+			}
+			out[j] = v;
+			if (j + 1 == want) consumed[f] = p + 1;
+			++j;
+		}
+	}
+}
+
+__device__ __forceinline__ uint32_t file_of_record(const uint64_t *__restrict__ rec_base, uint32_t n_files, uint64_t i)
+{
+	uint32_t lo = 0, hi = n_files;   // the last f with rec_base[f] <= i (files without records share their successor's base)
+	while (hi - lo > 1) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (rec_base[mid] <= i) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+// the signed name deltas of every record as 32-bit two's complement (fields as codec_emit_kernel left them)
+__global__ void codec_delta_kernel(const uint32_t *__restrict__ fields, uint64_t n, uint32_t *__restrict__ dq, uint32_t *__restrict__ dt)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t *f = fields + i * 8;
+	const uint32_t fl = f[1];
+	dq[i] = (fl & 2) ? 0u - f[0] : f[0];
+	dt[i] = (fl & 4) ? 0u - f[4] : f[4];
+}
+
+// fields -> records, in place (a lane reads its own 8 words, then writes them); sq / st = exclusive scans of dq / dt
+__global__ void codec_records_kernel(uint32_t *__restrict__ fields, uint64_t n, const uint32_t *__restrict__ dq, const uint32_t *__restrict__ dt,
+                                     const uint64_t *__restrict__ sq, const uint64_t *__restrict__ st, const uint64_t *__restrict__ rec_base,
+                                     uint32_t n_files)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	uint32_t *const p = fields + i * 8;
+	const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 4);   // f0..f3, f4..f7
+	const uint64_t r0 = rec_base[file_of_record(rec_base, n_files, i)];   // the file restarts from prev = {0, 0}
+	const uint32_t fl = a.y;
+	OvlRec r;
+	r.rev = fl & 1;
+	r.qname = (uint32_t)(sq[i] - sq[r0]) + dq[i];
+	r.qs = a.z;
+	r.qe = a.z + a.w;
+	r.tname = (uint32_t)(st[i] - st[r0]) + dt[i];
+	r.ts = b.y;
+	r.te = (fl & 8) ? b.y + a.w + b.z : b.y + a.w - b.z;
+	r.match = b.w;
+	*reinterpret_cast<uint4*>(p) = make_uint4(r.rev, r.qname, r.qs, r.qe);
+	*reinterpret_cast<uint4*>(p + 4) = make_uint4(r.tname, r.ts, r.te, r.match);
+}
+
+// ---- encode
+__device__ __forceinline__ uint32_t varint_len(uint32_t v) { return v < 128 ? 1u : (uint32_t)(32 - __clz((int)v) + 6) / 7u; }
+
+// the eight fields of ndgpu_ovl_encode for record r behind a record named (pq, pt)
+__device__ __forceinline__ void encode_fields(const OvlRec &r, uint32_t pq, uint32_t pt, uint32_t fld[8])
+{
+	uint32_t flags = r.rev;
+	const uint32_t qspan = r.qe - r.qs, tspan = r.te - r.ts;
+	fld[3] = qspan;
+	if (r.qname >= pq) fld[0] = r.qname - pq; else flags |= 2, fld[0] = pq - r.qname;
+	if (r.tname >= pt) fld[4] = r.tname - pt; else flags |= 4, fld[4] = pt - r.tname;
+	if (qspan >= tspan) fld[6] = qspan - tspan; else flags |= 8, fld[6] = tspan - qspan;
+	fld[1] = flags & 0xff, fld[2] = r.qs, fld[5] = r.ts, fld[7] = r.match;
+}
+
+// record i and its fields; the predecessor's names from the lane below, lane 0 reads them (record 0: the caller's prev).  Every lane of
+// the wavefront calls this (the lanes behind the last record with live = false).
+__device__ __forceinline__ void encode_record(const OvlRec *__restrict__ recs, uint64_t i, bool live, int lane, uint32_t prev_q, uint32_t prev_t,
+                                              uint32_t fld[8])
+{
+	OvlRec r = {0, 0, 0, 0, 0, 0, 0, 0};
+	if (live) r = recs[i];
+	uint32_t pq = __shfl_up(r.qname, 1, 64), pt = __shfl_up(r.tname, 1, 64);
+	if (lane == 0) {
+		pq = prev_q, pt = prev_t;
+		if (live && i > 0) pq = recs[i - 1].qname, pt = recs[i - 1].tname;
+	}
+	encode_fields(r, pq, pt, fld);
+}
+
+__global__ void __launch_bounds__(64) codec_size_kernel(const OvlRec *__restrict__ recs, uint64_t n, uint32_t prev_q, uint32_t prev_t,
+                                                         uint32_t *__restrict__ len)
+{
+	const int lane = threadIdx.x;
+	const uint64_t i = (uint64_t)blockIdx.x * 64 + lane;
+	uint32_t fld[8];
+	encode_record(recs, i, i < n, lane, prev_q, prev_t, fld);
+	uint32_t nb = 0;
+#pragma unroll
+	for (int k = 0; k < 8; ++k) nb += varint_len(fld[k]);
+	if (i < n) len[i] = nb;   // 8 .. 37: seven values of up to 5 bytes, the flags (masked to 8 bits) of up to 2
+}
+
+constexpr uint32_t kEncStageWords = (64 * 40 + 3 + 3) / 4 + 1;   // 64 records of 40 bytes behind up to 3 bytes of alignment
+
+// off = the exclusive scan of len (n + 1 entries); out is 4-byte aligned
+__global__ void __launch_bounds__(64) codec_write_kernel(const OvlRec *__restrict__ recs, uint64_t n, uint32_t prev_q, uint32_t prev_t,
+                                                          const uint64_t *__restrict__ off, uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage_w[kEncStageWords];
+	uint8_t *const stage = reinterpret_cast<uint8_t*>(stage_w);
+	const int lane = threadIdx.x;
+	const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + lane;
+	const uint64_t i1 = i0 + 64 < n ? i0 + 64 : n;
+	const uint64_t g0 = off[i0], g1 = off[i1];
+	const uint32_t head = (uint32_t)(g0 & 3);   // the stage holds the span at the alignment it has in `out`
+	uint32_t fld[8];
+	encode_record(recs, i, i < n, lane, prev_q, prev_t, fld);
+	if (i < n) {
+		uint32_t at = head + (uint32_t)(off[i] - g0);
+#pragma unroll
+		for (int k = 0; k < 8; ++k) {
+			const uint32_t v = fld[k];
+			for (int g = (int)varint_len(v) - 1; g >= 0; --g) stage[at++] = (uint8_t)((v >> (7 * g) & 127u) | (g ? 128u : 0u));
+		}
+	}
+	__syncthreads();
+	const uint32_t end = head + (uint32_t)(g1 - g0);                 // stage[head .. end) = out[g0 .. g1)
+	const uint32_t w_lo = (head + 3) & ~3u, w_hi = end & ~3u;        // whole dwords: stage[w_lo .. w_hi)
+	const uint32_t head_end = w_lo < end ? w_lo : end;
+	uint8_t *const base = out + (g0 - head);                          // of stage[0]: a dword boundary of `out`
+	if (head + lane < head_end) base[head + lane] = stage[head + lane];
+	for (uint32_t x = w_lo + 4 * (uint32_t)lane; x < w_hi; x += 256) *reinterpret_cast<uint32_t*>(base + x) = stage_w[x >> 2];
+	const uint32_t tail = w_hi > head_end ? w_hi : head_end;
+	if (tail + lane < end) base[tail + lane] = stage[tail + lane];
+}
+
+uint32_t codec_tile_bytes() { return kCodecTile; }
+void launch_codec_count(const uint8_t *img, const uint64_t *start, const uint64_t *bytes, const uint64_t *tile0, const uint32_t *tile_file,
+                        uint64_t n_tiles, uint32_t *tile_cnt, hipStream_t s)
+{
+	const CodecFiles F{img, start, bytes, tile0, tile_file};
+	if (n_tiles) ND_LAUNCH(codec_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, F, n_tiles, tile_cnt);
+}
+void launch_codec_file_plan(const uint64_t *tile0, const uint64_t *tile_first, uint32_t n_files, uint64_t *n_rec, hipStream_t s)
+{
+	if (n_files) ND_LAUNCH(codec_file_plan_kernel, GRID1(n_files), 0, s, tile0, tile_first, n_files, n_rec);
+}
+void launch_codec_emit(const uint8_t *img, const uint64_t *start, const uint64_t *bytes, const uint64_t *tile0, const uint32_t *tile_file,
+                       uint64_t n_tiles, const uint64_t *tile_first, const uint64_t *n_rec, const uint64_t *rec_base, OvlRec *recs,
+                       uint64_t *consumed, hipStream_t s)
+{
+	const CodecFiles F{img, start, bytes, tile0, tile_file};
+	if (n_tiles) ND_LAUNCH(codec_emit_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, F, n_tiles, tile_first, n_rec, rec_base, (uint32_t*)recs, consumed);
+}
+void launch_codec_delta(const OvlRec *recs, uint64_t n, uint32_t *dq, uint32_t *dt, hipStream_t s)
+{
+	if (n) ND_LAUNCH(codec_delta_kernel, GRID1(n), 0, s, (const uint32_t*)recs, n, dq, dt);
+}
+void launch_codec_records(OvlRec *recs, uint64_t n, const uint32_t *dq, const uint32_t *dt, const uint64_t *sq, const uint64_t *st,
+                          const uint64_t *rec_base, uint32_t n_files, hipStream_t s)
+{
+	if (n) ND_LAUNCH(codec_records_kernel, GRID1(n), 0, s, (uint32_t*)recs, n, dq, dt, sq, st, rec_base, n_files);
+}
+void launch_codec_size(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, uint32_t *len, hipStream_t s)
+{
+	if (n) ND_LAUNCH(codec_size_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, recs, n, prev_q, prev_t, len);
+}
+void launch_codec_write(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, const uint64_t *off, uint8_t *out, hipStream_t s)
+{
+	if (n) ND_LAUNCH(codec_write_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, recs, n, prev_q, prev_t, off, out);
+}
+
 } // namespace ndovl

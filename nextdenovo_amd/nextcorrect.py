@@ -165,6 +165,31 @@ def correct_and_write(db, recs, piles, args, OUT, IDX):
     return fail_seed
 
 
+def make_piles(args, n_reads, skip):
+    """sorted.ovl -> (recs8, pile_off, seeds): the pile admission of lib/nextcorrect.py:92-143 in one native pass (ndgpu_assemble_piles;
+    `assemble_piles` above is the line-by-line restatement the tests hold it against).  NDGPU_ADMIT_DEVICE=1: the admission on the
+    device (K16); NDGPU_CODEC_DEVICE=1: the file decoded on the device (K17); both: bytes up, piles down (ndgpu_admit_piles_image)."""
+    from nextdenovo_amd import overlap
+    th = (args.min_len_seed, args.min_len_aln, args.max_cov_aln, args.min_cov_seed, sorted(skip))
+    admit_device = os.environ.get("NDGPU_ADMIT_DEVICE") == "1"
+    if overlap.codec_device():
+        image = overlap.file_bytes(args.ovl)
+        if admit_device:
+            recs8, off, names, st = overlap.admit_piles_image(image, n_reads, *th)
+            if st["admit"]["groups_declined"] == 0:
+                return recs8, off, names
+            # (a declined stream may name reads beyond the read table, which n_ids below covers: it goes on as a record array)
+        srt = overlap.decode_images([image])[0]
+        n_ids = max(n_reads, int(max(srt["qname"].max(), srt["tname"].max())) + 1 if srt.size else 0)
+    else:
+        dec = ovl.decode_ovl(args.ovl)
+        n_ids = max(n_reads, int(dec[:, [0, 4]].max()) + 1 if dec.size else 0)
+        srt = overlap.from_decoded(dec)
+    if admit_device:
+        return overlap.admit_piles(srt, n_ids, *th)[:3]
+    return overlap.assemble_piles(srt, n_ids, *th)
+
+
 def main(args):
     OUT, IDX = sys.stdout, None
     skip = set()
@@ -182,17 +207,7 @@ def main(args):
 
     words, word_off, lens = ovl.load_read_db(args.idxs)
     db = api.ReadDB(words, word_off, lens)
-    recs = ovl.decode_ovl(args.ovl)
-    # pile admission (lib/nextcorrect.py:92-143): one native pass (ndgpu_assemble_piles) instead of a Python loop over every
-    # record; `assemble_piles` above is the line-by-line restatement the tests hold it against
-    from nextdenovo_amd import overlap
-    n_ids = max(int(lens.size), int(recs[:, [0, 4]].max()) + 1 if recs.size else 0)
-    if os.environ.get("NDGPU_ADMIT_DEVICE") == "1":   # the same admission on the device (ndgpu_admit_piles, K16)
-        recs, off, names, _ = overlap.admit_piles(overlap.from_decoded(recs), n_ids, args.min_len_seed, args.min_len_aln, args.max_cov_aln,
-                                                  args.min_cov_seed, sorted(skip))
-    else:
-        recs, off, names = overlap.assemble_piles(overlap.from_decoded(recs), n_ids, args.min_len_seed, args.min_len_aln, args.max_cov_aln,
-                                                  args.min_cov_seed, sorted(skip))
+    recs, off, names = make_piles(args, int(lens.size), skip)
     piles = [(int(names[p]), np.arange(int(off[p]), int(off[p + 1]))) for p in range(names.size)]
 
     fail_seed = correct_and_write(db, recs, piles, args, OUT, IDX)

@@ -581,3 +581,121 @@ def sort_piles(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int 
     sorted_recs = _take(lib, srt, nsrt.value, REC) if want_sorted else None
     return (recs, _take(lib, off, npiles.value + 1, np.uint64), _take(lib, seeds, npiles.value, np.uint32), bl, sorted_recs,
             {"sort": {n_: getattr(st, n_) for n_, _ in SortStats._fields_}, "admit": {n_: getattr(ast, n_) for n_, _ in AdmitStats._fields_}})
+
+
+# ---- K17: the `.ovl` codec on the device (ndgpu_ovl_decode_batch, ndgpu_ovl_encode_batch, ndgpu_ovl_sort_images,
+# ndgpu_admit_piles_image) ----
+class CodecStats(C.Structure):
+    _fields_ = [("decode_ms", C.c_double), ("encode_ms", C.c_double)] \
+        + [(n, C.c_uint64) for n in ("records", "bytes_in", "bytes_out", "bytes_uploaded", "bytes_downloaded", "host_decodes")]
+
+
+def codec_device() -> bool:
+    """NDGPU_CODEC_DEVICE=1: the stage commands decode and encode their `.ovl` files on the device."""
+    return os.environ.get("NDGPU_CODEC_DEVICE") == "1"
+
+
+def file_bytes(path):
+    """A file's bytes as a uint8 array, memory-mapped (an empty file cannot be mapped)."""
+    return np.memmap(path, dtype=np.uint8, mode="r") if os.path.getsize(path) else np.zeros(0, dtype=np.uint8)
+
+
+def _stats_dict(st) -> dict:
+    return {n_: getattr(st, n_) for n_, _ in type(st)._fields_}
+
+
+def _images(bufs):
+    """Byte images (bytes, or uint8 arrays such as memory-mapped files) -> (the arrays kept alive, pointer array, size array)."""
+    arrs = [np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else np.ascontiguousarray(b, dtype=np.uint8)
+            for b in bufs]
+    nf = len(arrs)
+    ptrs = (C.c_void_p * max(1, nf))(*[a.ctypes.data if a.size else None for a in arrs])
+    sizes = (C.c_uint64 * max(1, nf))(*[a.size for a in arrs])
+    return arrs, ptrs, sizes
+
+
+def _codec_fail(lib, name, n):
+    if n == -2:
+        return _fail(lib, name + " failed")
+    return RuntimeError({-1: name + ": no usable HIP device", -3: name + ": too many records for one call",
+                         -4: name + ": bad argument"}.get(int(n), "%s failed (%d)" % (name, n)))
+
+
+def decode_images(bufs, flags: int = 0):
+    """The records of `.ovl` byte images, decoded on the device (ndgpu_ovl_decode_batch); flags bit 0: the host loop.
+    Returns (records of all files in file order, records per file int64[n], bytes consumed per file uint64[n], stats dict)."""
+    lib = load()
+    P = C.c_void_p
+    lib.ndgpu_ovl_decode_batch.argtypes = [C.POINTER(P), C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.POINTER(P), P, P, C.POINTER(CodecStats)]
+    lib.ndgpu_ovl_decode_batch.restype = C.c_int64
+    arrs, ptrs, sizes = _images(bufs)
+    per_file = np.zeros(max(1, len(arrs)), dtype=np.int64)
+    used = np.zeros(max(1, len(arrs)), dtype=np.uint64)
+    recs, st = C.c_void_p(), CodecStats()
+    n = lib.ndgpu_ovl_decode_batch(ptrs, sizes, len(arrs), int(flags), C.byref(recs), _ptr(per_file), _ptr(used), C.byref(st))
+    if n < 0:
+        raise _codec_fail(lib, "ndgpu_ovl_decode_batch", n)
+    return _take(lib, recs, n, REC), per_file[:len(arrs)], used[:len(arrs)], _stats_dict(st)
+
+
+def encode_device(recs: np.ndarray, prev: np.ndarray, flags: int = 0, want_stats: bool = False):
+    """encode() on the device (ndgpu_ovl_encode_batch): the bytes of a record array; prev = uint32[2], updated in place.
+    flags bit 0: the host loop."""
+    lib = load()
+    P = C.c_void_p
+    lib.ndgpu_ovl_encode_batch.argtypes = [P, C.c_int64, P, C.c_int32, C.POINTER(P), C.POINTER(CodecStats)]
+    lib.ndgpu_ovl_encode_batch.restype = C.c_int64
+    recs = np.ascontiguousarray(recs, dtype=REC)
+    out, st = C.c_void_p(), CodecStats()
+    n = lib.ndgpu_ovl_encode_batch(_ptr(recs), recs.size, _ptr(prev), int(flags), C.byref(out), C.byref(st))
+    if n < 0:
+        raise _codec_fail(lib, "ndgpu_ovl_encode_batch", n)
+    b = _take(lib, out, n, np.uint8).tobytes()
+    return (b, _stats_dict(st)) if want_stats else b
+
+
+def sort_images(bufs, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int = 40, max_flank_len: int = 300, hq: bool = False, flags: int = 0):
+    """The `ovl_sort` command as one device pass (ndgpu_ovl_sort_images): the images of the step-1 files in, the image of
+    `sorted.ovl` out.  Returns (image uint8 array, [(seed id, 'c'|'k'), ...], {"sort": ..., "codec": ...})."""
+    lib = load()
+    P, PP = C.c_void_p, C.POINTER(C.c_void_p)
+    lib.ndgpu_ovl_sort_images.argtypes = [PP, C.POINTER(C.c_uint64), C.c_int32, P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          PP, C.POINTER(C.c_uint64), PP, PP, C.POINTER(C.c_int64), C.POINTER(SortStats), C.POINTER(CodecStats)]
+    lib.ndgpu_ovl_sort_images.restype = C.c_int64
+    arrs, ptrs, sizes = _images(bufs)
+    seed_len = np.ascontiguousarray(seed_len, dtype=np.uint32)
+    image, bid, bkind = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    nbytes, nbl = C.c_uint64(0), C.c_int64(0)
+    st, cst = SortStats(), CodecStats()
+    n = lib.ndgpu_ovl_sort_images(ptrs, sizes, len(arrs), _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len),
+                                  int(bool(hq)), int(flags), C.byref(image), C.byref(nbytes), C.byref(bid), C.byref(bkind), C.byref(nbl),
+                                  C.byref(st), C.byref(cst))
+    if n < 0:
+        raise _codec_fail(lib, "ndgpu_ovl_sort_images", n)
+    img = _take(lib, image, nbytes.value, np.uint8)
+    ids = _take(lib, bid, nbl.value, np.uint32)
+    kinds = _take(lib, bkind, nbl.value, np.uint8)
+    return img, list(zip(ids.tolist(), [chr(k) for k in kinds.tolist()])), {"sort": _stats_dict(st), "codec": _stats_dict(cst)}
+
+
+def admit_piles_image(buf, n_ids: int, min_len_seed: int, min_len_aln: int = 500, max_cov_aln: int = 130, min_cov_seed: int = 10,
+                      skip=(), flags: int = 0):
+    """admit_piles on the bytes of a sorted.ovl (ndgpu_admit_piles_image): uploaded as bytes, decoded and admitted on the device.
+    Returns (recs uint32[n,8], pile_off uint64[p+1], seeds uint32[p], {"admit": ..., "codec": ...})."""
+    lib = load()
+    P, PP, u32 = C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32
+    lib.ndgpu_admit_piles_image.argtypes = [P, C.c_uint64, u32, u32, u32, u32, u32, P, C.c_int64, C.c_int32, PP, PP, PP, C.POINTER(C.c_int64),
+                                            C.POINTER(AdmitStats), C.POINTER(CodecStats)]
+    lib.ndgpu_admit_piles_image.restype = C.c_int64
+    (a,), _p, _s = _images([buf])
+    sk = _skip_array(skip)
+    r8, off, seeds = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    npiles = C.c_int64(0)
+    st, cst = AdmitStats(), CodecStats()
+    n = lib.ndgpu_admit_piles_image(_ptr(a), a.size, int(n_ids), int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed), _ptr(sk),
+                                    sk.size, int(flags), C.byref(r8), C.byref(off), C.byref(seeds), C.byref(npiles), C.byref(st), C.byref(cst))
+    if n < 0:
+        raise _codec_fail(lib, "ndgpu_admit_piles_image", n)
+    recs = _take(lib, r8, n * 8, np.uint32).reshape(-1, 8)
+    return (recs, _take(lib, off, npiles.value + 1, np.uint64), _take(lib, seeds, npiles.value, np.uint32),
+            {"admit": _stats_dict(st), "codec": _stats_dict(cst)})

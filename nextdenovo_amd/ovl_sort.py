@@ -69,10 +69,15 @@ def run(argv) -> int:
     if a.flank <= 0:
         raise SystemExit("[ERROR] -l must be > 0")
     seed_len, min_len = read_idx(a.idx)
-    files = [overlap.from_decoded(ovl.decode_ovl(p)) for p in read_fofn(a.fofn)]
-    recs, bl, _ = overlap.sort_overlaps(files, seed_len, min_len, a.k, a.flank, hq=a.hq)
-    with open(a.out, "wb") as f:
-        f.write(overlap.encode(recs, np.zeros(2, dtype=np.uint32)))
+    if overlap.codec_device():   # the files as bytes to the device, the bytes of sorted.ovl back (ndgpu_ovl_sort_images, K17)
+        image, bl, _ = overlap.sort_images([overlap.file_bytes(p) for p in read_fofn(a.fofn)], seed_len, min_len, a.k, a.flank, hq=a.hq)
+        with open(a.out, "wb") as f:
+            f.write(image.data)
+    else:
+        files = [overlap.from_decoded(ovl.decode_ovl(p)) for p in read_fofn(a.fofn)]
+        recs, bl, _ = overlap.sort_overlaps(files, seed_len, min_len, a.k, a.flank, hq=a.hq)
+        with open(a.out, "wb") as f:
+            f.write(overlap.encode(recs, np.zeros(2, dtype=np.uint32)))
     with open(a.out + ".bl", "w") as f:
         for i, k in bl:
             f.write("%d %s\n" % (i, k))
