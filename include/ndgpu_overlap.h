@@ -259,6 +259,64 @@ int64_t ndgpu_admit_piles_image(const uint8_t *buf, uint64_t n_bytes, uint32_t n
                                 uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
                                 ndgpu_ovl_admit_stats *admit_stats, ndgpu_ovl_codec_stats *codec_stats);
 
+/* ---- record sets: the step-1 records of a job, wherever they are (K18; csrc/ovlsort_kernels.hip) ----
+ * A set holds n records in device memory of the library's block pool, in the order ndgpu_ovl_map returns them.  It is read-only once
+ * made; any number of sort calls may read it (the `ln -sf` mirror of a seed x seed job, nextDenovo:459, is one set read by the sorts
+ * of two seed files), from any thread.  A set is live pool memory until it is freed: ndgpu_ovl_trim does not touch it and
+ * ndgpu_ovl_pool_bytes counts it as in use.  The calls that make a set return it through their last argument, or NULL with the
+ * error codes -1 (no device) and -2 (a device operation failed: ndgpu_ovl_last_error; what was made so far is freed). */
+typedef struct ndgpu_ovl_recset ndgpu_ovl_recset;
+/* ndgpu_ovl_map with the records left on the device: same arguments, same return value, *set instead of *recs (an empty query set
+ * gives 0 and an empty set).  Every batch's records are appended device to device in read order; the call returns with the index's
+ * stream synchronised, so a consumer on another stream needs no event.  The 8-field records only (--mode 3 included): opt->step == 2
+ * is refused with -1. */
+int64_t ndgpu_ovl_map_dev(ndgpu_ovl_index *idx, const ndgpu_ovl_opt *opt, int32_t mid_occ, uint32_t n_reads, const uint32_t *words,
+                          uint64_t n_words, const uint64_t *word_off, const uint32_t *lens, const uint32_t *ids, ndgpu_ovl_recset **set);
+/* records in a set (0 for NULL) */
+int64_t ndgpu_ovl_recset_size(const ndgpu_ovl_recset *set);
+/* the records of a set to out[0 .. cap): returns their number, -4 when cap is smaller, -2 when the copy failed */
+int64_t ndgpu_ovl_recset_download(const ndgpu_ovl_recset *set, ndgpu_ovl_rec *out, int64_t cap);
+/* a set made from n host records (what another rank handed over arrives on the host); NULL on failure (ndgpu_ovl_last_error) */
+ndgpu_ovl_recset *ndgpu_ovl_recset_upload(const ndgpu_ovl_rec *recs, int64_t n);
+/* a new set: the n inputs back to back, copied device to device (the -I parts of one target, part-major); the inputs stay as they
+ * are.  NULL on failure. */
+ndgpu_ovl_recset *ndgpu_ovl_recset_concat(const ndgpu_ovl_recset *const *sets, int32_t n);
+/* K18, the stable split: out_sets[f] (n_files entries) = the records of `set` whose file_of[qname] == f, in their order in `set` --
+ * what a stable argsort by file and a cut at the file boundaries give on the host.  file_of has n_ids entries, < n_files each.  Two
+ * passes over the records (count per 512-record tile and file, one scan, scatter): no atomics on the output positions, so the order
+ * does not depend on how the device schedules lanes and wavefronts.  The output sets share one buffer, released with the last of
+ * them.  Returns 0; -1 no device; -2 a record's qname >= n_ids or its file_of entry is 0xffffffff (or a device operation failed:
+ * ndgpu_ovl_last_error != 0) -- no set is made; -4 a bad argument or n_files > 256 (the caller cuts on the host). */
+int64_t ndgpu_ovl_recset_split(const ndgpu_ovl_recset *set, const uint32_t *file_of, uint32_t n_ids, int32_t n_files,
+                               ndgpu_ovl_recset **out_sets);
+/* NULL is fine */
+void ndgpu_ovl_recset_free(ndgpu_ovl_recset *set);
+/* ndgpu_ovl_sort (hq != 0: ndgpu_ovl_sort_hq) and ndgpu_ovl_sort_piles with the input files as sets: every other argument, output and
+ * stats structure is theirs.  The records reach the sort's buffer by device-to-device copies and the file of every record is filled in
+ * on the device.  A sort in seed ranges (see ndgpu_ovl_sort) reads its files from host memory twice: for it the sets are downloaded
+ * once into buffers the call owns (counted in sets_downloaded).  Nothing is refused that the host-records calls accept. */
+int64_t ndgpu_ovl_sort_sets(const ndgpu_ovl_recset *const *files, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                            int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, ndgpu_ovl_rec **out,
+                            uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats);
+int64_t ndgpu_ovl_sort_piles_sets(const ndgpu_ovl_recset *const *files, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                                  int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, uint32_t min_len_seed,
+                                  uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                                  const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                                  int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                  ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats);
+/* counters of the process since the last reset (sets_live is never reset):
+ *   split_ms                          HIP-event time of the split calls (two kernel passes, the scan, the cut points' download)
+ *   sets_made, sets_live              sets handed out; sets not freed yet
+ *   bytes_downloaded, bytes_uploaded  record bytes copied to / from the host on behalf of sets (download, upload, a sort in seed ranges)
+ *   bytes_d2d                         record bytes copied device to device (map batches, concat, split, the sorts' input)
+ *   split_calls                       ndgpu_ovl_recset_split calls that ran
+ *   sets_downloaded                   sets a sort in seed ranges had to download */
+typedef struct ndgpu_ovl_recset_counters {
+	double split_ms;
+	uint64_t sets_made, sets_live, bytes_downloaded, bytes_uploaded, bytes_d2d, split_calls, sets_downloaded;
+} ndgpu_ovl_recset_counters;
+void ndgpu_ovl_recset_stats(ndgpu_ovl_recset_counters *out, int reset);
+
 /* ---- read ingestion: the 2-bit packing of `seq_dump` (seq2bit, lib/bseq.c:114-139; called from util/seq_dump.c:36-41) ----
  * Read i is the lens[i] ASCII bytes at ascii + ascii_off[i]; its ceil(lens[i]/16) words go to words + word_off[i] (word_off ascending,
  * reads back to back).  Bytes other than ACGTU (either case) are coded 4 and OR-ed in as the reference does, so they disturb the low

@@ -59,7 +59,9 @@ class _IndexCache:
     def __init__(self, opt, target):
         self.opt, self.target, self.parts, self.mid_occ = opt, target, {}, {}
 
-    def map(self, query, batch_size, dual):
+    def map(self, query, batch_size, dual, device=False):
+        """The job's records, the -I parts of the target one after the other (part-major); device: as a RecordSet (map_dev per part,
+        concat_sets)."""
         o = overlap.Opt.from_buffer_copy(self.opt)
         o.no_dual = 0 if dual else 1
         out = []
@@ -67,14 +69,22 @@ class _IndexCache:
         # every reference job is its own process: its occurrence threshold comes from the FIRST index part of ITS -I
         # split (main.c:489, options.c:70-71) -- kept per split layout, not per target file
         key = tuple(layout)
-        for lo, hi in layout:
-            ix = self.parts.get((lo, hi))
-            if ix is None:
-                ix = self.parts[(lo, hi)] = overlap.Index(self.opt, self.target.subset(lo, hi))
-            if key not in self.mid_occ:
-                self.mid_occ[key] = self.opt.mid_occ if self.opt.mid_occ > 0 else ix.mid_occ()
-            out.append(ix.map(query, self.mid_occ[key], opt=o))
-        return np.concatenate(out) if len(out) > 1 else out[0]
+        whole = False
+        try:
+            for lo, hi in layout:
+                ix = self.parts.get((lo, hi))
+                if ix is None:
+                    ix = self.parts[(lo, hi)] = overlap.Index(self.opt, self.target.subset(lo, hi))
+                if key not in self.mid_occ:
+                    self.mid_occ[key] = self.opt.mid_occ if self.opt.mid_occ > 0 else ix.mid_occ()
+                out.append((ix.map_dev if device else ix.map)(query, self.mid_occ[key], opt=o))
+            res = out[0] if len(out) == 1 else overlap.concat_sets(out) if device else np.concatenate(out)
+            whole = True
+            return res
+        finally:
+            if device and not (whole and len(out) == 1):   # the parts' own sets: a failed call's, or the ones just copied into one
+                for s in out:
+                    s.close()
 
     def close(self):
         for ix in self.parts.values():
@@ -94,6 +104,13 @@ def read_db_from_sets(sets):
         chunks.append(s.words)
         base += s.words.size
     return np.concatenate(chunks), word_off, lens
+
+
+def _close_sets(per_seed_files):
+    for lst in per_seed_files.values():
+        for _k, r in lst:
+            if isinstance(r, overlap.RecordSet):
+                r.close()
 
 
 def _keep_encode(recs) -> bytes:
@@ -157,27 +174,45 @@ def run(argv) -> int:
     seed_batch = 6000000000 if a.preset == "ava-hifi" else 3000000000  # -I 6G / 3G of the seed x seed jobs (nextDenovo:430,456)
 
     # --- raw_align: every job once, records kept in host memory
+    # NDGPU_RECS_DEVICE=1: a job's records stay on the device as a RecordSet (the mirror of a seed x seed job is the same object in two
+    # lists, closed after the last sort that reads it); every job runs before the first sort, so NDGPU_RECS_DEVICE_BYTES bounds the
+    # live sets: past it a job's records go to the host and travel as an array, as without the switch
+    on_device = overlap.recs_device()
     per_seed_files = {i: [] for i in range(len(seeds))}   # seed file -> [(k, records)] of the jobs that involve it
+    sorts_left = {}                                       # job -> sorts that have yet to read its RecordSet
+    sets_lock = __import__("threading").Lock()
     caches = {}
-    for k, i, kind, j, dual in job_matrix(len(seeds), len(parts)):
-        if i not in want and not (kind == "seed" and j in want):
-            continue
-        if i not in caches:
-            caches[i] = _IndexCache(opt, seeds[i])
-        query = parts[j] if kind == "part" else seeds[j]
-        recs = caches[i].map(query, minimap2_nd.IDX_BATCH if kind == "part" else seed_batch, dual)
-        per_seed_files[i].append((k, recs))
-        if kind == "seed" and j != i:
-            per_seed_files[j].append((k, recs))          # the `ln -sf` mirror of a seed x seed job (nextDenovo:459)
-        if a.keep:
-            os.makedirs(a.keep, exist_ok=True)
-            name = "%s.%d.ovl" % (os.path.basename(seed_paths[i]), k)
-            with open(os.path.join(a.keep, name), "wb") as f:
-                f.write(_keep_encode(recs))
-        if kind == "seed" and j == len(seeds) - 1:
-            caches.pop(i).close()                         # seed file i is not a target again
-    for c in caches.values():
-        c.close()
+    try:
+        for k, i, kind, j, dual in job_matrix(len(seeds), len(parts)):
+            if i not in want and not (kind == "seed" and j in want):
+                continue
+            if i not in caches:
+                caches[i] = _IndexCache(opt, seeds[i])
+            query = parts[j] if kind == "part" else seeds[j]
+            recs = caches[i].map(query, minimap2_nd.IDX_BATCH if kind == "part" else seed_batch, dual, device=on_device)
+            per_seed_files[i].append((k, recs))
+            if kind == "seed" and j != i:
+                per_seed_files[j].append((k, recs))          # the `ln -sf` mirror of a seed x seed job (nextDenovo:459)
+            if a.keep:
+                os.makedirs(a.keep, exist_ok=True)
+                name = "%s.%d.ovl" % (os.path.basename(seed_paths[i]), k)
+                with open(os.path.join(a.keep, name), "wb") as f:
+                    f.write(_keep_encode(recs.download() if on_device else recs))
+            if on_device:
+                kept = overlap.within_budget(recs)
+                if kept is not recs:   # past the budget: the array in the set's place
+                    for lst in per_seed_files.values():
+                        lst[:] = [(k_, kept if r is recs else r) for k_, r in lst]
+                else:
+                    sorts_left[k] = sum(1 for t in {i, j if kind == "seed" else i} if t in want)
+            if kind == "seed" and j == len(seeds) - 1:
+                caches.pop(i).close()                         # seed file i is not a target again
+    except BaseException:
+        _close_sets(per_seed_files)
+        raise
+    finally:
+        for c in caches.values():
+            c.close()
 
     # --- sort_align + seed_cns per seed file
     words, word_off, lens = read_db_from_sets(seeds + parts)
@@ -200,6 +235,13 @@ def run(argv) -> int:
                                                              min_cov_seed=a.min_cov_seed, use_bl=bool(a.blacklist), want_sorted=bool(a.keep))
         else:
             srt, bl, _ = overlap.sort_overlaps(files, seed_len, int(s.lens.min()) if len(s) else 0, a.sort_k, a.flank)
+        for k, r in per_seed_files[i]:   # the sort has read them: a set goes with the last sort that needed it
+            if isinstance(r, overlap.RecordSet):
+                with sets_lock:
+                    sorts_left[k] -= 1
+                    last = sorts_left[k] == 0
+                if last:
+                    r.close()
         if a.keep:
             so = os.path.join(a.keep, "input.seed.%s.sorted.ovl" % tag)
             with open(so, "wb") as f:
@@ -234,6 +276,7 @@ def run(argv) -> int:
             totals[0] += n_bases
             totals[1] += n_recs
     finally:
+        _close_sets(per_seed_files)   # (none is left after the last sort; a failed run's are)
         db.close()
     if world > 1:  # the stage's only collective: the final counts (RCCL over xGMI on a GPU node, gloo without one)
         import torch

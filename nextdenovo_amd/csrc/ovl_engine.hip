@@ -23,6 +23,7 @@
 #include "../../include/ndgpu_overlap.h"
 #include "ovl_device.h"
 #include "ovl_host.h"
+#include "ovl_recset.h"
 
 #include <map>
 #include <chrono>
@@ -368,6 +369,8 @@ struct DebugView {
 struct BatchOut {
 	std::vector<OvlRec> recs;
 	std::vector<OvlRec10> recs10;
+	DevBuf<OvlRec> dev;                            // the records where K5 left them, n_dev of them (a call that keeps them on the device)
+	uint64_t n_dev = 0;
 	std::vector<uint32_t> counts, chains;
 	std::vector<uint64_t> ca_x, ca_y, ca_off{0};   // (ca_off: relative to the batch)
 	ndgpu_ovl_stats st{};
@@ -390,6 +393,7 @@ struct MapCall {
 	unsigned pos_bits, rid_bits;   // sort key: bits of a target position, of a target read
 	bool hit_counts;    // the caller wants the hits of every read counted (Regs)
 	bool read_chains;   // ... the chains of every read (Rechain)
+	bool keep_on_device = false;   // the records stay on the device (DevRecs): no download
 };
 
 // One batch on its way through the steps of map_batch: its reads [r0, r0 + nb), its slice of the call's anchors, its stream, scratch,
@@ -662,8 +666,12 @@ static void map_batch(const MapCall &c, size_t bi, hipStream_t stream, Scratch &
 		dense10.download(out.recs10.data(), n_out, stream);
 	} else {
 		if (c.P.mode3 && n_out) extend_hits(b, dense, n_out);
-		out.recs.resize(n_out);
-		dense.download(out.recs.data(), n_out, stream);
+		if (c.keep_on_device) {
+			out.dev = std::move(dense), out.n_dev = n_out;
+		} else {
+			out.recs.resize(n_out);
+			dense.download(out.recs.data(), n_out, stream);
+		}
 	}
 	HIP_OK(hipStreamSynchronize(stream));
 	out.st.chain_cells += h_cells;
@@ -676,6 +684,12 @@ static void map_batch(const MapCall &c, size_t bi, hipStream_t stream, Scratch &
 		d.ax = std::move(A.ax); d.ay = std::move(A.ay); d.f = std::move(C.f); d.p = std::move(C.p);
 	}
 }
+
+// The record sink of a call that leaves its records on the device (ndgpu_ovl_map_dev): the first n records of buf, read order
+struct DevRecs {
+	DevBuf<OvlRec> buf;
+	uint64_t n = 0;
+};
 
 struct Engine {
 	int device = 0;
@@ -946,7 +960,7 @@ struct Engine {
 	// One pass over the query set.  `rc` belongs to map() below.
 	int64_t map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, const uint32_t *words, uint64_t n_words, const uint64_t *woff,
 	                 const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10, const Regs *regs,
-	                 const Rechain &rc);
+	                 const Rechain &rc, DevRecs *dev);
 	// -f FLOAT,INT (mm_mapopt_t::max_occ > mid_occ; minimap2/map.c:553-575 and :678-700): a query read that ends its chaining without a
 	// chain is seeded again with every minimizer below max_occ occurrences and chained again (with one segment per query that is the
 	// test together with `rep_len > 0`: a read none of whose minimizers was dropped would collect the same seeds again -- and in the
@@ -956,11 +970,11 @@ struct Engine {
 	// so the second pass's records are the reference's, in its order, whatever the mode of the call (records, hits, chains).
 	int64_t map(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, const uint32_t *words, uint64_t n_words, const uint64_t *woff,
 	            const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10 = nullptr,
-	            const Regs *regs = nullptr)
+	            const Regs *regs = nullptr, DevRecs *dev = nullptr)
 	{
-		if (o.max_occ <= mid) return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{});
+		if (o.max_occ <= mid) return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{}, dev);
 		std::vector<uint32_t> chains, rep;
-		int64_t n = map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{nullptr, &chains, &rep});
+		int64_t n = map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{nullptr, &chains, &rep}, dev);
 		if (n < 0) return n;
 		chains.resize(n_q, 0u);
 		rep.resize(n_q, 0u);
@@ -970,13 +984,13 @@ struct Engine {
 			if (!chains[i] && rep[i]) thr[i] = o.max_occ, ++again;   // map.c:553 / :678: no chain AND rep_len > 0
 		if (!again) return n;
 		st.rechained += again;
-		return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{thr.data(), nullptr, nullptr});
+		return map_once(o, mid, n_q, words, n_words, woff, lens, ids, out, out10, regs, Rechain{thr.data(), nullptr, nullptr}, dev);
 	}
 };
 
 int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, const uint32_t *words, uint64_t n_words, const uint64_t *woff,
                          const uint32_t *lens, const uint32_t *ids, std::vector<OvlRec> &out, std::vector<OvlRec10> *out10, const Regs *regs,
-                         const Rechain &rc)
+                         const Rechain &rc, DevRecs *dev)
 {
 	const OvlParams Pc = call_params(o, regs);
 	if (regs) {
@@ -997,8 +1011,10 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 	}
 	out.clear();
 	if (out10) out10->clear();
+	if (dev) dev->buf.release(), dev->n = 0;
 	if (rc.chains) rc.chains->clear();
 	if ((Pc.step2 != 0) != (out10 != nullptr)) return -1; // the two record types have an entry point each
+	if (dev && (out10 || regs)) return -1;                // the device sink takes the 8-field records of a plain map call
 	if (!n_q) return 0;
 
 	ReadSetDev Q;
@@ -1078,7 +1094,7 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 		r0 = r1;
 	}
 	const MapCall call{Pc, mid, ix, qd, T, Q, S, m_start.p, m_cnt.p, a_off.p, r_aoff_all.p, h_raoff, h_moff, ranges, pos_bits, rid_bits,
-	                   regs != nullptr, rc.chains != nullptr};
+	                   regs != nullptr, rc.chains != nullptr, dev != nullptr};
 	std::vector<BatchOut> outs(ranges.size());
 	run_batches(call, std::min<size_t>((size_t)lanes, ranges.size()), outs);
 
@@ -1105,12 +1121,33 @@ int64_t Engine::map_once(const ndgpu_ovl_opt &o, int32_t mid, uint32_t n_q, cons
 		st.ext_ms += b.ext_ms, st.tie_reads += b.tie_reads, st.chain_cells += b.chain_cells, st.chains += b.chains, st.overlaps += b.overlaps;
 		st.batches += b.batches, st.ext_problems += b.ext_problems, st.ext_launches += b.ext_launches;
 	}
+	if (dev) {
+		// The records stay on the device, batch after batch in read order.  Every batch's stream has been waited for (map_batch, the
+		// lanes), so the copies below see finished buffers; one batch with records -- the usual call -- hands its buffer over as it is.
+		uint64_t total = 0;
+		size_t with = 0;
+		for (const BatchOut &BO : outs) total += BO.n_dev, with += BO.n_dev != 0;
+		if (with == 1) {
+			for (BatchOut &BO : outs) if (BO.n_dev) dev->buf = std::move(BO.dev);
+		} else if (with > 1) {
+			dev->buf.alloc(total);
+			uint64_t at = 0;
+			for (const BatchOut &BO : outs) {
+				if (!BO.n_dev) continue;
+				HIP_OK(hipMemcpyAsync(dev->buf.p + at, BO.dev.p, BO.n_dev * sizeof(OvlRec), hipMemcpyDeviceToDevice, stream));
+				at += BO.n_dev;
+			}
+			g_recset.bytes_d2d += total * sizeof(OvlRec);
+		}
+		dev->n = total;
+		HIP_OK(hipStreamSynchronize(stream));   // a consumer on another stream needs no event (and the batches' buffers go back to the pool)
+	}
 	if (rc.rep) {   // (K3a ran over every query minimizer before the first batch: the flags are whole)
 		rc.rep->assign(n_q, 0u);
 		d_rep.download(rc.rep->data(), n_q, stream);
 		HIP_OK(hipStreamSynchronize(stream));
 	}
-	return out10 ? (int64_t)out10->size() : (int64_t)out.size();
+	return dev ? (int64_t)dev->n : out10 ? (int64_t)out10->size() : (int64_t)out.size();
 }
 
 } // namespace ndovl
@@ -1220,6 +1257,27 @@ int64_t ndgpu_ovl_map(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32_t mid_
 		int64_t n = h->e.map(*opt, mid_occ, n_reads, words, n_words, word_off, lens, ids, out);
 		if (n < 0) return n;
 		*recs = malloc_copy<ndgpu_ovl_rec>(out);
+		return n;
+	} catch (...) {
+		return -2;
+	}
+}
+
+// ndgpu_ovl_map with the device sink: the records become a set (ovl_recset.h).  A failure on the way frees what was made (the
+// sink's buffer and the batches' are blocks of the pool owned by objects of this call) and is reported as ndgpu_ovl_map reports it.
+int64_t ndgpu_ovl_map_dev(ndgpu_ovl_index *h, const ndgpu_ovl_opt *opt, int32_t mid_occ, uint32_t n_reads, const uint32_t *words,
+                          uint64_t n_words, const uint64_t *word_off, const uint32_t *lens, const uint32_t *ids, ndgpu_ovl_recset **set)
+{
+	*set = nullptr;
+	if (const char *msg = check_opt(*opt)) { fprintf(stderr, "[ndgpu_overlap] %s\n", msg); return -1; }
+	if (opt->step == 2) { fprintf(stderr, "[ndgpu_overlap] record sets hold the 8-field records: --step 2 records come from ndgpu_ovl_map2\n"); return -1; }
+	try {
+		HIP_OK(hipSetDevice(h->e.device));
+		std::vector<OvlRec> none;
+		DevRecs dev;
+		int64_t n = h->e.map(*opt, mid_occ, n_reads, words, n_words, word_off, lens, ids, none, nullptr, nullptr, &dev);
+		if (n < 0) return n;
+		*set = recset_own(std::move(dev.buf), dev.n);
 		return n;
 	} catch (...) {
 		return -2;

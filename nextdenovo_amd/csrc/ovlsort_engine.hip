@@ -12,6 +12,7 @@
 #include "../../include/ndgpu_overlap.h"
 #include "ovl_device.h"
 #include "ovl_host.h"
+#include "ovl_recset.h"
 
 namespace ndovl {
 
@@ -64,6 +65,16 @@ void launch_codec_records(OvlRec *recs, uint64_t n, const uint32_t *dq, const ui
                           const uint64_t *rec_base, uint32_t n_files, hipStream_t s);
 void launch_codec_size(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, uint32_t *len, hipStream_t s);
 void launch_codec_write(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_t prev_t, const uint64_t *off, uint8_t *out, hipStream_t s);
+
+// K18, the stable split of a record set, and the file of every record of a sort's input (csrc/ovlsort_kernels.hip)
+uint32_t split_tile_records();
+uint32_t split_max_files();
+void launch_split_count(const OvlRec *recs, uint64_t n, const uint32_t *file_of, uint32_t n_ids, uint32_t n_files, uint64_t n_tiles, uint32_t *cnt,
+                        uint32_t *bad_cnt, hipStream_t s);
+void launch_split_cuts(const uint64_t *first, uint64_t n_tiles, uint32_t n_files, uint64_t *cuts, hipStream_t s);
+void launch_split_scatter(const OvlRec *recs, uint64_t n, const uint32_t *file_of, uint32_t n_ids, uint32_t n_files, uint64_t n_tiles,
+                          const uint64_t *first, OvlRec *out, hipStream_t s);
+void launch_file_fill(const uint64_t *fstart, uint32_t n_files, uint64_t n, uint32_t *file_of, hipStream_t s);
 
 struct SortRun {
 	hipStream_t st = nullptr;
@@ -539,7 +550,8 @@ static void sort_out_of_core(SortRun &R, const ndgpu_ovl_rec *const *files, cons
 static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
                          uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, ndgpu_ovl_rec **out,
                          uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats, bool hq_mode, Admission *A = nullptr,
-                         const uint32_t *skip_ids = nullptr, int64_t n_skip = 0, const ImageSet *images = nullptr, EncodeTail *E = nullptr)
+                         const uint32_t *skip_ids = nullptr, int64_t n_skip = 0, const ImageSet *images = nullptr, EncodeTail *E = nullptr,
+                         const ndgpu_ovl_recset *const *sets = nullptr)
 {
 	*out = nullptr, *bl_id = nullptr, *bl_kind = nullptr, *n_bl = 0;
 	if (stats) memset(stats, 0, sizeof(*stats));
@@ -608,6 +620,30 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			if (E) E->st.bytes_in += img_bytes, E->st.records += at;
 		}
 
+		// the files as record sets (ovl_recset.h): the form of the sort is decided HERE, once, as for images.  In one piece the sets
+		// are copied into `raw` device to device below; a sort in seed ranges reads its files from host memory, piece by piece and
+		// twice, so it gets them downloaded once into a block this call owns and goes on as a call with host records.
+		bool from_sets = false;
+		if (sets) {
+			host_counts.assign((size_t)n_files, 0);
+			uint64_t total = 0;
+			for (int f = 0; f < n_files; ++f) host_counts[(size_t)f] = sets[f] ? (int64_t)sets[f]->n : 0, total += (uint64_t)host_counts[(size_t)f];
+			n_per_file = host_counts.data();
+			look_at_memory();
+			from_sets = fits(total);
+			if (!from_sets) {
+				OvlRec *at = host_recs.grow(total);
+				for (int f = 0; f < n_files; ++f) {
+					const uint64_t m = (uint64_t)host_counts[(size_t)f];
+					if (m) HIP_OK(hipMemcpyAsync(at, sets[f]->data(), m * sizeof(OvlRec), hipMemcpyDeviceToHost, R.st));
+					host_files.push_back((const ndgpu_ovl_rec*)at), at += m;
+				}
+				HIP_OK(hipStreamSynchronize(R.st));
+				files = host_files.data();
+				g_recset.sets_downloaded += (uint64_t)n_files, g_recset.bytes_downloaded += total * sizeof(OvlRec);
+			}
+		}
+
 		uint64_t n = 0;
 		std::vector<uint64_t> h_fstart((size_t)n_files + 1);
 		for (int f = 0; f < n_files; ++f) { h_fstart[f] = n; n += (uint64_t)n_per_file[f]; }
@@ -615,8 +651,8 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 		SortOut so;
 		if (n == 0) { hand_out(so, out, bl_id, bl_kind, n_bl); return 0; }   // (nothing in: an empty result, the stats stay zero)
 		if (A) A->begin(skip_ids, n_skip, R.st);
-		if (!images) look_at_memory();
-		const bool in_core = images ? raw_on_device : fits(n);
+		if (!images && !sets) look_at_memory();
+		const bool in_core = images ? raw_on_device : sets ? from_sets : fits(n);
 		uint64_t nc = 0, n_ranges = 1;
 		if (!in_core) {
 			if (raw_on_device || !files) throw std::runtime_error("a sort in seed ranges needs its records in host memory");
@@ -625,9 +661,13 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			sort_out_of_core(R, files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq_mode, piece_cap, range_cap, so,
 			                 &nc, &n_ranges, A, E);
 		} else {
-			std::vector<uint32_t> h_file_of(n);
+			std::vector<uint32_t> h_file_of(from_sets ? 0 : n);
 			DevBuf<OvlRec> raw(n);
-			for (int f = 0; f < n_files; ++f) {
+			for (int f = 0; f < n_files && from_sets; ++f)   // the sets' records: device to device on the sort's stream
+				if (n_per_file[f])
+					HIP_OK(hipMemcpyAsync(raw.p + h_fstart[f], sets[f]->data(), (size_t)n_per_file[f] * sizeof(OvlRec), hipMemcpyDeviceToDevice, R.st));
+			if (from_sets) g_recset.bytes_d2d += n * sizeof(OvlRec);
+			for (int f = 0; f < n_files && !from_sets; ++f) {
 				std::fill(h_file_of.begin() + h_fstart[f], h_file_of.begin() + h_fstart[f + 1], (uint32_t)f);
 				if (n_per_file[f] && !raw_on_device)
 					HIP_OK(hipMemcpyAsync(raw.p + h_fstart[f], files[f], (size_t)n_per_file[f] * sizeof(OvlRec), hipMemcpyHostToDevice, R.st));
@@ -641,8 +681,9 @@ static int64_t sort_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per
 			}
 			DevBuf<uint32_t> file_of(n), d_seed(n_ids + 1);
 			DevBuf<uint64_t> fstart((size_t)n_files + 1);
-			file_of.upload(h_file_of.data(), n, R.st);
+			if (!from_sets) file_of.upload(h_file_of.data(), n, R.st);
 			fstart.upload(h_fstart.data(), (size_t)n_files + 1, R.st);
+			if (from_sets) launch_file_fill(fstart.p, (uint32_t)n_files, n, file_of.p, R.st);   // (no n-entry host vector, no upload of it)
 			d_seed.upload(seed_len, n_ids, R.st);
 
 			// S1: candidates
@@ -827,12 +868,13 @@ extern "C" int64_t ndgpu_admit_piles(const ndgpu_ovl_rec *sorted, int64_t n, uin
 	}
 }
 
-extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
-                                        uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq,
-                                        uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
-                                        const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
-                                        int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
-                                        ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats)
+// ndgpu_ovl_sort_piles, the files as host records (files + n_per_file) or as record sets (sets)
+static int64_t sort_piles_impl(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, const ndgpu_ovl_recset *const *sets, int32_t n_files,
+                               const uint32_t *seed_len, uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq,
+                               uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                               const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                               int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                               ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats)
 {
 	*recs8 = nullptr, *pile_off = nullptr, *seeds = nullptr, *n_piles = 0;
 	if (sorted) *sorted = nullptr;
@@ -848,13 +890,13 @@ extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const
 		const bool host_only = flags & 1;
 		A.want_sorted = sorted != nullptr || host_only;
 		int64_t ns = sort_impl(files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, bl_id, bl_kind, n_bl, stats,
-		                       hq != 0, host_only ? nullptr : &A, skip_ids, n_skip);
+		                       hq != 0, host_only ? nullptr : &A, skip_ids, n_skip, nullptr, nullptr, sets);
 		if (ns < 0) return ns;
 		*astats = A.st;
 		if (A.declined && !A.want_sorted) {   // the sorted records were left on the device: once more, for the host routine
 			drop();
 			ns = sort_impl(files, n_per_file, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, &srt, bl_id, bl_kind, n_bl, stats,
-			               hq != 0);
+			               hq != 0, nullptr, nullptr, 0, nullptr, nullptr, sets);
 			if (ns < 0) return ns;
 		}
 		int64_t nr;
@@ -880,6 +922,18 @@ extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const
 		drop();
 		return -2;
 	}
+}
+
+extern "C" int64_t ndgpu_ovl_sort_piles(const ndgpu_ovl_rec *const *files, const int64_t *n_per_file, int32_t n_files, const uint32_t *seed_len,
+                                        uint32_t n_ids, int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq,
+                                        uint32_t min_len_seed, uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                                        const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                                        int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                        ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats)
+{
+	return sort_piles_impl(files, n_per_file, nullptr, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq, min_len_seed, min_len_aln,
+	                       max_cov_aln, min_cov_seed, use_bl, skip_ids, n_skip, flags, bl_id, bl_kind, n_bl, recs8, pile_off, seeds, n_piles, sorted,
+	                       n_sorted, stats, astats);
 }
 
 
@@ -1097,4 +1151,167 @@ extern "C" int64_t ndgpu_admit_piles_image(const uint8_t *buf, uint64_t n_bytes,
 	} catch (...) {
 		return -2;
 	}
+}
+
+
+// ---- record sets (ovl_recset.h; ndgpu_ovl_map_dev makes them in ovl_engine.hip) and K18, their stable split ----
+extern "C" int64_t ndgpu_ovl_recset_size(const ndgpu_ovl_recset *set) { return set ? (int64_t)set->n : 0; }
+
+extern "C" void ndgpu_ovl_recset_free(ndgpu_ovl_recset *set)
+{
+	if (!set) return;
+	delete set;   // (the block goes back to the pool with the last set that shares it)
+	--g_recset.sets_live;
+}
+
+extern "C" void ndgpu_ovl_recset_stats(ndgpu_ovl_recset_counters *out, int reset)
+{
+	RecsetCounters &c = g_recset;
+	if (out) {
+		out->split_ms = (double)c.split_ns.load() * 1e-6;
+		out->sets_made = c.sets_made, out->sets_live = c.sets_live, out->bytes_downloaded = c.bytes_downloaded, out->bytes_uploaded = c.bytes_uploaded;
+		out->bytes_d2d = c.bytes_d2d, out->split_calls = c.split_calls, out->sets_downloaded = c.sets_downloaded;
+	}
+	if (reset) c.split_ns = 0, c.sets_made = 0, c.bytes_downloaded = 0, c.bytes_uploaded = 0, c.bytes_d2d = 0, c.split_calls = 0, c.sets_downloaded = 0;
+}
+
+extern "C" int64_t ndgpu_ovl_recset_download(const ndgpu_ovl_recset *set, ndgpu_ovl_rec *out, int64_t cap)
+{
+	const uint64_t n = set ? set->n : 0;
+	if (cap < 0 || (uint64_t)cap < n || (n && !out)) return -4;
+	if (!n) return 0;
+	try {
+		if (select_device(true) < 0) return -1;
+		SortRun R;
+		HIP_OK(ndovl::create_stage_stream(&R.st));
+		const StreamGuard guard{R.st};
+		HIP_OK(hipMemcpyAsync(out, set->data(), n * sizeof(OvlRec), hipMemcpyDeviceToHost, R.st));
+		HIP_OK(hipStreamSynchronize(R.st));
+		g_recset.bytes_downloaded += n * sizeof(OvlRec);
+		return (int64_t)n;
+	} catch (...) {
+		return -2;
+	}
+}
+
+extern "C" ndgpu_ovl_recset *ndgpu_ovl_recset_upload(const ndgpu_ovl_rec *recs, int64_t n)
+{
+	if (n < 0 || (n > 0 && !recs)) return nullptr;
+	try {
+		if (n == 0) return recset_view(nullptr, 0, 0);
+		if (select_device(true) < 0) return nullptr;
+		SortRun R;
+		HIP_OK(ndovl::create_stage_stream(&R.st));
+		const StreamGuard guard{R.st};
+		DevBuf<OvlRec> d((size_t)n);
+		d.upload((const OvlRec*)recs, (size_t)n, R.st);
+		HIP_OK(hipStreamSynchronize(R.st));
+		g_recset.bytes_uploaded += (uint64_t)n * sizeof(OvlRec);
+		return recset_own(std::move(d), (uint64_t)n);
+	} catch (...) {
+		return nullptr;
+	}
+}
+
+extern "C" ndgpu_ovl_recset *ndgpu_ovl_recset_concat(const ndgpu_ovl_recset *const *sets, int32_t n)
+{
+	if (n < 0 || (n > 0 && !sets)) return nullptr;
+	try {
+		uint64_t total = 0;
+		for (int f = 0; f < n; ++f) total += sets[f] ? sets[f]->n : 0;
+		if (total == 0) return recset_view(nullptr, 0, 0);
+		if (select_device(true) < 0) return nullptr;
+		SortRun R;
+		HIP_OK(ndovl::create_stage_stream(&R.st));
+		const StreamGuard guard{R.st};
+		DevBuf<OvlRec> d(total);
+		uint64_t at = 0;
+		for (int f = 0; f < n; ++f) {
+			const uint64_t m = sets[f] ? sets[f]->n : 0;
+			if (m) HIP_OK(hipMemcpyAsync(d.p + at, sets[f]->data(), m * sizeof(OvlRec), hipMemcpyDeviceToDevice, R.st));
+			at += m;
+		}
+		HIP_OK(hipStreamSynchronize(R.st));
+		g_recset.bytes_d2d += total * sizeof(OvlRec);
+		return recset_own(std::move(d), total);
+	} catch (...) {
+		return nullptr;
+	}
+}
+
+// K18: count per (file, tile), one scan over the table in file-major order, the cut points, scatter.  The output sets are views into
+// one block.
+extern "C" int64_t ndgpu_ovl_recset_split(const ndgpu_ovl_recset *set, const uint32_t *file_of, uint32_t n_ids, int32_t n_files,
+                                          ndgpu_ovl_recset **out_sets)
+{
+	if (!out_sets || n_files <= 0) return -4;
+	for (int f = 0; f < n_files; ++f) out_sets[f] = nullptr;
+	const uint64_t n = set ? set->n : 0;
+	if ((uint32_t)n_files > split_max_files() || (n_ids > 0 && !file_of)) return -4;
+	try {
+		if (n == 0) {
+			for (int f = 0; f < n_files; ++f) out_sets[f] = recset_view(nullptr, 0, 0);
+			return 0;
+		}
+		if (select_device(true) < 0) return -1;
+		SortRun R;
+		HIP_OK(ndovl::create_stage_stream(&R.st));
+		const StreamGuard guard{R.st};
+		EvTimer tm(R.st);
+		tm.start();
+		const uint64_t tile = split_tile_records(), n_tiles = (n + tile - 1) / tile;
+		if (n_tiles >= 0x7fffffffull) throw std::runtime_error("too many records for one split call");
+		const size_t cells = (size_t)n_tiles * (size_t)n_files;
+		DevBuf<uint32_t> d_file(n_ids), cnt(cells + 1), bad(1);
+		DevBuf<uint64_t> first(cells + 1), cuts((size_t)n_files + 1);
+		d_file.upload(file_of, n_ids, R.st);
+		bad.zero(R.st);
+		HIP_OK(hipMemsetAsync(cnt.p + cells, 0, sizeof(uint32_t), R.st));   // (the scan's last entry = all rows)
+		launch_split_count(set->data(), n, d_file.p, n_ids, (uint32_t)n_files, n_tiles, cnt.p, bad.p, R.st);
+		R.exscan(cnt.p, first.p, cells + 1);
+		launch_split_cuts(first.p, n_tiles, (uint32_t)n_files, cuts.p, R.st);
+		std::vector<uint64_t> h_cuts((size_t)n_files + 1);
+		uint32_t h_bad = 0;
+		cuts.download(h_cuts.data(), (size_t)n_files + 1, R.st);
+		bad.download(&h_bad, 1, R.st);
+		HIP_OK(hipStreamSynchronize(R.st));   // (file_of, the caller's array, has been read)
+		HIP_OK(hipGetLastError());
+		++g_recset.split_calls;
+		if (h_bad) {   // a record that belongs to no file: no set is made
+			g_recset.split_ns += (uint64_t)(tm.stop() * 1e6);
+			fprintf(stderr, "[ndgpu_overlap] ndgpu_ovl_recset_split: %u records whose query read is in none of the %d files\n", h_bad, n_files);
+			return -2;
+		}
+		if (h_cuts[0] != 0 || h_cuts[(size_t)n_files] != n) throw std::runtime_error("split counts out of range");
+		auto out = std::make_shared<DevBuf<OvlRec>>((size_t)n);
+		launch_split_scatter(set->data(), n, d_file.p, n_ids, (uint32_t)n_files, n_tiles, first.p, out->p, R.st);
+		g_recset.split_ns += (uint64_t)(tm.stop() * 1e6);   // (waits for the stream)
+		HIP_OK(hipGetLastError());
+		g_recset.bytes_d2d += n * sizeof(OvlRec);
+		for (int f = 0; f < n_files; ++f) out_sets[f] = recset_view(out, h_cuts[(size_t)f], h_cuts[(size_t)f + 1] - h_cuts[(size_t)f]);
+		return 0;
+	} catch (...) {
+		for (int f = 0; f < n_files; ++f) ndgpu_ovl_recset_free(out_sets[f]), out_sets[f] = nullptr;
+		return -2;
+	}
+}
+
+extern "C" int64_t ndgpu_ovl_sort_sets(const ndgpu_ovl_recset *const *files, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                                       int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, ndgpu_ovl_rec **out,
+                                       uint32_t **bl_id, uint8_t **bl_kind, int64_t *n_bl, ndgpu_ovl_sort_stats *stats)
+{
+	return sort_impl(nullptr, nullptr, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, out, bl_id, bl_kind, n_bl, stats, hq != 0,
+	                 nullptr, nullptr, 0, nullptr, nullptr, files);
+}
+
+extern "C" int64_t ndgpu_ovl_sort_piles_sets(const ndgpu_ovl_recset *const *files, int32_t n_files, const uint32_t *seed_len, uint32_t n_ids,
+                                             int32_t min_seed_len, int32_t max_bin_cov, int32_t max_flank_len, int32_t hq, uint32_t min_len_seed,
+                                             uint32_t min_len_aln, uint32_t max_cov_aln, uint32_t min_cov_seed, int32_t use_bl,
+                                             const uint32_t *skip_ids, int64_t n_skip, int32_t flags, uint32_t **bl_id, uint8_t **bl_kind,
+                                             int64_t *n_bl, uint32_t **recs8, uint64_t **pile_off, uint32_t **seeds, int64_t *n_piles,
+                                             ndgpu_ovl_rec **sorted, int64_t *n_sorted, ndgpu_ovl_sort_stats *stats, ndgpu_ovl_admit_stats *astats)
+{
+	return sort_piles_impl(nullptr, nullptr, files, n_files, seed_len, n_ids, min_seed_len, max_bin_cov, max_flank_len, hq, min_len_seed, min_len_aln,
+	                       max_cov_aln, min_cov_seed, use_bl, skip_ids, n_skip, flags, bl_id, bl_kind, n_bl, recs8, pile_off, seeds, n_piles, sorted,
+	                       n_sorted, stats, astats);
 }

@@ -1102,4 +1102,159 @@ void launch_codec_write(const OvlRec *recs, uint64_t n, uint32_t prev_q, uint32_
 	if (n) ND_LAUNCH(codec_write_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, recs, n, prev_q, prev_t, off, out);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K18: the stable split of a record set by file (ndgpu_ovl_recset_split; on the host: np.argsort(file_of[qname], kind="stable") and a
+// cut at the file boundaries -- stage.Shard._overlaps_grouped).  File f's output is the records with file_of[qname] == f in input
+// order, so a record's output row is
+//     (records of files < f)  +  (records of file f in earlier tiles)  +  (records of file f earlier in its own tile).
+// A tile is kSplitIters x 64 consecutive records and belongs to one wavefront.  The count pass leaves cnt[f][tile]; an exclusive scan
+// over that table in file-major order is the first two terms for every (file, tile) at once, and its entries at the start of every
+// file's row are the cut points.  The scatter pass walks its tile again in the same order and keeps the third term as a running
+// count per file.  Inside a 64-record iteration the lanes of one file are told apart by ballots: the wavefront takes the file of its
+// first live lane, ballots the lanes that have the same one -- the popcount of the lower lanes in that ballot is the record's rank
+// among them --, drops them, and goes on until no lane is live: one round per distinct file present (mostly one or two; 64 at worst).
+// The per-file counts of a wavefront live in registers: lane l holds files l, l + 64, l + 128, l + 192 (n_files <= kSplitMaxFiles),
+// read by the others with a shuffle and advanced by their owner.  No LDS, no atomics on a position, nothing that depends on the order
+// lanes or wavefronts run in: every output row is a function of the input alone.
+// A record whose qname >= n_ids or whose file is not one of the n_files (0xffffffff = "no file") is counted in *bad and left out; the
+// host side then makes no set.
+
+constexpr uint32_t kSplitIters = 8;
+constexpr uint32_t kSplitTile = kSplitIters * 64;   // records of a tile
+constexpr uint32_t kSplitMaxFiles = 256;
+constexpr uint32_t kSplitSlots = kSplitMaxFiles / 64;
+
+// the file of record i (kNoSlot behind the last record), and whether the record is one the split refuses
+__device__ __forceinline__ uint32_t split_file(const OvlRec *__restrict__ recs, uint64_t i, uint64_t n, const uint32_t *__restrict__ file_of,
+                                               uint32_t n_ids, uint32_t n_files, bool *bad)
+{
+	*bad = false;
+	if (i >= n) return kNoSlot;
+	const uint32_t q = recs[i].qname;
+	const uint32_t f = q < n_ids ? file_of[q] : kNoSlot;
+	*bad = f >= n_files;
+	return f;
+}
+
+// the slot of v that belongs to file f (f wave-uniform; selects, so that v stays in registers)
+template <class T> __device__ __forceinline__ T split_slot(const T (&v)[kSplitSlots], uint32_t f)
+{
+	const uint32_t k = f >> 6;
+	return k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
+}
+
+// cnt[f * n_tiles + t] = records of file f in tile t (every entry written: the table needs no zeroing)
+__global__ void __launch_bounds__(64) split_count_kernel(const OvlRec *__restrict__ recs, uint64_t n, const uint32_t *__restrict__ file_of,
+                                                          uint32_t n_ids, uint32_t n_files, uint64_t n_tiles, uint32_t *__restrict__ cnt,
+                                                          uint32_t *__restrict__ bad_cnt)
+{
+	const uint64_t t = blockIdx.x;
+	if (t >= n_tiles) return;
+	const int lane = threadIdx.x;
+	uint32_t mine[kSplitSlots] = {0, 0, 0, 0}, n_bad = 0;
+	for (uint32_t it = 0; it < kSplitIters; ++it) {
+		const uint64_t i = t * kSplitTile + it * 64 + (uint32_t)lane;
+		bool bad;
+		const uint32_t f = split_file(recs, i, n, file_of, n_ids, n_files, &bad);
+		const bool ok = i < n && !bad;
+		n_bad += (uint32_t)__popcll(__ballot(bad));
+		unsigned long long live = __ballot(ok);
+		while (live) {
+			const uint32_t fc = __shfl(f, __ffsll((long long)live) - 1, 64);
+			const unsigned long long m = __ballot(ok && f == fc);
+			if (lane == (int)(fc & 63)) {
+#pragma unroll
+				for (uint32_t k = 0; k < kSplitSlots; ++k) if (k == fc >> 6) mine[k] += (uint32_t)__popcll(m);
+			}
+			live &= ~m;
+		}
+	}
+#pragma unroll
+	for (uint32_t k = 0; k < kSplitSlots; ++k) {
+		const uint32_t f = k * 64 + (uint32_t)lane;
+		if (f < n_files) cnt[(uint64_t)f * n_tiles + t] = mine[k];
+	}
+	if (lane == 0 && n_bad) atomicAdd(bad_cnt, n_bad);
+}
+
+// cuts[f] = the first output row of file f (first = the exclusive scan of cnt, n_files * n_tiles + 1 entries), cuts[n_files] = all rows
+__global__ void split_cuts_kernel(const uint64_t *__restrict__ first, uint64_t n_tiles, uint32_t n_files, uint64_t *__restrict__ cuts)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f <= n_files) cuts[f] = first[(uint64_t)f * n_tiles];
+}
+
+// the records to their rows; run only when the count pass found no refused record, so the rows are exactly [0, n)
+__global__ void __launch_bounds__(64) split_scatter_kernel(const OvlRec *__restrict__ recs, uint64_t n, const uint32_t *__restrict__ file_of,
+                                                            uint32_t n_ids, uint32_t n_files, uint64_t n_tiles, const uint64_t *__restrict__ first,
+                                                            OvlRec *__restrict__ out)
+{
+	const uint64_t t = blockIdx.x;
+	if (t >= n_tiles) return;
+	const int lane = threadIdx.x;
+	unsigned long long run[kSplitSlots];   // next row of the files this lane owns
+#pragma unroll
+	for (uint32_t k = 0; k < kSplitSlots; ++k) {
+		const uint32_t f = k * 64 + (uint32_t)lane;
+		run[k] = f < n_files ? first[(uint64_t)f * n_tiles + t] : 0ull;
+	}
+	for (uint32_t it = 0; it < kSplitIters; ++it) {
+		const uint64_t i = t * kSplitTile + it * 64 + (uint32_t)lane;
+		bool bad;
+		const uint32_t f = split_file(recs, i, n, file_of, n_ids, n_files, &bad);
+		const bool ok = i < n && !bad;
+		uint4 a = make_uint4(0, 0, 0, 0), b = a;
+		if (ok) {
+			const uint4 *src = reinterpret_cast<const uint4*>(recs + i);
+			a = src[0], b = src[1];
+		}
+		unsigned long long live = __ballot(ok);
+		while (live) {
+			const uint32_t fc = __shfl(f, __ffsll((long long)live) - 1, 64);
+			const unsigned long long m = __ballot(ok && f == fc);
+			const unsigned long long base = __shfl(split_slot(run, fc), (int)(fc & 63), 64);
+			if (ok && f == fc) {
+				const unsigned long long row = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1));
+				if (row < n) {   // (always, when the count pass refused nothing)
+					uint4 *dst = reinterpret_cast<uint4*>(out + row);
+					dst[0] = a, dst[1] = b;
+				}
+			}
+			if (lane == (int)(fc & 63)) {
+#pragma unroll
+				for (uint32_t k = 0; k < kSplitSlots; ++k) if (k == fc >> 6) run[k] += (unsigned long long)__popcll(m);
+			}
+			live &= ~m;
+		}
+	}
+}
+
+// file_of[i] = the file record i of the sort's input belongs to: the last f with fstart[f] <= i (fstart has n_files + 1 entries)
+__global__ void file_fill_kernel(const uint64_t *__restrict__ fstart, uint32_t n_files, uint64_t n, uint32_t *__restrict__ file_of)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) file_of[i] = file_of_record(fstart, n_files, i);
+}
+
+uint32_t split_tile_records() { return kSplitTile; }
+uint32_t split_max_files() { return kSplitMaxFiles; }
+void launch_split_count(const OvlRec *recs, uint64_t n, const uint32_t *file_of, uint32_t n_ids, uint32_t n_files, uint64_t n_tiles, uint32_t *cnt,
+                        uint32_t *bad_cnt, hipStream_t s)
+{
+	if (n_tiles) ND_LAUNCH(split_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, recs, n, file_of, n_ids, n_files, n_tiles, cnt, bad_cnt);
+}
+void launch_split_cuts(const uint64_t *first, uint64_t n_tiles, uint32_t n_files, uint64_t *cuts, hipStream_t s)
+{
+	ND_LAUNCH(split_cuts_kernel, GRID1(n_files + 1), 0, s, first, n_tiles, n_files, cuts);
+}
+void launch_split_scatter(const OvlRec *recs, uint64_t n, const uint32_t *file_of, uint32_t n_ids, uint32_t n_files, uint64_t n_tiles,
+                          const uint64_t *first, OvlRec *out, hipStream_t s)
+{
+	if (n_tiles) ND_LAUNCH(split_scatter_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, recs, n, file_of, n_ids, n_files, n_tiles, first, out);
+}
+void launch_file_fill(const uint64_t *fstart, uint32_t n_files, uint64_t n, uint32_t *file_of, hipStream_t s)
+{
+	if (n) ND_LAUNCH(file_fill_kernel, GRID1(n), 0, s, fstart, n_files, n, file_of);
+}
+
 } // namespace ndovl

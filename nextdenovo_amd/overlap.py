@@ -114,6 +114,31 @@ def _bind(lib):
     lib.ndgpu_s2_filter_encode.restype = C.c_int64
     lib.ndgpu_s2_bl.argtypes = [P, C.POINTER(P)]
     lib.ndgpu_s2_bl.restype = C.c_int64
+    # record sets (K18)
+    PP, u32 = C.POINTER(P), C.c_uint32
+    lib.ndgpu_ovl_map_dev.argtypes = lib.ndgpu_ovl_map.argtypes
+    lib.ndgpu_ovl_map_dev.restype = C.c_int64
+    lib.ndgpu_ovl_recset_size.argtypes = [P]
+    lib.ndgpu_ovl_recset_size.restype = C.c_int64
+    lib.ndgpu_ovl_recset_download.argtypes = [P, P, C.c_int64]
+    lib.ndgpu_ovl_recset_download.restype = C.c_int64
+    lib.ndgpu_ovl_recset_upload.argtypes = [P, C.c_int64]
+    lib.ndgpu_ovl_recset_upload.restype = P
+    lib.ndgpu_ovl_recset_concat.argtypes = [PP, C.c_int32]
+    lib.ndgpu_ovl_recset_concat.restype = P
+    lib.ndgpu_ovl_recset_split.argtypes = [P, P, u32, C.c_int32, PP]
+    lib.ndgpu_ovl_recset_split.restype = C.c_int64
+    lib.ndgpu_ovl_recset_free.argtypes = [P]
+    lib.ndgpu_ovl_recset_free.restype = None
+    lib.ndgpu_ovl_recset_stats.argtypes = [C.POINTER(RecsetCounters), C.c_int]
+    lib.ndgpu_ovl_recset_stats.restype = None
+    lib.ndgpu_ovl_sort_sets.argtypes = [PP, C.c_int32, P, u32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, PP, PP, PP, C.POINTER(C.c_int64),
+                                        C.POINTER(SortStats)]
+    lib.ndgpu_ovl_sort_sets.restype = C.c_int64
+    lib.ndgpu_ovl_sort_piles_sets.argtypes = [PP, C.c_int32, P, u32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u32, u32, u32, u32, C.c_int32, P,
+                                              C.c_int64, C.c_int32, PP, PP, C.POINTER(C.c_int64), PP, PP, PP, C.POINTER(C.c_int64), PP,
+                                              C.POINTER(C.c_int64), C.POINTER(SortStats), C.POINTER(AdmitStats)]
+    lib.ndgpu_ovl_sort_piles_sets.restype = C.c_int64
     return lib
 
 
@@ -235,6 +260,16 @@ class Index:
             raise _fail(self.lib, "ndgpu_ovl_map failed (%d)" % n)
         return _take(self.lib, recs, n, REC)
 
+    def map_dev(self, rs: ReadSet, mid_occ: int, opt: Opt | None = None) -> "RecordSet":
+        """map() with the records left on the device (ndgpu_ovl_map_dev): a RecordSet, for sort_overlaps / sort_piles / split_set."""
+        opt = opt or self.opt
+        h = C.c_void_p()
+        n = self.lib.ndgpu_ovl_map_dev(self.h, C.byref(opt), mid_occ, len(rs), _ptr(rs.words), rs.words.size, _ptr(rs.word_off),
+                                       _ptr(rs.lens), _ptr(rs.ids), C.byref(h))
+        if n < 0:
+            raise _fail(self.lib, "ndgpu_ovl_map_dev failed (%d)" % n)
+        return RecordSet(self.lib, h)
+
     def map2(self, rs: ReadSet, mid_occ: int, opt: Opt | None = None) -> np.ndarray:
         """--step 2 (--mode 0): the 10-field records that passed the mapper's own filters, in output order; the dovetail /
         contained filter and the encoder follow on the host (Step2Filter)."""
@@ -313,6 +348,177 @@ class Index:
 
     def reset_stats(self):
         self.lib.ndgpu_ovl_reset_stats(self.h)
+
+
+# ---- record sets: the step-1 records of a job, wherever they are (ndgpu_ovl_recset; K18 is their stable split) ----
+class RecsetCounters(C.Structure):
+    _fields_ = [("split_ms", C.c_double)] + [(n, C.c_uint64) for n in ("sets_made", "sets_live", "bytes_downloaded", "bytes_uploaded", "bytes_d2d",
+                                                                     "split_calls", "sets_downloaded")]
+
+
+_recset_local = {"live_bytes": 0, "budget_fallbacks": 0, "budget": None}
+_recset_lock = __import__("threading").Lock()
+
+
+class RecordSet:
+    """The records of one map call in device memory (read-only; any number of sorts may read it).  Live pool memory until close()."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.h = lib, handle.value if isinstance(handle, C.c_void_p) else int(handle)   # (the address: never 0)
+        self.size = int(lib.ndgpu_ovl_recset_size(self.h))
+        with _recset_lock:
+            _recset_local["live_bytes"] += self.size * REC.itemsize
+
+    @classmethod
+    def upload(cls, recs: np.ndarray) -> "RecordSet":
+        lib = load()
+        recs = np.ascontiguousarray(recs, dtype=REC)
+        h = lib.ndgpu_ovl_recset_upload(_ptr(recs), recs.size)
+        if not h:
+            raise _fail(lib, "ndgpu_ovl_recset_upload failed")
+        return cls(lib, C.c_void_p(h))
+
+    def _handle(self):
+        if self.h is None:
+            raise ValueError("the record set is closed")
+        return self.h
+
+    def __len__(self):
+        self._handle()
+        return self.size
+
+    def download(self) -> np.ndarray:
+        """The records as the structured array Index.map returns."""
+        out = np.zeros(self.size, dtype=REC)
+        n = self.lib.ndgpu_ovl_recset_download(self._handle(), _ptr(out), out.size)
+        if n != self.size:
+            raise _fail(self.lib, "ndgpu_ovl_recset_download failed (%d)" % n)
+        return out
+
+    def close(self):
+        if self.h is not None:
+            self.lib.ndgpu_ovl_recset_free(self.h)
+            self.h = None
+            with _recset_lock:
+                _recset_local["live_bytes"] -= self.size * REC.itemsize
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def concat_sets(sets) -> RecordSet:
+    """A new set: the inputs back to back (ndgpu_ovl_recset_concat); the inputs stay as they are."""
+    lib = load()
+    sets = list(sets)
+    ptrs = (C.c_void_p * max(1, len(sets)))(*[s._handle() for s in sets])
+    h = lib.ndgpu_ovl_recset_concat(ptrs, len(sets))
+    if not h:
+        raise _fail(lib, "ndgpu_ovl_recset_concat failed")
+    return RecordSet(lib, C.c_void_p(h))
+
+
+class TooManyFiles(ValueError):
+    """split_set: more files than the device split takes (ndgpu_ovl_recset_split returned -4): cut on the host."""
+
+
+def split_set(rs: RecordSet, ids_per_file, n_ids: int):
+    """K18 (ndgpu_ovl_recset_split): the records of `rs` cut into one set per file, file f = the records whose qname is in
+    ids_per_file[f], in their order in `rs` -- np.argsort(file_of[qname], kind="stable") and a cut at the file boundaries.
+    ValueError when a record's qname is in none of the files; TooManyFiles beyond 256 files."""
+    lib = load()
+    nf = len(ids_per_file)
+    file_of = np.full(int(n_ids), 0xffffffff, dtype=np.uint32)
+    for f, x in enumerate(ids_per_file):
+        file_of[np.asarray(x, dtype=np.int64)] = f
+    out = (C.c_void_p * max(1, nf))()
+    rc = int(lib.ndgpu_ovl_recset_split(rs._handle(), _ptr(file_of), file_of.size, nf, out))
+    if rc == -4:
+        raise TooManyFiles("ndgpu_ovl_recset_split takes 1 to 256 files, not %d" % nf)
+    if rc == -2:
+        lib.ndgpu_ovl_last_error.restype = C.c_int
+        err = int(lib.ndgpu_ovl_last_error())
+        if err == 0:
+            raise ValueError("ndgpu_ovl_recset_split: a record's query read is in none of the files")
+        raise MemoryError("ndgpu_ovl_recset_split: out of device memory") if err == 1 else RuntimeError("ndgpu_ovl_recset_split failed")
+    if rc < 0:
+        raise RuntimeError("ndgpu_ovl_recset_split failed (%d)" % rc)
+    return [RecordSet(lib, C.c_void_p(out[f])) for f in range(nf)]
+
+
+def recset_stats(reset: bool = False) -> dict:
+    """ndgpu_ovl_recset_stats, plus budget_fallbacks: jobs whose records went to the host because the live sets were past
+    NDGPU_RECS_DEVICE_BYTES (within_budget)."""
+    lib = load()
+    st = RecsetCounters()
+    lib.ndgpu_ovl_recset_stats(C.byref(st), 1 if reset else 0)
+    d = _stats_dict(st)
+    with _recset_lock:
+        d["budget_fallbacks"] = _recset_local["budget_fallbacks"]
+        if reset:
+            _recset_local["budget_fallbacks"] = 0
+    return d
+
+
+def recs_device() -> bool:
+    """NDGPU_RECS_DEVICE=1: the stage keeps the records of its map calls on the device, as RecordSets."""
+    return os.environ.get("NDGPU_RECS_DEVICE") == "1"
+
+
+def recs_device_budget() -> int:
+    """Bytes of records the stage may hold in live sets: NDGPU_RECS_DEVICE_BYTES, by default an eighth of the device's memory.  Read
+    once."""
+    with _recset_lock:
+        if _recset_local["budget"] is None:
+            e = os.environ.get("NDGPU_RECS_DEVICE_BYTES")
+            if e:
+                _recset_local["budget"] = int(e)
+            else:
+                try:
+                    import torch
+                    total = torch.cuda.mem_get_info()[1] if torch.cuda.is_available() else 288 << 30
+                except Exception:
+                    total = 288 << 30
+                _recset_local["budget"] = total // 8
+        return _recset_local["budget"]
+
+
+def within_budget(rs: RecordSet):
+    """`rs` itself while the live sets of the process stay inside the budget; past it the records as an array, the set freed."""
+    budget = recs_device_budget()
+    with _recset_lock:
+        inside = _recset_local["live_bytes"] <= budget
+    if inside:
+        return rs
+    recs = rs.download()
+    rs.close()
+    with _recset_lock:
+        _recset_local["budget_fallbacks"] += 1
+    return recs
+
+
+def _file_sets(files):
+    """A list of arrays and RecordSets as set handles: (pointer array, the temporary sets made for the arrays)."""
+    tmp, handles = [], []
+    try:
+        for f in files:
+            if not isinstance(f, RecordSet):
+                f = RecordSet.upload(f)
+                tmp.append(f)
+            handles.append(f._handle())
+    except BaseException:
+        for t in tmp:
+            t.close()
+        raise
+    return (C.c_void_p * max(1, len(handles)))(*handles), tmp
 
 
 def pool_bytes():
@@ -499,7 +705,8 @@ def from_decoded(a: np.ndarray) -> np.ndarray:
 
 def sort_overlaps(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int = 40, max_flank_len: int = 300, hq: bool = False):
     """The `ovl_sort` step on the device (ndgpu_ovl_sort).  files = list of record arrays (step-1 overlaps, one per
-    input file, fofn order).  Returns (sorted records, [(seed id, 'c'|'k'), ...], stats dict)."""
+    input file, fofn order) -- or of RecordSets, or of both: with a RecordSet among them the call is ndgpu_ovl_sort_sets and the
+    arrays are uploaded as sets of this call.  Returns (sorted records, [(seed id, 'c'|'k'), ...], stats dict)."""
     import time
     t_in = time.perf_counter()
     lib = load()
@@ -510,17 +717,28 @@ def sort_overlaps(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: i
                            C.POINTER(C.c_int64), C.POINTER(SortStats)]
             fn.restype = C.c_int64
         lib.ndgpu_ovl_sort._bound = True
-    files = [np.ascontiguousarray(f, dtype=REC) for f in files]
+    as_sets = any(isinstance(f, RecordSet) for f in files)
+    if not as_sets:
+        files = [np.ascontiguousarray(f, dtype=REC) for f in files]
     nf = len(files)
-    ptrs = (C.c_void_p * max(1, nf))(*[f.ctypes.data for f in files])
-    cnts = (C.c_int64 * max(1, nf))(*[f.size for f in files])
     seed_len = np.ascontiguousarray(seed_len, dtype=np.uint32)
     out, bid, bkind = C.c_void_p(), C.c_void_p(), C.c_void_p()
     nbl = C.c_int64(0)
     st = SortStats()
     t_call = time.perf_counter()
-    n = (lib.ndgpu_ovl_sort_hq if hq else lib.ndgpu_ovl_sort)(ptrs, cnts, nf, _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len),
-                           C.byref(out), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(st))
+    if as_sets:
+        ptrs, tmp = _file_sets(files)
+        try:
+            n = lib.ndgpu_ovl_sort_sets(ptrs, nf, _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len), int(bool(hq)),
+                                        C.byref(out), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(st))
+        finally:
+            for t in tmp:
+                t.close()
+    else:
+        ptrs = (C.c_void_p * max(1, nf))(*[f.ctypes.data for f in files])
+        cnts = (C.c_int64 * max(1, nf))(*[f.size for f in files])
+        n = (lib.ndgpu_ovl_sort_hq if hq else lib.ndgpu_ovl_sort)(ptrs, cnts, nf, _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len),
+                               C.byref(out), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(st))
     if n == -2:   # a device operation failed: MemoryError if it was memory (like every other entry point), RuntimeError otherwise
         raise _fail(lib, "ndgpu_ovl_sort failed (about 150 bytes of device memory per candidate overlap are needed; use more seed files: "
                          "seed_cutfiles)")
@@ -546,7 +764,8 @@ def sort_piles(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int 
                flags: int = 0, want_sorted: bool = False):
     """sort_overlaps followed by assemble_piles in one call (ndgpu_ovl_sort_piles): the sorted records are admitted on the device
     (K16) and only the piles come back.  The skip set is `skip` plus, with use_bl, the seeds of this sort's `.bl` verdicts; n_ids =
-    seed_len.size.  Returns (recs uint32[n,8], pile_off, seeds, bl list, sorted records or None, {"sort": ..., "admit": ...})."""
+    seed_len.size.  files: arrays, RecordSets or both, as for sort_overlaps (ndgpu_ovl_sort_piles_sets with a RecordSet among them).
+    Returns (recs uint32[n,8], pile_off, seeds, bl list, sorted records or None, {"sort": ..., "admit": ...})."""
     lib = load()
     if not hasattr(lib.ndgpu_ovl_sort_piles, "_bound"):
         P, PP, u32 = C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32
@@ -555,19 +774,30 @@ def sort_piles(files, seed_len: np.ndarray, min_seed_len: int, max_bin_cov: int 
                                              C.POINTER(C.c_int64), PP, C.POINTER(C.c_int64), C.POINTER(SortStats), C.POINTER(AdmitStats)]
         lib.ndgpu_ovl_sort_piles.restype = C.c_int64
         lib.ndgpu_ovl_sort_piles._bound = True
-    files = [np.ascontiguousarray(f, dtype=REC) for f in files]
+    as_sets = any(isinstance(f, RecordSet) for f in files)
+    if not as_sets:
+        files = [np.ascontiguousarray(f, dtype=REC) for f in files]
     nf = len(files)
-    ptrs = (C.c_void_p * max(1, nf))(*[f.ctypes.data for f in files])
-    cnts = (C.c_int64 * max(1, nf))(*[f.size for f in files])
     seed_len = np.ascontiguousarray(seed_len, dtype=np.uint32)
     sk = _skip_array(skip)
     bid, bkind, r8, off, seeds, srt = (C.c_void_p() for _ in range(6))
     nbl, npiles, nsrt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     st, ast = SortStats(), AdmitStats()
-    n = lib.ndgpu_ovl_sort_piles(ptrs, cnts, nf, _ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len), int(bool(hq)),
-                                 int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed), int(bool(use_bl)), _ptr(sk), sk.size,
-                                 int(flags), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(r8), C.byref(off), C.byref(seeds),
-                                 C.byref(npiles), C.byref(srt) if want_sorted else None, C.byref(nsrt), C.byref(st), C.byref(ast))
+    tail = (_ptr(seed_len), seed_len.size, int(min_seed_len), int(max_bin_cov), int(max_flank_len), int(bool(hq)),
+            int(min_len_seed), int(min_len_aln), int(max_cov_aln), int(min_cov_seed), int(bool(use_bl)), _ptr(sk), sk.size,
+            int(flags), C.byref(bid), C.byref(bkind), C.byref(nbl), C.byref(r8), C.byref(off), C.byref(seeds),
+            C.byref(npiles), C.byref(srt) if want_sorted else None, C.byref(nsrt), C.byref(st), C.byref(ast))
+    if as_sets:
+        ptrs, tmp = _file_sets(files)
+        try:
+            n = lib.ndgpu_ovl_sort_piles_sets(ptrs, nf, *tail)
+        finally:
+            for t in tmp:
+                t.close()
+    else:
+        ptrs = (C.c_void_p * max(1, nf))(*[f.ctypes.data for f in files])
+        cnts = (C.c_int64 * max(1, nf))(*[f.size for f in files])
+        n = lib.ndgpu_ovl_sort_piles(ptrs, cnts, nf, *tail)
     if n == -2:
         raise _fail(lib, "ndgpu_ovl_sort_piles failed (about 150 bytes of device memory per candidate overlap are needed; use more seed "
                          "files: seed_cutfiles)")

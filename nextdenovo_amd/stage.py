@@ -42,6 +42,8 @@ class DeviceBackend:
                 self.caches[key] = _IndexCache(self.opt, target)
             c = self.caches[key]
             self.calls += 1
+        if overlap.recs_device():   # NDGPU_RECS_DEVICE=1: a RecordSet -- or, past NDGPU_RECS_DEVICE_BYTES of live sets, its records
+            return overlap.within_budget(c.map(query, batch_size, dual, device=True))
         return c.map(query, batch_size, dual)
 
     def release(self, key, keep_stats=False):
@@ -62,6 +64,12 @@ class DeviceBackend:
                                                            min_len_aln=min_len_aln, max_cov_aln=max_cov_aln, min_cov_seed=min_cov_seed,
                                                            use_bl=use_bl)
         return sub, off, seeds, bl, st
+
+
+def _close_sets(files):
+    for f in files:
+        if isinstance(f, overlap.RecordSet):
+            f.close()
 
 
 def deal(lens: np.ndarray, read_cutoff: int, seed_cutoff: int, n_seed_files: int, block_size: int = 0):
@@ -378,6 +386,7 @@ class Shard:
         ex = self.exchange
         if ex is not None and not own_step:
             ex.begin_step()
+        got = {}   # job -> its records: an array, or with NDGPU_RECS_DEVICE=1 a RecordSet of the device backend
         try:
             jobs = self.jobs_of(i)
 
@@ -387,13 +396,12 @@ class Shard:
                 if tgt != i:  # that index is not needed again by this shard
                     be.release(tgt)
                 return r
-            got = {}
             # the jobs this rank owns first (the others wait for them), then what the others hand over
             own = [job for job in jobs if ex is None or job[2] == "part" or owner_of(job[1], job[3]) == i]
 
             def hand_over(k, tgt, kind, j):
                 if ex is not None and kind == "seed" and tgt != j:
-                    ex.put(k, got[k], i)
+                    ex.put(k, got[k].download() if isinstance(got[k], overlap.RecordSet) else got[k], i)
             if getattr(be, "concurrent", False) and len(own) > 2 and not os.environ.get("NDGPU_STAGE_SERIAL"):
                 self._overlaps_grouped(i, own, got, hand_over)
             else:
@@ -408,6 +416,9 @@ class Shard:
                         r = compute(k, tgt, kind, j, dual)
                     got[k] = r
             out = [got[k] for k, *_ in jobs]
+        except BaseException:
+            _close_sets(got.values())   # a failed attempt leaves no set behind (Shard.piles may run the stage once more)
+            raise
         finally:
             be.release(i, keep_stats=True)
             self.ovl_stats = getattr(be, "last_stats", None)
@@ -446,6 +457,16 @@ class Shard:
                         parts = [be.map(tgt, target, self._set(ids[0]), batch, dual)]
                     else:
                         recs = be.map(tgt, target, self._set(np.concatenate(ids)), batch, dual)
+                        parts = None
+                        if isinstance(recs, overlap.RecordSet):   # the same cut on the device (K18); beyond its 256 files, below
+                            whole = recs
+                            try:
+                                parts = overlap.split_set(whole, ids, int(self.lens.size))
+                            except overlap.TooManyFiles:
+                                recs = whole.download()
+                            finally:
+                                whole.close()
+                    if parts is None:   # a fused call's records in host memory: the cut with numpy
                         # a record's query is its qname (lib/ovl.h:20-25): which file of the call it came from
                         file_of = np.zeros(self.lens.size, dtype=np.int32)
                         for f, x in enumerate(ids):
@@ -462,6 +483,7 @@ class Shard:
                         parts = [recs[cut[f]:cut[f + 1]] for f in range(len(ids))]
                     for (k, _t, kind, j, _d), r in zip(members, parts):
                         got[k] = r
+                    for k, _t, kind, j, _d in members:
                         with hand_lock:
                             hand_over(k, tgt, kind, j)
                 if tgt != i:   # that index is not needed again by this shard
@@ -483,6 +505,7 @@ class Shard:
         step: the hand-over's number of this logical step (default: one more than this Shard's last) -- given by a caller that has the
         steps of one rank made by several Shards side by side."""
         import time
+        made = files is None   # the sets of a list made here are closed here; a caller's are the caller's
         if files is None:
             from . import api
             if getattr(self, "_release_first", False):
@@ -502,6 +525,15 @@ class Shard:
                     files = self.overlaps(i, own_step=True)
                 else:
                     raise
+        try:
+            return self._sort_and_admit(i, files)
+        finally:
+            if made:
+                _close_sets(files)
+
+    def _sort_and_admit(self, i, files):
+        """The sort and the pile admission of seed file i over its jobs' records (arrays, RecordSets or both)."""
+        import time
         t0 = time.perf_counter()
         seed_len = np.zeros(self.lens.size, dtype=np.uint32)
         sid = self.seed_ids[i]
