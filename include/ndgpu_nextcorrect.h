@@ -138,6 +138,16 @@ int ndgpu_correct_batch(int n_piles, char ***seqs, unsigned int **aln_start, uns
  * out[i]: malloc'd, NUL-terminated, what poa_to_consensus returns for job i's sequences.  Returns 0, < 0 on error. */
 typedef struct ndgpu_poa_job { const char *const *seqs; const uint16_t *len; int32_t seq_count; } ndgpu_poa_job;
 int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out);
+/* The same call with a choice of path; ndgpu_poa_batch is this call with flags 0.
+ *   bit 0: the host routine for every job, no device work (the cross-check leg);
+ *   bit 1: resident graphs -- a problem's graph lives on the device from its first sequence to its consensus string: graph growth,
+ *          topological order, the rows and the heaviest path run in kernels around the alignment, per round only 16 bytes a problem
+ *          go up and 8 come down.  A problem whose node bound sum(len + 1) exceeds 65,535, or that does not fit the memory plan, takes
+ *          the rounds of bit 2 inside the same call; one that reaches a capacity of its arena is computed by the host routine;
+ *   bit 2: the rounds of ndgpu_poa_batch's first description: alignments on the device, graphs on the host.
+ * Neither bit 1 nor bit 2: the environment variable NDGPU_POA_RESIDENT=1 (read once per process) selects bit 1's path, otherwise
+ * bit 2's.  The bytes returned are the same on every path.  Bits 1 and 2 together, or any other bit: -2, nothing written. */
+int ndgpu_poa_batch_flags(const ndgpu_poa_job *jobs, int n, int flags, char **out);
 
 /* The 8-mer ranking of a low-quality region's candidates (reference lib/nextcorrect.c:281-337, 405-440) for many candidate sets in
  * one call, one wavefront per set on the device.  A job is seq_count (1..40) sequences of len[k] bytes (0..9,999) in input order;
@@ -272,6 +282,12 @@ typedef struct {
     uint64_t aln_batch_launches; /* launches of the kernel that writes the runs (one per chunk of jobs that has a run) */
     uint64_t aln_batch_runs;     /* CIGAR runs written on the device */
     double aln_batch_ms;         /* HIP-event time of the run-length kernels (count + emit) */
+    uint64_t poa_resident_jobs;     /* POA problems that finished with their graph resident on the device */
+    uint64_t poa_resident_declined; /* offered to that path and not finished there (node bound, memory plan, a capacity reached) */
+    uint64_t poa_graph_launches;    /* launches of the four graph kernels */
+    double poa_graph_ms;            /* their HIP-event time */
+    uint64_t poa_h2d_bytes;         /* bytes the POA paths sent to the device */
+    uint64_t poa_d2h_bytes;         /* and brought back */
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);

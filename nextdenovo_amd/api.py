@@ -72,7 +72,9 @@ class Stats(C.Structure):
                 ("poa_cells", C.c_uint64), ("poa_ms", C.c_double),
                 ("rank_jobs", C.c_uint64), ("rank_tail", C.c_uint64), ("rank_launches", C.c_uint64), ("rank_ms", C.c_double),
                 ("aln_batch_jobs", C.c_uint64), ("aln_batch_launches", C.c_uint64), ("aln_batch_runs", C.c_uint64),
-                ("aln_batch_ms", C.c_double)]
+                ("aln_batch_ms", C.c_double),
+                ("poa_resident_jobs", C.c_uint64), ("poa_resident_declined", C.c_uint64), ("poa_graph_launches", C.c_uint64),
+                ("poa_graph_ms", C.c_double), ("poa_h2d_bytes", C.c_uint64), ("poa_d2h_bytes", C.c_uint64)]
 
 
 def lib_path() -> str:
@@ -118,6 +120,8 @@ def _bind(lib):
     lib.ndgpu_write_records.restype = C.c_int
     lib.ndgpu_poa_batch.argtypes = [C.POINTER(PoaJob), C.c_int, C.POINTER(C.c_void_p)]
     lib.ndgpu_poa_batch.restype = C.c_int
+    lib.ndgpu_poa_batch_flags.argtypes = [C.POINTER(PoaJob), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.ndgpu_poa_batch_flags.restype = C.c_int
     lib.ndgpu_lq_rank_batch.argtypes = [C.POINTER(RankJob), C.c_int, C.c_int, C.POINTER(RankResult)]
     lib.ndgpu_lq_rank_batch.restype = C.c_int
     lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
@@ -357,9 +361,11 @@ def ext_batch(jobs):
     return [(r.done, r.a, r.b, list(r.pos)) for r in res[:n]]
 
 
-def poa_batch(jobs):
-    """jobs: [[bytes, ...]] -> [bytes]: what poa_to_consensus returns for every job's sequences, through ndgpu_poa_batch (the
-    alignments of all jobs on the device in lockstep rounds; lib/dag.c:658-694)."""
+def poa_batch(jobs, resident=None, host=False):
+    """jobs: [[bytes, ...]] -> [bytes]: what poa_to_consensus returns for every job's sequences, through ndgpu_poa_batch_flags (the
+    alignments of all jobs on the device in lockstep rounds; lib/dag.c:658-694).  resident=True: the graphs live on the device from
+    the first sequence to the consensus string; False: they stay on the host between the rounds; None: NDGPU_POA_RESIDENT=1 selects
+    the former.  host=True: the host routine for every job.  The bytes are the same whichever way."""
     lib = load()
     n = len(jobs)
     arr = (PoaJob * max(1, n))()
@@ -372,9 +378,10 @@ def poa_batch(jobs):
         keep.append((cs, ln))
         arr[i] = PoaJob(C.cast(cs, C.POINTER(C.c_char_p)), C.cast(ln, C.POINTER(C.c_uint16)), k)
     out = (C.c_void_p * max(1, n))()
-    rc = lib.ndgpu_poa_batch(arr, n, out)
+    flags = (1 if host else 0) | (0 if resident is None else 2 if resident else 4)
+    rc = lib.ndgpu_poa_batch_flags(arr, n, flags, out)
     if rc != 0:
-        raise RuntimeError("ndgpu_poa_batch failed (%d)" % rc)
+        raise RuntimeError("ndgpu_poa_batch_flags failed (%d)" % rc)
     libc = C.CDLL(None)
     libc.free.argtypes = [C.c_void_p]
     res = []
@@ -455,11 +462,21 @@ def cigar_string(cigar) -> str:
     return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in cigar)
 
 
+_POA_RESIDENT_STATS = ("poa_resident_jobs", "poa_resident_declined", "poa_graph_launches", "poa_graph_ms", "poa_h2d_bytes", "poa_d2h_bytes")
+
+
 def stats() -> dict:
     lib = load()
     s = Stats()
     lib.ndgpu_get_stats(C.byref(s))
-    return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+    names = [f[0] for f in Stats._fields_]
+    # ndgpu_stats grows at its end (the C ABI); the dictionary lists the counters of the resident POA graphs with the other POA
+    # counters, behind poa_ms, so the keys that closed it before still close it
+    late = [n for n in names if n in _POA_RESIDENT_STATS]
+    names = [n for n in names if n not in _POA_RESIDENT_STATS]
+    at = names.index("poa_ms") + 1
+    names[at:at] = late
+    return {n: getattr(s, n) for n in names}
 
 
 def release_device_memory() -> int:

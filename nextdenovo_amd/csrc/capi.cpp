@@ -715,10 +715,16 @@ char *poa_to_consensus(const void *seqs, const int seq_count) {
 
 // poa_to_consensus for a batch of problems: the alignments on the device in lockstep rounds (DeviceAligner::run_poa); a problem
 // the device declines is computed by the host path here, in the same call
-int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) {
+int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) { return ndgpu_poa_batch_flags(jobs, n, 0, out); }
+
+// flags: bit 0 the host routine for every job; bit 1 resident graphs (K19), bit 2 K13's rounds, whatever NDGPU_POA_RESIDENT says
+int ndgpu_poa_batch_flags(const ndgpu_poa_job *jobs, int n, int flags, char **out) {
+    if ((flags & ~7) != 0 || (flags & 6) == 6) return -2;
     if (n <= 0) return 0;
+    const bool host_only = (flags & 1) != 0;
+    const int form = flags & 2 ? 1 : flags & 4 ? 2 : 0;
     int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+    if (!host_only && (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)) {
         fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_poa_batch runs its alignments on the device\n");
         return -1;
     }
@@ -733,12 +739,14 @@ int ndgpu_poa_batch(const ndgpu_poa_job *jobs, int n, char **out) {
     const int threads = effective_cpus();
     // (out of device memory: the range is halved until it fits; a single problem that does not fit goes the host way)
     std::vector<std::pair<size_t, size_t>> todo{{0, (size_t)n}};
+    if (host_only) todo.clear();
     while (!todo.empty()) {
         const auto [a, b] = todo.back();
         todo.pop_back();
         try {
             HipBackend be(0, threads);
-            (void)be.run_poa(ptr.data() + a, b - a);
+            if (form) be.run_poa_form(ptr.data() + a, b - a, form);
+            else (void)be.run_poa(ptr.data() + a, b - a);
         } catch (const DeviceOom &) {
             DeviceAligner::context(0).release_memory();
             DeviceAligner::forget_sizes();
@@ -998,6 +1006,9 @@ void ndgpu_get_stats(ndgpu_stats *o) {
     o->rank_jobs = s.rank_jobs, o->rank_tail = s.rank_tail, o->rank_launches = s.rank_launches, o->rank_ms = s.rank_ms;
     o->aln_batch_jobs = s.aln_batch_jobs, o->aln_batch_launches = s.aln_batch_launches, o->aln_batch_runs = s.aln_batch_runs;
     o->aln_batch_ms = s.aln_batch_ms;
+    o->poa_resident_jobs = s.poa_resident_jobs, o->poa_resident_declined = s.poa_resident_declined;
+    o->poa_graph_launches = s.poa_graph_launches, o->poa_graph_ms = s.poa_graph_ms;
+    o->poa_h2d_bytes = s.poa_h2d_bytes, o->poa_d2h_bytes = s.poa_d2h_bytes;
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }

@@ -287,6 +287,13 @@ enum class BufLevel { levelled, on_demand };
     X(int32_t, d_poa_s, device, levelled)                                                                                                 \
     X(uint16_t, d_poa_f, device, levelled)                                                                                                \
     X(uint32_t, d_poa_route, device, levelled)                                                                                            \
+    /* resident POA graphs (K19): problems, sequence table, the round's problems, X and error word per problem, strings; the arenas */     \
+    X(PoaGraphDev, d_poa_graphs, device, levelled)                                                                                        \
+    X(PoaSeqDev, d_poa_seqs, device, levelled)                                                                                            \
+    X(PoaRoundDev, d_poa_round, device, levelled)                                                                                         \
+    X(PoaXeDev, d_poa_xe, device, levelled)                                                                                               \
+    X(uint32_t, d_poa_out, device, levelled)                                                                                              \
+    X(uint64_t, d_poa_arena, device, on_demand) /* only under NDGPU_POA_RESIDENT=1 / the flags entry: never levelled */                   \
     /* forward / traceback (K7 / K8a) */                                                                                                  \
     X(uint32_t, d_pool, device, levelled)                                                                                                 \
     X(uint32_t, d_ops, device, levelled)                                                                                                  \
@@ -413,6 +420,21 @@ struct PoaBatch {  // run_poa: the problems, and the launch in progress -- its f
     uint64_t cells = 0, route_words = 0;
     explicit PoaBatch(size_t n) : probs(n) {}
 };
+struct PoaResident {  // run_poa's resident form: the problems whose graphs live on the device, index p = its place in every table
+    std::vector<size_t> req;            // p -> the request
+    std::vector<PoaGraphDev> graphs;
+    std::vector<PoaSeqDev> seqs;
+    std::vector<char> pool;             // every sequence, a NUL behind each
+    std::vector<PoaXeDev> xe;           // as the last round left them (X of a start chain = its length)
+    std::vector<uint8_t> live;          // still on the resident path
+    uint64_t arena_bytes = 0, out_bytes = 0;
+    size_t max_seqs = 0;
+    // the round in progress: its problems in launch order, the ids each launch's two forms take, the launches
+    std::vector<PoaRoundDev> round;
+    std::vector<uint32_t> ids;
+    struct Launch { size_t first, n_wave, n_group; uint64_t cells; };
+    std::vector<Launch> launches;
+};
 
 }  // namespace
 
@@ -488,6 +510,7 @@ struct DeviceAligner::State {
         kEvLinksBegin, kEvScoreBegin, kEvWalkBegin, kEvWalkEnd,  // count_and_score, score_pass: before K9 | K10 | the walk | behind it
         kEvLqMsaBegin, kEvLqMsaEnd,                              // launch_lq: around K12 (its K7 / K8a: lq_evs)
         kEvTailBegin, kEvTailEnd, kEvExtractRanked,  // K11, K13, K14, K15: around the launch in flight | behind K14 where it follows K11
+        kEvPoaRows, kEvPoaAlign, kEvPoaThread, kEvPoaEnd,  // a resident POA round: before K19's rows | K13's launches | K19's thread | behind it
         kEvCount
     };
     hipEvent_t evs[kEvCount] = {nullptr};
@@ -594,6 +617,12 @@ struct DeviceAligner::State {
     void stage_poa_slice(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r);
     void launch_poa_slice(PoaBatch &B, size_t r);
     void thread_routes(PoaBatch &B, PoaReq **reqs, const std::vector<size_t> &slice, size_t r);
+    void poa_rounds(PoaReq **reqs, size_t n);    // run_poa's two forms: K13's rounds with the graphs on the host | resident graphs (K19)
+    void poa_resident(PoaReq **reqs, size_t n);
+    void admit_poa_resident(PoaReq **reqs, size_t n, uint64_t budget, PoaResident &R, std::vector<PoaReq *> &rest);
+    void start_poa_graphs(PoaResident &R);
+    void poa_resident_round(PoaResident &R, PoaReq **reqs, size_t r, uint64_t budget);
+    void poa_resident_consensus(PoaResident &R, PoaReq **reqs);
     template <typename F>
     void poa_each(const std::vector<size_t> &ids, F f) {  // f(problem) over the context's host threads
         host_each(ids.size(), ids.size() < 8 || host_threads <= 1, host_threads, ids.size() / 4, true, [&](size_t k) { f(ids[k]); });
@@ -710,6 +739,9 @@ RuntimeStats DeviceAligner::total_stats() {
         t.tb_tasks += s.tb_tasks; t.tb_walkers += s.tb_walkers; t.tb_fallbacks += s.tb_fallbacks;
         t.poa_jobs += s.poa_jobs; t.poa_declined += s.poa_declined; t.poa_rounds += s.poa_rounds; t.poa_launches += s.poa_launches;
         t.poa_cells += s.poa_cells; t.poa_ms += s.poa_ms;
+        t.poa_resident_jobs += s.poa_resident_jobs; t.poa_resident_declined += s.poa_resident_declined;
+        t.poa_graph_launches += s.poa_graph_launches; t.poa_graph_ms += s.poa_graph_ms;
+        t.poa_h2d_bytes += s.poa_h2d_bytes; t.poa_d2h_bytes += s.poa_d2h_bytes;
         t.rank_jobs += s.rank_jobs; t.rank_tail += s.rank_tail; t.rank_launches += s.rank_launches; t.rank_ms += s.rank_ms;
         t.aln_batch_jobs += s.aln_batch_jobs; t.aln_batch_launches += s.aln_batch_launches; t.aln_batch_runs += s.aln_batch_runs;
         t.aln_batch_ms += s.aln_batch_ms;
@@ -927,6 +959,7 @@ struct PoaHooks {
     uint64_t budget = env_u64("NDGPU_POA_BUDGET", 0);         // of the trace budget's bytes (0: every problem is declined)
     int form = env_is("NDGPU_POA_FORM", "wave") ? 1 : env_is("NDGPU_POA_FORM", "group") ? 2 : 0;  // the kernel form every job takes
     uint32_t group_min = (uint32_t)env_u64("NDGPU_POA_GROUP_MIN", kPoaGroupMinLen);  // the query length the workgroup form takes over from
+    bool resident = env_is("NDGPU_POA_RESIDENT", "1");  // the graphs live on the device (K19); unset: K13's rounds with the graphs on the host
 };
 struct ExtractHooks {
     // NDGPU_EXTRACT_POOL=bytes: the first guess of K11's string pool (extract_into_pool) -- a small one makes the first call of a
@@ -2024,8 +2057,9 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
 // context's host threads thread the routes through the graphs and sort them (poa.cpp).  The workspace -- 6 bytes per cell of
 // (X + 1)(Y + 1) -- is charged to the trace budget of the memory plan.  A problem outside the device's limits (a sequence of 0 or
 // more than 9,999 bases) or whose round alone exceeds the budget is declined: req.done stays false and the caller takes the host path.
-// run_poa (below) is: admit (admit_poa) -> per round: export_rows -> per slice: the budget cut (next_poa_slice of nd_lqplan.h) ->
-// stage_poa_slice -> launch_poa_slice -> thread_routes -> the consensus of the problems still live.
+// poa_rounds (below; run_poa's form unless NDGPU_POA_RESIDENT=1 or the caller selects the resident one, K19, further down) is: admit
+// (admit_poa) -> per round: export_rows -> per slice: the budget cut (next_poa_slice of nd_lqplan.h) -> stage_poa_slice ->
+// launch_poa_slice -> thread_routes -> the consensus of the problems still live.
 
 // Which problems take the device path (PoaProb::live), each with its first sequence as a chain; returns the most sequences of one.
 size_t DeviceAligner::State::admit_poa(PoaReq **reqs, size_t n, uint64_t budget, PoaBatch &B) {
@@ -2104,6 +2138,9 @@ void DeviceAligner::State::launch_poa_slice(PoaBatch &B, size_t r) {
     h2d(d_poa_q.p, B.qpool.data(), B.qpool.size(), st);
     h2d(d_poa_rows.p, B.rows.data(), B.rows.size() * sizeof(PoaRowDev), st);
     h2d(d_poa_preds.p, B.preds.data(), B.preds.size() * sizeof(uint16_t), st);
+    stats.poa_h2d_bytes += B.jobs.size() * sizeof(PoaJobDev) + B.ids.size() * sizeof(uint32_t) + B.qpool.size() +
+                           B.rows.size() * sizeof(PoaRowDev) + B.preds.size() * sizeof(uint16_t);
+    stats.poa_d2h_bytes += B.jobs.size() * sizeof(PoaJobDev) + B.route_words * sizeof(uint32_t);
     mark(kEvTailBegin, st);
     NDGPU_DBG(st, "poa: round %zu, %zu + %zu jobs, %llu cells", r, B.n_wave, n_group, (unsigned long long)B.cells);
     launch_poa_align(d_poa_jobs.p, d_poa_ids.p, (int)B.n_wave, d_poa_ids.p + B.n_wave, (int)n_group, d_poa_q.p, d_poa_rows.p, d_poa_preds.p,
@@ -2134,10 +2171,16 @@ void DeviceAligner::State::thread_routes(PoaBatch &B, PoaReq **reqs, const std::
     });
 }
 
-void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
+void DeviceAligner::run_poa(PoaReq **reqs, size_t n, int form) {
     if (n == 0) return;
     State &S = *s_;
     const State::Phase phase(S);
+    if (form == 1 || (form == 0 && hooks_of<PoaHooks>().resident)) S.poa_resident(reqs, n);
+    else S.poa_rounds(reqs, n);
+}
+
+void DeviceAligner::State::poa_rounds(PoaReq **reqs, size_t n) {
+    State &S = *this;
     const PoaHooks &hk = hooks_of<PoaHooks>();
     const uint64_t budget = hk.budget_set ? hk.budget : (uint64_t)(S.trace_budget_bytes / 6);
     PoaBatch B(n);
@@ -2170,6 +2213,209 @@ void DeviceAligner::run_poa(PoaReq **reqs, size_t n) {
     });
     for (size_t i = 0; i < n; i++)
         if (!reqs[i]->done && !reqs[i]->failed) S.stats.poa_declined++;
+}
+
+// ---- POA problems with resident graphs (K19): a problem's graph lives in its arena on the device from its first sequence to its
+// consensus string; K13 runs unchanged on the tables K19's rows kernel makes there.  poa_resident (below) is: admit
+// (admit_poa_resident: the arenas from the bounds, the rest to poa_rounds) -> start_poa_graphs (every sequence up once, the first ones
+// as chains) -> per round poa_resident_round (the budget cut from the X of the round before -> the round's problems up, 16 bytes each
+// -> rows kernel -> K13 per launch of the cut -> thread kernel -> 8 bytes a problem down) -> poa_resident_consensus (the strings and
+// their lengths down in one copy).  Per round no table goes up and no route comes down.
+// The arenas are charged to the budget of the cells: they may take up to half of it (a problem behind that goes to poa_rounds), and
+// a round's launches share what the arenas leave.  A problem whose arena plus the cells of its largest round -- at least
+// (len_0 + 1)(len_r + 1), since a graph only grows -- exceed the budget does not start here either.
+
+void DeviceAligner::State::admit_poa_resident(PoaReq **reqs, size_t n, uint64_t budget, PoaResident &R, std::vector<PoaReq *> &rest) {
+    const uint64_t budget_bytes = budget > UINT64_MAX / 6 ? UINT64_MAX : budget * 6;
+    for (size_t i = 0; i < n; i++) {
+        PoaReq &rq = *reqs[i];
+        rq.done = false, rq.failed = false;
+        if (rq.seqs.size() > (size_t)kPoaMaxSeqs) {
+            stats.poa_jobs++;   // (poa_rounds counts the ones it is given)
+            rq.failed = true;
+            continue;
+        }
+        bool ok = !rq.seqs.empty();
+        uint64_t bound = 0, max_len = 0;
+        for (const std::string &q : rq.seqs) {
+            ok = ok && !q.empty() && q.size() <= (size_t)kPoaMaxSeqLen;
+            bound += q.size() + 1;
+            if (&q != &rq.seqs[0]) max_len = std::max<uint64_t>(max_len, q.size());
+        }
+        PoaArena A;
+        ok = ok && poa_arena_layout(bound, A);
+        if (ok) {
+            const uint64_t cells = rq.seqs.size() > 1 ? (uint64_t)(rq.seqs[0].size() + 1) * (max_len + 1) : 0;
+            ok = A.bytes + 6 * cells <= budget_bytes && R.arena_bytes + A.bytes <= budget_bytes / 2;
+        }
+        if (!ok) {
+            stats.poa_resident_declined++;
+            rest.push_back(&rq);
+            continue;
+        }
+        stats.poa_jobs++;
+        PoaGraphDev G;
+        memset(&G, 0, sizeof(G));
+        G.arena_off = R.arena_bytes, G.out_off = R.out_bytes;
+        G.seq_first = (uint32_t)R.seqs.size(), G.n_seq = (uint32_t)rq.seqs.size(), G.bound = (uint32_t)bound;
+        R.arena_bytes += A.bytes, R.out_bytes += (bound + 7) & ~(uint64_t)7;
+        for (const std::string &q : rq.seqs) {
+            R.seqs.push_back(PoaSeqDev{(uint64_t)R.pool.size(), (uint32_t)q.size(), 0});
+            R.pool.insert(R.pool.end(), q.begin(), q.end());
+            R.pool.push_back('\0');
+        }
+        R.req.push_back(i), R.graphs.push_back(G), R.live.push_back(1);
+        R.xe.push_back(PoaXeDev{(uint32_t)rq.seqs[0].size(), 0});
+        R.max_seqs = std::max(R.max_seqs, rq.seqs.size());
+    }
+}
+
+// Every buffer of the call but the cells, three uploads (problems, sequence table, sequences), the start kernel.
+void DeviceAligner::State::start_poa_graphs(PoaResident &R) {
+    hipStream_t st = stream;
+    const size_t np = R.req.size();
+    d_poa_graphs.reserve(np), d_poa_seqs.reserve(R.seqs.size()), d_poa_q.reserve(R.pool.size()), d_poa_jobs.reserve(np);
+    d_poa_round.reserve(np), d_poa_ids.reserve(np), d_poa_xe.reserve(np);
+    d_poa_out.reserve(((np + 1) & ~(size_t)1) + R.out_bytes / 4), d_poa_arena.reserve(R.arena_bytes / 8);
+    h2d(d_poa_graphs.p, R.graphs.data(), np * sizeof(PoaGraphDev), st);
+    h2d(d_poa_seqs.p, R.seqs.data(), R.seqs.size() * sizeof(PoaSeqDev), st);
+    h2d(d_poa_q.p, R.pool.data(), R.pool.size(), st);
+    stats.poa_h2d_bytes += np * sizeof(PoaGraphDev) + R.seqs.size() * sizeof(PoaSeqDev) + R.pool.size();
+    mark(kEvPoaRows, st);
+    NDGPU_DBG(st, "poa resident: start, %zu problems, %llu arena bytes", np, (unsigned long long)R.arena_bytes);
+    launch_poa_graph_start(d_poa_graphs.p, d_poa_xe.p, (unsigned char *)d_poa_arena.p, d_poa_q.p, d_poa_seqs.p, (int)np, st);
+    HIP_CHECK(hipGetLastError());
+    mark(kEvPoaAlign, st);
+    sync_drain(st);
+    stats.poa_graph_ms += ms(kEvPoaRows, kEvPoaAlign);
+    stats.poa_graph_launches++;
+}
+
+// Round r: sequence r of every live problem that has one.
+void DeviceAligner::State::poa_resident_round(PoaResident &R, PoaReq **reqs, size_t r, uint64_t budget) {
+    const PoaHooks &hk = hooks_of<PoaHooks>();
+    hipStream_t st = stream;
+    std::vector<size_t> round_ids, slice, dropped;
+    std::vector<PoaLoad> load;
+    for (size_t p = 0; p < R.req.size(); p++)
+        if (R.live[p] && reqs[R.req[p]]->seqs.size() > r) {
+            round_ids.push_back(p);
+            const uint64_t X = R.xe[p].X;
+            load.push_back(PoaLoad{(X + 1) * (uint64_t)(reqs[R.req[p]]->seqs[r].size() + 1), X});
+        }
+    if (round_ids.empty()) return;
+    stats.poa_rounds++;
+    // the budget cut, every launch of the round at once (it goes by the loads alone)
+    R.round.clear(), R.ids.clear(), R.launches.clear();
+    uint64_t max_cells = 0;
+    std::vector<uint32_t> ids_group;
+    for (size_t a = 0; a < round_ids.size();) {
+        a = next_poa_slice(load, a, budget, slice, dropped);
+        for (size_t k : dropped) R.live[round_ids[k]] = 0;  // (over what the arenas leave of the budget on its own: it leaves the device path)
+        if (slice.empty()) continue;
+        PoaResident::Launch L{R.ids.size(), 0, 0, 0};
+        ids_group.clear();
+        for (size_t k : slice) {
+            const size_t p = round_ids[k];
+            R.round.push_back(PoaRoundDev{(uint32_t)p, 0, L.cells});
+            L.cells += load[k].cells;
+            const uint32_t Y = (uint32_t)reqs[R.req[p]]->seqs[r].size();
+            const bool group = hk.form ? hk.form == 2 : Y >= hk.group_min;
+            (group ? ids_group : R.ids).push_back((uint32_t)p);
+        }
+        L.n_wave = R.ids.size() - L.first, L.n_group = ids_group.size();
+        R.ids.insert(R.ids.end(), ids_group.begin(), ids_group.end());
+        R.launches.push_back(L);
+        max_cells = std::max(max_cells, L.cells);
+    }
+    if (R.round.empty()) return;
+    d_poa_s.reserve(max_cells), d_poa_f.reserve(max_cells);
+    h2d(d_poa_round.p, R.round.data(), R.round.size() * sizeof(PoaRoundDev), st);
+    h2d(d_poa_ids.p, R.ids.data(), R.ids.size() * sizeof(uint32_t), st);
+    stats.poa_h2d_bytes += R.round.size() * sizeof(PoaRoundDev) + R.ids.size() * sizeof(uint32_t);
+    unsigned char *arena = (unsigned char *)d_poa_arena.p;
+    mark(kEvPoaRows, st);
+    NDGPU_DBG(st, "poa resident: round %zu, rows of %zu problems", r, R.round.size());
+    launch_poa_graph_rows(d_poa_graphs.p, d_poa_round.p, (int)R.round.size(), (uint32_t)r, arena, d_poa_seqs.p, d_poa_jobs.p, st);
+    mark(kEvPoaAlign, st);
+    uint64_t cells = 0;
+    for (const PoaResident::Launch &L : R.launches) {  // (one after the other on the stream: they share the cells)
+        NDGPU_DBG(st, "poa resident: round %zu, %zu + %zu jobs, %llu cells", r, L.n_wave, L.n_group, (unsigned long long)L.cells);
+        launch_poa_align(d_poa_jobs.p, d_poa_ids.p + L.first, (int)L.n_wave, d_poa_ids.p + L.first + L.n_wave, (int)L.n_group, d_poa_q.p,
+                         (const PoaRowDev *)arena, (const uint16_t *)arena, d_poa_s.p, d_poa_f.p, (uint32_t *)arena, st);
+        stats.poa_launches += (L.n_wave ? 1 : 0) + (L.n_group ? 1 : 0);
+        cells += L.cells;
+    }
+    mark(kEvPoaThread, st);
+    NDGPU_DBG(st, "poa resident: round %zu, thread", r);
+    launch_poa_graph_thread(d_poa_graphs.p, d_poa_xe.p, d_poa_round.p, (int)R.round.size(), (uint32_t)r, arena, d_poa_q.p, d_poa_seqs.p,
+                            d_poa_jobs.p, st);
+    HIP_CHECK(hipGetLastError());
+    mark(kEvPoaEnd, st);
+    d2h(R.xe.data(), d_poa_xe.p, R.xe.size() * sizeof(PoaXeDev), st);
+    sync_drain(st);
+    stats.poa_d2h_bytes += R.xe.size() * sizeof(PoaXeDev);
+    stats.poa_cells += cells;
+    stats.poa_graph_launches += 2;
+    const double g_ms = ms(kEvPoaRows, kEvPoaAlign) + ms(kEvPoaThread, kEvPoaEnd), a_ms = ms(kEvPoaAlign, kEvPoaThread);
+    stats.poa_graph_ms += g_ms, stats.poa_ms += a_ms;
+    size_t gone = 0;
+    for (const PoaRoundDev &d : R.round)
+        if (R.xe[d.prob].err) R.live[d.prob] = 0, gone++;   // a capacity or a trip bound reached: the host path computes it
+    if (trace_on())
+        fprintf(stderr, "[ndgpu trace] poa resident round %zu: %zu problems in %zu launches, %llu cells, graph %.3f ms, align %.3f ms, %zu left the path\n",
+                r, R.round.size(), R.launches.size(), (unsigned long long)cells, g_ms, a_ms, gone);
+}
+
+// The heaviest paths of the problems still live; strings and lengths down in one copy.
+void DeviceAligner::State::poa_resident_consensus(PoaResident &R, PoaReq **reqs) {
+    hipStream_t st = stream;
+    const size_t np = R.req.size();
+    R.ids.clear();
+    for (size_t p = 0; p < np; p++)
+        if (R.live[p]) R.ids.push_back((uint32_t)p);
+    if (R.ids.empty()) return;
+    const size_t len_words = (np + 1) & ~(size_t)1;   // the lengths, then the strings from a multiple of 8 bytes on
+    h2d(d_poa_ids.p, R.ids.data(), R.ids.size() * sizeof(uint32_t), st);
+    stats.poa_h2d_bytes += R.ids.size() * sizeof(uint32_t);
+    mark(kEvPoaRows, st);
+    NDGPU_DBG(st, "poa resident: consensus of %zu problems", R.ids.size());
+    launch_poa_graph_consensus(d_poa_graphs.p, d_poa_ids.p, (int)R.ids.size(), (unsigned char *)d_poa_arena.p, (char *)(d_poa_out.p + len_words),
+                               d_poa_out.p, st);
+    HIP_CHECK(hipGetLastError());
+    mark(kEvPoaAlign, st);
+    std::vector<uint32_t> out(len_words + R.out_bytes / 4);
+    d2h(out.data(), d_poa_out.p, out.size() * sizeof(uint32_t), st);
+    sync_drain(st);
+    stats.poa_d2h_bytes += out.size() * sizeof(uint32_t);
+    stats.poa_graph_ms += ms(kEvPoaRows, kEvPoaAlign);
+    stats.poa_graph_launches++;
+    const char *str = (const char *)(out.data() + len_words);
+    for (uint32_t p : R.ids) {
+        const uint32_t len = out[p];
+        if (len > R.graphs[p].bound) continue;   // (0xffffffff: the kernel gave the problem up)
+        PoaReq &rq = *reqs[R.req[p]];
+        rq.out.assign(str + R.graphs[p].out_off, len);
+        rq.done = true;
+        stats.poa_resident_jobs++;
+    }
+}
+
+void DeviceAligner::State::poa_resident(PoaReq **reqs, size_t n) {
+    const PoaHooks &hk = hooks_of<PoaHooks>();
+    const uint64_t budget = hk.budget_set ? hk.budget : (uint64_t)(trace_budget_bytes / 6);
+    PoaResident R;
+    std::vector<PoaReq *> rest;
+    admit_poa_resident(reqs, n, budget, R, rest);
+    if (!R.req.empty()) {
+        start_poa_graphs(R);
+        const uint64_t left = budget - (R.arena_bytes + 5) / 6;   // (the arenas took at most half)
+        for (size_t r = 1; r < R.max_seqs; r++) poa_resident_round(R, reqs, r, left);
+        poa_resident_consensus(R, reqs);
+        for (size_t p = 0; p < R.req.size(); p++)
+            if (!reqs[R.req[p]]->done) stats.poa_resident_declined++, stats.poa_declined++;
+    }
+    if (!rest.empty()) poa_rounds(rest.data(), rest.size());
 }
 
 // The ranking K14 left in a region's record (ranked != 0), for whoever asked: run_rank's problems, run_extract's regions.

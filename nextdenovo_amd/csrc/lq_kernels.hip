@@ -29,12 +29,15 @@
 //
 // K13 poa_align  the pseudo-seeds themselves: one sequence of a region's POA against its graph, a batch of regions per launch (at the
 //             end of this file; DeviceAligner::run_poa drives it in lockstep rounds).
-// K14 lq_rank    the 8-mer ranking of a region's candidates, one wavefront per region, behind K11 (after K13 in this file).
+// K14 lq_rank    the 8-mer ranking of a region's candidates, one wavefront per region, behind K11 (after K19 in this file).
+// K19 poa_graph_* the POA graph itself, resident from a problem's first sequence to its consensus string: four kernels around K13
+//             (behind K13 in this file; DeviceAligner::run_poa's resident form drives them).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "nd_device.h"
+#include "nd_lqplan.h"
 
 namespace ndgpu {
 
@@ -1026,6 +1029,439 @@ __global__ __launch_bounds__(NW * 64) void poa_align_kernel(PoaJobDev *__restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// K19: the POA graph itself (poa.cpp: Graph; lib/dag.c:223-250, 345-508, 555-595), resident in one arena per problem from its first
+// sequence to its consensus string (DESIGN.md section 0a''''''''; the arena: poa_arena_layout of nd_lqplan.h).  One wavefront per
+// problem, four kernels around K13, which runs unchanged on the tables poa_graph_rows makes:
+//   poa_graph_start      the first sequence as a chain, the identity order
+//   poa_graph_rows       rank, rows, predecessor rows in in-edge insertion order, sink flags, the PoaJobDev
+//   poa_graph_thread     the route K13 left threaded through the graph (set_route + thread_route), then the new order (toposort)
+//   poa_graph_consensus  the heaviest path and the string, cut at the first NUL
+// The graph: a node's in-edges and out-edges are singly linked lists in insertion order (head and tail per node, next per edge).
+// The nodes sharing a column are one list in creation order: al_head = the column's oldest node, al_next = the next younger one.
+// poa.cpp keeps per node a vector of the column's OTHER nodes; what its code does with those vectors depends on their order in two
+// places only -- the emission and the pushes of toposort, both through the vector of the group's head, the lowest id of the group
+// = the oldest node, whose vector is the younger nodes in creation order = this list behind its head -- and otherwise on the set
+// (thread_route looks for a byte, and a column never holds a byte twice: a node is created only when no node of the column has it).
+// The steps whose ORDER is the contract -- the threading walk, the DFS, the heaviest path -- run on lane 0; what is a map over nodes
+// runs on all lanes.  Every data-dependent loop has a trip bound from the arena's capacities and sets the problem's error word when
+// it reaches it; a problem with an error word is left alone by every later kernel (K13 gets a job of no rows) and the host path
+// computes it.  Hand-overs between lanes inside a kernel are marked "hand-over"; everything else crosses a kernel boundary.
+constexpr uint32_t kPoaNil = 0xffffu;
+
+struct PoaG {   // a problem's arena as typed pointers
+    uint64_t *labels;
+    double *sc;
+    PoaRowDev *rows;
+    uint32_t *route;
+    uint16_t *n_in, *in_head, *in_tail, *out_head, *out_tail, *al_head, *al_next, *al_tail, *e_from, *e_to, *e_next_in, *e_next_out;
+    uint16_t *order, *rank, *grp_of, *grp_head, *prev, *preds, *stack;
+    uint8_t *base, *done, *started;
+    uint64_t rows_off, preds_off, route_off;   // bytes from the batch's arena base
+};
+__device__ __forceinline__ PoaG poa_g(unsigned char *arena, uint64_t arena_off, uint32_t bound) {
+    PoaArena A;
+    (void)poa_arena_layout(bound, A);   // (the host admitted the bound)
+    unsigned char *p = arena + arena_off;
+    PoaG g;
+    g.labels = (uint64_t *)(p + A.off[kPaLabels]), g.sc = (double *)(p + A.off[kPaScore]), g.rows = (PoaRowDev *)(p + A.off[kPaRows]);
+    g.route = (uint32_t *)(p + A.off[kPaRoute]);
+    g.n_in = (uint16_t *)(p + A.off[kPaNIn]), g.in_head = (uint16_t *)(p + A.off[kPaInHead]), g.in_tail = (uint16_t *)(p + A.off[kPaInTail]);
+    g.out_head = (uint16_t *)(p + A.off[kPaOutHead]), g.out_tail = (uint16_t *)(p + A.off[kPaOutTail]);
+    g.al_head = (uint16_t *)(p + A.off[kPaAlHead]), g.al_next = (uint16_t *)(p + A.off[kPaAlNext]), g.al_tail = (uint16_t *)(p + A.off[kPaAlTail]);
+    g.e_from = (uint16_t *)(p + A.off[kPaEFrom]), g.e_to = (uint16_t *)(p + A.off[kPaETo]);
+    g.e_next_in = (uint16_t *)(p + A.off[kPaENextIn]), g.e_next_out = (uint16_t *)(p + A.off[kPaENextOut]);
+    g.order = (uint16_t *)(p + A.off[kPaOrder]), g.rank = (uint16_t *)(p + A.off[kPaRank]), g.grp_of = (uint16_t *)(p + A.off[kPaGrpOf]);
+    g.grp_head = (uint16_t *)(p + A.off[kPaGrpHead]), g.prev = (uint16_t *)(p + A.off[kPaPrev]);
+    g.preds = (uint16_t *)(p + A.off[kPaPreds]), g.stack = (uint16_t *)(p + A.off[kPaStack]);
+    g.base = p + A.off[kPaBase], g.done = p + A.off[kPaDone], g.started = p + A.off[kPaStarted];
+    g.rows_off = arena_off + A.off[kPaRows], g.preds_off = arena_off + A.off[kPaPreds], g.route_off = arena_off + A.off[kPaRoute];
+    return g;
+}
+
+// inclusive prefix sum over the 64 lanes (the moves of poa_prefix_max)
+__device__ __forceinline__ uint32_t poa_prefix_sum(uint32_t u) {
+    int v = (int)u;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+    return (uint32_t)v;
+}
+__device__ __forceinline__ uint32_t poa_or_lanes(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m);
+    return v;
+}
+
+// PoaGraph::start: node i = byte i of the first sequence, edge i = i -> i + 1 with label bit 0, order = identity; every node alone in
+// its column.  A lane writes the records of its own nodes and edges and reads none: the hand-over is the kernel boundary.
+__global__ __launch_bounds__(64) void poa_graph_start(PoaGraphDev *graphs, PoaXeDev *xe, unsigned char *arena, const char *seqs,
+                                                       const PoaSeqDev *__restrict__ seq_tab) {
+    PoaGraphDev &GD = graphs[blockIdx.x];
+    const uint32_t lane = threadIdx.x, bound = GD.bound;
+    const PoaG G = poa_g(arena, GD.arena_off, bound);
+    const PoaSeqDev s0 = seq_tab[GD.seq_first];
+    const unsigned char *s = (const unsigned char *)seqs + s0.off;
+    const uint32_t err = s0.len > bound ? kPoaErrNodes : 0u;   // (the bound counts len + 1 per sequence: cannot happen)
+    const uint32_t n = err ? 0u : s0.len;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const bool first = i == 0, last = i + 1 == n;
+        G.base[i] = s[i];
+        G.n_in[i] = first ? 0 : 1;
+        G.in_head[i] = G.in_tail[i] = (uint16_t)(first ? kPoaNil : i - 1);
+        G.out_head[i] = G.out_tail[i] = (uint16_t)(last ? kPoaNil : i);
+        G.al_head[i] = G.al_tail[i] = (uint16_t)i, G.al_next[i] = (uint16_t)kPoaNil;
+        G.order[i] = (uint16_t)i;
+        if (!last) {
+            G.e_from[i] = (uint16_t)i, G.e_to[i] = (uint16_t)(i + 1);
+            G.e_next_in[i] = G.e_next_out[i] = (uint16_t)kPoaNil;
+            G.labels[i] = 1ull;
+        }
+    }
+    if (lane == 0) {
+        GD.n_nodes = n, GD.n_edges = n ? n - 1 : 0u, GD.err = err;
+        xe[blockIdx.x] = PoaXeDev{n, err};
+    }
+}
+
+// Graph::build_rows + export_rows for sequence r of the round's problems: row i + 1 = node order[i].  pred_off is the exclusive prefix
+// sum of max(in-degree, 1) over the order (wavefront scan, chunk by chunk); a lane walks its node's in-edge list in insertion order
+// (at most in-degree steps) and writes rank[from] + 1 per edge, or row 0 alone.
+__global__ __launch_bounds__(64) void poa_graph_rows(PoaGraphDev *graphs, const PoaRoundDev *__restrict__ round, uint32_t r,
+                                                      unsigned char *arena, const PoaSeqDev *__restrict__ seq_tab, PoaJobDev *jobs) {
+    const PoaRoundDev rd = round[blockIdx.x];
+    PoaGraphDev &GD = graphs[rd.prob];
+    const uint32_t lane = threadIdx.x, bound = GD.bound;
+    const PoaG G = poa_g(arena, GD.arena_off, bound);
+    const PoaSeqDev sq = seq_tab[GD.seq_first + r];
+    const uint32_t X = GD.err ? 0u : GD.n_nodes;
+    uint32_t err = 0;
+    for (uint32_t i = lane; i < X; i += 64) G.rank[G.order[i]] = (uint16_t)i;
+    // hand-over: the walks below read rank entries that other lanes wrote -- fence + wavefront barrier
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    uint32_t carry = 0;
+    for (uint32_t c = 0; c < X; c += 64) {
+        const uint32_t i = c + lane;
+        const bool in = i < X;
+        const uint32_t v = in ? G.order[i] : 0u, nin = in ? G.n_in[v] : 0u, cnt = in ? (nin ? nin : 1u) : 0u;
+        const uint32_t incl = poa_prefix_sum(cnt), off = carry + incl - cnt;
+        if (in) {
+            if (off + cnt > 2u * bound) err |= kPoaErrPreds;   // (the sum is at most nodes + edges: cannot happen)
+            else {
+                PoaRowDev rw;
+                rw.pred_off = off, rw.n_pred = (uint16_t)cnt, rw.base = G.base[v], rw.sink = G.out_head[v] == kPoaNil;
+                G.rows[i] = rw;
+                if (nin == 0) G.preds[off] = 0;
+                else {
+                    uint32_t e = G.in_head[v], k = 0;
+                    for (; k < nin && e != kPoaNil; k++, e = G.e_next_in[e]) G.preds[off + k] = (uint16_t)(G.rank[G.e_from[e]] + 1u);
+                    if (k != nin || e != kPoaNil) err |= kPoaErrList;   // the list and its count disagree
+                }
+            }
+        }
+        carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    err = poa_or_lanes(err);
+    if (lane == 0) {
+        if (err) GD.err |= err;
+        PoaJobDev J;
+        J.X = err ? 0u : X, J.Y = sq.len;
+        J.q_off = sq.off, J.row_off = G.rows_off / sizeof(PoaRowDev), J.pred_off = G.preds_off / sizeof(uint16_t);
+        J.cell_off = rd.cell_off, J.route_off = G.route_off / sizeof(uint32_t);
+        J.route_len = 0, J.pad_ = 0;
+        jobs[rd.prob] = J;   // read by K13 and by poa_graph_thread: kernel boundary
+    }
+}
+
+// Graph::set_route + thread_route + toposort for sequence r of the round's problems.
+__global__ __launch_bounds__(64) void poa_graph_thread(PoaGraphDev *graphs, PoaXeDev *xe, const PoaRoundDev *__restrict__ round, uint32_t r,
+                                                        unsigned char *arena, const char *seqs, const PoaSeqDev *__restrict__ seq_tab,
+                                                        const PoaJobDev *__restrict__ jobs) {
+    const PoaRoundDev rd = round[blockIdx.x];
+    PoaGraphDev &GD = graphs[rd.prob];
+    const uint32_t lane = threadIdx.x, bound = GD.bound;
+    if (GD.err) {   // (uniform) an earlier kernel gave the problem up
+        if (lane == 0) xe[rd.prob] = PoaXeDev{GD.n_nodes, GD.err};
+        return;
+    }
+    const PoaG G = poa_g(arena, GD.arena_off, bound);
+    const PoaJobDev J = jobs[rd.prob];
+    const PoaSeqDev sq = seq_tab[GD.seq_first + r];
+    const unsigned char *s = (const unsigned char *)seqs + sq.off;   // s[Y] == NUL
+    const uint32_t X = J.X, Y = J.Y, n_route = J.route_len;
+    uint32_t err = n_route > X + Y || X != GD.n_nodes ? kPoaErrRoute : 0u;   // (K13's walk did not end: cannot happen)
+
+    // ---- the first and the last query offset the route consumes.  The walk back only ever lowers y, so the offsets of the words that
+    // consume one fall strictly along the walk: first = the least, last = the greatest (all lanes, then a butterfly)
+    uint32_t q_lo = 0xffffffffu, q_hi = 0;   // y = offset + 1; 0: none
+    if (!err)
+        for (uint32_t a = lane; a < n_route; a += 64) {
+            const uint32_t y = G.route[a] >> 16;
+            if (y) q_lo = y < q_lo ? y : q_lo, q_hi = y > q_hi ? y : q_hi;
+        }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)q_lo, m), hi = (uint32_t)__shfl_xor((int)q_hi, m);
+        q_lo = lo < q_lo ? lo : q_lo, q_hi = hi > q_hi ? hi : q_hi;
+    }
+    if (q_hi == 0 || q_hi > Y) err |= kPoaErrRoute;   // (a route consumes every query base's column at least once, none beyond Y)
+
+    uint32_t nn = GD.n_nodes, ne = GD.n_edges;
+    // ---- thread_route (dag.c:345-401), lane 0: nodes and edges are numbered in the order the walk makes them
+    if (lane == 0 && !err) {
+        const uint64_t bit = 1ull << r;
+        auto add_node = [&](uint32_t b) -> uint32_t {
+            if (nn >= bound) {
+                err |= kPoaErrNodes;
+                return kPoaNil;
+            }
+            const uint32_t id = nn++;
+            G.base[id] = (uint8_t)b, G.n_in[id] = 0;
+            G.in_head[id] = G.in_tail[id] = G.out_head[id] = G.out_tail[id] = (uint16_t)kPoaNil;
+            G.al_head[id] = G.al_tail[id] = (uint16_t)id, G.al_next[id] = (uint16_t)kPoaNil;
+            return id;
+        };
+        auto add_edge = [&](uint32_t from, uint32_t to) {
+            if (ne >= bound || from == kPoaNil || to == kPoaNil) {
+                err |= kPoaErrEdges;
+                return;
+            }
+            const uint32_t id = ne++;
+            G.e_from[id] = (uint16_t)from, G.e_to[id] = (uint16_t)to, G.labels[id] = bit;
+            G.e_next_in[id] = G.e_next_out[id] = (uint16_t)kPoaNil;
+            if (G.out_head[from] == kPoaNil) G.out_head[from] = (uint16_t)id;
+            else G.e_next_out[G.out_tail[from]] = (uint16_t)id;
+            G.out_tail[from] = (uint16_t)id;
+            if (G.in_head[to] == kPoaNil) G.in_head[to] = (uint16_t)id;
+            else G.e_next_in[G.in_tail[to]] = (uint16_t)id;
+            G.in_tail[to] = (uint16_t)id;
+            G.n_in[to] = (uint16_t)(G.n_in[to] + 1u);
+        };
+        // dag.c:236-250: `count` bytes from s[at] on (the tail's last one is the NUL); at most Y + 1 trips
+        auto add_chain = [&](uint32_t at, uint32_t count, uint32_t &first, uint32_t &head) {
+            for (uint32_t i = 0; i < count && !err; i++) {
+                const uint32_t id = add_node(s[at + i]);
+                if (first == kPoaNil) first = id;
+                else add_edge(head, id);
+                head = id;
+            }
+        };
+        const uint32_t start_q = q_lo - 1u, end_q = q_hi - 1u;
+        uint32_t first = kPoaNil, head = kPoaNil, tail_first = kPoaNil, tail_last = kPoaNil;
+        if (start_q > 0) add_chain(0, start_q, first, head);
+        if (end_q + 1u < Y) add_chain(end_q + 1u, Y - end_q, tail_first, tail_last);
+        bool prev_new = true;
+        for (uint32_t a = n_route; a-- > 0 && !err;) {   // the route forwards = K13's words backwards; n_route <= X + Y trips
+            const uint32_t w = G.route[a], x = w & 0xffffu, y = w >> 16;
+            if (!y) continue;
+            if (x > X) {
+                err |= kPoaErrRoute;
+                break;
+            }
+            const uint32_t b = s[y - 1u];
+            bool is_new = false;
+            uint32_t node;
+            if (!x) node = add_node(b), is_new = true;
+            else {
+                const uint32_t rn = G.order[x - 1u];   // (the order of the alignment: the new one is written below, after the walk)
+                if (G.base[rn] == b) node = rn;
+                else {
+                    uint32_t found = kPoaNil, t = 0;
+                    for (uint32_t m = G.al_head[rn]; m != kPoaNil; m = G.al_next[m]) {   // the column: at most `bound` nodes
+                        if (++t > bound) {
+                            err |= kPoaErrList;
+                            break;
+                        }
+                        if (G.base[m] == b) found = m;
+                    }
+                    if (found != kPoaNil) node = found;
+                    else {
+                        node = add_node(b), is_new = true;
+                        if (node != kPoaNil) {   // dag.c:190-202, 369-372: the new node joins the column of rn, as its youngest
+                            const uint32_t h = G.al_head[rn];
+                            G.al_head[node] = (uint16_t)h;
+                            G.al_next[G.al_tail[h]] = (uint16_t)node;
+                            G.al_tail[h] = (uint16_t)node;
+                        }
+                    }
+                }
+            }
+            if (err) break;
+            if (head != kPoaNil) {
+                bool add = is_new || prev_new;
+                if (!add) {   // dag.c:223-234 label_existing: every head -> node edge gets the bit; a new edge when there is none
+                    add = true;
+                    uint32_t t = 0;
+                    for (uint32_t e = G.out_head[head]; e != kPoaNil; e = G.e_next_out[e]) {   // at most `bound` edges
+                        if (++t > bound) {
+                            err |= kPoaErrList;
+                            break;
+                        }
+                        if (G.e_to[e] == node) G.labels[e] |= bit, add = false;
+                    }
+                }
+                if (add) add_edge(head, node);
+            }
+            head = node, prev_new = is_new;
+            if (first == kPoaNil) first = head;
+        }
+        if (!err && tail_first != kPoaNil) add_edge(head, tail_first);
+    }
+    // hand-over: lane 0 grew the graph, all lanes read it below -- fence + wavefront barrier; the counts travel by readlane
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    nn = (uint32_t)__builtin_amdgcn_readlane((int)nn, 0), ne = (uint32_t)__builtin_amdgcn_readlane((int)ne, 0);
+    err = poa_or_lanes(err);
+
+    // ---- toposort (dag.c:469-508 + 403-467).  Groups in ascending order of their heads = of the columns' oldest nodes (all lanes:
+    // a wavefront count of the heads before a node); the flags of a group are cleared by its head's lane
+    uint32_t ng = 0;
+    if (!err) {
+        for (uint32_t c = 0; c < nn; c += 64) {
+            const uint32_t i = c + lane;
+            const uint32_t hd = i < nn && G.al_head[i] == i ? 1u : 0u;
+            const uint32_t incl = poa_prefix_sum(hd), gi = ng + incl - hd;
+            if (hd) G.grp_head[gi] = (uint16_t)i, G.grp_of[i] = (uint16_t)gi, G.done[gi] = 0, G.started[gi] = 0;
+            ng += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+    // hand-over: a younger node of a column reads the group its head's lane just wrote -- fence + wavefront barrier
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    if (!err)
+        for (uint32_t i = lane; i < nn; i += 64) {
+            const uint32_t h = G.al_head[i];
+            if (h != i) G.grp_of[i] = G.grp_of[h];
+        }
+    // hand-over: lane 0's DFS reads every lane's groups and flags -- fence + wavefront barrier
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0 && !err) {
+        // The DFS with the stack discipline of poa.cpp.  `started` is not cleared per root: a started group pushes itself below its
+        // successors and is therefore popped again -- finished, its flag reset -- before the stack runs empty.
+        const uint32_t stack_cap = 2u * bound + 2u, trip_cap = 3u * bound + 3u;   // pops <= pushes <= roots + groups + edges
+        int fill = (int)nn - 1;
+        uint32_t scan = 0, trips = 0;
+        while (fill >= 0 && !err) {
+            uint32_t root = kPoaNil;
+            for (; scan < ng && root == kPoaNil; scan++) {   // (`scan` only moves on: at most ng trips over all roots)
+                if (G.done[scan]) continue;
+                bool pred = false;
+                uint32_t t = 0;
+                for (uint32_t m = G.grp_head[scan]; m != kPoaNil && !pred; m = G.al_next[m]) {
+                    if (++t > bound) {
+                        err |= kPoaErrList;
+                        break;
+                    }
+                    pred = G.n_in[m] != 0;
+                }
+                if (!pred) root = scan;
+            }
+            if (root == kPoaNil || err) {
+                err |= kPoaErrOrder;   // (the reference asserts: unreachable for the graphs built here)
+                break;
+            }
+            uint32_t sp = 0;
+            G.stack[sp++] = (uint16_t)root;
+            while (sp && !err) {
+                if (++trips > trip_cap) {
+                    err |= kPoaErrTrips;
+                    break;
+                }
+                const uint32_t g = G.stack[--sp];
+                if (G.done[g]) continue;
+                const uint32_t h = G.grp_head[g];
+                if (G.started[g]) {
+                    G.done[g] = 1, G.started[g] = 0;
+                    uint32_t t = 0;
+                    for (uint32_t m = h; m != kPoaNil; m = G.al_next[m]) {   // the head, then the column's nodes from the oldest on
+                        if (++t > bound || fill < 0) {
+                            err |= kPoaErrOrder;
+                            break;
+                        }
+                        G.order[fill--] = (uint16_t)m;
+                    }
+                    continue;
+                }
+                G.started[g] = 1;
+                G.stack[sp++] = (uint16_t)g;   // (sp < stack_cap: it was popped a moment ago)
+                uint32_t t = 0;
+                for (uint32_t m = h; m != kPoaNil && !err; m = G.al_next[m])
+                    for (uint32_t e = G.out_head[m]; e != kPoaNil; e = G.e_next_out[e]) {
+                        if (++t > bound) {   // the out-edges of a group: at most `bound` edges
+                            err |= kPoaErrList;
+                            break;
+                        }
+                        if (sp >= stack_cap) {
+                            err |= kPoaErrStack;
+                            break;
+                        }
+                        G.stack[sp++] = G.grp_of[G.e_to[e]];
+                    }
+            }
+        }
+    }
+    err = poa_or_lanes(err);
+    // the order, the graph and the counts are read by the next round's kernels: kernel boundary
+    if (lane == 0) {
+        GD.n_nodes = nn, GD.n_edges = ne, GD.err = err;
+        xe[rd.prob] = PoaXeDev{nn, err};
+    }
+}
+
+// Graph::heaviest_path (dag.c:555-595) + the cut at the first NUL, lane 0: scores in doubles -- every value is a multiple of 0.5 far
+// below 2^53, exact on the device as on the host -- the first edge of a node always taken, a later one only when strictly greater,
+// the best node the first of the order with the strictly greatest score.  `best` runs on from node to node, as in poa.cpp.
+__global__ __launch_bounds__(64) void poa_graph_consensus(PoaGraphDev *graphs, const uint32_t *__restrict__ ids, unsigned char *arena,
+                                                           char *out_all, uint32_t *out_len) {
+    const uint32_t prob = ids[blockIdx.x];
+    PoaGraphDev &GD = graphs[prob];
+    if (threadIdx.x != 0) return;
+    if (GD.err) {
+        out_len[prob] = 0xffffffffu;
+        return;
+    }
+    const uint32_t bound = GD.bound, n = GD.n_nodes, nseq = GD.n_seq;
+    const PoaG G = poa_g(arena, GD.arena_off, bound);
+    const uint64_t mask = nseq >= 64u ? ~0ull : ((1ull << nseq) - 1ull);
+    uint32_t err = 0, gnode = kPoaNil;
+    double best = -1, gbest = -1;
+    for (uint32_t i = 0; i < n && !err; i++) {
+        const uint32_t v = G.order[i], nin = G.n_in[v];
+        uint32_t bp = kPoaNil;
+        if (nin) {
+            uint32_t e = G.in_head[v], k = 0;
+            for (; k < nin && e != kPoaNil; k++, e = G.e_next_in[e]) {   // at most in-degree trips
+                const uint32_t from = G.e_from[e];
+                const double sc = G.sc[from] + (double)__popcll(G.labels[e] & mask) - 0.5 * (double)nin;
+                if (sc > best || bp == kPoaNil) best = sc, bp = from;
+            }
+            if (k != nin || e != kPoaNil) err |= kPoaErrList;
+        } else best = 0;
+        G.sc[v] = best, G.prev[v] = (uint16_t)bp;
+        if (best > gbest) gbest = best, gnode = v;
+    }
+    uint32_t len = 0;
+    for (uint32_t m = gnode; m != kPoaNil && !err; m = G.prev[m])   // a path: at most n nodes
+        if (++len > n) err |= kPoaErrTrips;
+    uint32_t cut = len;
+    if (!err) {
+        char *out = out_all + GD.out_off;   // (capacity bound >= n >= len)
+        uint32_t k = 0;
+        for (uint32_t m = gnode; m != kPoaNil && k < len; m = G.prev[m], k++) {
+            const uint32_t b = G.base[m], at = len - 1u - k;
+            out[at] = (char)b;
+            if (!b) cut = at;   // (the walk runs backwards: the last one seen is the first NUL of the string)
+        }
+    }
+    if (err) GD.err |= err;
+    out_len[prob] = err ? 0xffffffffu : cut;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // K14: the 8-mer ranking of a region's candidates (consensus.cpp: lq_rank_host; lib/nextcorrect.c:281-337, 405-440), one wavefront
 // per region, right behind K11 on the strings K11 left in the pool (or on the pool of a batch of problems: DeviceAligner::run_rank).
 // A sequence gives min(len, 40) - 8 k-mers of its head window (offset 0) or its tail window (offset len - 40 beyond 40 bases), each
@@ -1205,6 +1641,31 @@ void launch_poa_align(PoaJobDev *jobs, const uint32_t *ids_wave, int n_wave, con
     if (n_group > 0)
         hipLaunchKernelGGL(poa_align_kernel<kPoaGroupWaves>, dim3((unsigned)n_group), dim3(kPoaGroupWaves * 64), 0, st, jobs, ids_group, qpool,
                            rows, preds, S, F, route);
+}
+
+void launch_poa_graph_start(PoaGraphDev *graphs, PoaXeDev *xe, unsigned char *arena, const char *seqs, const PoaSeqDev *seq_tab, int n,
+                            void *stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(poa_graph_start, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, graphs, xe, arena, seqs, seq_tab);
+}
+
+void launch_poa_graph_rows(PoaGraphDev *graphs, const PoaRoundDev *round, int n_round, uint32_t r, unsigned char *arena,
+                           const PoaSeqDev *seq_tab, PoaJobDev *jobs, void *stream) {
+    if (n_round <= 0) return;
+    hipLaunchKernelGGL(poa_graph_rows, dim3((unsigned)n_round), dim3(64), 0, (hipStream_t)stream, graphs, round, r, arena, seq_tab, jobs);
+}
+
+void launch_poa_graph_thread(PoaGraphDev *graphs, PoaXeDev *xe, const PoaRoundDev *round, int n_round, uint32_t r, unsigned char *arena,
+                             const char *seqs, const PoaSeqDev *seq_tab, const PoaJobDev *jobs, void *stream) {
+    if (n_round <= 0) return;
+    hipLaunchKernelGGL(poa_graph_thread, dim3((unsigned)n_round), dim3(64), 0, (hipStream_t)stream, graphs, xe, round, r, arena, seqs, seq_tab,
+                       jobs);
+}
+
+void launch_poa_graph_consensus(PoaGraphDev *graphs, const uint32_t *ids, int n, unsigned char *arena, char *out, uint32_t *out_len,
+                                void *stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(poa_graph_consensus, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, graphs, ids, arena, out, out_len);
 }
 
 void launch_lq_rank(RegionDev *regions, const char *strpool, unsigned long long strpool_cap, uint32_t min_n, int n_regions, void *stream) {

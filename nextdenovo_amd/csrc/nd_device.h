@@ -223,6 +223,44 @@ constexpr uint32_t kPoaGroupMinLen = 1024;   // query bases from which the workg
 void launch_poa_align(PoaJobDev *jobs, const uint32_t *ids_wave, int n_wave, const uint32_t *ids_group, int n_group, const char *qpool,
                       const PoaRowDev *rows, const uint16_t *preds, int32_t *S, uint16_t *F, uint32_t *route, void *stream);
 
+// ---- POA: the graph itself on the device (K19, lq_kernels.hip; the arena's parts: poa_arena_layout of nd_lqplan.h) ----
+struct PoaGraphDev {         // one resident problem
+    uint64_t arena_off;      // first byte of its arena in the batch's arena buffer (a multiple of 8)
+    uint64_t out_off;        // first byte of its consensus string among the batch's strings (capacity: bound)
+    uint32_t seq_first;      // its first sequence's PoaSeqDev
+    uint32_t n_seq;
+    uint32_t bound;          // capacity in nodes and in edges (1..65535)
+    uint32_t n_nodes, n_edges;
+    uint32_t err;            // kPoaErr* bits; once set the kernels leave the problem alone and the host path computes it
+};
+struct PoaSeqDev {
+    uint64_t off;            // first byte in the batch's sequence pool; a NUL follows the last byte
+    uint32_t len, pad_;
+};
+struct PoaRoundDev {         // one problem of a round, in the order of the round's launches
+    uint32_t prob, pad_;
+    uint64_t cell_off;       // first cell of its (X + 1)(Y + 1) scores / origins in its launch
+};
+struct PoaXeDev {            // what the host reads per problem and round: 8 bytes
+    uint32_t X;              // nodes of the graph (rows of the next alignment)
+    uint32_t err;
+};
+enum : uint32_t {            // PoaGraphDev::err -- a capacity of the arena reached or a trip bound of a data-dependent loop
+    kPoaErrNodes = 1u, kPoaErrEdges = 2u, kPoaErrList = 4u, kPoaErrStack = 8u, kPoaErrTrips = 16u, kPoaErrOrder = 32u, kPoaErrRoute = 64u,
+    kPoaErrPreds = 128u
+};
+// start: the first sequence as a chain, the identity order (n problems).  rows: rank, rows, predecessor rows, sink flags and the
+// PoaJobDev K13 reads (jobs[prob]) for sequence r of the round's problems.  thread: the route K13 left threaded through the graph,
+// the new order.  consensus: heaviest path and string of problems ids[0 .. n), out_len[prob] = its length (cut at the first NUL).
+void launch_poa_graph_start(PoaGraphDev *graphs, PoaXeDev *xe, unsigned char *arena, const char *seqs, const PoaSeqDev *seq_tab, int n,
+                            void *stream);
+void launch_poa_graph_rows(PoaGraphDev *graphs, const PoaRoundDev *round, int n_round, uint32_t r, unsigned char *arena,
+                           const PoaSeqDev *seq_tab, PoaJobDev *jobs, void *stream);
+void launch_poa_graph_thread(PoaGraphDev *graphs, PoaXeDev *xe, const PoaRoundDev *round, int n_round, uint32_t r, unsigned char *arena,
+                             const char *seqs, const PoaSeqDev *seq_tab, const PoaJobDev *jobs, void *stream);
+void launch_poa_graph_consensus(PoaGraphDev *graphs, const uint32_t *ids, int n, unsigned char *arena, char *out, uint32_t *out_len,
+                                void *stream);
+
 // ---- scoring DP (K10), segment-parallel: see the head comment of the K10 section in msa_kernels.hip ----
 struct SegItem {            // work item of the segment kernel
     uint32_t pile;

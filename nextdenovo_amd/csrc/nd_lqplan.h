@@ -76,4 +76,65 @@ inline size_t next_poa_slice(const std::vector<PoaLoad> &load, size_t a, uint64_
     return a;
 }
 
+// ---- the arena of a resident POA graph (K19: the poa_graph_* kernels of lq_kernels.hip, run_poa's resident form) ----
+// One arena per problem, laid out once from a bound the host computes before the first launch: a sequence of Y bytes adds at most
+// Y + 1 nodes (its bases and the NUL of the tail chain) and at most Y + 1 edges, so bound = sum(len_k + 1) holds every node and every
+// edge the problem can ever have.  Ids are 16 bits with 0xffff for "none", hence bound <= 65,535 (ids 0 .. 65,534).
+// Every part starts at a multiple of 8 bytes, so that the tables K13 reads (rows, predecessor rows, route) have whole element
+// offsets from the batch's arena base.  Pure 64-bit arithmetic; the kernels compute the same layout from the same bound.
+#if defined(__HIPCC__)
+#define NDGPU_PLAN_HD __host__ __device__
+#else
+#define NDGPU_PLAN_HD
+#endif
+constexpr uint64_t kPoaArenaMaxBound = 65535;
+enum PoaPart : int {
+    kPaLabels,    // uint64 [bound]      per edge: bit i = sequence i walks it
+    kPaScore,     // double [bound]      per node: the heaviest path's score
+    kPaRows,      // 8 bytes [bound]     PoaRowDev, what K13 reads
+    kPaRoute,     // uint32 [bound]      K13's route words (X + Y <= bound of them)
+    kPaNIn,       // uint16 [bound]      per node: in-degree
+    kPaInHead, kPaInTail, kPaOutHead, kPaOutTail,   // uint16 [bound] per node: its in-edge / out-edge list in insertion order
+    kPaAlHead, kPaAlNext, kPaAlTail,                // uint16 [bound] per node: its column's oldest node, the next younger one; per oldest node: the youngest
+    kPaEFrom, kPaETo, kPaENextIn, kPaENextOut,      // uint16 [bound] per edge
+    kPaOrder, kPaRank, kPaGrpOf, kPaGrpHead, kPaPrev,   // uint16 [bound]
+    kPaPreds,     // uint16 [2 bound]    predecessor rows: sum over rows of max(in-degree, 1) <= nodes + edges
+    kPaStack,     // uint16 [2 bound + 2] the DFS stack: one root, a group per started group, a group per out-edge
+    kPaBase, kPaDone, kPaStarted,                   // uint8 [bound]
+    kPaCount
+};
+struct PoaArena {
+    uint64_t bound;
+    uint64_t off[kPaCount];   // bytes from the problem's arena base
+    uint64_t len[kPaCount];   // bytes of the part
+    uint64_t bytes;           // of the whole arena (a multiple of 8)
+};
+// false (nothing written): bound 0 or beyond 65,535 -- such a problem does not take the resident path
+NDGPU_PLAN_HD inline bool poa_arena_layout(uint64_t bound, PoaArena &A) {
+    if (bound == 0 || bound > kPoaArenaMaxBound) return false;
+    A.bound = bound;
+    uint64_t at = 0;
+#pragma unroll   // (device code: the offsets stay in registers)
+    for (int p = 0; p < (int)kPaCount; p++) {
+        const uint64_t elem = p <= (int)kPaRows ? 8 : p == (int)kPaRoute ? 4 : p <= (int)kPaStack ? 2 : 1;
+        const uint64_t count = p == (int)kPaPreds ? 2 * bound : p == (int)kPaStack ? 2 * bound + 2 : bound;
+        A.off[p] = at;
+        A.len[p] = elem * count;
+        at += (A.len[p] + 7) & ~(uint64_t)7;
+    }
+    A.bytes = at;
+    return true;
+}
+// the arenas of a batch back to back: off[i] = first byte of problem i's arena; returns the total.  A bound that has no layout
+// takes no room (off[i] = the next problem's).
+inline uint64_t poa_arena_offsets(const uint64_t *bounds, size_t n, uint64_t *off) {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        PoaArena A;
+        off[i] = at;
+        if (poa_arena_layout(bounds[i], A)) at += A.bytes;
+    }
+    return at;
+}
+
 }  // namespace ndgpu

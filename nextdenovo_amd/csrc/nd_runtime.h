@@ -76,6 +76,13 @@ struct RuntimeStats {
     uint64_t aln_batch_launches = 0;  // launches of K15's emit pass (one per chunk that has a run)
     uint64_t aln_batch_runs = 0;      // runs written
     double aln_batch_ms = 0;          // HIP-event time of K15 (count + emit)
+    // resident POA graphs (K19); the two byte counts are kept by both forms of run_poa
+    uint64_t poa_resident_jobs = 0;      // problems that finished on the resident path
+    uint64_t poa_resident_declined = 0;  // offered to it and not finished there: over the node bound or the budget, or a loop bound hit
+    uint64_t poa_graph_launches = 0;     // launches of K19's four kernels
+    double poa_graph_ms = 0;             // their HIP-event time
+    uint64_t poa_h2d_bytes = 0;          // what run_poa sent to the device
+    uint64_t poa_d2h_bytes = 0;          // and what it brought back
 };
 
 // Thrown when a device (or pinned host) allocation fails for lack of memory.  The C ABI catches it, releases the
@@ -115,7 +122,9 @@ class DeviceAligner {
     void run_extract(ExtractPile **piles, size_t n, bool offer_rank = true);
     void run_rank(RankReq *reqs, size_t n);   // the batched entry's problems: one pool up, one copy back
     void run_lq(LqRound **rounds, size_t n);
-    void run_poa(PoaReq **reqs, size_t n);   // req.done = false: declined, the caller's host path takes it
+    // req.done = false: declined, the caller's host path takes it.  form 0: NDGPU_POA_RESIDENT decides; 1: resident graphs (K19);
+    // 2: K13's rounds with the graphs on the host
+    void run_poa(PoaReq **reqs, size_t n, int form = 0);
     void end_batch();
     // resident read DB: every ndgpu_db handle owns its device copy (upload_db / free_db); a batch names the one its
     // AlnJob::q_dev / t_dev and MainPile::dev_off index into (use_db; nullptr: sequences come with the batch)
@@ -178,6 +187,7 @@ class HipBackend : public Backend {
         dev_.run_poa(reqs, n);
         return true;
     }
+    void run_poa_form(PoaReq **reqs, size_t n, int form) { dev_.run_poa(reqs, n, form); }   // the flags entry's choice of form
     void end_batch() override { finish(); }
 
   private:
