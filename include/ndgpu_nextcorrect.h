@@ -159,6 +159,32 @@ typedef struct ndgpu_rank_job { const char *const *seqs; const uint16_t *len; in
 typedef struct ndgpu_rank_result { uint8_t order[40]; uint16_t kscore[40]; int32_t tail; } ndgpu_rank_result;
 int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank_result *res);
 
+/* The consensus bases and low-quality windows of a main walk (the loop of generate_cns_from_best_score, reference
+ * lib/nextcorrect.c:1907-1982: raw reads, not -fast) for many walks in one call, one wavefront per walk on the device.  A job is n steps
+ * of a best_pp walk, origin first: seed position, best_link_count and coverage of the visited cell and its base code (A0 T1 G2 C3,
+ * 4 a gap, 5 N).  res[i]: the five counters of the loop, n_regions windows from (*regions)[2 * region_off] on as (start, end) pairs of
+ * seed positions in emission order, len words from (*bases)[base_off] on: pos << 8 | character (lower case: low coverage or quality),
+ * numbered as the reference numbers them before reverse_consensus_base; ok: the verdict of lib/nextcorrect.c:1986-1987 with the job's
+ * min_error_corrected_ratio.  *bases and *regions are one malloc'd block each, of exact size (free() them; one word when empty).
+ * flags bit 0: the engine's own host routine instead of the device (the same result; a cross-check).
+ * Returns 0; -2, with nothing computed or written, when n < 0, a pointer is NULL with n > 0, or a non-gap step has cov 0, a base above 5
+ * or a t_pos outside 0 .. 2^21 - 2; < 0 when no device can be used.  n = 0 is valid. */
+typedef struct ndgpu_walk_step { int32_t t_pos; uint16_t link, cov; uint8_t base; uint8_t pad_[3]; } ndgpu_walk_step;
+typedef struct ndgpu_cns_job {
+    const ndgpu_walk_step *steps;
+    uint32_t n;
+    int32_t min_cov;
+    uint32_t lq_max_len;
+    float min_error_corrected_ratio;
+} ndgpu_cns_job;
+typedef struct ndgpu_cns_result {
+    uint32_t len, uncorrected_len, lstrip, rstrip, lqseq_total_length;
+    int32_t ok;
+    uint32_t n_regions, pad_;
+    uint64_t base_off, region_off;
+} ndgpu_cns_result;
+int ndgpu_cns_windows_batch(const ndgpu_cns_job *jobs, int n, int flags, ndgpu_cns_result *res, uint32_t **bases, uint32_t **regions);
+
 /* align() / align_hq() for many pairs in one call.  The pairs share the launches of the forward and traceback kernels; a further kernel
  * pair run-length-encodes every alignment's columns on the device, so that what comes back per job is its summary and its CIGAR, not a
  * byte per column.  res[i]: status (0: none -- align() would leave its argument untouched, which includes a sequence with a byte
@@ -288,6 +314,13 @@ typedef struct {
     double poa_graph_ms;            /* their HIP-event time */
     uint64_t poa_h2d_bytes;         /* bytes the POA paths sent to the device */
     uint64_t poa_d2h_bytes;         /* and brought back */
+    uint64_t cns_jobs;              /* walks whose consensus words and windows the device made (ndgpu_cns_windows_batch, the engine's piles with NDGPU_CNS_DEVICE=1) */
+    uint64_t cns_declined;          /* offered to that kernel and left to the host routine */
+    uint64_t cns_launches;          /* its launches */
+    uint64_t cns_regions;           /* windows it emitted */
+    double cns_ms;                  /* its HIP-event time */
+    uint64_t cns_d2h_bytes;         /* result records, words and windows brought back */
+    uint64_t walk_d2h_bytes;        /* bytes of main walks (8 per slot of their capacity) the main phase brought back, with or without the kernel */
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);

@@ -34,6 +34,24 @@ class RankResult(C.Structure):
     _fields_ = [("order", C.c_uint8 * 40), ("kscore", C.c_uint16 * 40), ("tail", C.c_int32)]
 
 
+class WalkStep(C.Structure):
+    # ndgpu_walk_step
+    _fields_ = [("t_pos", C.c_int32), ("link", C.c_uint16), ("cov", C.c_uint16), ("base", C.c_uint8), ("pad_", C.c_uint8 * 3)]
+
+
+class CnsJob(C.Structure):
+    # ndgpu_cns_job
+    _fields_ = [("steps", C.c_void_p), ("n", C.c_uint32), ("min_cov", C.c_int32), ("lq_max_len", C.c_uint32),
+                ("min_error_corrected_ratio", C.c_float)]
+
+
+class CnsResult(C.Structure):
+    # ndgpu_cns_result
+    _fields_ = [("len", C.c_uint32), ("uncorrected_len", C.c_uint32), ("lstrip", C.c_uint32), ("rstrip", C.c_uint32),
+                ("lqseq_total_length", C.c_uint32), ("ok", C.c_int32), ("n_regions", C.c_uint32), ("pad_", C.c_uint32),
+                ("base_off", C.c_uint64), ("region_off", C.c_uint64)]
+
+
 class AlnJob(C.Structure):
     # ndgpu_aln_job
     _fields_ = [("q", C.c_char_p), ("q_len", C.c_int32), ("t", C.c_char_p), ("t_len", C.c_int32), ("hq", C.c_int32)]
@@ -74,7 +92,9 @@ class Stats(C.Structure):
                 ("aln_batch_jobs", C.c_uint64), ("aln_batch_launches", C.c_uint64), ("aln_batch_runs", C.c_uint64),
                 ("aln_batch_ms", C.c_double),
                 ("poa_resident_jobs", C.c_uint64), ("poa_resident_declined", C.c_uint64), ("poa_graph_launches", C.c_uint64),
-                ("poa_graph_ms", C.c_double), ("poa_h2d_bytes", C.c_uint64), ("poa_d2h_bytes", C.c_uint64)]
+                ("poa_graph_ms", C.c_double), ("poa_h2d_bytes", C.c_uint64), ("poa_d2h_bytes", C.c_uint64),
+                ("cns_jobs", C.c_uint64), ("cns_declined", C.c_uint64), ("cns_launches", C.c_uint64), ("cns_regions", C.c_uint64),
+                ("cns_ms", C.c_double), ("cns_d2h_bytes", C.c_uint64), ("walk_d2h_bytes", C.c_uint64)]
 
 
 def lib_path() -> str:
@@ -124,6 +144,9 @@ def _bind(lib):
     lib.ndgpu_poa_batch_flags.restype = C.c_int
     lib.ndgpu_lq_rank_batch.argtypes = [C.POINTER(RankJob), C.c_int, C.c_int, C.POINTER(RankResult)]
     lib.ndgpu_lq_rank_batch.restype = C.c_int
+    lib.ndgpu_cns_windows_batch.argtypes = [C.POINTER(CnsJob), C.c_int, C.c_int, C.POINTER(CnsResult), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p)]
+    lib.ndgpu_cns_windows_batch.restype = C.c_int
     lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.ndgpu_align_batch.restype = C.c_int
@@ -413,6 +436,51 @@ def lq_rank_batch(jobs, host=False):
     return [(list(res[i].order[:len(jobs[i])]), list(res[i].kscore[:len(jobs[i])]), int(res[i].tail)) for i in range(n)]
 
 
+def walk_steps(t_pos, link, cov, base):
+    """Four equally long integer sequences -> a numpy array of ndgpu_walk_step records (what cns_windows_batch takes as a job's steps)."""
+    import numpy as np
+    a = np.zeros(len(t_pos), dtype=np.dtype([("t_pos", "<i4"), ("link", "<u2"), ("cov", "<u2"), ("base", "u1"), ("pad_", "u1", (3,))]))
+    a["t_pos"], a["link"], a["cov"], a["base"] = t_pos, link, cov, base
+    return a
+
+
+def cns_windows_batch(jobs, host=False):
+    """jobs: [(steps, min_cov, lq_max_len, min_error_corrected_ratio)], steps as walk_steps() makes them (a best_pp walk, origin first)
+    -> one dict per job through ndgpu_cns_windows_batch: the loop of generate_cns_from_best_score (lib/nextcorrect.c:1907-1982) on the
+    device -- `bases` (numpy.uint32, pos << 8 | character, numbered as before reverse_consensus_base), `regions` (numpy.uint32 [k, 2]:
+    start, end in emission order), len, uncorrected_len, lstrip, rstrip, lqseq_total_length and ok, the verdict of :1986-1987.
+    host=True: the engine's own host routine instead of the device.  ValueError for a step the entry refuses (-2)."""
+    import numpy as np
+    lib = load()
+    n = len(jobs)
+    if n == 0:
+        return []
+    arr = (CnsJob * n)()
+    keep = []
+    for i, (steps, min_cov, lq_max_len, ratio) in enumerate(jobs):
+        st = np.ascontiguousarray(steps)
+        if st.dtype.itemsize != C.sizeof(WalkStep):
+            raise ValueError("steps must be records of ndgpu_walk_step (api.walk_steps)")
+        keep.append(st)
+        arr[i] = CnsJob(st.ctypes.data if st.size else None, int(st.size), int(min_cov), int(lq_max_len), float(ratio))
+    res = (CnsResult * n)()
+    bw, rw = C.c_void_p(), C.c_void_p()
+    rc = lib.ndgpu_cns_windows_batch(arr, n, 1 if host else 0, res, C.byref(bw), C.byref(rw))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("ndgpu_cns_windows_batch failed (%d)" % rc)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    n_words = sum(r.len for r in res)
+    n_reg = sum(r.n_regions for r in res)
+    words = np.ctypeslib.as_array(C.cast(bw, C.POINTER(C.c_uint32)), shape=(max(1, n_words),))[:n_words].copy()
+    regs = np.ctypeslib.as_array(C.cast(rw, C.POINTER(C.c_uint32)), shape=(max(1, 2 * n_reg),))[:2 * n_reg].copy().reshape(-1, 2)
+    libc.free(bw)
+    libc.free(rw)
+    return [dict(len=int(r.len), uncorrected_len=int(r.uncorrected_len), lstrip=int(r.lstrip), rstrip=int(r.rstrip),
+                 lqseq_total_length=int(r.lqseq_total_length), ok=bool(r.ok), bases=words[r.base_off:r.base_off + r.len],
+                 regions=regs[r.region_off:r.region_off + r.n_regions]) for r in res]
+
+
 def _align_call(fn, name, arr, n, host, strings):
     import numpy as np
     if n == 0:
@@ -465,6 +533,9 @@ def cigar_string(cigar) -> str:
 _POA_RESIDENT_STATS = ("poa_resident_jobs", "poa_resident_declined", "poa_graph_launches", "poa_graph_ms", "poa_h2d_bytes", "poa_d2h_bytes")
 
 
+_CNS_STATS = ("cns_jobs", "cns_declined", "cns_launches", "cns_regions", "cns_ms", "cns_d2h_bytes", "walk_d2h_bytes")
+
+
 def stats() -> dict:
     lib = load()
     s = Stats()
@@ -475,6 +546,11 @@ def stats() -> dict:
     late = [n for n in names if n in _POA_RESIDENT_STATS]
     names = [n for n in names if n not in _POA_RESIDENT_STATS]
     at = names.index("poa_ms") + 1
+    names[at:at] = late
+    # likewise the counters of the walk's consensus words and windows (K20), behind backtrack_ms
+    late = [n for n in names if n in _CNS_STATS]
+    names = [n for n in names if n not in _CNS_STATS]
+    at = names.index("backtrack_ms") + 1
     names[at:at] = late
     return {n: getattr(s, n) for n in names}
 

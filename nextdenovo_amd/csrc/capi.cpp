@@ -18,6 +18,7 @@
 
 #include "../../include/ndgpu_nextcorrect.h"
 #include "nd_host.h"
+#include "nd_cns.h"
 #include "nd_runtime.h"
 #include "nd_subplan.h"
 
@@ -245,6 +246,13 @@ void print_prof(int drivers, int threads_each) {  // NDGPU_PROF: the host driver
                     "(wall sums over contexts)\n", (unsigned long long)g_prof.c_jobs.load(), g_prof.c_pack * 1e-9, g_prof.c_dev * 1e-9,
             g_prof.c_decode * 1e-9);
     g_prof.c_pack = g_prof.c_dev = g_prof.c_decode = g_prof.c_jobs = 0;
+    {   // (device counters: since the last ndgpu_reset_stats, not since the last print)
+        const RuntimeStats s = DeviceAligner::total_stats();
+        fprintf(stderr, "[ndgpu prof] main walks since the last reset: %llu piles, %llu path items, walk_d2h_bytes %llu | K20: cns_d2h_bytes %llu, "
+                        "%llu walks, %llu declined, %llu launches, %.3f ms\n", (unsigned long long)s.piles, (unsigned long long)s.path_items,
+                (unsigned long long)s.walk_d2h_bytes, (unsigned long long)s.cns_d2h_bytes, (unsigned long long)s.cns_jobs,
+                (unsigned long long)s.cns_declined, (unsigned long long)s.cns_launches, s.cns_ms);
+    }
     for (auto &a : g_prof.adv_ns) a = 0;
     g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
     g_prof.m_prep = g_prof.m_aln = g_prof.m_tags = g_prof.m_msa = g_prof.m_post = 0;
@@ -822,6 +830,93 @@ int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank
     return 0;
 }
 
+// The consensus words and low-quality windows of a batch of walks: K20 on the device (DeviceAligner::run_cns), or -- flags bit 0 -- the
+// engine's own host routine (cns_windows_host); a walk the kernel declines takes the host routine too.  The verdict is cns_verdict.
+int ndgpu_cns_windows_batch(const ndgpu_cns_job *jobs, int n, int flags, ndgpu_cns_result *res, uint32_t **bases, uint32_t **regions) {
+    if (n == 0) return 0;
+    if (n < 0 || !jobs || !res || !bases || !regions) return -2;
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].n && !jobs[i].steps) return -2;
+        for (uint32_t k = 0; k < jobs[i].n; k++) {
+            const ndgpu_walk_step &s = jobs[i].steps[k];
+            if (s.base == 4) continue;
+            if (s.cov == 0 || s.base > 5 || s.t_pos < 0 || s.t_pos > (1 << 21) - 2) return -2;   // (t_pos + 1 has 21 bits in the tag)
+        }
+        total += jobs[i].n;
+    }
+    std::vector<PathStep> steps(total);
+    std::vector<CnsReq> reqs((size_t)n);
+    for (size_t i = 0, at = 0; i < (size_t)n; i++) {
+        const ndgpu_cns_job &j = jobs[i];
+        for (uint32_t k = 0; k < j.n; k++) {
+            PathStep &d = steps[at + k];
+            d.t_pos = j.steps[k].t_pos, d.delta = 0, d.base = j.steps[k].base, d.link = j.steps[k].link, d.cov = j.steps[k].cov;
+        }
+        reqs[i].steps = steps.data() + at, reqs[i].n = j.n, reqs[i].min_cov = j.min_cov, reqs[i].lq_max_len = j.lq_max_len;
+        at += j.n;
+    }
+    if (!(flags & 1)) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+            fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_cns_windows_batch runs on the device unless flags bit 0 is set\n");
+            return -1;
+        }
+        // (out of device memory: the range is halved until it fits)
+        std::vector<std::pair<size_t, size_t>> todo{{0, (size_t)n}};
+        while (!todo.empty()) {
+            const auto [a, b] = todo.back();
+            todo.pop_back();
+            try {
+                HipBackend be(0, 1);
+                be.run_cns(reqs.data() + a, b - a);
+            } catch (const DeviceOom &) {
+                DeviceAligner::context(0).release_memory();
+                DeviceAligner::forget_sizes();
+                if (b - a <= 1) return -3;
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    host_each((size_t)n, effective_cpus() <= 1 || n <= 1, effective_cpus(), (size_t)n, false, [&](size_t i) {
+        CnsReq &rq = reqs[i];
+        if (rq.done) return;
+        std::vector<CnsWindow> wins;
+        CnsCounts c;
+        cns_windows_host(rq.steps, rq.n, rq.min_cov, rq.lq_max_len, rq.words, wins, c);
+        rq.wins.clear();
+        for (const CnsWindow &w : wins) rq.wins.push_back(w.start), rq.wins.push_back(w.end);
+        const uint32_t counts[5] = {c.len, c.uncorrected_len, c.lstrip, c.rstrip, c.lqseq_total_length};
+        memcpy(rq.counts, counts, sizeof(counts));
+    });
+    size_t n_words = 0, n_wins = 0;
+    for (const CnsReq &rq : reqs) n_words += rq.words.size(), n_wins += rq.wins.size();
+    uint32_t *bw = (uint32_t *)malloc(std::max<size_t>(1, n_words) * sizeof(uint32_t));
+    uint32_t *rw = (uint32_t *)malloc(std::max<size_t>(1, n_wins) * sizeof(uint32_t));
+    if (!bw || !rw) {
+        free(bw), free(rw);
+        return -3;
+    }
+    size_t at_w = 0, at_r = 0;
+    for (int i = 0; i < n; i++) {
+        const CnsReq &rq = reqs[(size_t)i];
+        ndgpu_cns_result &o = res[i];
+        memset(&o, 0, sizeof(o));
+        CnsCounts c;
+        c.len = o.len = rq.counts[0], c.uncorrected_len = o.uncorrected_len = rq.counts[1], c.lstrip = o.lstrip = rq.counts[2];
+        c.rstrip = o.rstrip = rq.counts[3], c.lqseq_total_length = o.lqseq_total_length = rq.counts[4];
+        o.ok = cns_verdict(c, jobs[i].min_error_corrected_ratio) ? 1 : 0;
+        o.n_regions = (uint32_t)(rq.wins.size() / 2);
+        o.base_off = at_w, o.region_off = at_r / 2;
+        if (!rq.words.empty()) memcpy(bw + at_w, rq.words.data(), rq.words.size() * sizeof(uint32_t));
+        if (!rq.wins.empty()) memcpy(rw + at_r, rq.wins.data(), rq.wins.size() * sizeof(uint32_t));
+        at_w += rq.words.size(), at_r += rq.wins.size();
+    }
+    *bases = bw, *regions = rw;
+    return 0;
+}
+
 // ---- batched global alignment: align() / align_hq() for many pairs in one call, CIGARs built on the device (K15) ----
 namespace {
 struct AlnBatchSrc {            // where job i's bases are, for the strings flag
@@ -1009,6 +1104,8 @@ void ndgpu_get_stats(ndgpu_stats *o) {
     o->poa_resident_jobs = s.poa_resident_jobs, o->poa_resident_declined = s.poa_resident_declined;
     o->poa_graph_launches = s.poa_graph_launches, o->poa_graph_ms = s.poa_graph_ms;
     o->poa_h2d_bytes = s.poa_h2d_bytes, o->poa_d2h_bytes = s.poa_d2h_bytes;
+    o->cns_jobs = s.cns_jobs, o->cns_declined = s.cns_declined, o->cns_launches = s.cns_launches, o->cns_regions = s.cns_regions;
+    o->cns_ms = s.cns_ms, o->cns_d2h_bytes = s.cns_d2h_bytes, o->walk_d2h_bytes = s.walk_d2h_bytes;
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }

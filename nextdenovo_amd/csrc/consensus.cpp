@@ -14,6 +14,7 @@
 //     merge-sort qsort() on the reference's comparators.
 // Reference locations are cited at each step.
 #include "nd_host.h"
+#include "nd_cns.h"
 
 #include <algorithm>
 #include <cctype>
@@ -572,6 +573,9 @@ class PileImpl {
         main.max_cov_aln = prm.max_cov_aln;
         main.factor = prm.read_type == 3 ? 4 : 3;  // nextcorrect.c:2147
         main.hq = prm.read_type == 3;              // align_hq for HiFi, nextcorrect.c:2269
+        main.want_cns = cns_on_device() && !prm.fast && prm.read_type != 3;
+        main.min_cov = (int)prm.min_cov;
+        main.lq_max_len = lq_max_len;
     }
 
     void finish_error(unsigned code) {
@@ -597,7 +601,27 @@ class PileImpl {
     }
 
     // -- main phase: the device returns the best_pp walk --------------------------------
+    // The walk's consensus words and windows from the backend (K20; opt-in, see DESIGN.md section 0a'''''''''): raw reads, not -fast.
+    static bool cns_on_device() {
+        static const bool on = getenv("NDGPU_CNS_DEVICE") != nullptr && atoi(getenv("NDGPU_CNS_DEVICE")) != 0;
+        return on;
+    }
     void after_main() {
+        if (main.cns_ready) {  // the backend ran cns_from_best_score's loop: its words, windows and counters; the verdict is ours
+            std::vector<uint32_t> words, wins;
+            words.swap(main.cns_words), wins.swap(main.cns_windows);
+            main.cns_ready = false;
+            CnsCounts c;
+            c.len = main.cns_counts[0], c.uncorrected_len = main.cns_counts[1], c.lstrip = main.cns_counts[2], c.rstrip = main.cns_counts[3];
+            c.lqseq_total_length = main.cns_counts[4];
+            n_aligned = main.n_aligned;
+            if (!cns_from_words(words.data(), wins.data(), wins.size() / 2, c)) {
+                finish_error(2);
+                return;
+            }
+            to_extract();
+            return;
+        }
         std::vector<PathStep> path;
         path.swap(main.path);
         if (path.empty()) {  // no column carries a tag (reference: undefined behaviour)
@@ -615,6 +639,10 @@ class PileImpl {
             finish_error(2);
             return;
         }
+        to_extract();
+    }
+    // the windows as an extract request (none: straight to the first low-quality-region round)
+    void to_extract() {
         lq_iter = 0;
         lq_max_dif_len = 0;
         if (regions.empty()) {
@@ -748,70 +776,26 @@ class PileImpl {
         std::reverse(result.seq.begin(), result.seq.end());
     }
 
-    // lib/nextcorrect.c:1885-2006.  Returns false for the error_seed(2) outcome.
+    // lib/nextcorrect.c:1885-2006.  Returns false for the error_seed(2) outcome.  The loop is cns_windows_host (nd_cns.h); the verdict
+    // and reverse_consensus_base follow it here, whoever ran the loop.
     bool cns_from_best_score(const std::vector<PathStep> &path) {
-        int p = 0, lable = 1;
-        const int lq_min_length = 8;
-        int qv = 0, pqv, hq = 0, lq = 0, lq_l = 0, lq_s = -1, lq_e = -1;
-        int lqseq_total_length = 0;
-        const int min_cov = (int)prm.min_cov;
+        std::vector<uint32_t> words, flat;
+        std::vector<CnsWindow> wins;
+        CnsCounts c;
+        cns_windows_host(path.data(), path.size(), (int)prm.min_cov, lq_max_len, words, wins, c);
+        for (const CnsWindow &w : wins) flat.push_back(w.start), flat.push_back(w.end);
+        return cns_from_words(words.data(), flat.data(), wins.size(), c);
+    }
+    // words: pos << 8 | char in walk order; wins: (start, end) pairs in emission order
+    bool cns_from_words(const uint32_t *words, const uint32_t *wins, size_t n_wins, const CnsCounts &c) {
         cns = CnsData();
-        cns.bases.reserve(path.size());
         regions.clear();
-        for (const PathStep &cur : path) {
-            if (cur.base == 4) continue;
-            cns.bases.push_back(CnsBase{(unsigned)cur.t_pos, 0});
-            const int cov = cur.cov;
-            pqv = 100 * (int)cur.link / cov;
-            if (pqv > 40) hq++;
-            else {
-                hq = 0;
-                lqseq_total_length++;
-            }
-            if (hq > lq_min_length / 2 && lq_e - lq_s < lq_min_length / 2) {
-                qv = lq_l = lq = 0;
-                lq_s = -1;
-            }
-            if ((qv + pqv) / (lq_l + 1) < 40) {
-                if (lq_s == -1) lq_s = p;
-                lq_e = p;
-                lq = 1;
-                lq_l++;
-                qv += pqv;
-            } else if (lq && p - lq_e > 2 * lq_min_length && cns.bases[p].pos != cns.bases[p - 1].pos) {
-                if (lq_e - lq_s + 1 > lq_min_length && (unsigned)(lq_e - lq_s + 1) < lq_max_len) {
-                    lq_e = p - lq_min_length - 1;
-                    lq_s = lq_s > lq_min_length ? lq_s - lq_min_length : 1;
-                    LqRegion r;
-                    r.end = cns.bases[lq_s].pos;
-                    r.start = cns.bases[lq_e].pos;
-                    if (!regions.empty() && r.end == regions.back().start) {
-                        while (r.end == regions.back().start && lq_s < p - 4) r.end = cns.bases[++lq_s].pos;
-                    }
-                    regions.push_back(std::move(r));
-                }
-                qv = lq_l = lq = 0;
-                lq_s = -1;
-            } else if (lq && cns.bases[p].pos != cns.bases[p - 1].pos) {
-                qv = lq_l = 0;
-            }
-            if (cov > min_cov && pqv > 20) {
-                cns.bases[p].base = (char)kIntToBase[cur.base];
-                lable = 0;
-                cns.lstrip = 0;
-            } else {
-                cns.bases[p].base = (char)tolower(kIntToBase[cur.base]);
-                cns.uncorrected_len++;
-                cns.lstrip++;
-                if (lable) cns.rstrip++;
-            }
-            p++;
-        }
-        cns.len = (unsigned)p;
-        const float lhs = (float)(cns.uncorrected_len - cns.lstrip - cns.rstrip);
-        const float rhs = (float)(cns.len - cns.lstrip - cns.rstrip) * (1 - prm.min_error_corrected_ratio);
-        if (!(cns.len > 2 && (double)lqseq_total_length < cns.len * 0.8 && lhs < rhs)) return false;
-        std::reverse(cns.bases.begin(), cns.bases.end());
+        cns.len = c.len, cns.uncorrected_len = c.uncorrected_len, cns.lstrip = c.lstrip, cns.rstrip = c.rstrip;
+        if (!cns_verdict(c, prm.min_error_corrected_ratio)) return false;
+        cns.bases.resize(c.len);
+        for (uint32_t p = 0; p < c.len; p++) cns.bases[c.len - 1 - p] = CnsBase{words[p] >> 8, (char)(words[p] & 0xffu)};  // reverse_consensus_base
+        regions.resize(n_wins);
+        for (size_t i = 0; i < n_wins; i++) regions[i].start = wins[2 * i], regions[i].end = wins[2 * i + 1];
         return true;
     }
 

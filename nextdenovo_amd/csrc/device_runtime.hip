@@ -348,6 +348,13 @@ enum class BufLevel { levelled, on_demand };
     X(uint32_t, d_bt_off, device, levelled)                                                                                               \
     X(PathItem, d_path, device, levelled)                                                                                                 \
     X(ColBlock, d_blocks, device, levelled)                                                                                               \
+    /* K20: jobs, result records, a word per path slot, window slots, the dense words and windows that come down */                       \
+    X(CnsJobDev, d_cns_jobs, device, levelled)                                                                                            \
+    X(CnsOutDev, d_cns_out, device, levelled)                                                                                             \
+    X(uint32_t, d_cns_words, device, levelled)                                                                                            \
+    X(uint32_t, d_cns_wins, device, levelled)                                                                                             \
+    X(uint32_t, d_cns_dense, device, levelled)                                                                                            \
+    X(uint32_t, d_cns_wdense, device, levelled)                                                                                           \
     X(RegionDev, d_regions, device, levelled)                                                                                             \
     X(char, d_strpool, device, levelled)                                                                                                  \
     X(unsigned long long, d_cursor, device, levelled)                                                                                     \
@@ -384,8 +391,13 @@ struct MsaPlan {  // plan_msa: K10's work lists by tier, K9's column blocks, the
 };
 struct MsaResult {  // count_and_score: the last attempt's error words, its piles, its paths (a view into the download arena)
     uint32_t herr[kErrWords] = {};
-    const PathItem *hpath = nullptr;
+    const PathItem *hpath = nullptr;   // (nullptr where K20 took the walks: MsaResult::cns)
     std::vector<PileDev> piles;
+    std::vector<CnsOutDev> cns;        // K20's records, one per pile
+};
+struct CnsPlan {  // plan_cns: K20's jobs of a launch (one per pile, or per walk of run_cns) and the window slots they share
+    std::vector<CnsJobDev> jobs;
+    uint64_t win_slots = 0;
 };
 
 struct LqSrc {  // a sequence of an LQ call's pool: packed already (words), or ASCII
@@ -511,6 +523,7 @@ struct DeviceAligner::State {
         kEvLqMsaBegin, kEvLqMsaEnd,                              // launch_lq: around K12 (its K7 / K8a: lq_evs)
         kEvTailBegin, kEvTailEnd, kEvExtractRanked,  // K11, K13, K14, K15: around the launch in flight | behind K14 where it follows K11
         kEvPoaRows, kEvPoaAlign, kEvPoaThread, kEvPoaEnd,  // a resident POA round: before K19's rows | K13's launches | K19's thread | behind it
+        kEvCnsBegin, kEvCnsEnd,                            // launch_cns: around K20 and its gather
         kEvCount
     };
     hipEvent_t evs[kEvCount] = {nullptr};
@@ -598,7 +611,10 @@ struct DeviceAligner::State {
     void align_main(const std::vector<AlignChunk> &chunks, size_t np);
     void launch_tags(const CovPlanes &cov, size_t np);
     void upload_plan(const MsaPlan &plan);
-    MsaResult count_and_score(const MsaPlan &plan, const CovPlanes &cov);
+    MsaResult count_and_score(const MsaPlan &plan, const CovPlanes &cov, const CnsPlan *cns);
+    CnsPlan plan_cns(const MsaPlan &plan, MainPile **mp);
+    void launch_cns(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path);
+    void fetch_cns(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp);
     void score_pass(const MsaPlan &plan, const K10Args &k10);
     void rescue_pass(const MsaPlan &plan, const K10Args &k10);
     void k9_digest_trace(const K9Args &k9, size_t np);
@@ -745,6 +761,8 @@ RuntimeStats DeviceAligner::total_stats() {
         t.rank_jobs += s.rank_jobs; t.rank_tail += s.rank_tail; t.rank_launches += s.rank_launches; t.rank_ms += s.rank_ms;
         t.aln_batch_jobs += s.aln_batch_jobs; t.aln_batch_launches += s.aln_batch_launches; t.aln_batch_runs += s.aln_batch_runs;
         t.aln_batch_ms += s.aln_batch_ms;
+        t.cns_jobs += s.cns_jobs; t.cns_declined += s.cns_declined; t.cns_launches += s.cns_launches; t.cns_regions += s.cns_regions;
+        t.cns_ms += s.cns_ms; t.cns_d2h_bytes += s.cns_d2h_bytes; t.walk_d2h_bytes += s.walk_d2h_bytes;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -1612,7 +1630,8 @@ void DeviceAligner::end_batch() { s_->batch_mu.unlock(); }
 // ---- the main phase of a batch of piles, entirely on the device.  run_main (below) is the sequence of these steps:
 //   layout (layout_piles) -> align: K7 forward, K8a traceback (align_main) -> tags: K8s shift scan, accept, K8b tags, column scan
 //   (launch_tags) -> [one host sync: exact cell / link totals] -> plan (plan_msa) -> links + scoring: K9, K10 + walk
-//   (count_and_score) -> stats (tally_main) -> unpack (unpack_paths).
+//   (count_and_score) -> stats (tally_main) -> unpack (unpack_paths).  Where every pile of the launch asks for it, K20 takes the
+//   walks: plan_cns behind the plan, launch_cns inside count_and_score, fetch_cns instead of unpack (see the K20 section below).
 // A step reads what it is given and returns one result; pool, tasks, reads and piles are the context's own vectors (reads and
 // piles stay alive to end_batch: run_extract's kernels read their device copies).
 
@@ -1885,7 +1904,7 @@ void DeviceAligner::State::k9_digest_trace(const K9Args &k9, size_t np) {
 // hold raises err[0] and the sub-batch is counted and scored again with the full capacity (everything the kernels write is
 // rewritten), and if that overflows too, a third time with the lists in device memory, which cannot (nd_device.h: kLinkCap).
 // Returns the last attempt's error words, its piles and a view of its paths in the download arena.
-MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPlanes &cov) {
+MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPlanes &cov, const CnsPlan *cns) {
     const MainHooks &hooks = hooks_of<MainHooks>();
     hipStream_t st = stream;
     const K9Args k9{d_piles.p,   d_reads.p,      d_acc.p,      d_blocks.p, d_tags.p,    d_colidx.p,  cov.insmax, d_cellbase.p,
@@ -1896,9 +1915,28 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
     k10.sums = d_sums.p, k10.spec = d_spec.p, k10.fin = d_fin.p;
     k10.seg_len = hooks.k10_seg_len, k10.warm = hooks.k10_warm, k10.guard = hooks.k10_guard, k10.force_repair = hooks.k10_force_repair;
     const size_t np = piles.size();
-    const size_t down_bytes = np * sizeof(PileDev) + plan.paths * sizeof(PathItem) + 1024;
+    // what an attempt brings down: the piles, and either their walks or -- cns: K20 runs on the walks where bt_emit left them, in
+    // front of the synchronisation (the retry / rescue decision needs it anyway), so that its records ride down with the piles
+    const size_t down_bytes = np * sizeof(PileDev) + (cns ? np * sizeof(CnsOutDev) + 256 : plan.paths * sizeof(PathItem)) + 1024;
     MsaResult R;
     R.piles.resize(np);
+    if (cns) R.cns.resize(np);
+    const void *v_cns = nullptr;
+    auto walks_down = [&] {  // behind the walk: K20's records, or the walks themselves
+        if (cns) {
+            launch_cns(*cns, d_piles.p, d_path.p);
+            v_cns = d2h(nullptr, d_cns_out.p, np * sizeof(CnsOutDev), st);
+            stats.cns_d2h_bytes += np * sizeof(CnsOutDev);
+        } else {
+            R.hpath = (const PathItem *)d2h(nullptr, d_path.p, plan.paths * sizeof(PathItem), st);
+            stats.walk_d2h_bytes += plan.paths * sizeof(PathItem);
+        }
+    };
+    auto walks_landed = [&] {
+        if (!cns) return;
+        memcpy(R.cns.data(), v_cns, np * sizeof(CnsOutDev));
+        stats.cns_ms += ms(kEvCnsBegin, kEvCnsEnd);
+    };
     for (int attempt = hooks.k9_full ? 1 : 0, first = 1; attempt < 3; attempt++, first = 0) {
         reserve_down(down_bytes, st);
         h2d(d_piles.p, piles.data(), np * sizeof(PileDev), st);
@@ -1919,22 +1957,24 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
         NDGPU_DBG(st, "main: score + walk");
         score_pass(plan, k10);
         const void *v_piles = d2h(nullptr, d_piles.p, np * sizeof(PileDev), st);  // (re-taken by the rescue pass)
-        R.hpath = (const PathItem *)d2h(nullptr, d_path.p, plan.paths * sizeof(PathItem), st);
+        walks_down();
         const void *v_err = d2h(nullptr, d_err.p, sizeof(R.herr), st);
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipGetLastError());
         memcpy(R.piles.data(), v_piles, np * sizeof(PileDev));
         memcpy(R.herr, v_err, sizeof(R.herr));
+        walks_landed();
         bool rescue = false;
         for (size_t p = 0; p < np; p++) rescue = rescue || R.piles[p].err == 2;
         if (rescue) {
             rescue_pass(plan, k10);
             reserve_down(down_bytes, st);
             v_piles = d2h(nullptr, d_piles.p, np * sizeof(PileDev), st);
-            R.hpath = (const PathItem *)d2h(nullptr, d_path.p, plan.paths * sizeof(PathItem), st);
+            walks_down();
             HIP_CHECK(hipStreamSynchronize(st));
             HIP_CHECK(hipGetLastError());
             memcpy(R.piles.data(), v_piles, np * sizeof(PileDev));
+            walks_landed();
         }
         if (attempt < 2 && trace_on())
             fprintf(stderr, "[ndgpu trace] K9 blocks: compact %u (max cover %u), fallback %u (min cover %u)\n", R.herr[1], R.herr[3], R.herr[2],
@@ -1985,6 +2025,18 @@ void DeviceAligner::State::tally_main(const MsaPlan &plan, const std::vector<uin
     }
 }
 
+static void unpack_walk(const PathItem *src, uint32_t len, MainPile &M) {
+    M.path.resize(len);
+    for (uint32_t k = 0; k < len; k++) {
+        PathStep &d = M.path[k];
+        d.t_pos = tag_tpos(src[k].tag);
+        d.delta = (uint16_t)tag_delta(src[k].tag);
+        d.base = (uint8_t)tag_base(src[k].tag);
+        d.link = src[k].link;
+        d.cov = src[k].cov;
+    }
+}
+
 // The walk of every pile (one step per consensus position) into its MainPile: piles dealt to the context's host threads.
 static void unpack_paths(const std::vector<PileDev> &piles, const PathItem *hpath, const std::vector<uint8_t> &bad_pile, MainPile **mp,
                          int host_threads) {
@@ -1993,17 +2045,191 @@ static void unpack_paths(const std::vector<PileDev> &piles, const PathItem *hpat
         if (bad_pile[p]) return;
         const PileDev &P = piles[p];
         MainPile &M = *mp[p];
-        M.path.resize(P.path_len);
-        const PathItem *src = hpath + P.path_off;
-        for (uint32_t k = 0; k < P.path_len; k++) {
-            PathStep &d = M.path[k];
-            d.t_pos = tag_tpos(src[k].tag);
-            d.delta = (uint16_t)tag_delta(src[k].tag);
-            d.base = (uint8_t)tag_base(src[k].tag);
-            d.link = src[k].link;
-            d.cov = src[k].cov;
-        }
+        unpack_walk(hpath + P.path_off, P.path_len, M);
     });
+}
+
+// ---- K20: the walk's consensus words and low-quality windows on the device (nd_cns.h states the rule; DESIGN.md section 0a''''''''').
+// In run_main: plan_cns (jobs and buffers, behind upload_plan) -> launch_cns inside count_and_score, behind every walk -> fetch_cns
+// (exact-size copies of the dense words and windows; a declined pile's walk on its own, unpacked for the host routine).
+
+// Test hook NDGPU_CNS_DECLINE=<k>: every k-th walk offered to K20 is left to the host routine (counted over the process).
+static bool cns_decline_hook() {
+    static const uint64_t k = env_u64("NDGPU_CNS_DECLINE", 0);
+    static std::atomic<uint64_t> seen{0};
+    return k && seen.fetch_add(1) % k == k - 1;
+}
+// Window slots of a walk of at most `items` items: recorded emissions lie at least 25 indices apart (msa_kernels.hip, K20).
+static uint32_t cns_win_cap(uint64_t items) { return (uint32_t)(items / 24u + 1u); }
+
+CnsPlan DeviceAligner::State::plan_cns(const MsaPlan &plan, MainPile **mp) {
+    CnsPlan C;
+    const size_t np = piles.size();
+    C.jobs.resize(np);
+    for (size_t p = 0; p < np; p++) {
+        CnsJobDev &J = C.jobs[p];
+        memset(&J, 0, sizeof(J));
+        J.pile = (uint32_t)p;
+        J.win_off = C.win_slots;
+        J.n = piles[p].n_cells / 6 + 1;   // the capacity of the walk's slice (plan_msa): its length is not known yet
+        J.win_cap = cns_win_cap(J.n);
+        J.min_cov = mp[p]->min_cov;
+        J.lq_max_len = mp[p]->lq_max_len;
+        J.decline = cns_decline_hook() ? 1u : 0u;
+        C.win_slots += J.win_cap;
+    }
+    d_cns_jobs.reserve(np);
+    d_cns_out.reserve(np);
+    d_cns_words.reserve(plan.paths + 1);
+    d_cns_dense.reserve(plan.paths + 1);
+    d_cns_wins.reserve(2 * C.win_slots + 2);
+    d_cns_wdense.reserve(2 * C.win_slots + 2);
+    h2d(d_cns_jobs.p, C.jobs.data(), np * sizeof(CnsJobDev), stream);
+    return C;
+}
+
+void DeviceAligner::State::launch_cns(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path) {
+    hipStream_t st = stream;
+    mark(kEvCnsBegin, st);
+    NDGPU_DBG(st, "cns_windows: %zu walks", cns.jobs.size());
+    launch_cns_windows(d_cns_jobs.p, dev_piles, dev_path, d_cns_words.p, d_cns_wins.p, d_cns_out.p, d_cns_dense.p, d_cns_wdense.p,
+                       (int)cns.jobs.size(), st);
+    mark(kEvCnsEnd, st);
+    stats.cns_launches++;
+}
+
+void DeviceAligner::State::fetch_cns(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp) {
+    hipStream_t st = stream;
+    const size_t np = piles.size();
+    uint64_t n_words = 0, n_wins = 0, walk_bytes = 0, visited = 0;
+    size_t n_declined = 0;
+    for (size_t p = 0; p < np; p++) {
+        const CnsOutDev &O = res.cns[p];
+        if (O.err) n_declined++, walk_bytes += ((size_t)piles[p].path_len * sizeof(PathItem) + 255) & ~(size_t)255;
+        else n_words += O.len, n_wins += O.n_win, visited += O.visited;
+    }
+    reserve_down(n_words * 4 + n_wins * 8 + walk_bytes + 1024, st);
+    const uint32_t *w = (const uint32_t *)d2h(nullptr, d_cns_dense.p, n_words * 4, st);
+    const uint32_t *wn = (const uint32_t *)d2h(nullptr, d_cns_wdense.p, n_wins * 8, st);
+    std::vector<const PathItem *> walks(np, nullptr);
+    for (size_t p = 0; p < np; p++)
+        if (res.cns[p].err && !bad_pile[p]) {   // declined: this pile's walk alone, for the host routine
+            walks[p] = (const PathItem *)d2h(nullptr, d_path.p + piles[p].path_off, (size_t)piles[p].path_len * sizeof(PathItem), st);
+            stats.walk_d2h_bytes += (size_t)piles[p].path_len * sizeof(PathItem);
+        }
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    stats.cns_d2h_bytes += n_words * 4 + n_wins * 8;
+    for (size_t p = 0; p < np; p++) {
+        MainPile &M = *mp[p];
+        const CnsOutDev &O = res.cns[p];
+        if (O.err) {
+            if (bad_pile[p]) continue;
+            if (O.err != kCnsErrHook) fprintf(stderr, "[ndgpu] cns_windows: a walk of %u items left to the host routine (error word %u)\n", piles[p].path_len, O.err);
+            unpack_walk(walks[p], piles[p].path_len, M);
+            stats.cns_declined++;
+            continue;
+        }
+        if (!bad_pile[p]) {
+            M.cns_words.assign(w, w + O.len);
+            M.cns_windows.assign(wn, wn + 2 * (size_t)O.n_win);
+            const uint32_t counts[5] = {O.len, O.uncorrected_len, O.lstrip, O.rstrip, O.lqseq_total_length};
+            memcpy(M.cns_counts, counts, sizeof(counts));
+            M.cns_ready = true;
+            stats.cns_jobs++;
+            stats.cns_regions += O.n_win;
+        }
+        w += O.len, wn += 2 * (size_t)O.n_win;
+    }
+    if (trace_on())
+        fprintf(stderr, "[ndgpu trace] cns_windows %zu walks | K20 %.3f ms | %llu words, %llu windows, %zu declined | automaton stepped through %llu items (%.1f %% skipped idle)\n",
+                np, ms(kEvCnsBegin, kEvCnsEnd), (unsigned long long)n_words, (unsigned long long)n_wins, n_declined, (unsigned long long)visited,
+                n_words ? 100.0 * (double)(n_words - visited) / (double)n_words : 0.0);
+}
+
+// The batched entry's walks: the callers' steps go up as PathItems, K20 and its gather run as in run_main, the records come down,
+// then the dense words and windows at exact size.  A declined walk keeps done == false.
+void DeviceAligner::run_cns(CnsReq *reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    const State::Phase phase(S);
+    hipStream_t st = S.stream;
+    constexpr size_t kCnsSliceJobs = 4096, kCnsSliceItems = (size_t)32 << 20;
+    std::vector<PathItem> items;
+    CnsPlan C;
+    std::vector<CnsOutDev> outs;
+    for (size_t a = 0; a < n;) {
+        items.clear(), C.jobs.clear();
+        C.win_slots = 0;
+        size_t b = a;
+        for (; b < n && b - a < kCnsSliceJobs; b++) {
+            const CnsReq &rq = reqs[b];
+            if (b > a && items.size() + rq.n > kCnsSliceItems) break;
+            CnsJobDev J;
+            memset(&J, 0, sizeof(J));
+            J.path_off = items.size();
+            J.n = (uint32_t)rq.n;
+            J.win_off = C.win_slots;
+            J.win_cap = cns_win_cap(rq.n);
+            J.min_cov = rq.min_cov;
+            J.lq_max_len = rq.lq_max_len;
+            J.decline = cns_decline_hook() ? 1u : 0u;
+            C.win_slots += J.win_cap;
+            C.jobs.push_back(J);
+            for (size_t k = 0; k < rq.n; k++) {
+                const PathStep &s = rq.steps[k];
+                PathItem it;
+                it.tag = s.base == 4 ? 4u : tag_pack(s.t_pos, 0u, s.base);
+                it.link = s.link, it.cov = s.cov;
+                items.push_back(it);
+            }
+        }
+        const size_t m = b - a;
+        S.d_cns_jobs.reserve(m);
+        S.d_cns_out.reserve(m);
+        S.d_path.reserve(items.size() + 1);
+        S.d_cns_words.reserve(items.size() + 1);
+        S.d_cns_dense.reserve(items.size() + 1);
+        S.d_cns_wins.reserve(2 * C.win_slots + 2);
+        S.d_cns_wdense.reserve(2 * C.win_slots + 2);
+        S.h2d(S.d_cns_jobs.p, C.jobs.data(), m * sizeof(CnsJobDev), st);
+        S.h2d(S.d_path.p, items.data(), items.size() * sizeof(PathItem), st);
+        S.launch_cns(C, nullptr, S.d_path.p);
+        HIP_CHECK(hipGetLastError());
+        outs.resize(m);
+        S.d2h(outs.data(), S.d_cns_out.p, m * sizeof(CnsOutDev), st);
+        S.sync_drain(st);
+        S.stats.cns_ms += S.ms(State::kEvCnsBegin, State::kEvCnsEnd);
+        uint64_t n_words = 0, n_wins = 0;
+        for (const CnsOutDev &O : outs)
+            if (!O.err) n_words += O.len, n_wins += O.n_win;
+        S.reserve_down(n_words * 4 + n_wins * 8 + 1024, st);
+        const uint32_t *w = (const uint32_t *)S.d2h(nullptr, S.d_cns_dense.p, n_words * 4, st);
+        const uint32_t *wn = (const uint32_t *)S.d2h(nullptr, S.d_cns_wdense.p, n_wins * 8, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        S.stats.cns_d2h_bytes += m * sizeof(CnsOutDev) + n_words * 4 + n_wins * 8;
+        for (size_t i = 0; i < m; i++) {
+            CnsReq &rq = reqs[a + i];
+            const CnsOutDev &O = outs[i];
+            rq.done = !O.err;
+            if (O.err) {
+                S.stats.cns_declined++;
+                continue;
+            }
+            rq.words.assign(w, w + O.len);
+            rq.wins.assign(wn, wn + 2 * (size_t)O.n_win);
+            const uint32_t counts[5] = {O.len, O.uncorrected_len, O.lstrip, O.rstrip, O.lqseq_total_length};
+            memcpy(rq.counts, counts, sizeof(counts));
+            w += O.len, wn += 2 * (size_t)O.n_win;
+            S.stats.cns_jobs++;
+            S.stats.cns_regions += O.n_win;
+        }
+        S.drain();
+        if (trace_on())
+            fprintf(stderr, "[ndgpu trace] cns_windows %zu walks (batched entry) | K20 %.3f ms | %llu words, %llu windows\n", m,
+                    S.ms(State::kEvCnsBegin, State::kEvCnsEnd), (unsigned long long)n_words, (unsigned long long)n_wins);
+        a = b;
+    }
 }
 
 void DeviceAligner::run_main(MainPile **mp, size_t np) {
@@ -2040,7 +2266,13 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     S.stats.cells_msa += plan.cells;
     S.stats.piles += np;
     S.upload_plan(plan);
-    MsaResult res = S.count_and_score(plan, cov);
+    bool want_cns = np > 0;   // K20 takes the walks when every pile of the launch asks (the engine asks under NDGPU_CNS_DEVICE=1)
+    for (size_t p = 0; p < np; p++) {
+        want_cns = want_cns && mp[p]->want_cns;
+        mp[p]->cns_ready = false;
+    }
+    const CnsPlan cns = want_cns ? S.plan_cns(plan, mp) : CnsPlan();
+    MsaResult res = S.count_and_score(plan, cov, want_cns ? &cns : nullptr);
     piles.swap(res.piles);
     g_prof.m_msa += (tp[4] = wall_ns()) - tp[3];
     if (res.herr[0]) {
@@ -2048,7 +2280,8 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
         abort();
     }
     S.tally_main(plan, L.bad_pile, mp, tp);
-    unpack_paths(piles, res.hpath, L.bad_pile, mp, S.host_threads);
+    if (want_cns) S.fetch_cns(cns, res, L.bad_pile, mp);
+    else unpack_paths(piles, res.hpath, L.bad_pile, mp, S.host_threads);
     g_prof.m_post += wall_ns() - tp[4];
 }
 

@@ -1773,6 +1773,197 @@ __global__ __launch_bounds__(64) void bt_emit_kernel(const PileDev *__restrict__
     } while (g != kTagHead && (uint32_t)tag_tpos(g) >= c0);
 }
 
+// ---- K20: consensus words and low-quality windows of the walk -------------------------------------------------------------------
+// The device form of cns_windows_host (nd_cns.h; generate_cns_from_best_score's loop, lib/nextcorrect.c:1907-1982): one wavefront per
+// walk, 64 PathItems a chunk.  What does not depend on the window state is a lane's own: pqv, the character and its case, the index
+// p among the non-gap items (a running base + the popcount of the lower non-gap lanes), "pos differs from the previous non-gap
+// item's" and hq, the run of pqv > 40 ending at the item (both carried over the chunk edge); the five counters are popcounts and
+// runs of the chunk's ballots.  The chunk's words are stored at p and handed over (fence + wavefront barrier) BEFORE the window
+// automaton runs over the chunk: the window rule reads pos at earlier indices -- lq_s, lq_e and the ++lq_s loop up to p - 4 -- which
+// may lie in this chunk or thousands of items back.
+//
+// The automaton (qv, lq_l, lq, lq_s, lq_e) is sequential by contract (whether an item joins depends on the running mean), so it runs
+// wave-uniform, statement for statement in the reference's order; an item's pqv comes out of its lane by readlane at a uniform
+// index, its hq > 4 and pos-differs bits out of ballots, so the scalar unit carries the loop and no LDS round trip is paid.
+//
+// The skip.  In the state lq == 0, qv == 0, lq_l == 0, lq_s == -1 ("idle": the start, and what rule 1 and an emission leave):
+//   * rule 1 (hq > 4 && lq_e - lq_s < 4) assigns qv = lq_l = lq = 0, lq_s = -1: the values they have; lq_e stays in either case;
+//   * the join needs (0 + pqv) / (0 + 1) < 40, that is pqv < 40;
+//   * both else-if branches need lq != 0;
+//   * the character, the counters and hq do not read the state.
+// So an item with pqv >= 40 leaves the idle state as it is, and from that state -- and only from exactly that state -- the loop goes
+// to the next set bit of ballot(non-gap && pqv < 40), or to the next chunk.
+//
+// Windows.  A recorded emission at p needs a window of more than 8 indices (lq_e - lq_s + 1 > 8) that ended more than 16 before p;
+// it leaves the idle state, so the next window starts at a join behind p, is longer than 8 and ends more than 16 before its own
+// emission: recorded emissions lie at least 25 indices apart, the first at p >= 25, and a walk of `len` non-gap items has at most
+// len / 24 + 1.  win_cap is that of the walk's capacity in items; a slice that still fills sets kCnsErrWindows.
+__device__ __forceinline__ unsigned long long lanes_lt(int lane) { return (1ull << lane) - 1ull; }  // bits 0..lane-1
+__device__ __forceinline__ uint32_t cns_uniform_load(const uint32_t *p) {  // one address for the wavefront: the value as a scalar
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)*p);
+}
+
+__global__ __launch_bounds__(64) void cns_windows_kernel(const CnsJobDev *__restrict__ jobs, const PileDev *__restrict__ piles,
+                                                          const PathItem *__restrict__ path, uint32_t *words, uint32_t *wins,
+                                                          CnsOutDev *__restrict__ out) {
+    const CnsJobDev J = jobs[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    uint64_t path_off = J.path_off;
+    uint32_t n = J.n;
+    if (piles) {
+        path_off = piles[J.pile].path_off;
+        n = piles[J.pile].path_len;
+    }
+    CnsOutDev O;
+    O.len = O.uncorrected_len = O.lstrip = O.rstrip = O.lqseq_total_length = O.n_win = O.err = O.visited = 0;
+    if (J.decline) O.err = kCnsErrHook;
+    else if (n >= (1u << 30) || (piles && n > J.n)) O.err = kCnsErrLen;   // (piles given: J.n is the capacity of the walk's slice)
+    if (O.err) {
+        if (lane == 0) out[blockIdx.x] = O;
+        return;
+    }
+    const PathItem *src = path + path_off;
+    uint32_t *W = words + path_off;
+    uint32_t *WN = wins + 2u * J.win_off;
+    const unsigned long long lt = lanes_lt(lane), le = lanes_le(lane);
+    int pbase = 0;                      // non-gap items in front of the chunk
+    int carry_hq = 0, seen_upper = 0;   // the run of pqv > 40 that ends at the chunk's edge; an upper-case base was seen
+    uint32_t carry_pos = 0xffffffffu;   // pos of the last non-gap item in front of the chunk
+    int qv = 0, lq_l = 0, lq = 0, lq_s = -1, lq_e = -1;
+    uint32_t last_start = 0, err = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u) {   // (trip bound: n / 64 + 1)
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool valid = i < n;
+        PathItem it;
+        it.tag = 4u, it.link = 0, it.cov = 0;
+        if (valid) it = src[i];
+        const uint32_t base = it.tag & 7u;
+        const bool nongap = valid && base != 4u;
+        if (wave_ballot(nongap && it.cov == 0)) {  // (a column on the walk is covered by the seed at least)
+            err |= kCnsErrCov;
+            break;
+        }
+        const unsigned long long ng = wave_ballot(nongap);
+        if (!ng) continue;
+        const int cov = (int)it.cov;
+        const int pqv = nongap ? 100 * (int)it.link / cov : 0;
+        const uint32_t pos = (uint32_t)tag_tpos(it.tag);
+        const int p = pbase + __popcll(ng & lt);
+        const unsigned long long before = ng & lt;
+        const uint32_t ppos = __shfl(pos, before ? 63 - __clzll((long long)before) : lane);
+        const bool pdif = nongap && (before ? ppos != pos : carry_pos != pos);
+        const bool low = nongap && pqv <= 40;
+        const unsigned long long lowm = wave_ballot(low);
+        int hq = 0;
+        if (nongap && !low) {
+            const unsigned long long m = lowm & lt;
+            hq = m ? __popcll(ng & le & ~lanes_le(63 - __clzll((long long)m))) : carry_hq + __popcll(ng & le);
+        }
+        const unsigned long long hq4m = wave_ballot(nongap && hq > kCnsLqMinLength / 2);
+        const unsigned long long lt40m = wave_ballot(nongap && pqv < 40);
+        const unsigned long long pdm = wave_ballot(pdif);
+        const bool upper = nongap && cov > J.min_cov && pqv > 20;
+        const unsigned long long upm = wave_ballot(upper), lowerm = ng & ~upm;
+        if (nongap) {
+            const uint32_t ch = (uint32_t)(0x4d4d4e2d43475441ull >> (8u * base)) & 0xffu;   // "ATGC-NMM"
+            W[p] = pos << 8 | (upper ? ch : ch | 0x20u);
+        }
+        // the counters: popcounts, and the lower-case runs at either end
+        O.lqseq_total_length += (uint32_t)__popcll(lowm);
+        O.uncorrected_len += (uint32_t)__popcll(lowerm);
+        if (upm) {
+            O.lstrip = (uint32_t)__popcll(lowerm & ~lanes_le(63 - __clzll((long long)upm)));
+            if (!seen_upper) O.rstrip += (uint32_t)__popcll(lowerm & lanes_lt(__builtin_ctzll(upm)));
+            seen_upper = 1;
+        } else {
+            O.lstrip += (uint32_t)__popcll(lowerm);
+            if (!seen_upper) O.rstrip += (uint32_t)__popcll(lowerm);
+        }
+        carry_hq = lowm ? __popcll(ng & ~lanes_le(63 - __clzll((long long)lowm))) : carry_hq + __popcll(ng);
+        carry_pos = (uint32_t)__builtin_amdgcn_readlane((int)pos, 63 - __clzll((long long)ng));
+        // hand-over: the automaton reads words other lanes wrote, of this chunk and of earlier ones -- fence + wavefront barrier
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+        unsigned long long todo = ng;
+        while (todo) {   // (trip bound: 64, a bit leaves `todo` every turn)
+            unsigned long long cand = todo;
+            if (!lq && !qv && !lq_l && lq_s == -1) {   // idle: nothing happens before the next item with pqv < 40 (see above)
+                cand &= lt40m;
+                if (!cand) break;
+            }
+            const int L = __builtin_ctzll(cand);
+            todo &= ~lanes_le(L);   // (the items skipped and this one)
+            O.visited++;
+            const int pq = __builtin_amdgcn_readlane(pqv, L);
+            const int pp = pbase + __popcll(ng & lanes_lt(L));
+            const bool pd = (pdm >> L) & 1ull;
+            if (((hq4m >> L) & 1ull) && lq_e - lq_s < kCnsLqMinLength / 2) {
+                qv = lq_l = lq = 0;
+                lq_s = -1;
+            }
+            if ((qv + pq) / (lq_l + 1) < 40) {
+                if (lq_s == -1) lq_s = pp;
+                lq_e = pp;
+                lq = 1;
+                lq_l++;
+                qv += pq;
+            } else if (lq && pp - lq_e > 2 * kCnsLqMinLength && pd) {
+                if (lq_e - lq_s + 1 > kCnsLqMinLength && (uint32_t)(lq_e - lq_s + 1) < J.lq_max_len) {
+                    lq_e = pp - kCnsLqMinLength - 1;
+                    lq_s = lq_s > kCnsLqMinLength ? lq_s - kCnsLqMinLength : 1;
+                    uint32_t w_end = cns_uniform_load(W + lq_s) >> 8;
+                    const uint32_t w_start = cns_uniform_load(W + lq_e) >> 8;
+                    if (O.n_win) {
+                        uint32_t trips = 0;
+                        while (w_end == last_start && lq_s < pp - 4) {
+                            if (++trips > n) {   // (cannot happen: lq_s grows towards pp - 4 < n)
+                                err |= kCnsErrTrips;
+                                break;
+                            }
+                            w_end = cns_uniform_load(W + ++lq_s) >> 8;
+                        }
+                    }
+                    if (O.n_win < J.win_cap) {
+                        if (lane == 0) WN[2u * O.n_win] = w_start, WN[2u * O.n_win + 1u] = w_end;
+                    } else err |= kCnsErrWindows;
+                    O.n_win++;
+                    last_start = w_start;
+                }
+                qv = lq_l = lq = 0;
+                lq_s = -1;
+            } else if (lq && pd) {
+                qv = lq_l = 0;
+            }
+        }
+        pbase += __popcll(ng);
+    }
+    O.len = (uint32_t)pbase;
+    O.err = err;
+    if (lane == 0) out[blockIdx.x] = O;
+}
+
+// Walk b's words and windows into the dense buffers: at the sums of the lengths / window counts of the walks in front of it
+// (exclusive; a declined walk counts as empty), which every wavefront adds up for itself.
+__global__ __launch_bounds__(64) void cns_gather_kernel(const CnsJobDev *__restrict__ jobs, const PileDev *__restrict__ piles,
+                                                         const CnsOutDev *__restrict__ out, const uint32_t *__restrict__ words,
+                                                         const uint32_t *__restrict__ wins, uint32_t *__restrict__ dense_words,
+                                                         uint32_t *__restrict__ dense_wins) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    unsigned long long sw = 0, sn = 0;
+    for (uint32_t j = lane; j < b; j += 64u)
+        if (!out[j].err) sw += out[j].len, sn += out[j].n_win;
+    for (int m = 32; m; m >>= 1) {
+        sw += __shfl_xor(sw, m);
+        sn += __shfl_xor(sn, m);
+    }
+    const CnsOutDev O = out[b];
+    if (O.err) return;
+    const CnsJobDev J = jobs[b];
+    const uint64_t path_off = piles ? piles[J.pile].path_off : J.path_off;
+    for (uint32_t k = lane; k < O.len; k += 64u) dense_words[sw + k] = words[path_off + k];
+    for (uint32_t k = lane; k < 2u * O.n_win; k += 64u) dense_wins[2ull * sn + k] = wins[2ull * J.win_off + k];
+}
+
 // ---- K11 -------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void extract_kernel(const PileDev *__restrict__ piles,
                                                       const ReadDev *__restrict__ reads,
@@ -1989,6 +2180,14 @@ void launch_score_backtrack(const K10Args &a, const SegItem *items_small, int n_
         hipLaunchKernelGGL(bt_emit_kernel, dim3((unsigned)((n_all + 63) / 64)), dim3(64), 0, st, a.piles, items_all, n_all, a.coverage,
                            a.cell_base, a.cell_best_pp, a.cell_best_link, a.seg_len, bt_entry, bt_off, path);
     }
+}
+
+void launch_cns_windows(const CnsJobDev *jobs, const PileDev *piles, const PathItem *path, uint32_t *words, uint32_t *wins, CnsOutDev *out,
+                        uint32_t *dense_words, uint32_t *dense_wins, int n, void *stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(cns_windows_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, path, words, wins, out);
+    hipLaunchKernelGGL(cns_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, out, words, wins, dense_words,
+                       dense_wins);
 }
 
 void launch_extract(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const uint32_t *tags,

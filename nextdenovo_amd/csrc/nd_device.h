@@ -298,6 +298,31 @@ struct PathItem {           // one visited cell of the best_pp walk (origin firs
     uint16_t cov;           // coverage of the column
 };
 
+// ---- K20: consensus words and low-quality windows of the walk (cns_windows_kernel, msa_kernels.hip; the rule: nd_cns.h) ----
+struct CnsJobDev {          // one walk
+    uint64_t path_off;      // its first PathItem, and its first word in the per-walk word slices (piles given: taken from PileDev)
+    uint64_t win_off;       // its first window slot (two words a window: start, end)
+    uint32_t n;             // items of the walk (piles given: the capacity of its slice; the length is PileDev::path_len)
+    uint32_t win_cap;       // window slots: (capacity in items) / 24 + 1, see the kernel
+    int32_t min_cov;
+    uint32_t lq_max_len;
+    uint32_t pile;          // piles given: the walk's PileDev
+    uint32_t decline;       // test hook: the kernel leaves the walk with kCnsErrHook
+};
+struct CnsOutDev {          // what the host reads per walk: 32 bytes
+    uint32_t len, uncorrected_len, lstrip, rstrip, lqseq_total_length;
+    uint32_t n_win;
+    uint32_t err;           // kCnsErr* bits; nonzero: declined, the host routine takes the walk
+    uint32_t visited;       // items the window automaton stepped through (the rest it skipped from its idle state)
+};
+constexpr int kCnsLqMinLength = 8;   // lq_min_length (lib/nextcorrect.c:1890)
+enum : uint32_t { kCnsErrWindows = 1u, kCnsErrTrips = 2u, kCnsErrCov = 4u, kCnsErrHook = 8u, kCnsErrLen = 16u };
+// K20 over jobs [0, n): words[path_off + p] = pos << 8 | char, wins[2 (win_off + k)] = start, [.. + 1] = end, out[i].  piles != nullptr: job i reads
+// path_off and n from piles[jobs[i].pile] (the walk where bt_emit left it).  Then the gather: job i's words to dense_words at the sum of
+// the lengths in front of it, its windows to dense_wins at the sum of the window counts (declined walks count as empty).
+void launch_cns_windows(const CnsJobDev *jobs, const PileDev *piles, const PathItem *path, uint32_t *words, uint32_t *wins, CnsOutDev *out,
+                        uint32_t *dense_words, uint32_t *dense_wins, int n, void *stream);
+
 struct ColBlock {           // work item of the link-counting kernel
     uint32_t pile;
     uint32_t col0;

@@ -103,10 +103,21 @@ struct MainPile {
     unsigned min_len_aln = 500, max_cov_aln = 130;
     int factor = 3;
     int hq = 0;
+    // optional: the engine would take the walk's consensus words and low-quality windows (cns_windows_host of nd_cns.h) instead of
+    // the walk itself
+    bool want_cns = false;
+    int min_cov = 0;
+    unsigned lq_max_len = 0;
     // outputs
     std::vector<PathStep> path;
     unsigned n_aligned = 0;              // reads that entered the MSA (incl. the seed)
     int slot = -1;                       // backend-private handle, valid until end_batch()
+    // optional output, where want_cns and the backend offers it: cns_words[p] = pos << 8 | char of the p-th non-gap step, cns_windows =
+    // (start, end) pairs in emission order, cns_counts = len, uncorrected_len, lstrip, rstrip, lqseq_total_length; `path` stays empty.
+    // A backend that does not fill these leaves cns_ready false, and the engine takes the walk.
+    bool cns_ready = false;
+    std::vector<uint32_t> cns_words, cns_windows;
+    uint32_t cns_counts[5] = {0, 0, 0, 0, 0};
 };
 
 // Candidate strings of one low-quality region (lib/nextcorrect.c:373-404).

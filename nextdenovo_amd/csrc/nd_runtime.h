@@ -83,6 +83,25 @@ struct RuntimeStats {
     double poa_graph_ms = 0;             // their HIP-event time
     uint64_t poa_h2d_bytes = 0;          // what run_poa sent to the device
     uint64_t poa_d2h_bytes = 0;          // and what it brought back
+    // consensus words and low-quality windows of the walk on the device (K20)
+    uint64_t cns_jobs = 0;               // walks K20 finished (run_main's piles, run_cns's jobs)
+    uint64_t cns_declined = 0;           // walks it left to the host routine (an error word, or the hook NDGPU_CNS_DECLINE)
+    uint64_t cns_launches = 0;           // launches of K20 (each with its gather)
+    uint64_t cns_regions = 0;            // windows it emitted
+    double cns_ms = 0;                   // HIP-event time of K20 and its gather
+    uint64_t cns_d2h_bytes = 0;          // result records, dense words and windows brought back
+    uint64_t walk_d2h_bytes = 0;         // bytes of the walks (PathItems) run_main brought back, with or without K20
+};
+
+// One walk of the batched entry ndgpu_cns_windows_batch (DeviceAligner::run_cns): what cns_windows_host (nd_cns.h) returns for it.
+struct CnsReq {
+    const PathStep *steps = nullptr;
+    size_t n = 0;
+    int min_cov = 0;
+    unsigned lq_max_len = 0;
+    bool done = false;
+    std::vector<uint32_t> words, wins;   // pos << 8 | char; (start, end) pairs
+    uint32_t counts[5] = {0, 0, 0, 0, 0};  // len, uncorrected_len, lstrip, rstrip, lqseq_total_length
 };
 
 // Thrown when a device (or pinned host) allocation fails for lack of memory.  The C ABI catches it, releases the
@@ -121,6 +140,7 @@ class DeviceAligner {
     // offer_rank: piles that ask for it (ExtractPile::rank) get their regions ranked by K14 behind K11
     void run_extract(ExtractPile **piles, size_t n, bool offer_rank = true);
     void run_rank(RankReq *reqs, size_t n);   // the batched entry's problems: one pool up, one copy back
+    void run_cns(CnsReq *reqs, size_t n);     // the batched entry's walks through K20; req.done = false: declined, the host routine takes it
     void run_lq(LqRound **rounds, size_t n);
     // req.done = false: declined, the caller's host path takes it.  form 0: NDGPU_POA_RESIDENT decides; 1: resident graphs (K19);
     // 2: K13's rounds with the graphs on the host
@@ -173,6 +193,7 @@ class HipBackend : public Backend {
         dev_.run_extract(piles, n, !host_rank);
     }
     void run_rank(RankReq *reqs, size_t n) { dev_.run_rank(reqs, n); }
+    void run_cns(CnsReq *reqs, size_t n) { dev_.run_cns(reqs, n); }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
     void run_align_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) { dev_.align_batch_runs(jobs, n, res, runs); }
     bool run_lq(LqRound **rounds, size_t n) override {
