@@ -185,6 +185,40 @@ typedef struct ndgpu_cns_result {
 } ndgpu_cns_result;
 int ndgpu_cns_windows_batch(const ndgpu_cns_job *jobs, int n, int flags, ndgpu_cns_result *res, uint32_t **bases, uint32_t **regions);
 
+/* The loop behind a main walk in each of its three forms, for many walks in one call.  mode 0: raw reads -- exactly what
+ * ndgpu_cns_windows_batch answers for the job's first five fields.  mode 1: HiFi reads (generate_cns_from_best_score_kmer, reference
+ * lib/nextcorrect.c:1807-1860): the counters len and lqseq_total_length (the other three stay 0), words and windows as above (a window
+ * may have been widened by a merge), ok: the verdict of :1864-1865; `seed` is the seed's ASCII bases, seed_len of them, read at every
+ * non-gap step's t_pos through the engine's table (ACGT in either case 0..3 in the walk's numbering, N 5, M 6, anything else 4).
+ * mode 2: -fast (generate_cns_from_best_score_fast, :1724-1777): len and identity as the engine reports them, lq_total_len, and len'
+ * bytes from (*seqs)[seq_off] on, len' = seq_len: the chosen stretch of the emitted string, reversed; ok = 1; lq_max_len,
+ * min_error_corrected_ratio and the seed are not read.  *bases, *regions as above; *seqs is one malloc'd byte block of exact size (free()
+ * it; one byte when empty), the strings one behind the other without padding.  flags bit 0: the engine's host routines.
+ * Returns 0; -2, with nothing computed or written, in the cases of ndgpu_cns_windows_batch, for a mode above 2, for mode 1 with a NULL
+ * seed, and for mode 1 with a non-gap step whose t_pos >= seed_len; < 0 when no device can be used.  n = 0 is valid. */
+typedef struct ndgpu_cns_walk_job {
+    const ndgpu_walk_step *steps;
+    uint32_t n;
+    int32_t min_cov;
+    uint32_t lq_max_len;
+    float min_error_corrected_ratio;
+    int32_t mode;
+    uint32_t seed_len;
+    const char *seed;
+} ndgpu_cns_walk_job;
+typedef struct ndgpu_cns_walk_result {
+    uint32_t len, uncorrected_len, lstrip, rstrip, lqseq_total_length;
+    int32_t ok;
+    uint32_t n_regions, pad_;
+    uint64_t base_off, region_off;
+    uint32_t lq_total_len, seq_len;   /* mode 2 */
+    float identity;
+    uint32_t pad2_;
+    uint64_t seq_off;
+} ndgpu_cns_walk_result;
+int ndgpu_cns_walk_batch(const ndgpu_cns_walk_job *jobs, int n, int flags, ndgpu_cns_walk_result *res, uint32_t **bases, uint32_t **regions,
+                         char **seqs);
+
 /* align() / align_hq() for many pairs in one call.  The pairs share the launches of the forward and traceback kernels; a further kernel
  * pair run-length-encodes every alignment's columns on the device, so that what comes back per job is its summary and its CIGAR, not a
  * byte per column.  res[i]: status (0: none -- align() would leave its argument untouched, which includes a sequence with a byte
@@ -324,6 +358,21 @@ typedef struct {
 } ndgpu_stats;
 void ndgpu_get_stats(ndgpu_stats *out);
 void ndgpu_reset_stats(void);
+
+/* The HiFi and -fast forms of the loop behind the main walk on the device (ndgpu_cns_walk_batch in modes 1 and 2; the engine's piles
+ * with NDGPU_CNS_HIFI=1 / NDGPU_CNS_FAST=1).  Counters of their own: ndgpu_stats keeps its layout, its cns_* fields stay the raw-read
+ * form's and its walk_d2h_bytes goes on counting every walk that does come down.  ndgpu_reset_stats clears these too. */
+typedef struct {
+    uint64_t hifi_jobs;             /* HiFi walks the device finished */
+    uint64_t hifi_declined;         /* ... offered to the kernel and left to the host routine */
+    uint64_t hifi_regions;          /* windows it emitted (a merge emits none) */
+    uint64_t fast_jobs;             /* -fast walks the device finished */
+    uint64_t fast_declined;
+    uint64_t launches;              /* launches of the kernel */
+    double ms;                      /* its HIP-event time */
+    uint64_t d2h_bytes;             /* result records (32 bytes a walk), words, windows and strings brought back */
+} ndgpu_cns_mode_stats;
+void ndgpu_get_cns_mode_stats(ndgpu_cns_mode_stats *out);
 /* The device contexts keep their (grow-only) buffers between calls.  This hands them back -- for a caller that alternates
  * the consensus with another memory-hungry stage on the same device (the overlap stage of a genome-scale read set) and
  * finds that stage short of memory.  Safe to call at any time from any thread: a context that is in the middle of a batch

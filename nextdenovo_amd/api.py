@@ -52,6 +52,26 @@ class CnsResult(C.Structure):
                 ("base_off", C.c_uint64), ("region_off", C.c_uint64)]
 
 
+class CnsWalkJob(C.Structure):
+    # ndgpu_cns_walk_job
+    _fields_ = [("steps", C.c_void_p), ("n", C.c_uint32), ("min_cov", C.c_int32), ("lq_max_len", C.c_uint32),
+                ("min_error_corrected_ratio", C.c_float), ("mode", C.c_int32), ("seed_len", C.c_uint32), ("seed", C.c_char_p)]
+
+
+class CnsWalkResult(C.Structure):
+    # ndgpu_cns_walk_result
+    _fields_ = [("len", C.c_uint32), ("uncorrected_len", C.c_uint32), ("lstrip", C.c_uint32), ("rstrip", C.c_uint32),
+                ("lqseq_total_length", C.c_uint32), ("ok", C.c_int32), ("n_regions", C.c_uint32), ("pad_", C.c_uint32),
+                ("base_off", C.c_uint64), ("region_off", C.c_uint64), ("lq_total_len", C.c_uint32), ("seq_len", C.c_uint32),
+                ("identity", C.c_float), ("pad2_", C.c_uint32), ("seq_off", C.c_uint64)]
+
+
+class CnsModeStats(C.Structure):
+    # ndgpu_cns_mode_stats
+    _fields_ = [("hifi_jobs", C.c_uint64), ("hifi_declined", C.c_uint64), ("hifi_regions", C.c_uint64), ("fast_jobs", C.c_uint64),
+                ("fast_declined", C.c_uint64), ("launches", C.c_uint64), ("ms", C.c_double), ("d2h_bytes", C.c_uint64)]
+
+
 class AlnJob(C.Structure):
     # ndgpu_aln_job
     _fields_ = [("q", C.c_char_p), ("q_len", C.c_int32), ("t", C.c_char_p), ("t_len", C.c_int32), ("hq", C.c_int32)]
@@ -147,6 +167,11 @@ def _bind(lib):
     lib.ndgpu_cns_windows_batch.argtypes = [C.POINTER(CnsJob), C.c_int, C.c_int, C.POINTER(CnsResult), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_void_p)]
     lib.ndgpu_cns_windows_batch.restype = C.c_int
+    lib.ndgpu_cns_walk_batch.argtypes = [C.POINTER(CnsWalkJob), C.c_int, C.c_int, C.POINTER(CnsWalkResult), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.ndgpu_cns_walk_batch.restype = C.c_int
+    lib.ndgpu_get_cns_mode_stats.argtypes = [C.POINTER(CnsModeStats)]
+    lib.ndgpu_get_cns_mode_stats.restype = None
     lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.ndgpu_align_batch.restype = C.c_int
@@ -479,6 +504,63 @@ def cns_windows_batch(jobs, host=False):
     return [dict(len=int(r.len), uncorrected_len=int(r.uncorrected_len), lstrip=int(r.lstrip), rstrip=int(r.rstrip),
                  lqseq_total_length=int(r.lqseq_total_length), ok=bool(r.ok), bases=words[r.base_off:r.base_off + r.len],
                  regions=regs[r.region_off:r.region_off + r.n_regions]) for r in res]
+
+
+def cns_walk_batch(jobs, host=False):
+    """jobs: [(steps, min_cov, lq_max_len, min_error_corrected_ratio, mode, seed)], steps as walk_steps() makes them, mode 0 raw reads
+    (what cns_windows_batch answers), 1 HiFi reads (seed: the seed's bases as bytes, read at every non-gap step's t_pos), 2 -fast (seed
+    None) -> one dict per job through ndgpu_cns_walk_batch.  Modes 0 and 1: the keys of cns_windows_batch (mode 1 counts len and
+    lqseq_total_length alone).  Mode 2: len and identity (numpy.float32) as the engine reports them, lq_total_len, seq (bytes, the chosen
+    stretch reversed), ok True.  Every dict carries its mode.  host=True: the engine's own host routines instead of the device.
+    ValueError for what the entry refuses (-2)."""
+    import numpy as np
+    lib = load()
+    n = len(jobs)
+    if n == 0:
+        return []
+    arr = (CnsWalkJob * n)()
+    keep = []
+    for i, (steps, min_cov, lq_max_len, ratio, mode, seed) in enumerate(jobs):
+        st = np.ascontiguousarray(steps)
+        if st.dtype.itemsize != C.sizeof(WalkStep):
+            raise ValueError("steps must be records of ndgpu_walk_step (api.walk_steps)")
+        seed = None if seed is None else bytes(seed)
+        keep.append((st, seed))
+        arr[i] = CnsWalkJob(st.ctypes.data if st.size else None, int(st.size), int(min_cov), int(lq_max_len), float(ratio), int(mode),
+                            0 if seed is None else len(seed), seed)
+    res = (CnsWalkResult * n)()
+    bw, rw, sw = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    rc = lib.ndgpu_cns_walk_batch(arr, n, 1 if host else 0, res, C.byref(bw), C.byref(rw), C.byref(sw))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("ndgpu_cns_walk_batch failed (%d)" % rc)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    n_words = sum(r.len for r, j in zip(res, jobs) if j[4] != 2)
+    n_reg = sum(r.n_regions for r in res)
+    n_seq = sum(r.seq_len for r in res)
+    words = np.ctypeslib.as_array(C.cast(bw, C.POINTER(C.c_uint32)), shape=(max(1, n_words),))[:n_words].copy()
+    regs = np.ctypeslib.as_array(C.cast(rw, C.POINTER(C.c_uint32)), shape=(max(1, 2 * n_reg),))[:2 * n_reg].copy().reshape(-1, 2)
+    seqs = C.string_at(sw, n_seq)
+    libc.free(bw)
+    libc.free(rw)
+    libc.free(sw)
+    out = []
+    for r, j in zip(res, jobs):
+        if j[4] == 2:
+            out.append(dict(mode=2, len=int(r.len), identity=np.float32(r.identity), lq_total_len=int(r.lq_total_len), ok=bool(r.ok),
+                            seq=seqs[r.seq_off:r.seq_off + r.seq_len]))
+        else:
+            out.append(dict(mode=int(j[4]), len=int(r.len), uncorrected_len=int(r.uncorrected_len), lstrip=int(r.lstrip),
+                            rstrip=int(r.rstrip), lqseq_total_length=int(r.lqseq_total_length), ok=bool(r.ok),
+                            bases=words[r.base_off:r.base_off + r.len], regions=regs[r.region_off:r.region_off + r.n_regions]))
+    return out
+
+
+def cns_mode_stats() -> dict:
+    """ndgpu_cns_mode_stats: the counters of the HiFi and -fast forms on the device (K21), cleared by reset_stats()."""
+    s = CnsModeStats()
+    load().ndgpu_get_cns_mode_stats(C.byref(s))
+    return {n: getattr(s, n) for n, _ in CnsModeStats._fields_}
 
 
 def _align_call(fn, name, arr, n, host, strings):

@@ -252,6 +252,10 @@ void print_prof(int drivers, int threads_each) {  // NDGPU_PROF: the host driver
                         "%llu walks, %llu declined, %llu launches, %.3f ms\n", (unsigned long long)s.piles, (unsigned long long)s.path_items,
                 (unsigned long long)s.walk_d2h_bytes, (unsigned long long)s.cns_d2h_bytes, (unsigned long long)s.cns_jobs,
                 (unsigned long long)s.cns_declined, (unsigned long long)s.cns_launches, s.cns_ms);
+        fprintf(stderr, "[ndgpu prof] K21 since the last reset: d2h_bytes %llu, HiFi %llu walks, %llu declined, %llu windows | -fast %llu walks, "
+                        "%llu declined | %llu launches, %.3f ms\n", (unsigned long long)s.cnsw_d2h_bytes, (unsigned long long)s.cnsw_hifi_jobs,
+                (unsigned long long)s.cnsw_hifi_declined, (unsigned long long)s.cnsw_hifi_regions, (unsigned long long)s.cnsw_fast_jobs,
+                (unsigned long long)s.cnsw_fast_declined, (unsigned long long)s.cnsw_launches, s.cnsw_ms);
     }
     for (auto &a : g_prof.adv_ns) a = 0;
     g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
@@ -917,6 +921,150 @@ int ndgpu_cns_windows_batch(const ndgpu_cns_job *jobs, int n, int flags, ndgpu_c
     return 0;
 }
 
+// The loop behind a batch of walks in any of its three forms.  Mode 0 is ndgpu_cns_windows_batch itself, called for the mode-0 jobs of
+// the batch; modes 1 and 2 go through K21 (DeviceAligner::run_cns_walk) or -- flags bit 0, or a walk the kernel declines -- through
+// cns_kmer_host / cns_fast_host.  The verdict, the length and the identity are computed here from either's counters.
+int ndgpu_cns_walk_batch(const ndgpu_cns_walk_job *jobs, int n, int flags, ndgpu_cns_walk_result *res, uint32_t **bases, uint32_t **regions,
+                         char **seqs) {
+    if (n == 0) return 0;
+    if (n < 0 || !jobs || !res || !bases || !regions || !seqs) return -2;
+    size_t total = 0, seed_total = 0;
+    std::vector<ndgpu_cns_job> raw;
+    std::vector<size_t> walk_ids;
+    for (int i = 0; i < n; i++) {
+        const ndgpu_cns_walk_job &j = jobs[i];
+        if (j.n && !j.steps) return -2;
+        if (j.mode < 0 || j.mode > 2) return -2;
+        if (j.mode == 1 && !j.seed) return -2;
+        for (uint32_t k = 0; k < j.n; k++) {
+            const ndgpu_walk_step &s = j.steps[k];
+            if (s.base == 4) continue;
+            if (s.cov == 0 || s.base > 5 || s.t_pos < 0 || s.t_pos > (1 << 21) - 2) return -2;
+            if (j.mode == 1 && (uint32_t)s.t_pos >= j.seed_len) return -2;
+        }
+        if (j.mode == 0) raw.push_back(ndgpu_cns_job{j.steps, j.n, j.min_cov, j.lq_max_len, j.min_error_corrected_ratio});
+        else {
+            walk_ids.push_back((size_t)i);
+            total += j.n;
+            if (j.mode == 1) seed_total += j.seed_len;
+        }
+    }
+    // the mode-0 jobs: the existing entry's answer, word for word
+    std::vector<ndgpu_cns_result> raw_res(raw.size());
+    uint32_t *raw_bases = nullptr, *raw_regions = nullptr;
+    if (!raw.empty()) {
+        const int rc = ndgpu_cns_windows_batch(raw.data(), (int)raw.size(), flags, raw_res.data(), &raw_bases, &raw_regions);
+        if (rc != 0) return rc;
+    }
+    struct Keep {   // (frees the two blocks on every way out)
+        uint32_t *a, *b;
+        ~Keep() { free(a), free(b); }
+    } keep{raw_bases, raw_regions};
+    std::vector<PathStep> steps(total);
+    std::vector<uint8_t> codes(seed_total);
+    std::vector<CnsWalkReq> reqs(walk_ids.size());
+    for (size_t r = 0, at = 0, sat = 0; r < reqs.size(); r++) {
+        const ndgpu_cns_walk_job &j = jobs[walk_ids[r]];
+        for (uint32_t k = 0; k < j.n; k++) {
+            PathStep &d = steps[at + k];
+            d.t_pos = j.steps[k].t_pos, d.delta = 0, d.base = j.steps[k].base, d.link = j.steps[k].link, d.cov = j.steps[k].cov;
+        }
+        CnsWalkReq &rq = reqs[r];
+        rq.steps = steps.data() + at, rq.n = j.n, rq.min_cov = j.min_cov, rq.mode = j.mode;
+        at += j.n;
+        if (j.mode == 1) {
+            for (uint32_t k = 0; k < j.seed_len; k++) codes[sat + k] = cns_base_code((unsigned char)j.seed[k]);
+            rq.seed_codes = codes.data() + sat, rq.seed_len = j.seed_len;
+            sat += j.seed_len;
+        }
+    }
+    if (!(flags & 1) && !reqs.empty()) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+            fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_cns_walk_batch runs on the device unless flags bit 0 is set\n");
+            return -1;
+        }
+        std::vector<std::pair<size_t, size_t>> todo{{0, reqs.size()}};   // (out of device memory: the range is halved until it fits)
+        while (!todo.empty()) {
+            const auto [a, b] = todo.back();
+            todo.pop_back();
+            try {
+                HipBackend be(0, 1);
+                be.run_cns_walk(reqs.data() + a, b - a);
+            } catch (const DeviceOom &) {
+                DeviceAligner::context(0).release_memory();
+                DeviceAligner::forget_sizes();
+                if (b - a <= 1) return -3;
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    host_each(reqs.size(), effective_cpus() <= 1 || reqs.size() <= 1, effective_cpus(), reqs.size(), false, [&](size_t r) {
+        CnsWalkReq &rq = reqs[r];
+        if (rq.done) return;
+        if (rq.mode == 1) {
+            std::vector<CnsWindow> wins;
+            CnsCounts c;
+            cns_kmer_host(rq.steps, rq.n, rq.seed_codes, rq.min_cov, rq.words, wins, c);
+            rq.wins.clear();
+            for (const CnsWindow &w : wins) rq.wins.push_back(w.start), rq.wins.push_back(w.end);
+            rq.len = c.len, rq.lqseq_total_length = c.lqseq_total_length;
+        } else {
+            CnsFastOut o;
+            cns_fast_host(rq.steps, rq.n, rq.min_cov, o);
+            rq.lq_m = o.lq_m, rq.hq_m = o.hq_m, rq.lqseq_total_length = o.lq_total_len, rq.len = o.out_len;
+            rq.seq.swap(o.seq);
+        }
+    });
+    size_t n_words = 0, n_wins = 0, n_seq = 0;
+    for (const ndgpu_cns_result &r : raw_res) n_words += r.len, n_wins += 2 * (size_t)r.n_regions;
+    for (const CnsWalkReq &rq : reqs) n_words += rq.words.size(), n_wins += rq.wins.size(), n_seq += rq.seq.size();
+    uint32_t *bw = (uint32_t *)malloc(std::max<size_t>(1, n_words) * sizeof(uint32_t));
+    uint32_t *rw = (uint32_t *)malloc(std::max<size_t>(1, n_wins) * sizeof(uint32_t));
+    char *sw = (char *)malloc(std::max<size_t>(1, n_seq));
+    if (!bw || !rw || !sw) {
+        free(bw), free(rw), free(sw);
+        return -3;
+    }
+    size_t at_w = 0, at_r = 0, at_s = 0, i_raw = 0, i_walk = 0;
+    for (int i = 0; i < n; i++) {
+        ndgpu_cns_walk_result &o = res[i];
+        memset(&o, 0, sizeof(o));
+        if (jobs[i].mode == 0) {
+            const ndgpu_cns_result &r = raw_res[i_raw++];
+            o.len = r.len, o.uncorrected_len = r.uncorrected_len, o.lstrip = r.lstrip, o.rstrip = r.rstrip;
+            o.lqseq_total_length = r.lqseq_total_length, o.ok = r.ok, o.n_regions = r.n_regions;
+            o.base_off = at_w, o.region_off = at_r / 2;
+            if (r.len) memcpy(bw + at_w, raw_bases + r.base_off, (size_t)r.len * sizeof(uint32_t));
+            if (r.n_regions) memcpy(rw + at_r, raw_regions + 2 * r.region_off, 2 * (size_t)r.n_regions * sizeof(uint32_t));
+            at_w += r.len, at_r += 2 * (size_t)r.n_regions;
+            continue;
+        }
+        const CnsWalkReq &rq = reqs[i_walk++];
+        o.base_off = at_w, o.region_off = at_r / 2, o.seq_off = at_s;
+        if (rq.mode == 1) {
+            CnsCounts c;
+            c.len = o.len = rq.len, c.lqseq_total_length = o.lqseq_total_length = rq.lqseq_total_length;
+            o.ok = cns_kmer_verdict(c, jobs[i].min_error_corrected_ratio) ? 1 : 0;
+            o.n_regions = (uint32_t)(rq.wins.size() / 2);
+            if (!rq.words.empty()) memcpy(bw + at_w, rq.words.data(), rq.words.size() * sizeof(uint32_t));
+            if (!rq.wins.empty()) memcpy(rw + at_r, rq.wins.data(), rq.wins.size() * sizeof(uint32_t));
+            at_w += rq.words.size(), at_r += rq.wins.size();
+        } else {
+            o.len = cns_fast_len(rq.lq_m, rq.hq_m);
+            o.identity = cns_fast_identity(rq.lqseq_total_length, o.len);
+            o.lq_total_len = rq.lqseq_total_length;
+            o.seq_len = (uint32_t)rq.seq.size();
+            o.ok = 1;
+            if (!rq.seq.empty()) memcpy(sw + at_s, rq.seq.data(), rq.seq.size());
+            at_s += rq.seq.size();
+        }
+    }
+    *bases = bw, *regions = rw, *seqs = sw;
+    return 0;
+}
+
 // ---- batched global alignment: align() / align_hq() for many pairs in one call, CIGARs built on the device (K15) ----
 namespace {
 struct AlnBatchSrc {            // where job i's bases are, for the strings flag
@@ -1109,6 +1257,14 @@ void ndgpu_get_stats(ndgpu_stats *o) {
 }
 
 void ndgpu_reset_stats(void) { DeviceAligner::reset_all_stats(); }
+
+void ndgpu_get_cns_mode_stats(ndgpu_cns_mode_stats *o) {
+    if (!o) return;
+    const RuntimeStats s = DeviceAligner::total_stats();
+    o->hifi_jobs = s.cnsw_hifi_jobs, o->hifi_declined = s.cnsw_hifi_declined, o->hifi_regions = s.cnsw_hifi_regions;
+    o->fast_jobs = s.cnsw_fast_jobs, o->fast_declined = s.cnsw_fast_declined, o->launches = s.cnsw_launches;
+    o->ms = s.cnsw_ms, o->d2h_bytes = s.cnsw_d2h_bytes;
+}
 
 uint64_t ndgpu_release_memory(void) {
     size_t f0 = 0, f1 = 0, t = 0;

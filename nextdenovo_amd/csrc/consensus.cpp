@@ -573,7 +573,10 @@ class PileImpl {
         main.max_cov_aln = prm.max_cov_aln;
         main.factor = prm.read_type == 3 ? 4 : 3;  // nextcorrect.c:2147
         main.hq = prm.read_type == 3;              // align_hq for HiFi, nextcorrect.c:2269
-        main.want_cns = cns_on_device() && !prm.fast && prm.read_type != 3;
+        // which loop follows the walk, and whether the backend is asked to run it (K20 raw reads; K21 HiFi reads and -fast, which
+        // wins over HiFi here as in after_main)
+        main.cns_mode = prm.fast ? 2 : prm.read_type == 3 ? 1 : 0;
+        main.want_cns = prm.fast ? cns_fast_on_device() : prm.read_type == 3 ? cns_hifi_on_device() : cns_on_device();
         main.min_cov = (int)prm.min_cov;
         main.lq_max_len = lq_max_len;
     }
@@ -606,7 +609,39 @@ class PileImpl {
         static const bool on = getenv("NDGPU_CNS_DEVICE") != nullptr && atoi(getenv("NDGPU_CNS_DEVICE")) != 0;
         return on;
     }
+    // K21 (opt-in, DESIGN.md section 0a''''''''''): NDGPU_CNS_HIFI=1 -- read type 3, not -fast; NDGPU_CNS_FAST=1 -- -fast, any read type.
+    // Independent of NDGPU_CNS_DEVICE, which goes on meaning raw reads alone.
+    static bool cns_hifi_on_device() {
+        static const bool on = getenv("NDGPU_CNS_HIFI") != nullptr && atoi(getenv("NDGPU_CNS_HIFI")) != 0;
+        return on;
+    }
+    static bool cns_fast_on_device() {
+        static const bool on = getenv("NDGPU_CNS_FAST") != nullptr && atoi(getenv("NDGPU_CNS_FAST")) != 0;
+        return on;
+    }
     void after_main() {
+        if (main.cns_ready && main.cns_mode == 2) {  // the backend ran cns_fast's loop and scan: length and identity are ours
+            main.cns_ready = false;
+            std::string seq;
+            seq.swap(main.cns_seq);
+            fast_result(main.cns_fast[0], main.cns_fast[1], main.cns_fast[2], std::move(seq));
+            phase = PileEngine::DONE;
+            return;
+        }
+        if (main.cns_ready && main.cns_mode == 1) {  // the backend ran cns_kmer's loop: the verdict and the reversal are ours
+            std::vector<uint32_t> words, wins;
+            words.swap(main.cns_words), wins.swap(main.cns_windows);
+            main.cns_ready = false;
+            CnsCounts c;
+            c.len = main.cns_counts[0], c.lqseq_total_length = main.cns_counts[4];
+            n_aligned = main.n_aligned;
+            if (!cns_kmer_from_words(words.data(), wins.data(), wins.size() / 2, c)) {
+                finish_error(2);
+                return;
+            }
+            to_extract();
+            return;
+        }
         if (main.cns_ready) {  // the backend ran cns_from_best_score's loop: its words, windows and counters; the verdict is ours
             std::vector<uint32_t> words, wins;
             words.swap(main.cns_words), wins.swap(main.cns_windows);
@@ -730,50 +765,17 @@ class PileImpl {
         g_prof.lqstart_ns += now_ns() - t1;
     }
 
-    // lib/nextcorrect.c:1717-1784
+    // lib/nextcorrect.c:1717-1784.  The loop, the table of lower-case runs and its scan are cns_fast_host (nd_cns.h); length and identity
+    // follow here, whoever ran the loop.
     void cns_fast(const std::vector<PathStep> &path) {
-        std::string out;
-        LqReg lq[kLqRegMax];
-        int lq_i = 0;
-        const int min_cov = (int)prm.min_cov;
-        for (const PathStep &cur : path) {
-            if (cur.base != 4) {
-                if ((int)cur.cov > min_cov) {
-                    out.push_back((char)kIntToBase[cur.base]);
-                    if (lq[lq_i].end >= lq[lq_i].start + 50 || !lq_i) {
-                        if (++lq_i >= kLqRegMax) break;
-                    } else lq[lq_i].end = 0;
-                } else {
-                    out.push_back((char)tolower(kIntToBase[cur.base]));
-                    if (!lq[lq_i].end) {
-                        lq[lq_i].start = (unsigned)out.size() - 1;
-                        lq[lq_i].lqlen = 0;
-                    }
-                    lq[lq_i].end = (unsigned)out.size() - 1;
-                    lq[lq_i].lq_total_len++;
-                    lq[lq_i].lqlen++;
-                }
-            }
-        }
-        int i, lq_m = 0, hq_m = (int)lq[0].start, l = hq_m;
-        unsigned lq_total_len = lq[0].lq_total_len - lq[0].lqlen;
-        for (i = 1; i < kLqRegMax && lq[i].end; i++) {
-            if (lq[i].start - lq[i - 1].end > (unsigned)l) {
-                lq_m = (int)lq[i - 1].end + 1;
-                hq_m = (int)lq[i].start;
-                lq_total_len = lq[i].lq_total_len - lq[i].lqlen;
-                l = hq_m - lq_m;
-            }
-        }
-        if (i < kLqRegMax && (unsigned)out.size() - lq[i - 1].end > (unsigned)l) {
-            lq_m = (int)lq[i - 1].end + 1;
-            hq_m = (int)out.size();
-            lq_total_len = lq[i].lq_total_len;
-        }
-        result.len = (unsigned)(hq_m - lq_m);
-        result.identity = 1 - (float)lq_total_len / result.len;
-        result.seq = (size_t)lq_m <= out.size() ? out.substr((size_t)lq_m, result.len) : std::string();
-        std::reverse(result.seq.begin(), result.seq.end());
+        CnsFastOut o;
+        cns_fast_host(path.data(), path.size(), (int)prm.min_cov, o);
+        fast_result(o.lq_m, o.hq_m, o.lq_total_len, std::move(o.seq));
+    }
+    void fast_result(uint32_t lq_m, uint32_t hq_m, uint32_t lq_total_len, std::string &&seq) {
+        result.len = cns_fast_len(lq_m, hq_m);
+        result.identity = cns_fast_identity(lq_total_len, result.len);
+        result.seq = std::move(seq);
     }
 
     // lib/nextcorrect.c:1885-2006.  Returns false for the error_seed(2) outcome.  The loop is cns_windows_host (nd_cns.h); the verdict
@@ -799,54 +801,33 @@ class PileImpl {
         return true;
     }
 
-    // HiFi backtrack + LQ windows: lib/nextcorrect.c:1786-1883
+    // HiFi backtrack + LQ windows: lib/nextcorrect.c:1786-1883.  The loop is cns_kmer_host (nd_cns.h); the verdict and
+    // reverse_consensus_base follow it here, whoever ran the loop.
     bool cns_kmer(const std::vector<PathStep> &path) {
         const char *seed = !seq_ptr.empty() ? seq_ptr[0] : (seed_copy.empty() ? nullptr : seed_copy.c_str());
         if (!seed) {
             fprintf(stderr, "[ndgpu] HiFi consensus needs the seed sequence on the host\n");
             return false;
         }
-        const int lq_min_length = 2, dag_min_qv = 80;
-        int p = 0, qv, lq = 0, lq_s = -1, lq_e = -1, lqseq_total_length = 0;
-        const int min_cov = (int)prm.min_cov;
+        std::vector<uint32_t> words, flat;
+        std::vector<CnsWindow> wins;
+        CnsCounts c;
+        cns_kmer_host(path.data(), path.size(), CnsSeedAscii{seed}, (int)prm.min_cov, words, wins, c);
+        for (const CnsWindow &w : wins) flat.push_back(w.start), flat.push_back(w.end);
+        return cns_kmer_from_words(words.data(), flat.data(), wins.size(), c);
+    }
+    bool cns_kmer_from_words(const uint32_t *words, const uint32_t *wins, size_t n_wins, const CnsCounts &c) {
         cns = CnsData();
-        cns.bases.reserve(path.size());
         regions.clear();
-        for (const PathStep &cur : path) {
-            if (cur.base == 4) continue;
-            cns.bases.push_back(CnsBase{(unsigned)cur.t_pos, 0});
-            const int cov = cur.cov;
-            qv = 100 * (int)cur.link / cov;
-            if (cov < 4) {
-                lq = 0;
-                lq_s = -1;
-                lqseq_total_length++;
-            } else if (qv < dag_min_qv || cur.base != base_code(seed[cur.t_pos])) {
-                if (lq_s == -1) lq_s = p;
-                lq_e = p;
-                lq = 1;
-                lqseq_total_length++;
-            } else if (lq && p - lq_e > 2 * lq_min_length && cns.bases[p].pos != cns.bases[p - 1].pos) {
-                lq_e = p - lq_min_length - 1;
-                lq_s = lq_s > lq_min_length ? lq_s - lq_min_length : 1;
-                if (!regions.empty() && cns.bases[lq_s].pos >= regions.back().start) {
-                    regions.back().start = cns.bases[lq_e].pos;
-                } else {
-                    LqRegion r;
-                    r.end = cns.bases[lq_s].pos;
-                    r.start = cns.bases[lq_e].pos;
-                    regions.push_back(std::move(r));
-                }
-                lq = 0;
-                lq_s = -1;
-            }
-            cns.bases[p].base = cov > min_cov ? (char)kIntToBase[cur.base] : (char)tolower(kIntToBase[cur.base]);
-            p++;
+        cns.len = c.len;  // uncorrected_len, lstrip, rstrip stay 0 in this variant
+        if (!cns_kmer_verdict(c, prm.min_error_corrected_ratio)) {
+            // (the reference leaves the loop's bases and windows behind the refusal; nothing reads them)
+            return false;
         }
-        cns.len = (unsigned)p;  // uncorrected_len, lstrip, rstrip stay 0 in this variant
-        const float rhs = (float)cns.len * (1 - prm.min_error_corrected_ratio);
-        if (!(cns.len > 2 && (double)lqseq_total_length < cns.len * 0.8 && 0.0f < rhs)) return false;
-        std::reverse(cns.bases.begin(), cns.bases.end());
+        cns.bases.resize(c.len);
+        for (uint32_t p = 0; p < c.len; p++) cns.bases[c.len - 1 - p] = CnsBase{words[p] >> 8, (char)(words[p] & 0xffu)};  // reverse_consensus_base
+        regions.resize(n_wins);
+        for (size_t i = 0; i < n_wins; i++) regions[i].start = wins[2 * i], regions[i].end = wins[2 * i + 1];
         return true;
     }
 

@@ -355,6 +355,13 @@ enum class BufLevel { levelled, on_demand };
     X(uint32_t, d_cns_wins, device, levelled)                                                                                             \
     X(uint32_t, d_cns_dense, device, levelled)                                                                                            \
     X(uint32_t, d_cns_wdense, device, levelled)                                                                                           \
+    /* K21 (words, windows and their dense forms are K20's buffers: a launch runs one of the two): jobs, result records, a character */  \
+    /* per path slot, the dense strings that come down, the seeds' byte codes of the batched entry */                                     \
+    X(CnsWalkJobDev, d_cnsw_jobs, device, levelled)                                                                                       \
+    X(CnsWalkOutDev, d_cnsw_out, device, levelled)                                                                                        \
+    X(uint8_t, d_cnsw_chars, device, levelled)                                                                                            \
+    X(uint8_t, d_cnsw_seq, device, levelled)                                                                                              \
+    X(uint8_t, d_cnsw_seed, device, levelled)                                                                                             \
     X(RegionDev, d_regions, device, levelled)                                                                                             \
     X(char, d_strpool, device, levelled)                                                                                                  \
     X(unsigned long long, d_cursor, device, levelled)                                                                                     \
@@ -394,10 +401,14 @@ struct MsaResult {  // count_and_score: the last attempt's error words, its pile
     const PathItem *hpath = nullptr;   // (nullptr where K20 took the walks: MsaResult::cns)
     std::vector<PileDev> piles;
     std::vector<CnsOutDev> cns;        // K20's records, one per pile
+    std::vector<CnsWalkOutDev> cnsw;   // or K21's (CnsPlan::walk)
 };
 struct CnsPlan {  // plan_cns: K20's jobs of a launch (one per pile, or per walk of run_cns) and the window slots they share
     std::vector<CnsJobDev> jobs;
     uint64_t win_slots = 0;
+    bool walk = false;                 // a pile of the launch is HiFi or -fast: K21 takes the launch, its jobs are wjobs
+    std::vector<CnsWalkJobDev> wjobs;
+    bool any_hifi = false, any_fast = false;
 };
 
 struct LqSrc {  // a sequence of an LQ call's pool: packed already (words), or ASCII
@@ -524,6 +535,7 @@ struct DeviceAligner::State {
         kEvTailBegin, kEvTailEnd, kEvExtractRanked,  // K11, K13, K14, K15: around the launch in flight | behind K14 where it follows K11
         kEvPoaRows, kEvPoaAlign, kEvPoaThread, kEvPoaEnd,  // a resident POA round: before K19's rows | K13's launches | K19's thread | behind it
         kEvCnsBegin, kEvCnsEnd,                            // launch_cns: around K20 and its gather
+        kEvCnswBegin, kEvCnswEnd,                          // launch_cns_walk: around K21 and its gather
         kEvCount
     };
     hipEvent_t evs[kEvCount] = {nullptr};
@@ -615,6 +627,10 @@ struct DeviceAligner::State {
     CnsPlan plan_cns(const MsaPlan &plan, MainPile **mp);
     void launch_cns(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path);
     void fetch_cns(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp);
+    CnsPlan plan_cns_walk(const MsaPlan &plan, MainPile **mp);
+    void reserve_cns_walk(const CnsPlan &cns, size_t slots);
+    void launch_cns_walk_jobs(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path);
+    void fetch_cns_walk(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp);
     void score_pass(const MsaPlan &plan, const K10Args &k10);
     void rescue_pass(const MsaPlan &plan, const K10Args &k10);
     void k9_digest_trace(const K9Args &k9, size_t np);
@@ -763,6 +779,9 @@ RuntimeStats DeviceAligner::total_stats() {
         t.aln_batch_ms += s.aln_batch_ms;
         t.cns_jobs += s.cns_jobs; t.cns_declined += s.cns_declined; t.cns_launches += s.cns_launches; t.cns_regions += s.cns_regions;
         t.cns_ms += s.cns_ms; t.cns_d2h_bytes += s.cns_d2h_bytes; t.walk_d2h_bytes += s.walk_d2h_bytes;
+        t.cnsw_hifi_jobs += s.cnsw_hifi_jobs; t.cnsw_hifi_declined += s.cnsw_hifi_declined; t.cnsw_hifi_regions += s.cnsw_hifi_regions;
+        t.cnsw_fast_jobs += s.cnsw_fast_jobs; t.cnsw_fast_declined += s.cnsw_fast_declined; t.cnsw_launches += s.cnsw_launches;
+        t.cnsw_ms += s.cnsw_ms; t.cnsw_d2h_bytes += s.cnsw_d2h_bytes;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -1917,13 +1936,19 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
     const size_t np = piles.size();
     // what an attempt brings down: the piles, and either their walks or -- cns: K20 runs on the walks where bt_emit left them, in
     // front of the synchronisation (the retry / rescue decision needs it anyway), so that its records ride down with the piles
+    static_assert(sizeof(CnsWalkOutDev) == sizeof(CnsOutDev), "K20's and K21's records ride down in the same room");
     const size_t down_bytes = np * sizeof(PileDev) + (cns ? np * sizeof(CnsOutDev) + 256 : plan.paths * sizeof(PathItem)) + 1024;
     MsaResult R;
     R.piles.resize(np);
-    if (cns) R.cns.resize(np);
+    if (cns && cns->walk) R.cnsw.resize(np);
+    else if (cns) R.cns.resize(np);
     const void *v_cns = nullptr;
     auto walks_down = [&] {  // behind the walk: K20's records, or the walks themselves
-        if (cns) {
+        if (cns && cns->walk) {
+            launch_cns_walk_jobs(*cns, d_piles.p, d_path.p);
+            v_cns = d2h(nullptr, d_cnsw_out.p, np * sizeof(CnsWalkOutDev), st);
+            stats.cnsw_d2h_bytes += np * sizeof(CnsWalkOutDev);
+        } else if (cns) {
             launch_cns(*cns, d_piles.p, d_path.p);
             v_cns = d2h(nullptr, d_cns_out.p, np * sizeof(CnsOutDev), st);
             stats.cns_d2h_bytes += np * sizeof(CnsOutDev);
@@ -1934,6 +1959,11 @@ MsaResult DeviceAligner::State::count_and_score(const MsaPlan &plan, const CovPl
     };
     auto walks_landed = [&] {
         if (!cns) return;
+        if (cns->walk) {
+            memcpy(R.cnsw.data(), v_cns, np * sizeof(CnsWalkOutDev));
+            stats.cnsw_ms += ms(kEvCnswBegin, kEvCnswEnd);
+            return;
+        }
         memcpy(R.cns.data(), v_cns, np * sizeof(CnsOutDev));
         stats.cns_ms += ms(kEvCnsBegin, kEvCnsEnd);
     };
@@ -2232,6 +2262,224 @@ void DeviceAligner::run_cns(CnsReq *reqs, size_t n) {
     }
 }
 
+// ---- K21: the HiFi and -fast forms on the device (nd_cns.h states the rules; DESIGN.md section 0a'''''''''').  In run_main the
+// steps are K20's: plan_cns_walk -> launch_cns_walk_jobs inside count_and_score -> fetch_cns_walk.  A launch goes to K21 when every
+// pile asks and one of them is HiFi or -fast; a raw pile of such a launch is declined by the kernel (kCnsErrMode) and takes the host
+// routine -- the engine's calls carry one set of arguments, so its launches do not mix raw piles with the others.
+
+// Window slots of a HiFi walk of at most `items` items: emissions lie at least 6 indices apart (msa_kernels.hip, K21).
+static uint32_t cns_walk_win_cap(uint64_t items) { return (uint32_t)(items / 6u + 1u); }
+
+void DeviceAligner::State::reserve_cns_walk(const CnsPlan &C, size_t slots) {
+    const size_t m = C.wjobs.size();
+    d_cnsw_jobs.reserve(m);
+    d_cnsw_out.reserve(m);
+    d_cns_words.reserve(C.any_hifi ? slots + 1 : 1);
+    d_cns_dense.reserve(C.any_hifi ? slots + 1 : 1);
+    d_cns_wins.reserve(2 * C.win_slots + 2);
+    d_cns_wdense.reserve(2 * C.win_slots + 2);
+    d_cnsw_chars.reserve(C.any_fast ? slots + 1 : 1);
+    d_cnsw_seq.reserve(C.any_fast ? slots + 1 : 1);
+}
+
+CnsPlan DeviceAligner::State::plan_cns_walk(const MsaPlan &plan, MainPile **mp) {
+    CnsPlan C;
+    C.walk = true;
+    const size_t np = piles.size();
+    C.wjobs.resize(np);
+    for (size_t p = 0; p < np; p++) {
+        CnsWalkJobDev &J = C.wjobs[p];
+        memset(&J, 0, sizeof(J));
+        J.pile = (uint32_t)p;
+        J.mode = (uint32_t)mp[p]->cns_mode;
+        J.n = piles[p].n_cells / 6 + 1;   // the capacity of the walk's slice (plan_msa)
+        J.min_cov = mp[p]->min_cov;
+        J.decline = cns_decline_hook() ? 1u : 0u;
+        if (J.mode == kCnsModeHifi) {
+            J.win_off = C.win_slots;
+            J.win_cap = cns_walk_win_cap(J.n);
+            C.win_slots += J.win_cap;
+            C.any_hifi = true;
+        } else if (J.mode == kCnsModeFast) C.any_fast = true;
+    }
+    reserve_cns_walk(C, plan.paths);
+    d_cnsw_seed.reserve(1);
+    h2d(d_cnsw_jobs.p, C.wjobs.data(), np * sizeof(CnsWalkJobDev), stream);
+    return C;
+}
+
+void DeviceAligner::State::launch_cns_walk_jobs(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path) {
+    hipStream_t st = stream;
+    mark(kEvCnswBegin, st);
+    NDGPU_DBG(st, "cns_walk: %zu walks", cns.wjobs.size());
+    launch_cns_walk(d_cnsw_jobs.p, dev_piles, dev_path, d_pool.p, db_pool, d_cnsw_seed.p, d_cns_words.p, d_cns_wins.p, d_cnsw_chars.p,
+                    d_cnsw_out.p, d_cns_dense.p, d_cns_wdense.p, d_cnsw_seq.p, (int)cns.wjobs.size(), st);
+    mark(kEvCnswEnd, st);
+    stats.cnsw_launches++;
+}
+
+void DeviceAligner::State::fetch_cns_walk(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp) {
+    hipStream_t st = stream;
+    const size_t np = piles.size();
+    uint64_t n_words = 0, n_wins = 0, n_bytes = 0, walk_bytes = 0;
+    size_t n_mode[3] = {0, 0, 0}, n_declined = 0;
+    for (size_t p = 0; p < np; p++) {
+        const CnsWalkOutDev &O = res.cnsw[p];
+        n_mode[cns.wjobs[p].mode < 3u ? cns.wjobs[p].mode : 0u]++;
+        if (O.err) n_declined++, walk_bytes += ((size_t)piles[p].path_len * sizeof(PathItem) + 255) & ~(size_t)255;
+        else n_words += O.n_words, n_wins += O.n_win, n_bytes += O.n_bytes;
+    }
+    reserve_down(n_words * 4 + n_wins * 8 + n_bytes + walk_bytes + 2048, st);
+    const uint32_t *w = (const uint32_t *)d2h(nullptr, d_cns_dense.p, n_words * 4, st);
+    const uint32_t *wn = (const uint32_t *)d2h(nullptr, d_cns_wdense.p, n_wins * 8, st);
+    const char *sq = (const char *)d2h(nullptr, d_cnsw_seq.p, n_bytes, st);
+    std::vector<const PathItem *> walks(np, nullptr);
+    for (size_t p = 0; p < np; p++)
+        if (res.cnsw[p].err && !bad_pile[p]) {   // declined: this pile's walk alone, for the host routine
+            walks[p] = (const PathItem *)d2h(nullptr, d_path.p + piles[p].path_off, (size_t)piles[p].path_len * sizeof(PathItem), st);
+            stats.walk_d2h_bytes += (size_t)piles[p].path_len * sizeof(PathItem);
+        }
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipGetLastError());
+    stats.cnsw_d2h_bytes += n_words * 4 + n_wins * 8 + n_bytes;
+    for (size_t p = 0; p < np; p++) {
+        MainPile &M = *mp[p];
+        const CnsWalkOutDev &O = res.cnsw[p];
+        const uint32_t mode = cns.wjobs[p].mode;
+        if (O.err) {
+            if (bad_pile[p]) continue;
+            if (O.err != kCnsErrHook && O.err != kCnsErrMode)
+                fprintf(stderr, "[ndgpu] cns_walk: a walk of %u items left to the host routine (error word %u)\n", piles[p].path_len, O.err);
+            unpack_walk(walks[p], piles[p].path_len, M);
+            if (mode == kCnsModeHifi) stats.cnsw_hifi_declined++;
+            else if (mode == kCnsModeFast) stats.cnsw_fast_declined++;
+            continue;
+        }
+        if (!bad_pile[p] && piles[p].path_len) {   // (a walk of no items: `path` stays empty and the engine ends the pile as ever)
+            if (mode == kCnsModeHifi) {
+                M.cns_words.assign(w, w + O.n_words);
+                M.cns_windows.assign(wn, wn + 2 * (size_t)O.n_win);
+                const uint32_t counts[5] = {O.len, 0, 0, 0, O.lqseq_total_length};
+                memcpy(M.cns_counts, counts, sizeof(counts));
+                stats.cnsw_hifi_jobs++;
+                stats.cnsw_hifi_regions += O.n_win;
+            } else {
+                const uint32_t fast[4] = {O.lq_m, O.hq_m, O.lqseq_total_length, O.len};
+                memcpy(M.cns_fast, fast, sizeof(fast));
+                M.cns_seq.assign(sq, sq + O.n_bytes);
+                stats.cnsw_fast_jobs++;
+            }
+            M.cns_ready = true;
+        }
+        w += O.n_words, wn += 2 * (size_t)O.n_win, sq += O.n_bytes;
+    }
+    if (trace_on())
+        fprintf(stderr, "[ndgpu trace] cns_walk %zu walks: %zu HiFi, %zu -fast, %zu raw (left to the host) | K21 %.3f ms | %llu words, %llu windows, %llu bytes, %zu declined\n",
+                np, n_mode[1], n_mode[2], n_mode[0], ms(kEvCnswBegin, kEvCnswEnd), (unsigned long long)n_words, (unsigned long long)n_wins,
+                (unsigned long long)n_bytes, n_declined);
+}
+
+// The batched entry's walks of modes 1 and 2: steps up as PathItems, the HiFi seeds as byte codes, K21 and its gather, the records
+// down, then words, windows and strings at exact size (the strings unpadded, one behind the other).  A declined walk keeps done == false.
+void DeviceAligner::run_cns_walk(CnsWalkReq *reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    const State::Phase phase(S);
+    hipStream_t st = S.stream;
+    constexpr size_t kSliceJobs = 4096, kSliceItems = (size_t)32 << 20;
+    std::vector<PathItem> items;
+    std::vector<uint8_t> seeds;
+    CnsPlan C;
+    C.walk = true;
+    std::vector<CnsWalkOutDev> outs;
+    for (size_t a = 0; a < n;) {
+        items.clear(), seeds.clear(), C.wjobs.clear();
+        C.win_slots = 0;
+        C.any_hifi = C.any_fast = false;
+        size_t b = a;
+        for (; b < n && b - a < kSliceJobs; b++) {
+            const CnsWalkReq &rq = reqs[b];
+            if (b > a && (items.size() + rq.n > kSliceItems || seeds.size() + rq.seed_len > kSliceItems)) break;
+            CnsWalkJobDev J;
+            memset(&J, 0, sizeof(J));
+            J.path_off = items.size();
+            J.n = (uint32_t)rq.n;
+            J.mode = (uint32_t)rq.mode;
+            J.min_cov = rq.min_cov;
+            J.decline = cns_decline_hook() ? 1u : 0u;
+            if (J.mode == kCnsModeHifi) {
+                J.win_off = C.win_slots;
+                J.win_cap = cns_walk_win_cap(rq.n);
+                C.win_slots += J.win_cap;
+                J.seed_off = seeds.size();
+                J.seed_len = (uint32_t)rq.seed_len;
+                seeds.insert(seeds.end(), rq.seed_codes, rq.seed_codes + rq.seed_len);
+                C.any_hifi = true;
+            } else C.any_fast = true;
+            C.wjobs.push_back(J);
+            for (size_t k = 0; k < rq.n; k++) {
+                const PathStep &s = rq.steps[k];
+                PathItem it;
+                it.tag = s.base == 4 ? 4u : tag_pack(s.t_pos, 0u, s.base);
+                it.link = s.link, it.cov = s.cov;
+                items.push_back(it);
+            }
+        }
+        const size_t m = b - a;
+        S.d_path.reserve(items.size() + 1);
+        S.reserve_cns_walk(C, items.size());
+        S.d_cnsw_seed.reserve(seeds.size() + 1);
+        S.h2d(S.d_cnsw_jobs.p, C.wjobs.data(), m * sizeof(CnsWalkJobDev), st);
+        S.h2d(S.d_path.p, items.data(), items.size() * sizeof(PathItem), st);
+        S.h2d(S.d_cnsw_seed.p, seeds.data(), seeds.size(), st);
+        S.launch_cns_walk_jobs(C, nullptr, S.d_path.p);
+        HIP_CHECK(hipGetLastError());
+        outs.resize(m);
+        S.d2h(outs.data(), S.d_cnsw_out.p, m * sizeof(CnsWalkOutDev), st);
+        S.sync_drain(st);
+        S.stats.cnsw_ms += S.ms(State::kEvCnswBegin, State::kEvCnswEnd);
+        uint64_t n_words = 0, n_wins = 0, n_bytes = 0;
+        for (const CnsWalkOutDev &O : outs)
+            if (!O.err) n_words += O.n_words, n_wins += O.n_win, n_bytes += O.n_bytes;
+        S.reserve_down(n_words * 4 + n_wins * 8 + n_bytes + 2048, st);
+        const uint32_t *w = (const uint32_t *)S.d2h(nullptr, S.d_cns_dense.p, n_words * 4, st);
+        const uint32_t *wn = (const uint32_t *)S.d2h(nullptr, S.d_cns_wdense.p, n_wins * 8, st);
+        const char *sq = (const char *)S.d2h(nullptr, S.d_cnsw_seq.p, n_bytes, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        S.stats.cnsw_d2h_bytes += m * sizeof(CnsWalkOutDev) + n_words * 4 + n_wins * 8 + n_bytes;
+        size_t n_mode[3] = {0, 0, 0};
+        for (size_t i = 0; i < m; i++) {
+            CnsWalkReq &rq = reqs[a + i];
+            const CnsWalkOutDev &O = outs[i];
+            const bool hifi = rq.mode == (int)kCnsModeHifi;
+            n_mode[hifi ? 1 : 2]++;
+            rq.done = !O.err;
+            if (O.err) {
+                (hifi ? S.stats.cnsw_hifi_declined : S.stats.cnsw_fast_declined)++;
+                continue;
+            }
+            if (hifi) {
+                rq.words.assign(w, w + O.n_words);
+                rq.wins.assign(wn, wn + 2 * (size_t)O.n_win);
+                rq.len = O.len, rq.lqseq_total_length = O.lqseq_total_length;
+                S.stats.cnsw_hifi_jobs++;
+                S.stats.cnsw_hifi_regions += O.n_win;
+            } else {
+                rq.lq_m = O.lq_m, rq.hq_m = O.hq_m, rq.lqseq_total_length = O.lqseq_total_length, rq.len = O.len;
+                rq.seq.assign(sq, sq + O.n_bytes);
+                S.stats.cnsw_fast_jobs++;
+            }
+            w += O.n_words, wn += 2 * (size_t)O.n_win, sq += O.n_bytes;
+        }
+        S.drain();
+        if (trace_on())
+            fprintf(stderr, "[ndgpu trace] cns_walk %zu walks (batched entry): %zu HiFi, %zu -fast | K21 %.3f ms | %llu words, %llu windows, %llu bytes\n",
+                    m, n_mode[1], n_mode[2], S.ms(State::kEvCnswBegin, State::kEvCnswEnd), (unsigned long long)n_words,
+                    (unsigned long long)n_wins, (unsigned long long)n_bytes);
+        a = b;
+    }
+}
+
 void DeviceAligner::run_main(MainPile **mp, size_t np) {
     State &S = *s_;
     uint64_t tp[5] = {wall_ns()};
@@ -2267,11 +2515,13 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
     S.stats.piles += np;
     S.upload_plan(plan);
     bool want_cns = np > 0;   // K20 takes the walks when every pile of the launch asks (the engine asks under NDGPU_CNS_DEVICE=1)
+    bool walk_modes = false;  // ... and K21 where one of them is a HiFi or -fast pile (NDGPU_CNS_HIFI=1, NDGPU_CNS_FAST=1)
     for (size_t p = 0; p < np; p++) {
         want_cns = want_cns && mp[p]->want_cns;
+        walk_modes = walk_modes || mp[p]->cns_mode != (int)kCnsModeRaw;
         mp[p]->cns_ready = false;
     }
-    const CnsPlan cns = want_cns ? S.plan_cns(plan, mp) : CnsPlan();
+    const CnsPlan cns = !want_cns ? CnsPlan() : walk_modes ? S.plan_cns_walk(plan, mp) : S.plan_cns(plan, mp);
     MsaResult res = S.count_and_score(plan, cov, want_cns ? &cns : nullptr);
     piles.swap(res.piles);
     g_prof.m_msa += (tp[4] = wall_ns()) - tp[3];
@@ -2280,7 +2530,8 @@ void DeviceAligner::run_main(MainPile **mp, size_t np) {
         abort();
     }
     S.tally_main(plan, L.bad_pile, mp, tp);
-    if (want_cns) S.fetch_cns(cns, res, L.bad_pile, mp);
+    if (want_cns && cns.walk) S.fetch_cns_walk(cns, res, L.bad_pile, mp);
+    else if (want_cns) S.fetch_cns(cns, res, L.bad_pile, mp);
     else unpack_paths(piles, res.hpath, L.bad_pile, mp, S.host_threads);
     g_prof.m_post += wall_ns() - tp[4];
 }

@@ -1964,6 +1964,282 @@ __global__ __launch_bounds__(64) void cns_gather_kernel(const CnsJobDev *__restr
     for (uint32_t k = lane; k < 2u * O.n_win; k += 64u) dense_wins[2ull * sn + k] = wins[2ull * J.win_off + k];
 }
 
+// ---- K21: the HiFi and -fast forms of the loop behind the walk ---------------------------------------------------------------------
+// The device forms of cns_kmer_host and cns_fast_host (nd_cns.h; lib/nextcorrect.c:1807-1860 and :1724-1777), laid out as K20: one
+// wavefront per walk, 64 PathItems a chunk, the mode in the job record; what an item is on its own in the lanes, what depends on the
+// items before it wave-uniform.
+//
+// HiFi.  A lane's own: qv, the character (upper case: cov > min_cov alone), the index p, "pos differs from the previous non-gap
+// item's" (carried over the chunk edge) as K20 has them; the seed's code at t_pos, one gathered load a lane (piles given: from the
+// seed's 2-bit bases, which are the codes base_code gives the host -- a pile whose seed holds another byte than ACGT never gets a
+// walk, layout_piles); and the item's class as ballots: c4 (cov < 4), bad (else: qv < 80 or the base is not the seed's), good (else).
+// lqseq_total_length is the popcount of c4 | bad.  The automaton (lq, lq_s, lq_e) and the window list run wave-uniform, statement
+// for statement; pos at lq_s / lq_e comes through loads at one address behind the fence + wavefront barrier that hands the chunk's
+// words over.  A merge rewrites the last window's start, so that value is kept in a register (last_start) beside the store.
+//
+// The skip.  lq == 0 holds exactly when lq_s == -1: both are so at the start, a c4 item and an emission set both, a bad item sets
+// lq = 1 and lq_s >= 0, nothing else writes either.  In that state a c4 item assigns the values they have and a good item does
+// nothing (its branch needs lq), so only a bad item changes anything: the loop goes to the next set bit of the ballot of bad.  While
+// lq == 1 a c4 or bad item acts, and a good one only where pos differs and p - lq_e > 4; the loop visits the bits of
+// c4 | bad | (good & pos-differs) and tests p - lq_e there.  Either way a bit leaves `todo` every turn: at most 64 turns a chunk.
+//
+// Windows.  A window is pushed (or merged) by an emission at an index p with p - lq_e > 4, lq_e the index of a bad item b <= lq_e
+// that set lq: p >= b + 5.  The emission leaves lq == 0, so the next one needs a bad item b' > p and lies at p' >= b' + 5 >= p + 6.
+// Emissions are at least 6 indices apart, the first at p >= 5: a walk of `len` non-gap items has at most len / 6 of them.  win_cap
+// is (capacity in items) / 6 + 1; a slice that still fills sets kCnsErrWindows.
+__device__ __forceinline__ void cns_walk_hifi(const CnsWalkJobDev &J, const PileDev *piles, const PathItem *src, uint32_t n,
+                                              const uint32_t *pool, const uint32_t *db_pool, const uint8_t *seed_codes, uint32_t *W,
+                                              uint32_t *WN, CnsWalkOutDev &O, int lane) {
+    const uint32_t *sp = nullptr;
+    const uint8_t *sc = nullptr;
+    uint64_t so = 0;
+    uint32_t seed_len = J.seed_len;
+    if (piles) {
+        const uint64_t off = piles[J.pile].seed_off;
+        sp = (off >> 63) ? db_pool : pool;
+        so = off & kOffMask;
+        seed_len = piles[J.pile].seed_len;
+    } else sc = seed_codes + J.seed_off;
+    const unsigned long long lt = lanes_lt(lane);
+    int pbase = 0;
+    uint32_t carry_pos = 0xffffffffu;
+    int lq = 0, lq_s = -1, lq_e = -1;
+    uint32_t last_start = 0, err = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u) {   // (trip bound: n / 64 + 1)
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool valid = i < n;
+        PathItem it;
+        it.tag = 4u, it.link = 0, it.cov = 0;
+        if (valid) it = src[i];
+        const uint32_t base = it.tag & 7u;
+        const bool nongap = valid && base != 4u;
+        if (wave_ballot(nongap && it.cov == 0)) {
+            err |= kCnsErrCov;
+            break;
+        }
+        const unsigned long long ng = wave_ballot(nongap);
+        if (!ng) continue;
+        const uint32_t pos = (uint32_t)tag_tpos(it.tag);
+        if (wave_ballot(nongap && pos >= seed_len)) {   // (a column on the walk lies inside the seed)
+            err |= kCnsErrSeed;
+            break;
+        }
+        uint32_t scode = 0;
+        if (nongap) scode = sp ? cns_code(code_at(sp, so + pos)) : (uint32_t)sc[pos];
+        const int cov = (int)it.cov;
+        const int qv = nongap ? 100 * (int)it.link / cov : 0;
+        const unsigned long long before = ng & lt;
+        const int p = pbase + __popcll(before);
+        const uint32_t ppos = __shfl(pos, before ? 63 - __clzll((long long)before) : lane);
+        const bool pdif = nongap && (before ? ppos != pos : carry_pos != pos);
+        const bool c4 = nongap && cov < 4;
+        const bool bad = nongap && !c4 && (qv < 80 || base != scode);
+        const unsigned long long c4m = wave_ballot(c4), badm = wave_ballot(bad), pdm = wave_ballot(pdif);
+        const unsigned long long goodm = ng & ~(c4m | badm);
+        if (nongap) {
+            const uint32_t ch = (uint32_t)(0x4d4d4e2d43475441ull >> (8u * base)) & 0xffu;   // "ATGC-NMM"
+            W[p] = pos << 8 | (cov > J.min_cov ? ch : ch | 0x20u);
+        }
+        O.lqseq_total_length += (uint32_t)__popcll(c4m | badm);
+        carry_pos = (uint32_t)__builtin_amdgcn_readlane((int)pos, 63 - __clzll((long long)ng));
+        // hand-over: the automaton reads words other lanes wrote, of this chunk and of earlier ones -- fence + wavefront barrier
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+        unsigned long long todo = ng;
+        while (todo) {   // (trip bound: 64, a bit leaves `todo` every turn)
+            const unsigned long long cand = todo & (lq ? (c4m | badm | (goodm & pdm)) : badm);   // (the skip, see above)
+            if (!cand) break;
+            const int L = __builtin_ctzll(cand);
+            todo &= ~lanes_le(L);
+            const int pp = pbase + __popcll(ng & lanes_lt(L));
+            if ((c4m >> L) & 1ull) {
+                lq = 0;
+                lq_s = -1;
+            } else if ((badm >> L) & 1ull) {
+                if (lq_s == -1) lq_s = pp;
+                lq_e = pp;
+                lq = 1;
+            } else if (lq && pp - lq_e > 4) {   // (a good item whose pos differs: cand holds no other)
+                lq_e = pp - 3;
+                lq_s = lq_s > 2 ? lq_s - 2 : 1;
+                const uint32_t w_end = cns_uniform_load(W + lq_s) >> 8;
+                const uint32_t w_start = cns_uniform_load(W + lq_e) >> 8;
+                if (O.n_win && w_end >= last_start) {   // the merge: the last window's start moves
+                    if (O.n_win <= J.win_cap && lane == 0) WN[2u * (O.n_win - 1u)] = w_start;
+                } else {
+                    if (O.n_win < J.win_cap) {
+                        if (lane == 0) WN[2u * O.n_win] = w_start, WN[2u * O.n_win + 1u] = w_end;
+                    } else err |= kCnsErrWindows;
+                    O.n_win++;
+                }
+                last_start = w_start;
+                lq = 0;
+                lq_s = -1;
+            }
+        }
+        pbase += __popcll(ng);
+    }
+    O.len = O.n_words = (uint32_t)pbase;
+    O.err = err;
+}
+
+// -fast.  lower = non-gap && cov <= min_cov decides the character and everything else.  The reference's table of ten slots only
+// changes at the ends of the runs of equal case among the non-gap items:
+//   * a lower-case run of k items from string index q0 on does: if the slot is empty (end == 0) start = q0, lqlen = 0; then
+//     end = q0 + k - 1, lq_total_len += k, lqlen += k.  (Index 0: its item leaves end == 0, "empty", so the run opens again at index
+//     1 -- that item is taken alone.)  A run that goes on in the next chunk finds end != 0 and only extends;
+//   * of an upper-case run only the first item acts: it closes the slot (end >= start + 50, or slot 0) or empties it (end = 0);
+//     every later one finds an empty slot of index >= 1, and 0 >= start + 50 never holds.  An upper-case run that goes on from the
+//     chunk before finds the slot empty likewise, unless it is the walk's first upper-case item, which closes slot 0.
+// So the wave-uniform part visits the run boundaries of the chunk's ballot of `lower` (at most 64 a chunk) and adds by popcounts.
+// The slots themselves: a closed slot never changes again and the final scan (:1758-1772) reads the closed slots in order, each
+// against the one before it, so the scan is folded in where a slot closes -- lq_m, hq_m, l, lq_total_len and the previous slot's end
+// are the scan's whole state -- and only the open slot (c_*) is kept: scalars, nothing indexed, no scratch.  Closing slot 0 starts
+// the scan (hq_m = l = its start).  When the tenth slot would open the walk ends with the string it has (the reference's break).
+// Behind the loop the open slot joins the scan if it is not empty (the reference's loop condition lq[i].end), and the tail (:1768)
+// takes lq_total_len of the slot behind the last one scanned: the open slot's if that is empty, a fresh one's (0) otherwise.
+__device__ __forceinline__ void cns_walk_fast(const CnsWalkJobDev &J, const PathItem *src, uint32_t n, uint8_t *C, CnsWalkOutDev &O,
+                                              int lane) {
+    const unsigned long long lt = lanes_lt(lane);
+    uint32_t qbase = 0, out_len = 0, err = 0;
+    uint32_t c_start = 0, c_end = 0, c_lqlen = 0, c_total = 0;   // the open slot lq[lq_i]
+    int lq_i = 0;
+    uint32_t lq_m = 0, hq_m = 0, lq_total = 0, prev_end = 0;     // the scan so far, over the closed slots
+    int l = 0;
+    bool stop = false;
+    auto scan_slot = [&](int idx) {   // slot idx joins the scan with the open slot's values
+        if (idx == 0) {
+            lq_m = 0, hq_m = c_start, l = (int)hq_m;
+            lq_total = c_total - c_lqlen;
+        } else if (c_start - prev_end > (uint32_t)l) {
+            lq_m = prev_end + 1u, hq_m = c_start;
+            lq_total = c_total - c_lqlen;
+            l = (int)hq_m - (int)lq_m;
+        }
+        prev_end = c_end;
+    };
+    for (uint32_t i0 = 0; i0 < n && !stop; i0 += 64u) {   // (trip bound: n / 64 + 1)
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool valid = i < n;
+        PathItem it;
+        it.tag = 4u, it.link = 0, it.cov = 0;
+        if (valid) it = src[i];
+        const uint32_t base = it.tag & 7u;
+        const bool nongap = valid && base != 4u;
+        if (wave_ballot(nongap && it.cov == 0)) {
+            err |= kCnsErrCov;
+            break;
+        }
+        const unsigned long long ng = wave_ballot(nongap);
+        if (!ng) continue;
+        const bool lower = nongap && (int)it.cov <= J.min_cov;
+        const unsigned long long lowm = wave_ballot(lower);
+        if (nongap) {
+            const uint32_t ch = (uint32_t)(0x4d4d4e2d43475441ull >> (8u * base)) & 0xffu;   // "ATGC-NMM"
+            C[qbase + (uint32_t)__popcll(ng & lt)] = (uint8_t)(lower ? ch | 0x20u : ch);
+        }
+        unsigned long long todo = ng;
+        while (todo) {   // (trip bound: 64, a run leaves `todo` every turn)
+            const int L = __builtin_ctzll(todo);
+            const bool low = (lowm >> L) & 1ull;
+            const unsigned long long other = todo & (low ? ~lowm : lowm);   // the next item of the other case
+            const unsigned long long run = other ? todo & lanes_lt(__builtin_ctzll(other)) : todo;
+            todo &= ~run;
+            uint32_t k = (uint32_t)__popcll(run), q0 = qbase + (uint32_t)__popcll(ng & lanes_lt(L));
+            if (low) {
+                if (q0 == 0u) {   // the item at index 0: start = 0, end = 0 (still "empty"), one counted
+                    c_start = 0u, c_end = 0u, c_lqlen = 1u, c_total += 1u;
+                    q0 = 1u, k--;
+                }
+                if (k) {
+                    if (!c_end) c_start = q0, c_lqlen = 0u;
+                    c_end = q0 + k - 1u;
+                    c_total += k, c_lqlen += k;
+                }
+            } else if (c_end >= c_start + 50u || !lq_i) {
+                scan_slot(lq_i);
+                c_start = c_end = c_lqlen = c_total = 0u;
+                if (++lq_i >= 10) {   // LQREG_MAX_COUNT: the walk ends here, this character included
+                    out_len = q0 + 1u;
+                    stop = true;
+                    break;
+                }
+            } else c_end = 0u;
+        }
+        qbase += (uint32_t)__popcll(ng);
+    }
+    if (!stop) out_len = qbase;
+    int idx;
+    uint32_t next_total = 0;
+    if (lq_i == 0 || (lq_i < 10 && c_end)) {
+        scan_slot(lq_i);
+        idx = lq_i + 1;
+    } else {
+        idx = lq_i;
+        next_total = c_total;
+    }
+    if (idx < 10 && out_len - prev_end > (uint32_t)l) {
+        lq_m = prev_end + 1u, hq_m = out_len;
+        lq_total = next_total;
+    }
+    if (lq_m > hq_m || hq_m > out_len) err |= kCnsErrRange;   // (cannot happen: the slots lie inside the string, in order)
+    O.len = out_len;
+    O.lqseq_total_length = lq_total;
+    O.lq_m = lq_m, O.hq_m = hq_m;
+    O.n_bytes = err ? 0u : hq_m - lq_m;
+    O.err = err;
+}
+
+__global__ __launch_bounds__(64) void cns_walk_kernel(const CnsWalkJobDev *__restrict__ jobs, const PileDev *__restrict__ piles,
+                                                       const PathItem *__restrict__ path, const uint32_t *__restrict__ pool,
+                                                       const uint32_t *__restrict__ db_pool, const uint8_t *__restrict__ seed_codes,
+                                                       uint32_t *words, uint32_t *wins, uint8_t *chars, CnsWalkOutDev *__restrict__ out) {
+    const CnsWalkJobDev J = jobs[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    uint64_t path_off = J.path_off;
+    uint32_t n = J.n;
+    if (piles) {
+        path_off = piles[J.pile].path_off;
+        n = piles[J.pile].path_len;
+    }
+    CnsWalkOutDev O;
+    O.len = O.lqseq_total_length = O.n_win = O.err = O.lq_m = O.hq_m = O.n_words = O.n_bytes = 0;
+    if (J.decline) O.err = kCnsErrHook;
+    else if (n >= (1u << 30) || (piles && n > J.n)) O.err = kCnsErrLen;
+    else if (J.mode != kCnsModeHifi && J.mode != kCnsModeFast) O.err = kCnsErrMode;
+    if (!O.err) {
+        if (J.mode == kCnsModeHifi)
+            cns_walk_hifi(J, piles, path + path_off, n, pool, db_pool, seed_codes, words + path_off, wins + 2u * J.win_off, O, lane);
+        else cns_walk_fast(J, path + path_off, n, chars + path_off, O, lane);
+    }
+    if (lane == 0) out[blockIdx.x] = O;
+}
+
+// Walk b's words, windows and -fast string into the dense buffers, at the sums over the walks in front of it (exclusive; a
+// declined walk counts as empty); the string is the stretch [lq_m, hq_m) of the emitted characters, reversed.
+__global__ __launch_bounds__(64) void cns_walk_gather_kernel(const CnsWalkJobDev *__restrict__ jobs, const PileDev *__restrict__ piles,
+                                                              const CnsWalkOutDev *__restrict__ out, const uint32_t *__restrict__ words,
+                                                              const uint32_t *__restrict__ wins, const uint8_t *__restrict__ chars,
+                                                              uint32_t *__restrict__ dense_words, uint32_t *__restrict__ dense_wins,
+                                                              uint8_t *__restrict__ dense_seq) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    unsigned long long sw = 0, sn = 0, sb = 0;
+    for (uint32_t j = lane; j < b; j += 64u)
+        if (!out[j].err) sw += out[j].n_words, sn += out[j].n_win, sb += out[j].n_bytes;
+    for (int m = 32; m; m >>= 1) {
+        sw += __shfl_xor(sw, m);
+        sn += __shfl_xor(sn, m);
+        sb += __shfl_xor(sb, m);
+    }
+    const CnsWalkOutDev O = out[b];
+    if (O.err) return;
+    const CnsWalkJobDev J = jobs[b];
+    const uint64_t path_off = piles ? piles[J.pile].path_off : J.path_off;
+    for (uint32_t k = lane; k < O.n_words; k += 64u) dense_words[sw + k] = words[path_off + k];
+    for (uint32_t k = lane; k < 2u * O.n_win; k += 64u) dense_wins[2ull * sn + k] = wins[2ull * J.win_off + k];
+    for (uint32_t k = lane; k < O.n_bytes; k += 64u) dense_seq[sb + k] = chars[path_off + O.hq_m - 1u - k];
+}
+
 // ---- K11 -------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void extract_kernel(const PileDev *__restrict__ piles,
                                                       const ReadDev *__restrict__ reads,
@@ -2188,6 +2464,16 @@ void launch_cns_windows(const CnsJobDev *jobs, const PileDev *piles, const PathI
     hipLaunchKernelGGL(cns_windows_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, path, words, wins, out);
     hipLaunchKernelGGL(cns_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, out, words, wins, dense_words,
                        dense_wins);
+}
+
+void launch_cns_walk(const CnsWalkJobDev *jobs, const PileDev *piles, const PathItem *path, const uint32_t *pool, const uint32_t *db_pool,
+                     const uint8_t *seed_codes, uint32_t *words, uint32_t *wins, uint8_t *chars, CnsWalkOutDev *out, uint32_t *dense_words,
+                     uint32_t *dense_wins, uint8_t *dense_seq, int n, void *stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(cns_walk_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, path, pool, db_pool, seed_codes,
+                       words, wins, chars, out);
+    hipLaunchKernelGGL(cns_walk_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, out, words, wins, chars,
+                       dense_words, dense_wins, dense_seq);
 }
 
 void launch_extract(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const uint32_t *tags,

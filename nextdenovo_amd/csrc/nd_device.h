@@ -323,6 +323,38 @@ enum : uint32_t { kCnsErrWindows = 1u, kCnsErrTrips = 2u, kCnsErrCov = 4u, kCnsE
 void launch_cns_windows(const CnsJobDev *jobs, const PileDev *piles, const PathItem *path, uint32_t *words, uint32_t *wins, CnsOutDev *out,
                         uint32_t *dense_words, uint32_t *dense_wins, int n, void *stream);
 
+// ---- K21: the HiFi and -fast forms of the loop behind the walk (cns_walk_kernel, msa_kernels.hip; the rules: nd_cns.h) ----
+enum : uint32_t { kCnsModeRaw = 0u, kCnsModeHifi = 1u, kCnsModeFast = 2u };   // (raw is K20's: K21 declines it with kCnsErrMode)
+struct CnsWalkJobDev {      // one walk: CnsJobDev's fields, the mode and where the seed's codes are
+    uint64_t path_off;      // its first PathItem, its first word (HiFi) and its first character (-fast) in the per-walk slices
+    uint64_t win_off;       // its first window slot
+    uint64_t seed_off;      // piles not given, HiFi: the first of the seed's byte codes in `seed_codes`
+    uint32_t n;             // items of the walk (piles given: the capacity of its slice)
+    uint32_t win_cap;       // window slots: (capacity in items) / 6 + 1, see the kernel
+    int32_t min_cov;
+    uint32_t mode;          // kCnsMode*
+    uint32_t pile;          // piles given: the walk's PileDev (HiFi: the seed's codes come from its packed bases)
+    uint32_t decline;       // test hook
+    uint32_t seed_len;      // piles not given, HiFi: codes at seed_off
+    uint32_t pad_;
+};
+struct CnsWalkOutDev {      // what the host reads per walk: 32 bytes
+    uint32_t len;           // HiFi: consensus bases; -fast: characters emitted (the walk is cut where the tenth slot would open)
+    uint32_t lqseq_total_length;   // HiFi: bases with cov < 4, qv < 80 or another base than the seed's; -fast: lq_total_len of the result
+    uint32_t n_win;         // HiFi: windows
+    uint32_t err;           // kCnsErr* bits; nonzero: declined
+    uint32_t lq_m, hq_m;    // -fast: the chosen stretch of the emitted string
+    uint32_t n_words;       // words the gather writes for the walk (HiFi: len) ...
+    uint32_t n_bytes;       // ... and bytes (-fast: hq_m - lq_m)
+};
+enum : uint32_t { kCnsErrSeed = 32u, kCnsErrMode = 64u, kCnsErrRange = 128u };   // (beside K20's bits)
+// K21 over jobs [0, n), then its gather: words and windows as K20's, the -fast strings (each [lq_m, hq_m) reversed) to dense_seq at the
+// sum of n_bytes in front.  piles != nullptr: path_off, the length and (HiFi) the seed's 2-bit codes in pool / db_pool come from
+// piles[jobs[i].pile]; otherwise the HiFi seeds are byte codes in seed_codes.
+void launch_cns_walk(const CnsWalkJobDev *jobs, const PileDev *piles, const PathItem *path, const uint32_t *pool, const uint32_t *db_pool,
+                     const uint8_t *seed_codes, uint32_t *words, uint32_t *wins, uint8_t *chars, CnsWalkOutDev *out, uint32_t *dense_words,
+                     uint32_t *dense_wins, uint8_t *dense_seq, int n, void *stream);
+
 struct ColBlock {           // work item of the link-counting kernel
     uint32_t pile;
     uint32_t col0;

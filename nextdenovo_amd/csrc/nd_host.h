@@ -106,6 +106,7 @@ struct MainPile {
     // optional: the engine would take the walk's consensus words and low-quality windows (cns_windows_host of nd_cns.h) instead of
     // the walk itself
     bool want_cns = false;
+    int cns_mode = 0;                    // which loop, where want_cns: 0 raw reads (cns_windows_host), 1 HiFi (cns_kmer_host), 2 -fast (cns_fast_host)
     int min_cov = 0;
     unsigned lq_max_len = 0;
     // outputs
@@ -118,6 +119,9 @@ struct MainPile {
     bool cns_ready = false;
     std::vector<uint32_t> cns_words, cns_windows;
     uint32_t cns_counts[5] = {0, 0, 0, 0, 0};
+    // cns_mode 2: cns_fast = lq_m, hq_m, lq_total_len, characters emitted; cns_seq = the stretch [lq_m, hq_m), reversed
+    uint32_t cns_fast[4] = {0, 0, 0, 0};
+    std::string cns_seq;
 };
 
 // Candidate strings of one low-quality region (lib/nextcorrect.c:373-404).

@@ -91,6 +91,31 @@ struct RuntimeStats {
     double cns_ms = 0;                   // HIP-event time of K20 and its gather
     uint64_t cns_d2h_bytes = 0;          // result records, dense words and windows brought back
     uint64_t walk_d2h_bytes = 0;         // bytes of the walks (PathItems) run_main brought back, with or without K20
+    // the HiFi and -fast forms of that loop on the device (K21; ndgpu_cns_mode_stats)
+    uint64_t cnsw_hifi_jobs = 0;         // HiFi walks K21 finished (run_main's piles, run_cns_walk's jobs)
+    uint64_t cnsw_hifi_declined = 0;     // ... and left to the host routine
+    uint64_t cnsw_hifi_regions = 0;      // windows it emitted
+    uint64_t cnsw_fast_jobs = 0;         // -fast walks it finished
+    uint64_t cnsw_fast_declined = 0;
+    uint64_t cnsw_launches = 0;          // launches of K21 (each with its gather)
+    double cnsw_ms = 0;                  // their HIP-event time
+    uint64_t cnsw_d2h_bytes = 0;         // result records, dense words, windows and strings brought back
+};
+
+// One walk of the batched entry ndgpu_cns_walk_batch in mode 1 (HiFi: cns_kmer_host of nd_cns.h) or 2 (-fast: cns_fast_host).
+struct CnsWalkReq {
+    const PathStep *steps = nullptr;
+    size_t n = 0;
+    int min_cov = 0;
+    int mode = 1;
+    const uint8_t *seed_codes = nullptr;   // mode 1: the seed's codes (cns_base_code), seed_len of them
+    size_t seed_len = 0;
+    bool done = false;
+    std::vector<uint32_t> words, wins;     // mode 1
+    uint32_t len = 0;                      // mode 1: consensus bases; mode 2: characters emitted
+    uint32_t lqseq_total_length = 0;       // mode 2: lq_total_len of the result
+    uint32_t lq_m = 0, hq_m = 0;           // mode 2
+    std::string seq;                       // mode 2: [lq_m, hq_m) reversed
 };
 
 // One walk of the batched entry ndgpu_cns_windows_batch (DeviceAligner::run_cns): what cns_windows_host (nd_cns.h) returns for it.
@@ -141,6 +166,7 @@ class DeviceAligner {
     void run_extract(ExtractPile **piles, size_t n, bool offer_rank = true);
     void run_rank(RankReq *reqs, size_t n);   // the batched entry's problems: one pool up, one copy back
     void run_cns(CnsReq *reqs, size_t n);     // the batched entry's walks through K20; req.done = false: declined, the host routine takes it
+    void run_cns_walk(CnsWalkReq *reqs, size_t n);   // ... of modes 1 and 2 through K21
     void run_lq(LqRound **rounds, size_t n);
     // req.done = false: declined, the caller's host path takes it.  form 0: NDGPU_POA_RESIDENT decides; 1: resident graphs (K19);
     // 2: K13's rounds with the graphs on the host
@@ -194,6 +220,7 @@ class HipBackend : public Backend {
     }
     void run_rank(RankReq *reqs, size_t n) { dev_.run_rank(reqs, n); }
     void run_cns(CnsReq *reqs, size_t n) { dev_.run_cns(reqs, n); }
+    void run_cns_walk(CnsWalkReq *reqs, size_t n) { dev_.run_cns_walk(reqs, n); }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
     void run_align_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) { dev_.align_batch_runs(jobs, n, res, runs); }
     bool run_lq(LqRound **rounds, size_t n) override {
