@@ -219,6 +219,46 @@ typedef struct ndgpu_cns_walk_result {
 int ndgpu_cns_walk_batch(const ndgpu_cns_walk_job *jobs, int n, int flags, ndgpu_cns_walk_result *res, uint32_t **bases, uint32_t **regions,
                          char **seqs);
 
+/* The phasing and ranking of the low-quality-region candidates of HiFi piles (generate_lqseqs_from_tags_kmer, lib/nextcorrect.c:787-948
+ * with the helpers of 512-737: from the candidates as extracted up to the sort by score), for many piles in one call.  A job is a
+ * pile: n_aligned reads, n_regions regions in order, each with its inclusive seed columns start / end and n_cand candidates (0..40):
+ * bytes, lengths and source reads (each below n_aligned).  regions_out receives one record per region, the jobs' regions one behind
+ * the other; piles_out one per job.  A record's kind is 0 (the region had no candidates), 1 (dropped: lq.len = 0), 2 (a candidate
+ * becomes the pseudo-seed: seed is its input index, seed_pos its position, lower says that the pseudo-seed goes to lower case, n is
+ * -2) or 3 (ranked: the first n positions reach the selection loop; tail says that the tail windows were ranked too).  perm[j] is the
+ * input index of the candidate at position j of lq.seqs as the routine leaves it, kscore[j] its score as left by the last step that
+ * wrote it, for every j below n_cand; indexs is the region's flag as the phasing left it.
+ * flags bit 0: the engine's host rule; otherwise the device computes, and a pile it declines (more than 2,048 aligned reads, more
+ * than 65,535 regions, or a pile of its own too large for the device's memory) takes the host rule.  Returns 0; -2, with nothing computed or written, for a NULL array, n_cand outside
+ * 0..40, a NULL candidate of nonzero length, a source read not below n_aligned; < 0 when no device can be used.  n = 0 is valid. */
+typedef struct ndgpu_phase_region_in {
+    uint32_t start, end;
+    int32_t n_cand;
+    uint32_t pad_;
+    const char *const *seqs;
+    const uint16_t *len;
+    const uint16_t *src;
+} ndgpu_phase_region_in;
+typedef struct ndgpu_phase_job {
+    uint32_t n_aligned;
+    uint32_t n_regions;
+    const ndgpu_phase_region_in *regions;
+} ndgpu_phase_job;
+typedef struct ndgpu_phase_region {   /* 128 bytes */
+    uint8_t kind, lower, indexs, tail;
+    int16_t n;
+    uint8_t seed, seed_pos;
+    uint8_t perm[40];
+    uint16_t kscore[40];
+} ndgpu_phase_region;
+typedef struct ndgpu_phase_pile {
+    uint8_t has_heter;   /* a heterozygous site, or a candidate for one, was seen */
+    uint8_t pass2;       /* ... and no SNP phased the seed: the second pass ran */
+    uint8_t declined;    /* the device left the pile to the host rule */
+    uint8_t pad_;
+} ndgpu_phase_pile;
+int ndgpu_hifi_phase_batch(const ndgpu_phase_job *jobs, int n, int flags, ndgpu_phase_region *regions_out, ndgpu_phase_pile *piles_out);
+
 /* align() / align_hq() for many pairs in one call.  The pairs share the launches of the forward and traceback kernels; a further kernel
  * pair run-length-encodes every alignment's columns on the device, so that what comes back per job is its summary and its CIGAR, not a
  * byte per column.  res[i]: status (0: none -- align() would leave its argument untouched, which includes a sequence with a byte
@@ -373,6 +413,23 @@ typedef struct {
     uint64_t d2h_bytes;             /* result records (32 bytes a walk), words, windows and strings brought back */
 } ndgpu_cns_mode_stats;
 void ndgpu_get_cns_mode_stats(ndgpu_cns_mode_stats *out);
+/* The phasing and ranking of HiFi candidates on the device (ndgpu_hifi_phase_batch; the engine's piles with NDGPU_PHASE_DEVICE=1).
+ * Counters of their own: ndgpu_stats keeps its layout.  ndgpu_reset_stats clears these too. */
+typedef struct {
+    uint64_t piles;                 /* piles the device finished */
+    uint64_t regions;               /* their regions ... */
+    uint64_t kind[4];               /* ... by kind: empty, dropped, seed, ranked */
+    uint64_t pass2_piles;           /* piles whose second pass ran */
+    uint64_t tail_passes;           /* ranked regions that took the tail pass */
+    uint64_t declined[5];           /* piles left to the host rule: reads over capacity, regions over 65,535, strings outside the pool,
+                                       the hook NDGPU_PHASE_DECLINE, a source read out of range */
+    uint64_t launches;              /* launches of the kernel pair */
+    double ms;                      /* its HIP-event time */
+    uint64_t d2h_record_bytes;      /* pile records (32 bytes) and region records (128 bytes) brought back */
+    uint64_t d2h_string_bytes;      /* candidate strings brought back beside them (the engine's piles) */
+    uint64_t seed_lower;            /* seed regions whose pseudo-seed goes to lower case */
+} ndgpu_phase_stats;
+void ndgpu_get_phase_stats(ndgpu_phase_stats *out);
 /* The device contexts keep their (grow-only) buffers between calls.  This hands them back -- for a caller that alternates
  * the consensus with another memory-hungry stage on the same device (the overlap stage of a genome-scale read set) and
  * finds that stage short of memory.  Safe to call at any time from any thread: a context that is in the middle of a batch

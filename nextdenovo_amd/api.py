@@ -72,6 +72,35 @@ class CnsModeStats(C.Structure):
                 ("fast_declined", C.c_uint64), ("launches", C.c_uint64), ("ms", C.c_double), ("d2h_bytes", C.c_uint64)]
 
 
+class PhaseRegionIn(C.Structure):
+    # ndgpu_phase_region_in
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_cand", C.c_int32), ("pad_", C.c_uint32), ("seqs", C.POINTER(C.c_char_p)),
+                ("len", C.POINTER(C.c_uint16)), ("src", C.POINTER(C.c_uint16))]
+
+
+class PhaseJob(C.Structure):
+    # ndgpu_phase_job
+    _fields_ = [("n_aligned", C.c_uint32), ("n_regions", C.c_uint32), ("regions", C.POINTER(PhaseRegionIn))]
+
+
+class PhaseRegion(C.Structure):
+    # ndgpu_phase_region
+    _fields_ = [("kind", C.c_uint8), ("lower", C.c_uint8), ("indexs", C.c_uint8), ("tail", C.c_uint8), ("n", C.c_int16),
+                ("seed", C.c_uint8), ("seed_pos", C.c_uint8), ("perm", C.c_uint8 * 40), ("kscore", C.c_uint16 * 40)]
+
+
+class PhasePile(C.Structure):
+    # ndgpu_phase_pile
+    _fields_ = [("has_heter", C.c_uint8), ("pass2", C.c_uint8), ("declined", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+class PhaseStats(C.Structure):
+    # ndgpu_phase_stats
+    _fields_ = [("piles", C.c_uint64), ("regions", C.c_uint64), ("kind", C.c_uint64 * 4), ("pass2_piles", C.c_uint64),
+                ("tail_passes", C.c_uint64), ("declined", C.c_uint64 * 5), ("launches", C.c_uint64), ("ms", C.c_double),
+                ("d2h_record_bytes", C.c_uint64), ("d2h_string_bytes", C.c_uint64), ("seed_lower", C.c_uint64)]
+
+
 class AlnJob(C.Structure):
     # ndgpu_aln_job
     _fields_ = [("q", C.c_char_p), ("q_len", C.c_int32), ("t", C.c_char_p), ("t_len", C.c_int32), ("hq", C.c_int32)]
@@ -172,6 +201,10 @@ def _bind(lib):
     lib.ndgpu_cns_walk_batch.restype = C.c_int
     lib.ndgpu_get_cns_mode_stats.argtypes = [C.POINTER(CnsModeStats)]
     lib.ndgpu_get_cns_mode_stats.restype = None
+    lib.ndgpu_hifi_phase_batch.argtypes = [C.POINTER(PhaseJob), C.c_int, C.c_int, C.POINTER(PhaseRegion), C.POINTER(PhasePile)]
+    lib.ndgpu_hifi_phase_batch.restype = C.c_int
+    lib.ndgpu_get_phase_stats.argtypes = [C.POINTER(PhaseStats)]
+    lib.ndgpu_get_phase_stats.restype = None
     lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.ndgpu_align_batch.restype = C.c_int
@@ -561,6 +594,63 @@ def cns_mode_stats() -> dict:
     s = CnsModeStats()
     load().ndgpu_get_cns_mode_stats(C.byref(s))
     return {n: getattr(s, n) for n, _ in CnsModeStats._fields_}
+
+
+PHASE_EMPTY, PHASE_DROPPED, PHASE_SEED, PHASE_RANKED = 0, 1, 2, 3
+
+
+def hifi_phase_batch(jobs, host=False):
+    """jobs: [(n_aligned, [(start, end, [bytes, ...], [source read, ...]), ...])] -- a HiFi pile each: its regions in order, every one
+    with its inclusive seed columns and 0..40 candidates -> one dict per job through ndgpu_hifi_phase_batch
+    (generate_lqseqs_from_tags_kmer, lib/nextcorrect.c:787-948 with the helpers of 512-737): has_heter, pass2, declined and `regions`,
+    one dict per region: kind (PHASE_*), lower, indexs, tail, n, seed, seed_pos, and perm / kscore over the region's candidates -- the
+    input index and the score of the candidate at every position of lq.seqs as the routine leaves it.  host=True: the engine's own
+    host rule instead of the device (K22)."""
+    lib = load()
+    n = len(jobs)
+    arr = (PhaseJob * max(1, n))()
+    keep = []
+    total = 0
+    for i, (n_aligned, regions) in enumerate(jobs):
+        m = len(regions)
+        ra = (PhaseRegionIn * max(1, m))()
+        for r, (start, end, seqs, src) in enumerate(regions):
+            k = len(seqs)
+            if len(src) != k:
+                raise ValueError("a source read per candidate")
+            cs = (C.c_char_p * max(1, k))()
+            cs[:k] = list(seqs)
+            ln = (C.c_uint16 * max(1, k))(*[len(s) for s in seqs])
+            sr = (C.c_uint16 * max(1, k))(*src)
+            keep.append((cs, ln, sr))
+            ra[r] = PhaseRegionIn(start, end, k, 0, C.cast(cs, C.POINTER(C.c_char_p)), C.cast(ln, C.POINTER(C.c_uint16)),
+                                  C.cast(sr, C.POINTER(C.c_uint16)))
+        keep.append(ra)
+        arr[i] = PhaseJob(n_aligned, m, C.cast(ra, C.POINTER(PhaseRegionIn)))
+        total += m
+    res = (PhaseRegion * max(1, total))()
+    piles = (PhasePile * max(1, n))()
+    rc = lib.ndgpu_hifi_phase_batch(arr, n, 1 if host else 0, res, piles)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("ndgpu_hifi_phase_batch failed (%d)" % rc)
+    out, at = [], 0
+    for i, (_, regions) in enumerate(jobs):
+        regs = []
+        for r, (_, _, seqs, _) in enumerate(regions):
+            g = res[at + r]
+            k = len(seqs)
+            regs.append(dict(kind=int(g.kind), lower=int(g.lower), indexs=int(g.indexs), tail=int(g.tail), n=int(g.n), seed=int(g.seed),
+                             seed_pos=int(g.seed_pos), perm=list(g.perm[:k]), kscore=list(g.kscore[:k])))
+        at += len(regions)
+        out.append(dict(has_heter=int(piles[i].has_heter), pass2=int(piles[i].pass2), declined=int(piles[i].declined), regions=regs))
+    return out
+
+
+def phase_stats() -> dict:
+    """ndgpu_phase_stats: the counters of the phasing and ranking of HiFi candidates on the device (K22), cleared by reset_stats()."""
+    s = PhaseStats()
+    load().ndgpu_get_phase_stats(C.byref(s))
+    return {n: (list(getattr(s, n)) if n in ("kind", "declined") else getattr(s, n)) for n, _ in PhaseStats._fields_}
 
 
 def _align_call(fn, name, arr, n, host, strings):

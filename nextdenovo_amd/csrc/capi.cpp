@@ -256,6 +256,13 @@ void print_prof(int drivers, int threads_each) {  // NDGPU_PROF: the host driver
                         "%llu declined | %llu launches, %.3f ms\n", (unsigned long long)s.cnsw_d2h_bytes, (unsigned long long)s.cnsw_hifi_jobs,
                 (unsigned long long)s.cnsw_hifi_declined, (unsigned long long)s.cnsw_hifi_regions, (unsigned long long)s.cnsw_fast_jobs,
                 (unsigned long long)s.cnsw_fast_declined, (unsigned long long)s.cnsw_launches, s.cnsw_ms);
+        uint64_t declined = 0;
+        for (int k = 0; k < 5; k++) declined += s.phase_declined[k];
+        fprintf(stderr, "[ndgpu prof] K22 since the last reset: %llu piles, %llu regions (%llu seed, %llu ranked, %llu dropped), %llu declined | "
+                        "%llu launches, %.3f ms | d2h: records %llu bytes, strings %llu bytes\n", (unsigned long long)s.phase_piles,
+                (unsigned long long)s.phase_regions, (unsigned long long)s.phase_kind[2], (unsigned long long)s.phase_kind[3],
+                (unsigned long long)s.phase_kind[1], (unsigned long long)declined, (unsigned long long)s.phase_launches, s.phase_ms,
+                (unsigned long long)s.phase_d2h_records, (unsigned long long)s.phase_d2h_strings);
     }
     for (auto &a : g_prof.adv_ns) a = 0;
     g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
@@ -834,6 +841,71 @@ int ndgpu_lq_rank_batch(const ndgpu_rank_job *jobs, int n, int flags, ndgpu_rank
     return 0;
 }
 
+// The phasing and ranking of the candidates of a batch of HiFi piles: K22 on the device (DeviceAligner::run_phase), or -- flags bit 0 --
+// the engine's own host rule (hifi_phase_host of nd_phase.h); a pile the kernel declines takes the host rule too.
+int ndgpu_hifi_phase_batch(const ndgpu_phase_job *jobs, int n, int flags, ndgpu_phase_region *regions_out, ndgpu_phase_pile *piles_out) {
+    static_assert(sizeof(ndgpu_phase_region) == sizeof(PhaseRecord), "the records are copied as they stand");
+    if (n == 0) return 0;
+    if (n < 0 || !jobs || !piles_out) return -2;
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        const ndgpu_phase_job &j = jobs[i];
+        if (j.n_regions && !j.regions) return -2;
+        for (uint32_t r = 0; r < j.n_regions; r++) {
+            const ndgpu_phase_region_in &g = j.regions[r];
+            if (g.n_cand < 0 || g.n_cand > kPhaseCanMax) return -2;
+            if (g.n_cand && (!g.seqs || !g.len || !g.src)) return -2;
+            for (int c = 0; c < g.n_cand; c++)
+                if ((g.len[c] && !g.seqs[c]) || g.src[c] >= j.n_aligned) return -2;
+        }
+        total += j.n_regions;
+    }
+    if (total && !regions_out) return -2;
+    std::vector<PhaseRegionIn> in(total);
+    std::vector<PhaseRecord> recs(total);
+    std::vector<PhaseReq> reqs((size_t)n);
+    for (size_t i = 0, at = 0; i < (size_t)n; i++) {
+        const ndgpu_phase_job &j = jobs[i];
+        for (uint32_t r = 0; r < j.n_regions; r++) {
+            const ndgpu_phase_region_in &g = j.regions[r];
+            in[at + r] = PhaseRegionIn{g.start, g.end, g.n_cand, g.seqs, g.len, g.src};
+        }
+        reqs[i].n_aligned = j.n_aligned, reqs[i].regions = in.data() + at, reqs[i].n_regions = j.n_regions, reqs[i].out = recs.data() + at;
+        at += j.n_regions;
+    }
+    if (!(flags & 1)) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+            fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_hifi_phase_batch runs on the device unless flags bit 0 is set\n");
+            return -1;
+        }
+        // (out of device memory: the range is halved until it fits)
+        std::vector<std::pair<size_t, size_t>> todo{{0, (size_t)n}};
+        while (!todo.empty()) {
+            const auto [a, b] = todo.back();
+            todo.pop_back();
+            try {
+                HipBackend be(0, 1);
+                be.run_phase(reqs.data() + a, b - a);
+            } catch (const DeviceOom &) {
+                DeviceAligner::context(0).release_memory();
+                DeviceAligner::forget_sizes();
+                if (b - a <= 1) continue;   // (a single pile that does not fit: declined, the host rule takes it)
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    host_each((size_t)n, effective_cpus() <= 1 || n <= 1, effective_cpus(), (size_t)n, false, [&](size_t i) {
+        PhaseReq &rq = reqs[i];
+        piles_out[i].declined = !(flags & 1) && !rq.done ? 1 : 0;
+        if (!rq.done) hifi_phase_host(rq.n_aligned, rq.regions, rq.n_regions, rq.out, rq.pile);
+        piles_out[i].has_heter = rq.pile.has_heter, piles_out[i].pass2 = rq.pile.pass2, piles_out[i].pad_ = 0;
+    });
+    if (total) memcpy(regions_out, recs.data(), total * sizeof(PhaseRecord));
+    return 0;
+}
+
 // The consensus words and low-quality windows of a batch of walks: K20 on the device (DeviceAligner::run_cns), or -- flags bit 0 -- the
 // engine's own host routine (cns_windows_host); a walk the kernel declines takes the host routine too.  The verdict is cns_verdict.
 int ndgpu_cns_windows_batch(const ndgpu_cns_job *jobs, int n, int flags, ndgpu_cns_result *res, uint32_t **bases, uint32_t **regions) {
@@ -1264,6 +1336,17 @@ void ndgpu_get_cns_mode_stats(ndgpu_cns_mode_stats *o) {
     o->hifi_jobs = s.cnsw_hifi_jobs, o->hifi_declined = s.cnsw_hifi_declined, o->hifi_regions = s.cnsw_hifi_regions;
     o->fast_jobs = s.cnsw_fast_jobs, o->fast_declined = s.cnsw_fast_declined, o->launches = s.cnsw_launches;
     o->ms = s.cnsw_ms, o->d2h_bytes = s.cnsw_d2h_bytes;
+}
+
+void ndgpu_get_phase_stats(ndgpu_phase_stats *o) {
+    if (!o) return;
+    const RuntimeStats s = DeviceAligner::total_stats();
+    o->piles = s.phase_piles, o->regions = s.phase_regions, o->pass2_piles = s.phase_pass2, o->tail_passes = s.phase_tail;
+    for (int k = 0; k < 4; k++) o->kind[k] = s.phase_kind[k];
+    for (int k = 0; k < 5; k++) o->declined[k] = s.phase_declined[k];
+    o->launches = s.phase_launches, o->ms = s.phase_ms;
+    o->d2h_record_bytes = s.phase_d2h_records, o->d2h_string_bytes = s.phase_d2h_strings;
+    o->seed_lower = s.phase_lower;
 }
 
 uint64_t ndgpu_release_memory(void) {

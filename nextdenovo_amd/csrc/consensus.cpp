@@ -686,7 +686,9 @@ class PileImpl {
             return;
         }
         extract.slot = main.slot;
-        extract.rank = rank_on_device() && prm.read_type != 3;  // (HiFi: its ranking sits behind the phasing, on the host)
+        extract.rank = rank_on_device() && prm.read_type != 3;  // (HiFi: its ranking sits behind the phasing: K22, below)
+        extract.phase = phase_on_device() && prm.read_type == 3;
+        extract.n_aligned = n_aligned;
         extract.regions.resize(regions.size());
         for (size_t i = 0; i < regions.size(); i++) {
             extract.regions[i].start = regions[i].start;
@@ -716,6 +718,11 @@ class PileImpl {
     // The 8-mer ranking of the regions' candidates by the backend, behind its extraction (K14; opt-in, see DESIGN.md section 0a''').
     static bool rank_on_device() {
         static const bool on = getenv("NDGPU_RANK_DEVICE") != nullptr && atoi(getenv("NDGPU_RANK_DEVICE")) != 0;
+        return on;
+    }
+    // The phasing and ranking of a HiFi pile's candidates by the backend, behind its extraction (K22; opt-in, see DESIGN.md section 0a''''''''''').
+    static bool phase_on_device() {
+        static const bool on = getenv("NDGPU_PHASE_DEVICE") != nullptr && atoi(getenv("NDGPU_PHASE_DEVICE")) != 0;
         return on;
     }
     void post_poa(size_t region, std::vector<std::string> &&in, int add_len, bool check_len) {
@@ -831,123 +838,27 @@ class PileImpl {
         return true;
     }
 
-    // ---- helpers of the HiFi candidate phasing (lib/nextcorrect.c:512-737)
-    struct Phs { uint16_t d = 0, s = 0; int del = 0; };
-    static bool same_seq(const LqSeq &a, const LqSeq &b) { return a.len == b.len && a.seq == b.seq; }
-
-    static int remove_differ_len(LqRegion &lq) {  // :512-539
-        int s, j, k = (int)(lq.end - lq.start + 1);
-        const int offset = std::min(std::max(30, k / 10), k / 3);
-        int8_t dif[kLqCanMax] = {0};
-        for (j = s = 0; j < lq.len; j++) {
-            if (lq.seqs[j].len + offset >= k && lq.seqs[j].len <= k + offset) s++;
-            else dif[j] = 1;
+    // HiFi: generate_lqseqs_from_tags_kmer, lib/nextcorrect.c:740-1008, on the extracted candidates: lay them out, phase and rank them
+    // (hifi_phase_host of nd_phase.h, lines 787-948 with the helpers of 512-737 -- or the records the backend left where the pile asked
+    // for them: K22), apply the records, then the selection loop and the POA hand-over as ever.
+    // What applying a record relies on: perm is a permutation of the region's candidates, kind, n and seed_pos lie inside them.
+    static bool phase_record_ok(const PhaseRecord &r, size_t n_cand) {
+        if (n_cand > (size_t)kPhaseCanMax || r.kind > kPhaseRanked) return false;
+        if (r.kind == kPhaseEmpty) return n_cand == 0;
+        uint64_t seen = 0;
+        for (size_t p = 0; p < n_cand; p++) {
+            if (r.perm[p] >= n_cand || (seen >> r.perm[p]) & 1u) return false;
+            seen |= 1ull << r.perm[p];
         }
-        if (s != lq.len && (s >= lq.len / 2 || (s >= lq.len / 3 && s >= 3))) {
-            k = lq.len;
-            for (j = 0; j < lq.len && j < k; j++)
-                if (dif[j])
-                    for (k--; k > j; k--)
-                        if (!dif[k]) {
-                            std::swap(lq.seqs[j], lq.seqs[k]);
-                            break;
-                        }
-            lq.len = k;
-        }
-        return s;
+        if (r.kind == kPhaseSeed) return r.seed_pos < n_cand && r.n == -2;
+        if (r.kind == kPhaseRanked) return r.n >= 1 && (size_t)r.n <= n_cand;
+        return r.n == 0;
     }
-
-    static void compact_flagged(LqRegion &lq, const int8_t *dif) {  // :599-609
-        int j, k;
-        for (k = lq.len, j = 0; j < lq.len && j < k; j++)
-            if (dif[j])
-                for (k--; k > j; k--)
-                    if (!dif[k]) {
-                        std::swap(lq.seqs[j], lq.seqs[k]);
-                        break;
-                    }
-        lq.len = k;
-    }
-
-    static void select_most2(LqRegion &lq, int len, int *m1, int *m2) {  // :632-653
-        int j, k;
-        int8_t used[kLqCanMax] = {0};
-        for (*m1 = *m2 = j = 0; j < std::min(lq.len, len); j++) {
-            lq.seqs[j].kscore = 1;
-            if (used[j]) continue;
-            for (k = j + 1; k < lq.len; k++)
-                if (same_seq(lq.seqs[j], lq.seqs[k])) {
-                    used[k] = 1;
-                    lq.seqs[j].kscore++;
-                }
-            if (lq.seqs[j].kscore > lq.seqs[*m1].kscore ||
-                (lq.seqs[j].kscore == lq.seqs[*m1].kscore && lq.seqs[j].order < lq.seqs[*m1].order)) {
-                *m2 = *m1;
-                *m1 = j;
-            } else if (*m2 == *m1 || lq.seqs[j].kscore > lq.seqs[*m2].kscore) {
-                *m2 = j;
-            }
-        }
-    }
-
-    static void select_most2_with_kscore(LqRegion &lq, int len, int *m1, int *m2) {  // :656-668
-        int j;
-        for (*m1 = *m2 = j = 0; j < std::min(lq.len, len); j++) {
-            if (lq.seqs[j].kscore > lq.seqs[*m1].kscore ||
-                (lq.seqs[j].kscore == lq.seqs[*m1].kscore && lq.seqs[j].order < lq.seqs[*m1].order)) {
-                *m2 = *m1;
-                *m1 = j;
-            } else if (*m2 == *m1 || lq.seqs[j].kscore > lq.seqs[*m2].kscore) {
-                *m2 = j;
-            }
-        }
-    }
-
-    static void run_ends(const std::string &q, int *s, int *e) {  // :678-683
-        const int n = (int)q.size();
-        *s = 0;
-        while (*s + 1 < n && q[*s] == q[*s + 1]) (*s)++;
-        *e = n - 1;
-        while (*e > 0 && q[*e - 1] == q[*e]) (*e)--;
-    }
-    static int homo_end_same(const std::string &a, const std::string &b) {  // :684-697
-        int as, ae, bs, be;
-        run_ends(a, &as, &ae);
-        run_ends(b, &bs, &be);
-        if (ae <= as && be <= bs) return 1;
-        if (ae - as != be - bs) return 0;
-        for (int i = 0; i <= ae - as; i++)
-            if (a[i + as] != b[i + bs]) return 0;
-        return 1;
-    }
-    static int prefixhomo_same(const std::string &a, const std::string &b) {  // :699-714
-        int i = 0, j = 0;
-        const int na = (int)a.size(), nb = (int)b.size();
-        while (i < na && j < nb) {
-            if (a[i] != b[j]) return 0;
-            while (i + 1 < na && a[i] == a[i + 1]) i++;
-            while (j + 1 < nb && b[j] == b[j + 1]) j++;
-            i++;
-            j++;
-        }
-        return 1;
-    }
-    static int trim_endssr_same(const std::string &x, const std::string &y) {  // :716-737
-        const std::string *a = &x, *b = &y;
-        if (a->size() < b->size()) std::swap(a, b);
-        const int na = (int)a->size(), nb = (int)b->size();
-        int i;
-        for (i = 0; i < nb; i++)
-            if ((*a)[i] != (*b)[i]) return 0;
-        for (int j = na - 1; j >= i; j--)
-            if ((*a)[j] != (*b)[nb - (na - j)]) return 0;
-        return 1;
-    }
-
-    // HiFi: generate_lqseqs_from_tags_kmer, lib/nextcorrect.c:740-1008, on the extracted candidates
     int lqseqs_from_candidates_kmer() {
         int max_aln_length = 0, max_aln_lqseq_len = 0;
-        int s = 0, k = 0, j, index;
+        int k, j;
+        bool phased = extract.phase;
+        size_t n_cands = 0;
         for (size_t ri = 0; ri < regions.size(); ri++) {
             LqRegion &lq = regions[ri];
             RegionReq &rq = extract.regions[ri];
@@ -964,141 +875,59 @@ class PileImpl {
                 lq.seqs.push_back(std::move(q));
                 lq.len++;
             }
+            n_cands += lq.seqs.size();
+            phased = phased && rq.phased;
         }
-        std::vector<Phs> phase(n_aligned ? n_aligned : 1);
-        int has_heter = 0;
-        for (LqRegion &lq : regions) {  // heterozygous sites first (:789-810)
-            if (!lq.len) continue;
-            select_most2(lq, lq.len, &s, &k);
-            if (s != k && lq.seqs[k].kscore >= 3 && lq.seqs[s].len == lq.seqs[k].len) {
-                if (s == 0 || k == 0) {
-                    const int heter = s == 0 ? k : s;
-                    for (j = 0; j < lq.len; j++) {
-                        index = lq.seqs[j].order;
-                        if (same_seq(lq.seqs[0], lq.seqs[j])) phase[index].s++;
-                        else if (same_seq(lq.seqs[heter], lq.seqs[j])) phase[index].d++;
-                    }
+        std::vector<PhaseRecord> recs(regions.size());
+        if (phased) {
+            for (size_t ri = 0; ri < regions.size() && phased; ri++) {
+                recs[ri] = extract.regions[ri].phase;
+                phased = phase_record_ok(recs[ri], regions[ri].seqs.size());
+            }
+            if (!phased) fprintf(stderr, "[ndgpu] a backend's phasing record does not fit its region: the pile takes the host rule\n");
+        }
+        if (!phased) {
+            std::vector<const char *> ptr(n_cands);
+            std::vector<uint16_t> len(n_cands), src(n_cands);
+            std::vector<PhaseRegionIn> in(regions.size());
+            size_t at = 0;
+            for (size_t ri = 0; ri < regions.size(); ri++) {
+                const LqRegion &lq = regions[ri];
+                in[ri] = PhaseRegionIn{lq.start, lq.end, lq.len, ptr.data() + at, len.data() + at, src.data() + at};
+                for (const LqSeq &q : lq.seqs) ptr[at] = q.seq.data(), len[at] = q.len, src[at] = q.order, at++;
+            }
+            PhasePileOut pile;
+            hifi_phase_host(n_aligned, in.data(), in.size(), recs.data(), pile);
+        }
+        for (size_t ri = 0; ri < regions.size(); ri++) {
+            LqRegion &lq = regions[ri];
+            const PhaseRecord &rec = recs[ri];
+            if (rec.kind == kPhaseEmpty) continue;
+            {  // lq.seqs as the rule left them
+                std::vector<LqSeq> moved(lq.seqs.size());
+                for (size_t p = 0; p < moved.size(); p++) {
+                    moved[p] = std::move(lq.seqs[rec.perm[p]]);
+                    moved[p].kscore = rec.kscore[p];
                 }
-                lq.indexs = 1;
-            } else lq.indexs = 0;
-            if (!has_heter && (lq.indexs == 1 ||
-                               (s != k && lq.seqs[k].kscore >= 5 &&
-                                lq.seqs[s].kscore + lq.seqs[k].kscore >= lq.len * 0.8 &&
-                                !prefixhomo_same(lq.seqs[s].seq, lq.seqs[k].seq))))
-                has_heter = 1;
-        }
-        if (has_heter && !phase[0].s) {  // :812-854
-            for (LqRegion &lq : regions) {
-                if (!lq.len) continue;
-                select_most2_with_kscore(lq, lq.len, &s, &k);
-                if (s != k && lq.seqs[k].kscore >= 5 && (lq.seqs[s].kscore + lq.seqs[k].kscore) >= lq.len * 0.8 &&
-                    (lq.seqs[s].len >= lq.seqs[k].len + 5 || lq.seqs[k].len >= lq.seqs[s].len + 5 ||
-                     !prefixhomo_same(lq.seqs[s].seq, lq.seqs[k].seq))) {
-                    int s_, k_;
-                    if (s == 0) { s_ = 1; k_ = 0; }
-                    else if (k == 0) { s_ = 0; k_ = 1; }
-                    else {
-                        s_ = homo_end_same(lq.seqs[s].seq, lq.seqs[0].seq) || trim_endssr_same(lq.seqs[s].seq, lq.seqs[0].seq) ||
-                             prefixhomo_same(lq.seqs[s].seq, lq.seqs[0].seq);
-                        k_ = homo_end_same(lq.seqs[k].seq, lq.seqs[0].seq) || trim_endssr_same(lq.seqs[k].seq, lq.seqs[0].seq) ||
-                             prefixhomo_same(lq.seqs[k].seq, lq.seqs[0].seq);
-                    }
-                    int same, heter;
-                    if (s_ && !k_) { same = s; heter = k; }
-                    else if (k_ && !s_) { same = k; heter = s; }
-                    else continue;
-                    for (j = 0; j < lq.len; j++) {
-                        index = lq.seqs[j].order;
-                        if (same_seq(lq.seqs[same], lq.seqs[j])) phase[index].s++;
-                        else if (same_seq(lq.seqs[heter], lq.seqs[j])) phase[index].d++;
-                    }
-                    lq.indexs = 2;
-                } else lq.indexs = 0;
+                lq.seqs.swap(moved);
             }
-        }
-        for (LqRegion &lq : regions) {  // mark_del_lqseq, :570-588
-            if (!lq.len) continue;
-            int kk = 0;
-            for (j = 1; j < lq.len; j++) {
-                const int i = lq.seqs[j].order;
-                if (phase[i].s >= 3 && !phase[i].d) kk++;
+            lq.indexs = rec.indexs;
+            if (rec.kind == kPhaseDropped) {
+                lq.len = 0;
+                continue;
             }
-            for (j = 0; j < lq.len; j++) {
-                const int i = lq.seqs[j].order;
-                if (kk >= 2) {
-                    if (phase[i].d) phase[i].del = 1;
-                } else if (phase[i].s < phase[i].d || phase[i].d >= 3) phase[i].del = 1;
-            }
-        }
-        for (LqRegion &lq : regions) {  // remove_differ_phase_lqseq, :590-610
-            if (!lq.len) continue;
-            int8_t dif[kLqCanMax] = {0};
-            for (j = 0; j < lq.len; j++)
-                if (phase[lq.seqs[j].order].del) dif[j] = 1;
-            compact_flagged(lq, dif);
-        }
-        KmerBins bins;
-        for (LqRegion &lq : regions) {  // :874-984
-            if (!lq.len) continue;
-            select_most2(lq, lq.len, &s, &k);
-            index = lq.seqs[s].order;
-            if (lq.indexs && s != k && s != 0 && lq.seqs[k].kscore >= 3 && phase[index].s >= phase[index].d + 3) {
-                int sp = 0, kp = 0;
-                for (j = 1; j < lq.len; j++) {
-                    index = lq.seqs[j].order;
-                    if (phase[index].d >= 3) continue;
-                    if (same_seq(lq.seqs[s], lq.seqs[j])) sp += phase[index].s - phase[index].d;
-                    else if (same_seq(lq.seqs[k], lq.seqs[j])) kp += phase[index].s - phase[index].d;
-                }
-                if (sp < kp) s = k;
-            } else if (lq.seqs[0].len > 50 && lq.seqs[s].kscore < lq.len / 3 && lq.seqs[s].kscore < 3) {
-                const int sl = remove_differ_len(lq);
-                if (sl <= 3) {  // large length SD: keep the seed's own version
-                    s = 0;
-                    lq.seqs[s].kscore = 65534;
-                }
-            }
-            if (lq.seqs[s].kscore > 2 || lq.seqs[s].kscore >= lq.len / 2) {
-                lq.sudoseed = lq.seqs[s].seq;
-                lq.sudoseed_len = lq.seqs[s].len;
+            if (rec.kind == kPhaseSeed) {
+                const LqSeq &q = lq.seqs[rec.seed_pos];
+                lq.sudoseed = q.seq;
+                lq.sudoseed_len = q.len;
                 lq.has_seed = true;
-                if (lq.seqs[s].kscore < lq.len / 2)
+                if (rec.lower)
                     for (char &ch : lq.sudoseed) ch = (char)tolower(ch);
                 lq.len = -2;
             } else {
-                remove_differ_len(lq);
-                if (lq.len > 4) {
-                    std::stable_sort(lq.seqs.begin(), lq.seqs.begin() + lq.len,
-                                     [](const LqSeq &a, const LqSeq &b) { return a.len < b.len; });  // compare_seq_by_len
-                    k = lq.len / 2;
-                    while (lq.len > k && (lq.seqs[lq.len - 1].len > 2 * lq.seqs[k].len ||
-                                          lq.seqs[lq.len - 1].len >= 1.4 * lq.seqs[lq.len - 2].len))
-                        lq.len--;
-                    if (k == lq.len) { lq.len = 0; continue; }
-                    j = 0;
-                    k = lq.len / 2;
-                    if (lq.seqs[j].len < lq.seqs[k].len / 2) {
-                        std::reverse(lq.seqs.begin(), lq.seqs.begin() + lq.len);
-                        while (lq.seqs[lq.len - 1].len < lq.seqs[k].len / 2) lq.len--;
-                        if (k == lq.len) { lq.len = 0; continue; }
-                    }
-                }
-                count_kmers(lq, bins, kLqCanMax, 0);
-                count_kscore(lq, bins.data(), 0);
+                lq.len = rec.n;
                 unsigned klastscore, kmaxscore;
                 unsigned kmaxlen = lq.seqs[0].len;
-                if (kmaxlen > 100) {
-                    uint16_t saved[65536 / 256];  // indexed by source-read rank (< aligned reads)
-                    std::vector<uint16_t> big;
-                    uint16_t *sv = saved;
-                    if (n_aligned > sizeof(saved) / sizeof(saved[0])) { big.resize(n_aligned); sv = big.data(); }
-                    for (j = 0; j < lq.len; j++) sv[lq.seqs[j].order] = lq.seqs[j].kscore;
-                    count_kmers(lq, bins, kLqCanMax, 1);
-                    count_kscore(lq, bins.data(), 1);
-                    for (j = 0; j < lq.len; j++) lq.seqs[j].kscore = (uint16_t)(lq.seqs[j].kscore + sv[lq.seqs[j].order]);
-                }
-                sort_by_kscore_desc(lq);
-                kmaxlen = lq.seqs[0].len;
                 klastscore = kmaxscore = lq.seqs[0].kscore;
                 for (k = j = 0; j < lq.len; j++) {
                     const unsigned ks = lq.seqs[j].kscore;
@@ -1122,7 +951,7 @@ class PileImpl {
                     std::vector<std::string> in;
                     for (int x = 0; x < k; x++) in.push_back(lq.seqs[j + x].seq);
                     if (poa_as_request()) {  // (the rest of this region's turn: after_poa)
-                        post_poa((size_t)(&lq - regions.data()), std::move(in), max_aln_lqseq_len, false);
+                        post_poa(ri, std::move(in), max_aln_lqseq_len, false);
                         continue;
                     }
                     { const uint64_t tp = now_ns(); lq.sudoseed = poa_consensus(in); poa_ns_local += now_ns() - tp; }

@@ -365,6 +365,10 @@ enum class BufLevel { levelled, on_demand };
     X(RegionDev, d_regions, device, levelled)                                                                                             \
     X(char, d_strpool, device, levelled)                                                                                                  \
     X(unsigned long long, d_cursor, device, levelled)                                                                                     \
+    /* K22: the piles that ask, a record and the work words per region of the launch -- only in launches with such a pile */             \
+    X(PhasePileDev, d_phase_piles, device, levelled)                                                                                      \
+    X(PhaseRegionDev, d_phase_out, device, levelled)                                                                                      \
+    X(uint32_t, d_phase_work, device, levelled)                                                                                           \
     /* host side: run_chunk's ops and every caller's AlnOut records; the two transfer arenas (see State::h2d / d2h) */                    \
     X(uint32_t, h_ops, pinned, levelled)                                                                                                  \
     X(AlnOut, h_outs, pinned, levelled)                                                                                                   \
@@ -536,6 +540,7 @@ struct DeviceAligner::State {
         kEvPoaRows, kEvPoaAlign, kEvPoaThread, kEvPoaEnd,  // a resident POA round: before K19's rows | K13's launches | K19's thread | behind it
         kEvCnsBegin, kEvCnsEnd,                            // launch_cns: around K20 and its gather
         kEvCnswBegin, kEvCnswEnd,                          // launch_cns_walk: around K21 and its gather
+        kEvPhaseBegin, kEvPhaseEnd,                        // phase_on_pool: around K22's two kernels
         kEvCount
     };
     hipEvent_t evs[kEvCount] = {nullptr};
@@ -660,6 +665,7 @@ struct DeviceAligner::State {
         host_each(ids.size(), ids.size() < 8 || host_threads <= 1, host_threads, ids.size() / 4, true, [&](size_t k) { f(ids[k]); });
     }
     unsigned extract_into_pool(std::vector<RegionDev> &regs, bool rank, std::vector<char> &hstr);
+    void phase_on_pool(std::vector<PhasePileDev> &pp, std::vector<PhaseRegionDev> &recs, size_t n_regions, size_t pool_cap, const char *who);
 };
 
 static int g_ctx_creating = -1;  // index of the context under construction (guarded by g_ctx_mu)
@@ -782,6 +788,11 @@ RuntimeStats DeviceAligner::total_stats() {
         t.cnsw_hifi_jobs += s.cnsw_hifi_jobs; t.cnsw_hifi_declined += s.cnsw_hifi_declined; t.cnsw_hifi_regions += s.cnsw_hifi_regions;
         t.cnsw_fast_jobs += s.cnsw_fast_jobs; t.cnsw_fast_declined += s.cnsw_fast_declined; t.cnsw_launches += s.cnsw_launches;
         t.cnsw_ms += s.cnsw_ms; t.cnsw_d2h_bytes += s.cnsw_d2h_bytes;
+        t.phase_piles += s.phase_piles; t.phase_regions += s.phase_regions; t.phase_pass2 += s.phase_pass2; t.phase_tail += s.phase_tail; t.phase_lower += s.phase_lower;
+        for (int k = 0; k < 4; k++) t.phase_kind[k] += s.phase_kind[k];
+        for (int k = 0; k < 5; k++) t.phase_declined[k] += s.phase_declined[k];
+        t.phase_launches += s.phase_launches; t.phase_ms += s.phase_ms;
+        t.phase_d2h_records += s.phase_d2h_records; t.phase_d2h_strings += s.phase_d2h_strings;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -3033,14 +3044,148 @@ unsigned DeviceAligner::State::extract_into_pool(std::vector<RegionDev> &regs, b
     }
 }
 
+// ---- the phasing and ranking of HiFi candidates (K22)
+
+// Test hook NDGPU_PHASE_DECLINE=<k>: every k-th pile offered to K22 is left to the host rule (counted over the process).
+static bool phase_decline_hook() {
+    static const uint64_t k = env_u64("NDGPU_PHASE_DECLINE", 0);
+    static std::atomic<uint64_t> seen{0};
+    return k && seen.fetch_add(1) % k == k - 1;
+}
+
+// K22 over the region records and the string pool as they stand on the device (behind K11 in run_extract, behind run_phase's upload):
+// pp names the piles that ask and their regions among the launch's n_regions.  The piles' records and the regions' records come back
+// in two exact-size copies; a pile with an error word is counted as declined, its regions' records mean nothing.
+void DeviceAligner::State::phase_on_pool(std::vector<PhasePileDev> &pp, std::vector<PhaseRegionDev> &recs, size_t n_regions, size_t pool_cap,
+                                         const char *who) {
+    hipStream_t st = stream;
+    d_phase_piles.reserve(pp.size());
+    d_phase_out.reserve(n_regions);
+    d_phase_work.reserve(n_regions * kPhaseWorkWords);
+    h2d(d_phase_piles.p, pp.data(), pp.size() * sizeof(PhasePileDev), st);
+    HIP_CHECK(hipMemsetAsync(d_phase_out.p, 0, n_regions * sizeof(PhaseRegionDev), st));
+    mark(kEvPhaseBegin, st);
+    NDGPU_DBG(st, "phase: %zu piles, %zu regions", pp.size(), n_regions);
+    launch_hifi_phase(d_regions.p, d_strpool.p, (unsigned long long)pool_cap, d_phase_piles.p, (int)pp.size(), d_phase_out.p, d_phase_work.p,
+                      (int)n_regions, st);
+    HIP_CHECK(hipGetLastError());
+    mark(kEvPhaseEnd, st);
+    recs.resize(n_regions);
+    d2h(pp.data(), d_phase_piles.p, pp.size() * sizeof(PhasePileDev), st);
+    d2h(recs.data(), d_phase_out.p, n_regions * sizeof(PhaseRegionDev), st);
+    sync_drain(st);
+    const double t_ms = ms(kEvPhaseBegin, kEvPhaseEnd);
+    stats.phase_ms += t_ms;
+    stats.phase_launches++;
+    stats.phase_d2h_records += pp.size() * sizeof(PhasePileDev) + n_regions * sizeof(PhaseRegionDev);
+    uint64_t n_done = 0, n_decl = 0, n_kind[4] = {0, 0, 0, 0}, n_tail = 0, n_pass2 = 0, n_lower = 0;
+    for (const PhasePileDev &P : pp) {
+        if (P.err) {
+            n_decl++;
+            for (int b = 0; b < 5; b++) stats.phase_declined[b] += (P.err >> b) & 1u;
+            if (P.err != kPhaseErrHook)
+                fprintf(stderr, "[ndgpu] hifi_phase: a pile of %u regions, %u reads left to the host rule (error word %u)\n", P.n_regions,
+                        P.n_aligned, P.err);
+            continue;
+        }
+        n_done++;
+        n_pass2 += P.pass2;
+        for (uint32_t r = 0; r < P.n_regions; r++) {
+            const PhaseRegionDev &o = recs[P.first_region + r];
+            if (o.kind > kPhaseRanked) {  // (cannot happen: every region of a pile the kernel finished has its record)
+                fprintf(stderr, "[ndgpu] FATAL: the phasing kernel left a region unfinished (kind %u)\n", (unsigned)o.kind);
+                abort();
+            }
+            n_kind[o.kind]++;
+            n_tail += o.tail;
+            n_lower += o.kind == kPhaseSeed ? o.lower : 0;
+        }
+    }
+    stats.phase_piles += n_done, stats.phase_pass2 += n_pass2, stats.phase_tail += n_tail, stats.phase_lower += n_lower;
+    for (int k = 0; k < 4; k++) stats.phase_kind[k] += n_kind[k], stats.phase_regions += n_kind[k];
+    if (trace_on())
+        fprintf(stderr, "[ndgpu trace] hifi_phase %zu piles (%s): %zu regions | K22 %.3f ms | empty %llu, dropped %llu, seed %llu, ranked %llu "
+                "(%llu tail passes), %llu second passes, %llu declined\n", pp.size(), who, n_regions, t_ms, (unsigned long long)n_kind[0],
+                (unsigned long long)n_kind[1], (unsigned long long)n_kind[2], (unsigned long long)n_kind[3], (unsigned long long)n_tail,
+                (unsigned long long)n_pass2, (unsigned long long)n_decl);
+}
+
+// The batched entry's piles: the candidates go up as one pool, laid out as K11 leaves them (RegionDev::n_ok / cand_off / cand_len /
+// cand_rank), one launch per slice; a declined pile keeps done == false.
+void DeviceAligner::run_phase(PhaseReq *reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    const State::Phase phase(S);
+    hipStream_t st = S.stream;
+    constexpr size_t kSliceBytes = (size_t)256 << 20, kSliceRegions = 1 << 18;
+    std::vector<RegionDev> regs;
+    std::vector<char> pool;
+    std::vector<PhasePileDev> pp;
+    std::vector<PhaseRegionDev> recs;
+    for (size_t a = 0; a < n;) {
+        regs.clear(), pool.clear(), pp.clear();
+        size_t b = a;
+        for (; b < n; b++) {
+            const PhaseReq &rq = reqs[b];
+            size_t bytes = 0;
+            for (size_t r = 0; r < rq.n_regions; r++)
+                for (int c = 0; c < rq.regions[r].n_cand; c++) bytes += rq.regions[r].len[c];
+            if (b > a && (pool.size() + bytes > kSliceBytes || regs.size() + rq.n_regions > kSliceRegions)) break;
+            PhasePileDev P;
+            memset(&P, 0, sizeof(P));
+            P.first_region = (uint32_t)regs.size(), P.n_regions = (uint32_t)rq.n_regions, P.n_aligned = rq.n_aligned;
+            P.decline = phase_decline_hook() ? 1u : 0u;
+            pp.push_back(P);
+            for (size_t r = 0; r < rq.n_regions; r++) {
+                const PhaseRegionIn &in = rq.regions[r];
+                RegionDev g;
+                memset(&g, 0, sizeof(g));
+                g.pile = (uint32_t)(b - a);
+                g.start = in.start, g.end = in.end;
+                g.n_ok = (uint32_t)in.n_cand;
+                for (int c = 0; c < in.n_cand; c++) {
+                    g.cand_off[c] = (uint32_t)pool.size();
+                    g.cand_len[c] = in.len[c];
+                    g.cand_rank[c] = in.src[c];
+                    pool.insert(pool.end(), in.seq[c], in.seq[c] + in.len[c]);
+                }
+                regs.push_back(g);
+            }
+        }
+        if (!regs.empty()) {
+            S.d_regions.reserve(regs.size());
+            S.d_strpool.reserve(pool.size() + 1);
+            S.h2d(S.d_regions.p, regs.data(), regs.size() * sizeof(RegionDev), st);
+            S.h2d(S.d_strpool.p, pool.data(), pool.size(), st);
+            S.phase_on_pool(pp, recs, regs.size(), pool.size(), "batched entry");
+        }
+        for (size_t i = a; i < b; i++) {
+            PhaseReq &rq = reqs[i];
+            const PhasePileDev &P = pp[i - a];
+            if (regs.empty()) {   // (piles without regions: nothing to phase)
+                rq.done = true;
+                continue;
+            }
+            rq.done = !P.err;
+            if (!rq.done) continue;
+            rq.pile.has_heter = (uint8_t)(P.has_heter != 0u), rq.pile.pass2 = (uint8_t)(P.pass2 != 0u);
+            for (size_t r = 0; r < rq.n_regions; r++) rq.out[r] = recs[P.first_region + r];
+        }
+        a = b;
+    }
+}
+
 // The records and their strings into the callers' regions: piles dealt to the context's host threads.
-static void fill_regions(ExtractPile **ep, size_t n, const std::vector<RegionDev> &regs, const std::vector<char> &hstr, int host_threads) {
+static void fill_regions(ExtractPile **ep, size_t n, const std::vector<RegionDev> &regs, const std::vector<char> &hstr, int host_threads,
+                         const std::vector<PhaseRegionDev> &phase_recs, const std::vector<uint8_t> &pile_phased) {
     std::vector<size_t> first(n + 1, 0);
     for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + ep[i]->regions.size();
     host_ranges(n, n < 32 || host_threads <= 1, host_threads, n / 8, [&](size_t a, size_t b) {
         for (size_t i = a; i < b; i++) {
             size_t k = first[i];
             for (RegionReq &r : ep[i]->regions) {
+                r.phased = pile_phased[i] != 0;
+                if (r.phased) r.phase = phase_recs[k];
                 const RegionDev &g = regs[k++];
                 r.n_large = g.n_large;
                 r.ranked = g.ranked != 0;
@@ -3074,7 +3219,28 @@ void DeviceAligner::run_extract(ExtractPile **ep, size_t n, bool offer_rank) {
         fprintf(stderr, "[ndgpu] extract: %zu regions, %llu ranked on the device, %llu tail passes%s\n", regs.size(),
                 (unsigned long long)n_ranked, (unsigned long long)n_tail, again);
     }
-    fill_regions(ep, n, regs, hstr, S.host_threads);
+    // K22 behind K11 (and K14): the HiFi piles of this launch that ask, on the records and the strings where K11 left them.  Every
+    // string still comes down: the engine's selection loop, its POA hand-over and the low-quality-region rounds read them.
+    std::vector<PhaseRegionDev> phase_recs;
+    std::vector<uint8_t> pile_phased(n, 0);
+    if (std::any_of(ep, ep + n, [](const ExtractPile *p) { return p->phase && !p->regions.empty(); })) {
+        std::vector<PhasePileDev> pp;
+        std::vector<size_t> owner;
+        size_t first = 0;
+        for (size_t i = 0; i < n; first += ep[i]->regions.size(), i++) {
+            if (!ep[i]->phase || ep[i]->regions.empty()) continue;
+            PhasePileDev P;
+            memset(&P, 0, sizeof(P));
+            P.first_region = (uint32_t)first, P.n_regions = (uint32_t)ep[i]->regions.size(), P.n_aligned = ep[i]->n_aligned;
+            P.decline = phase_decline_hook() ? 1u : 0u;
+            pp.push_back(P);
+            owner.push_back(i);
+        }
+        S.phase_on_pool(pp, phase_recs, regs.size(), hstr.size() - 1, "behind extract");   // (the pool as far as K11 wrote it)
+        for (size_t k = 0; k < pp.size(); k++) pile_phased[owner[k]] = pp[k].err ? 0 : 1;
+        S.stats.phase_d2h_strings += hstr.size() - 1;
+    }
+    fill_regions(ep, n, regs, hstr, S.host_threads, phase_recs, pile_phased);
 }
 
 }  // namespace ndgpu

@@ -1616,6 +1616,536 @@ __global__ __launch_bounds__(64) void lq_rank_kernel(RegionDev *__restrict__ reg
     if (lane == 0) G.rank_tail = tail ? 1u : 0u, G.ranked = 1u;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// K22: the phasing and ranking of a HiFi pile's candidates (nd_phase.h: hifi_phase_host; lib/nextcorrect.c:512-737, 787-948), behind
+// K11 on the strings K11 left in the pool (or on the pool of a batch of piles: DeviceAligner::run_phase).
+//
+// hifi_phase_kernel: one workgroup of four wavefronts per pile; a wavefront takes the regions w, w + 4, ...  The rule's steps over
+// all regions of a pile are loops over the pile's regions between __syncthreads(): (1) classes, select_most2, the first pass over the
+// heterozygous sites; (2) the second pass, where has_heter && !phase[0].s; (3) mark_del; (4) the compaction, the decision, the sort
+// by length and the trims.  The pile's phase[] table lives in LDS, a word for s and a word for d (bit 31: del) per read, added to
+// with LDS atomics -- sums, whatever the order; the reference's uint16_t is the low half of the word, so that it wraps as the
+// reference's does.  A region's candidates sit one per lane, position j in lane j, as two words: A = input index | class << 8 |
+// kscore << 16 and B = length | source read << 16; class = the smallest input index with the same string (exact: lanes over bytes
+// hash every string, pairs of equal length and hash are compared byte by byte), and same_seq is a comparison of classes ever after.
+// Swaps, the sort and the reversal are shuffles of the two words; the partition by swaps runs on wave-uniform scalars over the
+// ballot of the flags, its pairs are disjoint.  Between the steps A waits in `work`, 40 words a region.  The strings are read again
+// only by the three predicates of the second pass (uniform scalar loops) and by the ranking.  A region that reaches the ranking is
+// left as kPhasePending for hifi_phase_rank_kernel.
+// hifi_phase_rank_kernel: one wavefront per region, K14's method with c = 40: every sequence is counted, so a pass holds up to
+// 40 x 32 distinct k-mers in a 2,048-slot table; the tail windows are staged over the head windows; the head scores are kept by
+// source read (the last position of a read wins, as the reference's table indexed by read does).
+constexpr int kPhThreads = 256, kPhWaves = kPhThreads / 64;
+constexpr uint32_t kPhDel = 1u << 31;
+constexpr uint8_t kPhWorking = 254;   // a region between the steps (kPhasePending: it waits for the ranking)
+constexpr int kPhSlots = 2048;
+
+struct PhaseLds {
+    uint32_t s[kPhaseReads];   // [15:0]: phase[].s
+    uint32_t d[kPhaseReads];   // [15:0]: phase[].d, bit 31: phase[].del
+    uint32_t heter, err;
+};
+
+__device__ __forceinline__ uint32_t ph_sum(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ int ph_sum(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// class of the candidate in every lane < nc: the smallest input index with the same bytes
+__device__ __forceinline__ uint32_t ph_classes(const unsigned char *__restrict__ pool, uint32_t off, uint32_t len, int nc, int lane) {
+    uint32_t hash = 0;
+    for (int i = 0; i < nc; i++) {
+        const uint32_t oi = __shfl(off, i), li = __shfl(len, i);
+        uint32_t h = 0;
+        for (uint32_t b = (uint32_t)lane; b < li; b += 64u) h += ((uint32_t)pool[(size_t)oi + b] + 1u) * ((b * 0x9e3779b1u) | 1u);
+        h = ph_sum(h);
+        if (lane == i) hash = h;
+    }
+    uint32_t cls = (uint32_t)lane;
+    bool found = false;
+    for (int j = 0; j < nc; j++) {   // the classes' first members, ascending
+        const uint32_t oj = __shfl(off, j), lj = __shfl(len, j), hj = __shfl(hash, j), cj = __shfl(cls, j);
+        if (cj != (uint32_t)j) continue;
+        unsigned long long m = __ballot(lane > j && lane < nc && !found && len == lj && hash == hj);
+        for (int t = 0; t < 64 && m != 0ull; t++) {
+            const int i = __ffsll((long long)m) - 1;
+            m &= m - 1ull;
+            const uint32_t oi = __shfl(off, i);
+            uint32_t diff = 0;
+            for (uint32_t b = (uint32_t)lane; b < lj; b += 64u) diff |= (uint32_t)(pool[(size_t)oi + b] ^ pool[(size_t)oj + b]);
+            if (__ballot(diff != 0u) == 0ull && lane == i) cls = (uint32_t)j, found = true;
+        }
+    }
+    return cls;
+}
+
+// the election of select_most2_lqseq / select_most2_lqseq_with_kscore over the eligible positions of [0, n)
+__device__ __forceinline__ int ph_elect(uint32_t A, uint32_t B, unsigned long long elig, int n) {   // m1 | m2 << 8
+    int m1 = 0, m2 = 0;
+    uint32_t ks1 = __shfl(A, 0) >> 16, or1 = __shfl(B, 0) >> 16, ks2 = ks1;
+    for (int j = 0; j < n; j++) {
+        const uint32_t ksj = __shfl(A, j) >> 16, orj = __shfl(B, j) >> 16;
+        if (!((elig >> j) & 1ull)) continue;
+        if (ksj > ks1 || (ksj == ks1 && orj < or1)) {
+            m2 = m1, ks2 = ks1;
+            m1 = j, ks1 = ksj, or1 = orj;
+        } else if (m2 == m1 || ksj > ks2) {
+            m2 = j, ks2 = ksj;
+        }
+    }
+    return m1 | m2 << 8;
+}
+
+// select_most2_lqseq: a class's first position of [0, n) takes the class's size there, every other position 1
+__device__ __forceinline__ int ph_most2(uint32_t &A, uint32_t B, int n, int lane) {
+    const uint32_t cls = (A >> 8) & 0xffu;
+    uint32_t size = 0;
+    bool first = true;
+    for (int q = 0; q < n; q++) {
+        const uint32_t cq = (__shfl(A, q) >> 8) & 0xffu;
+        if (cq == cls) {
+            size++;
+            if (q < lane) first = false;
+        }
+    }
+    if (lane < n) A = (A & 0xffffu) | (first ? size : 1u) << 16;
+    return ph_elect(A, B, __ballot(lane < n && first), n);
+}
+
+// the partition by swaps (lib/nextcorrect.c:524-537, 599-609) over the flags D of [0, n): returns the new length
+__device__ __forceinline__ int ph_partition(uint32_t &A, uint32_t &B, unsigned long long D, int n, int lane) {
+    int k = n, partner = lane;
+    for (int j = 0; j < n && j < k; j++) {
+        if (!((D >> j) & 1ull)) continue;
+        for (k--; k > j; k--)
+            if (!((D >> k) & 1ull)) {
+                if (lane == j) partner = k;
+                if (lane == k) partner = j;
+                break;
+            }
+    }
+    A = __shfl(A, partner), B = __shfl(B, partner);
+    return k;
+}
+
+// remove_differ_len_lqseq (:512-539)
+__device__ __forceinline__ int ph_differ_len(uint32_t &A, uint32_t &B, int &n, int span, int lane) {
+    const int a = span / 10 > 30 ? span / 10 : 30, offset = a < span / 3 ? a : span / 3;
+    const int len = (int)(B & 0xffffu);
+    const bool ok = len + offset >= span && len <= span + offset;
+    const unsigned long long in = __ballot(lane < n), okm = __ballot(lane < n && ok);
+    const int s = __popcll(okm);
+    if (s != n && (s >= n / 2 || (s >= n / 3 && s >= 3))) n = ph_partition(A, B, in & ~okm, n, lane);
+    return s;
+}
+
+// the three predicates of the second pass: wave-uniform scalar loops over the pool's bytes
+__device__ __forceinline__ int ph_prefixhomo(const unsigned char *a, int na, const unsigned char *b, int nb) {
+    int i = 0, j = 0;
+    while (i < na && j < nb) {
+        if (a[i] != b[j]) return 0;
+        while (i + 1 < na && a[i] == a[i + 1]) i++;
+        while (j + 1 < nb && b[j] == b[j + 1]) j++;
+        i++, j++;
+    }
+    return 1;
+}
+__device__ __forceinline__ void ph_run_ends(const unsigned char *q, int n, int &s, int &e) {
+    s = 0;
+    while (s + 1 < n && q[s] == q[s + 1]) s++;
+    e = n - 1;
+    while (e > 0 && q[e - 1] == q[e]) e--;
+}
+__device__ __forceinline__ int ph_homo_end(const unsigned char *a, int na, const unsigned char *b, int nb) {
+    int as, ae, bs, be;
+    ph_run_ends(a, na, as, ae);
+    ph_run_ends(b, nb, bs, be);
+    if (ae <= as && be <= bs) return 1;
+    if (ae - as != be - bs) return 0;
+    for (int i = 0; i <= ae - as; i++)
+        if (a[i + as] != b[i + bs]) return 0;
+    return 1;
+}
+__device__ __forceinline__ int ph_trim_endssr(const unsigned char *a, int na, const unsigned char *b, int nb) {
+    if (na < nb) {
+        const unsigned char *t = a;
+        a = b, b = t;
+        const int tn = na;
+        na = nb, nb = tn;
+    }
+    int i;
+    for (i = 0; i < nb; i++)
+        if (a[i] != b[i]) return 0;
+    for (int j = na - 1; j >= i; j--) {
+        const int at = nb - (na - j);
+        if (at < 0 || a[j] != b[at]) return 0;   // (in front of the shorter string: a mismatch, as in nd_phase.h)
+    }
+    return 1;
+}
+__device__ __forceinline__ int ph_like_first(const unsigned char *a, int na, const unsigned char *b, int nb) {
+    return ph_homo_end(a, na, b, nb) || ph_trim_endssr(a, na, b, nb) || ph_prefixhomo(a, na, b, nb);
+}
+
+// a region's positions from `work` and its record of K11
+__device__ __forceinline__ void ph_load(const RegionDev &G, const uint32_t *__restrict__ W, int nc, int lane, uint32_t &A, uint32_t &B,
+                                        uint32_t &off) {
+    A = 0u, B = 0u, off = 0u;
+    if (lane < nc) {
+        A = W[lane];
+        const uint32_t i = A & 0xffu;
+        B = (uint32_t)G.cand_len[i] | (uint32_t)G.cand_rank[i] << 16;
+        off = G.cand_off[i];
+    }
+}
+__device__ __forceinline__ void ph_finish(PhaseRegionDev &O, uint32_t A, int nc, int lane, uint8_t kind, int n, uint32_t lower,
+                                          uint32_t seed, uint32_t seed_pos) {
+    if (lane < kPhaseCanMax) {
+        O.perm[lane] = lane < nc ? (uint8_t)(A & 0xffu) : (uint8_t)0;
+        O.kscore[lane] = lane < nc ? (uint16_t)(A >> 16) : (uint16_t)0;
+    }
+    if (lane == 0) O.kind = kind, O.lower = (uint8_t)lower, O.tail = 0, O.n = (int16_t)n, O.seed = (uint8_t)seed, O.seed_pos = (uint8_t)seed_pos;
+}
+
+__global__ __launch_bounds__(kPhThreads) void hifi_phase_kernel(const RegionDev *__restrict__ regions, const char *__restrict__ strpool,
+                                                                 unsigned long long cap, PhasePileDev *__restrict__ piles,
+                                                                 PhaseRegionDev *__restrict__ out, uint32_t *__restrict__ work) {
+    __shared__ PhaseLds L;
+    PhasePileDev &P = piles[blockIdx.x];
+    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t first = P.first_region, nreg = P.n_regions, n_aligned = P.n_aligned;
+    {
+        uint32_t e = P.decline ? kPhaseErrHook : 0u;
+        if (n_aligned > kPhaseReads) e |= kPhaseErrReads;
+        if (nreg > kPhaseRegionsMax) e |= kPhaseErrRegions;
+        if (e) {   // (the whole workgroup)
+            if (tid == 0) P.err = e, P.has_heter = 0u, P.pass2 = 0u;
+            return;
+        }
+    }
+    for (uint32_t i = (uint32_t)tid; i < n_aligned; i += (uint32_t)kPhThreads) L.s[i] = 0u, L.d[i] = 0u;
+    if (tid == 0) L.heter = 0u, L.err = 0u;
+    __syncthreads();
+    const unsigned char *pool = (const unsigned char *)strpool;
+
+    // (1) classes, select_most2, the heterozygous sites (:789-810)
+    for (uint32_t r = (uint32_t)w; r < nreg; r += (uint32_t)kPhWaves) {
+        const RegionDev &G = regions[first + r];
+        PhaseRegionDev &O = out[first + r];
+        uint32_t *W = work + (size_t)(first + r) * kPhaseWorkWords;
+        const int nc = (int)G.n_ok;
+        if (nc == 0) continue;   // (the record stays as the caller cleared it: kPhaseEmpty)
+        if (nc > kPhaseCanMax) {
+            if (lane == 0) atomicOr(&L.err, kPhaseErrPool);
+            continue;
+        }
+        uint32_t off = 0, len = 0, src = 0;
+        if (lane < nc) off = G.cand_off[lane], len = G.cand_len[lane], src = G.cand_rank[lane];
+        const bool bad_pool = __ballot(lane < nc && (unsigned long long)off + len > cap) != 0ull;
+        const bool bad_src = __ballot(lane < nc && src >= n_aligned) != 0ull;
+        if (bad_pool || bad_src) {
+            if (lane == 0) atomicOr(&L.err, (bad_pool ? kPhaseErrPool : 0u) | (bad_src ? kPhaseErrSource : 0u));
+            continue;
+        }
+        uint32_t A = (uint32_t)lane | ph_classes(pool, off, len, nc, lane) << 8;
+        if (lane >= nc) A = 0u;
+        const uint32_t B = len | src << 16;
+        const int sk = ph_most2(A, B, nc, lane), s = sk & 0xff, k = sk >> 8;
+        const uint32_t As = __shfl(A, s), Ak = __shfl(A, k), Bs = __shfl(B, s), Bk = __shfl(B, k);
+        const uint32_t os = __shfl(off, s), ok = __shfl(off, k);
+        const uint32_t kss = As >> 16, ksk = Ak >> 16, ls = Bs & 0xffffu, lk = Bk & 0xffffu;
+        uint32_t indexs = 0;
+        if (s != k && ksk >= 3u && ls == lk) {
+            if (s == 0 || k == 0) {
+                const uint32_t c0 = ((s == 0 ? As : Ak) >> 8) & 0xffu, ch = ((s == 0 ? Ak : As) >> 8) & 0xffu, c = (A >> 8) & 0xffu;
+                if (lane < nc) {
+                    if (c == c0) atomicAdd(&L.s[src], 1u);
+                    else if (c == ch) atomicAdd(&L.d[src], 1u);
+                }
+            }
+            indexs = 1;
+        }
+        bool het = indexs == 1u;
+        if (!het && s != k && ksk >= 5u && (double)(int)(kss + ksk) >= (double)nc * 0.8)
+            het = !ph_prefixhomo(pool + os, (int)ls, pool + ok, (int)lk);
+        if (het && lane == 0) atomicOr(&L.heter, 1u);
+        if (lane < (int)kPhaseWorkWords) W[lane] = A;
+        if (lane == 0) O.kind = kPhWorking, O.indexs = (uint8_t)indexs, O.n = (int16_t)nc;
+    }
+    __syncthreads();
+    const uint32_t err = L.err, heter = L.heter;
+    const bool pass2 = heter != 0u && (L.s[0] & 0xffffu) == 0u;
+    __syncthreads();   // (phase[0].s is read before the second pass adds to it)
+    if (err) {
+        if (tid == 0) P.err = err, P.has_heter = 0u, P.pass2 = 0u;
+        return;
+    }
+    if (tid == 0) P.err = 0u, P.has_heter = heter, P.pass2 = pass2 ? 1u : 0u;
+
+    // (2) no SNP was found, but a candidate site (:812-854)
+    if (pass2)
+        for (uint32_t r = (uint32_t)w; r < nreg; r += (uint32_t)kPhWaves) {
+            const RegionDev &G = regions[first + r];
+            PhaseRegionDev &O = out[first + r];
+            const int nc = (int)G.n_ok;
+            if (nc == 0) continue;
+            uint32_t A, B, off;
+            ph_load(G, work + (size_t)(first + r) * kPhaseWorkWords, nc, lane, A, B, off);
+            const int sk = ph_elect(A, B, ~0ull, nc), s = sk & 0xff, k = sk >> 8;
+            const uint32_t As = __shfl(A, s), Ak = __shfl(A, k), Bs = __shfl(B, s), Bk = __shfl(B, k), B0 = __shfl(B, 0);
+            const unsigned char *ps = pool + __shfl(off, s), *pk = pool + __shfl(off, k), *p0 = pool + __shfl(off, 0);
+            const int kss = (int)(As >> 16), ksk = (int)(Ak >> 16), ls = (int)(Bs & 0xffffu), lk = (int)(Bk & 0xffffu), l0 = (int)(B0 & 0xffffu);
+            if (s != k && ksk >= 5 && (double)(kss + ksk) >= (double)nc * 0.8 &&
+                (ls >= lk + 5 || lk >= ls + 5 || !ph_prefixhomo(ps, ls, pk, lk))) {
+                int s_, k_;
+                if (s == 0) s_ = 1, k_ = 0;
+                else if (k == 0) s_ = 0, k_ = 1;
+                else s_ = ph_like_first(ps, ls, p0, l0), k_ = ph_like_first(pk, lk, p0, l0);
+                if ((s_ != 0) != (k_ != 0)) {
+                    const uint32_t cs = ((s_ ? As : Ak) >> 8) & 0xffu, ch = ((s_ ? Ak : As) >> 8) & 0xffu, c = (A >> 8) & 0xffu;
+                    if (lane < nc) {
+                        if (c == cs) atomicAdd(&L.s[B >> 16], 1u);
+                        else if (c == ch) atomicAdd(&L.d[B >> 16], 1u);
+                    }
+                    if (lane == 0) O.indexs = 2;
+                }   // (else: indexs stays)
+            } else if (lane == 0) O.indexs = 0;
+        }
+    __syncthreads();
+
+    // (3) mark_del_lqseq (:570-588)
+    for (uint32_t r = (uint32_t)w; r < nreg; r += (uint32_t)kPhWaves) {
+        const RegionDev &G = regions[first + r];
+        const int nc = (int)G.n_ok;
+        if (nc == 0) continue;
+        uint32_t A, B, off;
+        ph_load(G, work + (size_t)(first + r) * kPhaseWorkWords, nc, lane, A, B, off);
+        const uint32_t src = B >> 16, s16 = L.s[src] & 0xffffu, d16 = L.d[src] & 0xffffu;
+        const int kk = __popcll(__ballot(lane >= 1 && lane < nc && s16 >= 3u && d16 == 0u));
+        if (lane < nc && (kk >= 2 ? d16 != 0u : (s16 < d16 || d16 >= 3u))) atomicOr(&L.d[src], kPhDel);
+    }
+    __syncthreads();
+
+    // (4) remove_differ_phase_lqseq (:590-610) and a region's turn up to its ranking (:874-933)
+    for (uint32_t r = (uint32_t)w; r < nreg; r += (uint32_t)kPhWaves) {
+        const RegionDev &G = regions[first + r];
+        PhaseRegionDev &O = out[first + r];
+        uint32_t *W = work + (size_t)(first + r) * kPhaseWorkWords;
+        const int nc = (int)G.n_ok;
+        if (nc == 0) continue;
+        uint32_t A, B, off;
+        ph_load(G, W, nc, lane, A, B, off);
+        int n = ph_partition(A, B, __ballot(lane < nc && (L.d[B >> 16] & kPhDel) != 0u), nc, lane);
+        if (n == 0) {   // every candidate's read was phased away
+            ph_finish(O, A, nc, lane, kPhaseDropped, 0, 0u, 0u, 0u);
+            continue;
+        }
+        const uint32_t indexs = O.indexs;
+        const int span = (int)(G.end - G.start + 1u);
+        const int sk = ph_most2(A, B, n, lane);
+        int s = sk & 0xff, k = sk >> 8;
+        {
+            const uint32_t As = __shfl(A, s), Ak = __shfl(A, k), Bs = __shfl(B, s), B0 = __shfl(B, 0);
+            const int kss = (int)(As >> 16), ksk = (int)(Ak >> 16);
+            const int ps = (int)(L.s[Bs >> 16] & 0xffffu), pd = (int)(L.d[Bs >> 16] & 0xffffu);
+            const int my_s = (int)(L.s[B >> 16] & 0xffffu), my_d = (int)(L.d[B >> 16] & 0xffffu);
+            if (indexs && s != k && s != 0 && ksk >= 3 && ps >= pd + 3) {
+                const uint32_t cs = (As >> 8) & 0xffu, ck = (Ak >> 8) & 0xffu, c = (A >> 8) & 0xffu;
+                const bool act = lane >= 1 && lane < n && my_d < 3;
+                const int sp = ph_sum(act && c == cs ? my_s - my_d : 0), kp = ph_sum(act && c != cs && c == ck ? my_s - my_d : 0);
+                if (sp < kp) s = k;
+            } else if ((int)(B0 & 0xffffu) > 50 && kss < n / 3 && kss < 3) {
+                const int sl = ph_differ_len(A, B, n, span, lane);
+                if (sl <= 3) {   // large length SD: the seed's own version
+                    s = 0;
+                    if (lane == 0) A = (A & 0xffffu) | 65534u << 16;
+                }
+            }
+        }
+        const uint32_t Af = __shfl(A, s);
+        const int ksf = (int)(Af >> 16);
+        if (ksf > 2 || ksf >= n / 2) {
+            ph_finish(O, A, nc, lane, kPhaseSeed, -2, ksf < n / 2 ? 1u : 0u, Af & 0xffu, (uint32_t)s);
+            continue;
+        }
+        ph_differ_len(A, B, n, span, lane);
+        bool dropped = false;
+        if (n > 4) {
+            {   // qsort(compare_seq_by_len), stable: a rank by counting, then the inverse by search
+                const uint32_t len = B & 0xffffu;
+                int rk = lane < n ? 0 : lane;
+                for (int q = 0; q < n; q++) {
+                    const uint32_t lq = __shfl(B, q) & 0xffffu;
+                    if (lane < n && (lq < len || (lq == len && q < lane))) rk++;
+                }
+                int from = lane;
+                for (int q = 0; q < n; q++)
+                    if (__shfl(rk, q) == lane) from = q;
+                A = __shfl(A, from), B = __shfl(B, from);
+            }
+            k = n / 2;
+            for (int t = 0; t < kPhaseCanMax && n > k; t++) {
+                const int l1 = (int)(__shfl(B, n - 1) & 0xffffu), lk = (int)(__shfl(B, k) & 0xffffu), l2 = (int)(__shfl(B, n - 2) & 0xffffu);
+                if (!(l1 > 2 * lk || (double)l1 >= 1.4 * (double)l2)) break;
+                n--;
+            }
+            if (k == n) dropped = true;
+            else {
+                k = n / 2;
+                if ((int)(__shfl(B, 0) & 0xffffu) < (int)(__shfl(B, k) & 0xffffu) / 2) {
+                    const int from = lane < n ? n - 1 - lane : lane;   // reverse_lqseq
+                    A = __shfl(A, from), B = __shfl(B, from);
+                    for (int t = 0; t < kPhaseCanMax && n > 1; t++) {
+                        if (!((int)(__shfl(B, n - 1) & 0xffffu) < (int)(__shfl(B, k) & 0xffffu) / 2)) break;
+                        n--;
+                    }
+                    if (k == n) dropped = true;
+                }
+            }
+        }
+        if (dropped) {
+            ph_finish(O, A, nc, lane, kPhaseDropped, 0, 0u, 0u, 0u);
+            continue;
+        }
+        if (lane < (int)kPhaseWorkWords) W[lane] = A;
+        if (lane == 0) O.n = (int16_t)n, O.kind = kPhasePending;
+    }
+}
+
+struct PhRankLds {
+    uint32_t tab[kPhSlots];                // [31:16] k-mer, [15:0] count; 0: empty
+    uint32_t off[kRankMax];                // input order: pool offset, length, source read
+    uint16_t len[kRankMax], src[kRankMax];
+    uint16_t km[kRankMax * kRankKm];       // input order: the staged window's k-mers
+    uint16_t sc[kRankMax], saved[kRankMax];  // by position
+    uint8_t code[kRankMax * kRankWin];     // input order: the staged window's byte codes
+    uint8_t ord[kRankMax];                 // position -> input index
+};
+__device__ __forceinline__ uint32_t ph_slot(uint32_t km) { return (km * 0x9e3bu >> 3) & (uint32_t)(kPhSlots - 1); }
+
+// the window's k-mers of every sequence, input order (K14: rank_stage)
+__device__ __forceinline__ void ph_stage(PhRankLds &T, const unsigned char *__restrict__ pool, int nc, int from_tail, int lane) {
+    for (int i = lane; i < nc * kRankWin; i += 64) {
+        const int s = i / kRankWin, b = i - s * kRankWin, len = (int)T.len[s];
+        const int o = from_tail && len > kRankWin ? len - kRankWin : 0;
+        T.code[i] = b < len ? (uint8_t)rank_code(pool[(size_t)T.off[s] + (size_t)(o + b)]) : (uint8_t)0;
+    }
+    __syncthreads();
+    for (int i = lane; i < nc * kRankKm; i += 64) {
+        const int s = i / kRankKm, k = i - s * kRankKm;
+        uint32_t km = 0;
+        if (k < rank_nkm((int)T.len[s])) {
+            const uint8_t *c = &T.code[s * kRankWin + k];
+#pragma unroll
+            for (int x = 0; x < kRankK; x++) km = km << 2 | c[x];
+        }
+        T.km[i] = (uint16_t)km;
+    }
+    __syncthreads();
+}
+
+// count the k-mers of the positions [0, n), score every one of them (K14: rank_pass with c >= n)
+__device__ __forceinline__ void ph_pass(PhRankLds &T, int n, int lane) {
+    for (int i = lane; i < kPhSlots; i += 64) T.tab[i] = 0u;
+    __syncthreads();
+    for (int i = lane; i < n * kRankKm; i += 64) {
+        const int p = i / kRankKm, k = i - p * kRankKm, s = (int)T.ord[p];
+        if (k >= rank_nkm((int)T.len[s])) continue;
+        const uint32_t km = T.km[s * kRankKm + k];
+        uint32_t h = ph_slot(km);
+        for (int t = 0; t < kPhSlots; t++, h = (h + 1u) & (uint32_t)(kPhSlots - 1)) {   // (<= 1,280 keys in 2,048 slots: an empty one exists)
+            uint32_t cur = T.tab[h];
+            if (cur == 0u) {
+                cur = atomicCAS(&T.tab[h], 0u, km << 16 | 1u);
+                if (cur == 0u) break;
+            }
+            if ((cur >> 16) == km) {
+                atomicAdd(&T.tab[h], 1u);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i0 = 0; i0 < n * kRankKm; i0 += 64) {   // a position per half wavefront, a k-mer per lane of it
+        const int i = i0 + lane, p = i / kRankKm, k = i - p * kRankKm;
+        uint32_t v = 0;
+        if (p < n) {
+            const int s = (int)T.ord[p];
+            if (k < rank_nkm((int)T.len[s])) {
+                const uint32_t km = T.km[s * kRankKm + k];
+                uint32_t h = ph_slot(km);
+                for (int t = 0; t < kPhSlots; t++, h = (h + 1u) & (uint32_t)(kPhSlots - 1)) {
+                    const uint32_t cur = T.tab[h];
+                    if (cur == 0u) break;
+                    if ((cur >> 16) == km) {
+                        v = cur & 0xffffu;
+                        break;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = kRankKm / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+        if (p < n && k == 0) T.sc[p] = (uint16_t)v;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void hifi_phase_rank_kernel(const RegionDev *__restrict__ regions, const char *__restrict__ strpool,
+                                                              PhaseRegionDev *__restrict__ out, const uint32_t *__restrict__ work) {
+    __shared__ PhRankLds T;
+    static_assert(kRankKm == 32 && kRankMax == kPhaseCanMax, "a position's k-mers are one half wavefront");
+    PhaseRegionDev &O = out[blockIdx.x];
+    if (O.kind != kPhasePending) return;   // (the whole wavefront)
+    const RegionDev &G = regions[blockIdx.x];
+    const int lane = (int)threadIdx.x, nc = (int)G.n_ok, n = (int)O.n;
+    if (nc < 1 || nc > kRankMax || n < 1 || n > nc) return;   // (cannot happen: hifi_phase_kernel left the region)
+    const uint32_t A = lane < nc ? work[(size_t)blockIdx.x * kPhaseWorkWords + (uint32_t)lane] : 0u;
+    if (lane < nc) T.off[lane] = G.cand_off[lane], T.len[lane] = G.cand_len[lane], T.src[lane] = G.cand_rank[lane];
+    if (lane < n) T.ord[lane] = (uint8_t)(A & 0xffu);
+    __syncthreads();
+    const unsigned char *pool = (const unsigned char *)strpool;
+    ph_stage(T, pool, nc, 0, lane);
+    ph_pass(T, n, lane);
+    const bool tail = T.len[T.ord[0]] > 100u;
+    if (tail) {
+        if (lane < n) {   // save_kscore by source read: the last position of a read wins
+            uint16_t v = T.sc[lane];
+            const uint16_t src = T.src[T.ord[lane]];
+            for (int q = lane + 1; q < n; q++)
+                if (T.src[T.ord[q]] == src) v = T.sc[q];
+            T.saved[lane] = v;
+        }
+        ph_stage(T, pool, nc, 1, lane);
+        ph_pass(T, n, lane);
+        if (lane < n) T.sc[lane] = (uint16_t)(T.sc[lane] + T.saved[lane]);
+        __syncthreads();
+    }
+    {   // qsort(compare_seq_by_kscore), stable, descending: a rank by counting
+        uint32_t s = 0, o = 0, r = 0;
+        if (lane < n) {
+            s = T.sc[lane], o = T.ord[lane];
+            for (int q = 0; q < n; q++) {
+                const uint32_t t = T.sc[q];
+                r += (t > s || (t == s && q < lane)) ? 1u : 0u;
+            }
+        }
+        __syncthreads();
+        if (lane < n) T.sc[r] = (uint16_t)s, T.ord[r] = (uint8_t)o;
+        __syncthreads();
+    }
+    if (lane < kPhaseCanMax) {
+        O.perm[lane] = lane < n ? T.ord[lane] : lane < nc ? (uint8_t)(A & 0xffu) : (uint8_t)0;
+        O.kscore[lane] = lane < n ? T.sc[lane] : lane < nc ? (uint16_t)(A >> 16) : (uint16_t)0;
+    }
+    if (lane == 0) O.kind = kPhaseRanked, O.lower = 0, O.tail = tail ? 1 : 0, O.seed = 0, O.seed_pos = 0;
+}
+
 }  // namespace
 
 void launch_lq_msa(LqPileDev *piles, LqJobDev *jobs, const LqPieceDev *pieces, const AlnTask *tasks, const AlnOut *outs, const uint32_t *ops,
@@ -1671,6 +2201,14 @@ void launch_poa_graph_consensus(PoaGraphDev *graphs, const uint32_t *ids, int n,
 void launch_lq_rank(RegionDev *regions, const char *strpool, unsigned long long strpool_cap, uint32_t min_n, int n_regions, void *stream) {
     if (n_regions <= 0) return;
     hipLaunchKernelGGL(lq_rank_kernel, dim3((unsigned)n_regions), dim3(64), 0, (hipStream_t)stream, regions, strpool, strpool_cap, min_n);
+}
+
+void launch_hifi_phase(const RegionDev *regions, const char *strpool, unsigned long long strpool_cap, PhasePileDev *piles, int n_piles,
+                       PhaseRegionDev *out, uint32_t *work, int n_regions, void *stream) {
+    if (n_piles <= 0 || n_regions <= 0) return;
+    hipLaunchKernelGGL(hifi_phase_kernel, dim3((unsigned)n_piles), dim3(kPhThreads), 0, (hipStream_t)stream, regions, strpool, strpool_cap,
+                       piles, out, work);
+    hipLaunchKernelGGL(hifi_phase_rank_kernel, dim3((unsigned)n_regions), dim3(64), 0, (hipStream_t)stream, regions, strpool, out, work);
 }
 
 }  // namespace ndgpu

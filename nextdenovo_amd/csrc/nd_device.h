@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "nd_lockstep.h"
+#include "nd_phase.h"
 
 namespace ndgpu {
 
@@ -448,6 +449,35 @@ void launch_extract(const PileDev *piles, const ReadDev *reads, const uint32_t *
 
 // K14: ranks the candidates of every region with want_rank and min_n <= n_ok <= 40 whose strings lie inside strpool[0, strpool_cap)
 void launch_lq_rank(RegionDev *regions, const char *strpool, unsigned long long strpool_cap, uint32_t min_n, int n_regions, void *stream);
+
+// ---- K22: the phasing and ranking of a HiFi pile's candidates (hifi_phase_kernel + hifi_phase_rank_kernel, lq_kernels.hip; the
+// rule: hifi_phase_host of nd_phase.h) ----
+// A pile's table of per-read phase scores lives in LDS, two words a read: a pile with more aligned reads is declined.
+constexpr uint32_t kPhaseReads = 2048;
+constexpr uint32_t kPhaseRegionsMax = 65535;   // beyond: the reference's 16-bit scores may wrap; declined
+typedef PhaseRecord PhaseRegionDev;            // one per region, indexed like the launch's RegionDev records
+struct PhasePileDev {       // one pile that asks: 32 bytes
+    uint32_t first_region;  // its regions are RegionDev / PhaseRegionDev [first_region, first_region + n_regions)
+    uint32_t n_regions;
+    uint32_t n_aligned;
+    uint32_t decline;       // test hook: the kernel leaves the pile with kPhaseErrHook
+    // outputs
+    uint32_t err;           // kPhaseErr* bits; nonzero: declined, the host rule takes the pile
+    uint32_t has_heter, pass2;
+    uint32_t pad_;
+};
+enum : uint32_t {
+    kPhaseErrReads = 1u,    // n_aligned > kPhaseReads
+    kPhaseErrRegions = 2u,  // n_regions > kPhaseRegionsMax
+    kPhaseErrPool = 4u,     // a candidate's bytes lie outside the string pool, or a region has more than 40 candidates
+    kPhaseErrHook = 8u,
+    kPhaseErrSource = 16u   // a candidate's source read is not below n_aligned
+};
+constexpr uint32_t kPhaseWorkWords = 40;       // words of work state per region between the kernel's steps
+constexpr uint8_t kPhasePending = 255;         // (device only) PhaseRecord::kind of a region that waits for its ranking
+// work: kPhaseWorkWords words per region; out is cleared by the caller before the launch
+void launch_hifi_phase(const RegionDev *regions, const char *strpool, unsigned long long strpool_cap, PhasePileDev *piles, int n_piles,
+                       PhaseRegionDev *out, uint32_t *work, int n_regions, void *stream);
 
 constexpr uint64_t kOffDb = 1ull << 63;   // offset flag: sequence lives in the resident read DB
 constexpr uint64_t kOffMask = kOffDb - 1;

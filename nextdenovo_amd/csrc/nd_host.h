@@ -9,6 +9,8 @@
 #include <thread>
 #include <vector>
 
+#include "nd_phase.h"
+
 namespace ndgpu {
 
 // ABI-compatible with the reference's `consensus_trimed` (lib/nextcorrect.h:70-74).
@@ -138,11 +140,17 @@ struct RegionReq {
     uint8_t rank_tail = 0;               // the tail windows were ranked too
     uint8_t rank_order[40] = {0};        // candidate index at rank r
     uint16_t rank_kscore[40] = {0};      // its score
+    // optional: the HiFi phasing and ranking of `cands` (hifi_phase_host of nd_phase.h), where ExtractPile::phase asked for it and the
+    // backend offers it.  A backend that does not fill the record leaves phased false, and the engine runs the rule on the host.
+    bool phased = false;
+    PhaseRecord phase;
 };
 
 struct ExtractPile {
     int slot = -1;
     bool rank = false;                   // the engine would take a ranking of every region with five or more candidates
+    bool phase = false;                  // (HiFi) the engine would take the phasing records of the pile's regions
+    unsigned n_aligned = 0;              // ... of a pile with this many aligned reads (MainPile::n_aligned)
     std::vector<RegionReq> regions;
 };
 

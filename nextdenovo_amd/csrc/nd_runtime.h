@@ -100,6 +100,28 @@ struct RuntimeStats {
     uint64_t cnsw_launches = 0;          // launches of K21 (each with its gather)
     double cnsw_ms = 0;                  // their HIP-event time
     uint64_t cnsw_d2h_bytes = 0;         // result records, dense words, windows and strings brought back
+    // the phasing and ranking of HiFi candidates on the device (K22; ndgpu_phase_stats)
+    uint64_t phase_piles = 0;            // piles K22 finished (run_extract's piles, run_phase's jobs)
+    uint64_t phase_regions = 0;          // their regions ...
+    uint64_t phase_kind[4] = {0, 0, 0, 0};  // ... by kind (kPhaseEmpty, kPhaseDropped, kPhaseSeed, kPhaseRanked)
+    uint64_t phase_pass2 = 0;            // piles whose second pass ran
+    uint64_t phase_tail = 0;             // ranked regions that took the tail pass
+    uint64_t phase_lower = 0;            // seed regions whose pseudo-seed goes to lower case
+    uint64_t phase_declined[5] = {0, 0, 0, 0, 0};  // piles left to the host rule, by kPhaseErr* bit: reads, regions, pool, hook, source
+    uint64_t phase_launches = 0;         // launches of K22 (its two kernels)
+    double phase_ms = 0;                 // their HIP-event time
+    uint64_t phase_d2h_records = 0;      // bytes of pile and region records brought back
+    uint64_t phase_d2h_strings = 0;      // bytes of candidate strings brought back beside them (run_extract)
+};
+
+// One pile of the batched entry ndgpu_hifi_phase_batch (DeviceAligner::run_phase): what hifi_phase_host (nd_phase.h) returns for it.
+struct PhaseReq {
+    unsigned n_aligned = 0;
+    const PhaseRegionIn *regions = nullptr;
+    size_t n_regions = 0;
+    PhaseRecord *out = nullptr;            // n_regions records
+    PhasePileOut pile;
+    bool done = false;                     // false: declined, the host rule takes the pile
 };
 
 // One walk of the batched entry ndgpu_cns_walk_batch in mode 1 (HiFi: cns_kmer_host of nd_cns.h) or 2 (-fast: cns_fast_host).
@@ -167,6 +189,7 @@ class DeviceAligner {
     void run_rank(RankReq *reqs, size_t n);   // the batched entry's problems: one pool up, one copy back
     void run_cns(CnsReq *reqs, size_t n);     // the batched entry's walks through K20; req.done = false: declined, the host routine takes it
     void run_cns_walk(CnsWalkReq *reqs, size_t n);   // ... of modes 1 and 2 through K21
+    void run_phase(PhaseReq *reqs, size_t n);        // the batched entry's HiFi piles through K22: one pool up, the records back
     void run_lq(LqRound **rounds, size_t n);
     // req.done = false: declined, the caller's host path takes it.  form 0: NDGPU_POA_RESIDENT decides; 1: resident graphs (K19);
     // 2: K13's rounds with the graphs on the host
@@ -221,6 +244,7 @@ class HipBackend : public Backend {
     void run_rank(RankReq *reqs, size_t n) { dev_.run_rank(reqs, n); }
     void run_cns(CnsReq *reqs, size_t n) { dev_.run_cns(reqs, n); }
     void run_cns_walk(CnsWalkReq *reqs, size_t n) { dev_.run_cns_walk(reqs, n); }
+    void run_phase(PhaseReq *reqs, size_t n) { dev_.run_phase(reqs, n); }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
     void run_align_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) { dev_.align_batch_runs(jobs, n, res, runs); }
     bool run_lq(LqRound **rounds, size_t n) override {
