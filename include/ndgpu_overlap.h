@@ -378,7 +378,9 @@ int64_t ndgpu_ovl_map2_realign(ndgpu_ovl_index *idx, ndgpu_ovl_index *q_mini, nd
                                const uint32_t *q_words, uint64_t q_n_words, const uint64_t *q_word_off, const uint32_t *q_lens,
                                const uint32_t *q_ids, ndgpu_ovl_rec10 **recs);
 /* replaces: filter_ovl (lib/ovl.c:449-563), whose per-read state lives for the whole run (opt.os, main.c:272), encode_ovl_i
- * (lib/ovl.c:205-253) and out_bl (lib/ovl.c:339-362).  Host code: a record's verdict depends on every record before it. */
+ * (lib/ovl.c:205-253) and out_bl (lib/ovl.c:339-362).  The state is host memory.  A record's verdict depends on the records before it
+ * only through "has this read looked contained twice yet": the host loop walks the records in order, K23 (opt-in, below) computes
+ * the same verdicts, bytes and per-read state on the device without such a walk. */
 typedef struct ndgpu_s2_state ndgpu_s2_state;
 ndgpu_s2_state *ndgpu_s2_new(void);
 void ndgpu_s2_free(ndgpu_s2_state *st);
@@ -387,6 +389,28 @@ void ndgpu_s2_free(ndgpu_s2_state *st);
  * bytes 00 FF (init_ovl_mode, lib/ovl.c:70-75), the caller's to write.  Returns the byte count, < 0 on error. */
 int64_t ndgpu_s2_filter_encode(ndgpu_s2_state *st, const ndgpu_ovl_rec10 *recs, int64_t n, int32_t maxhan1, int32_t maxhan2,
                                uint32_t prev[2], uint8_t **out, uint8_t *kept);
+/* ndgpu_s2_filter_encode with a choice of path; that call is this one with flags 0.
+ *   bit 0: the host loop;  bit 1: the device (K23).
+ *   Neither: NDGPU_S2_DEVICE=1 in the environment, read at each call, selects bit 1.
+ *   Both, or any other bit: -2, nothing written.
+ * Verdicts, bytes, prev[] and the later .bl text are the same on every path.  A device call the kernels cannot compute as the
+ * reference does -- a query or target span under 21 bases, an identity above 32,767, a read whose 16-bit end counter would reach
+ * its limit, no fixed point within NDGPU_S2_MAX_ROUNDS (16) rounds, 2^31 records or more, no device or no device memory,
+ * NDGPU_S2_DECLINE=1 -- runs through the host loop on the untouched state and is counted in `declined`.  Host and device calls may
+ * alternate on one state. */
+int64_t ndgpu_s2_filter_encode_flags(ndgpu_s2_state *st, const ndgpu_ovl_rec10 *recs, int64_t n, int32_t maxhan1, int32_t maxhan2,
+                                     uint32_t prev[2], int flags, uint8_t **out, uint8_t *kept);
+/* counters of the process since the last reset: calls, records in, records kept, calls the device computed; `declined` by reason;
+ * rounds of the fixed point (all device calls, the most of one call); distinct reads of the device calls; merged intervals
+ * downloaded; bytes to and from the device; kernel and primitive launches; device time of the calls */
+typedef struct ndgpu_s2_stats {
+	uint64_t calls, records, kept, device_calls;
+	uint64_t declined[6];      /* short span, identity, counter at its limit, rounds, memory / size, the hook */
+	uint64_t rounds, max_rounds, reads_touched, spans_down, bytes_up, bytes_down, launches;
+	double ms;                 /* HIP events */
+} ndgpu_s2_stats;
+void ndgpu_s2_get_stats(ndgpu_s2_stats *out);
+void ndgpu_s2_reset_stats(void);
 /* the `.bl` text written when the run ends (*text malloc'd, ndgpu_ovl_free); the state is spent afterwards */
 int64_t ndgpu_s2_bl(ndgpu_s2_state *st, char **text);
 

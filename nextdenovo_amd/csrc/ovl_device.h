@@ -188,4 +188,28 @@ void launch_ext_apply(OvlRec *recs, uint64_t n, const int32_t *ext_x, const int3
                       const uint32_t *tid, const uint32_t *tlen, const OvlParams &P, uint32_t *keep, hipStream_t s);
 void launch_scatter_recs(const OvlRec *recs, uint64_t n, const uint32_t *keep, const uint64_t *pos, OvlRec *out, hipStream_t s);
 
+// K23, the step-2 writer (ovlsort_kernels.hip): what one call adds to a read that is alive when the call ends -- overlaps reaching its
+// 5' / 3' end, the dovetail maxima, the first longest internal overlap (0, 0: none), the intervals it covers before their union
+struct S2ReadOut { uint32_t lc, rc, lim, rim, llm, rlm, long_s, long_e, n_alive; };
+void launch_s2_classify(const OvlRec10 *recs, uint32_t n, uint32_t h2, uint32_t *ekey, uint32_t *eval, uint32_t *rinfo, uint32_t *flagw, hipStream_t s);
+void launch_s2_segments(const uint32_t *skey, const uint32_t *sval, uint64_t m, uint32_t *head, uint64_t *rank, bool second, uint32_t *seg_start,
+                        uint32_t *seg_name, uint32_t *seg_first, uint32_t *segof, hipStream_t s);
+void launch_s2_init(const uint32_t *con0, uint32_t d, uint32_t *alive, hipStream_t s);
+void launch_s2_events(const uint32_t *seg_start, uint32_t d, const uint32_t *sval, const uint32_t *rinfo, const uint32_t *segof, const uint32_t *con0,
+                      const uint32_t *alive_old, uint32_t *alive_new, uint32_t *con, uint32_t *changed, hipStream_t s);
+void launch_s2_verdict(const OvlRec10 *recs, uint32_t n, uint32_t h1, uint32_t h2, const uint32_t *rinfo, const uint32_t *segof, const uint32_t *alive,
+                       uint32_t *einfo, uint32_t *keptw, uint8_t *kept, hipStream_t s);
+void launch_s2_reduce(const uint32_t *seg_start, uint32_t d, const uint32_t *sval, const uint32_t *einfo, const OvlRec10 *recs, const uint32_t *con,
+                      S2ReadOut *out, uint32_t *n_alive, hipStream_t s);
+void launch_s2_span_keys(const uint32_t *sval, uint64_t m, const uint32_t *segof, const uint32_t *einfo, const uint32_t *con, const OvlRec10 *recs,
+                         uint64_t *key, uint64_t *val, hipStream_t s);
+void launch_s2_union(const uint64_t *off, uint32_t d, const uint64_t *key, const uint64_t *val, uint2 *merged, uint32_t *n_merged, hipStream_t s);
+void launch_s2_span_gather(const uint64_t *off, const uint64_t *dense_off, uint32_t d, const uint32_t *n_merged, const uint2 *merged, uint2 *dense,
+                           hipStream_t s);
+void launch_s2_compact(const uint32_t *keptw, const uint64_t *rank, uint32_t n, uint32_t *kidx, hipStream_t s);
+void launch_s2_size10(const OvlRec10 *recs, const uint32_t *kidx, const uint64_t *rank, uint32_t n, uint32_t prev_q, uint32_t prev_t, uint32_t *len,
+                      hipStream_t s);
+void launch_s2_write10(const OvlRec10 *recs, const uint32_t *kidx, uint64_t nk, uint32_t prev_q, uint32_t prev_t, const uint64_t *off, uint8_t *out,
+                       hipStream_t s);
+
 } // namespace ndovl

@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ovl_device.h"
 #include "ovl_pool.h"
 
 // (a device filled to the brim makes the runtime's own allocations fail too -- launch arguments, staging: "out of memory" may
@@ -93,5 +94,36 @@ template <class Out, class T> Out *malloc_copy(const T *src, size_t n)
 	return p;
 }
 template <class Out, class T> Out *malloc_copy(const std::vector<T> &v) { return malloc_copy<Out>(v.data(), v.size()); }
+
+// K23: one ndgpu_s2_filter_encode_flags call on the device (ovlsort_engine.hip), in the two steps the run's read table
+// (ovl_step2.cpp, the one authority) needs: s2_group names the reads the records touch, the caller looks up how often each has
+// looked contained so far, s2_solve computes the rest.  Nothing here knows the table.  Both throw on a device error.
+struct S2Call {
+	// in
+	const OvlRec10 *recs = nullptr;
+	uint32_t n = 0, h1 = 0, h2 = 0, prev[2] = {0, 0}, max_rounds = 16;
+	uint8_t *kept = nullptr;                    // n verdicts (may be null)
+	// out of s2_group: per distinct read, by name: its name and first entry (2 * record + side); order = the reads by first entry
+	uint32_t decline = 0;                       // bit 0: a span under 21 bases, bit 1: an identity beyond 15 bits -- nothing else is set then
+	std::vector<uint32_t> name, first, order;
+	// in of s2_solve
+	std::vector<uint32_t> con0;                 // contained count of every read when the call starts
+	// out of s2_solve
+	bool converged = false;                     // false: the rounds ran out, nothing below is set
+	uint32_t rounds = 0;
+	std::vector<uint32_t> con;                  // contained count after the call
+	std::vector<S2ReadOut> out;
+	std::vector<uint64_t> span_off;             // reads + 1 offsets into spans
+	std::vector<uint2> spans;                   // the merged intervals (s + 10, e - 10) of the reads alive at the end, ascending
+	uint8_t *bytes = nullptr;                   // malloc'd (the caller's to free or hand out)
+	uint64_t n_bytes = 0, n_kept = 0;
+	uint32_t prev_out[2] = {0, 0};
+	uint64_t bytes_up = 0, bytes_down = 0, launches = 0;
+	double ms = 0;
+	void *dev = nullptr;                        // the call's device buffers between the two steps
+};
+void s2_group(S2Call &c);
+void s2_solve(S2Call &c);
+void s2_release(S2Call &c);   // the device buffers, and bytes when the caller has not taken them
 
 } // namespace ndovl

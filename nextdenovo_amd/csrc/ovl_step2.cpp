@@ -5,8 +5,11 @@
 //            overlaps reach its 5' / 3' end, the best identity / longest span of the dovetails at either end, how often it
 //            looked contained, the longest internal overlap and a list of covered intervals.  An overlap is kept when it is a
 //            dovetail within maxhan1 (or covers one of the reads end to end within maxhan1) and neither read has looked
-//            contained twice.  The verdict of a record depends on every record before it, whichever query it came from, so this
-//            is a sequential pass over the device's records (a few hundred ns per record), not a kernel.
+//            contained twice.  The verdict of a record depends on every record before it, whichever query it came from: the
+//            host loop below is a sequential pass over the device's records (a few hundred ns per record).  The dependence is
+//            narrow, though -- a record needs to know only whether its two reads have looked contained twice before it -- and K23
+//            (ovlsort_kernels.hip, opt-in: ndgpu_s2_filter_encode_flags) computes the same verdicts, bytes and per-read state
+//            without the pass; s2_on_device below applies what it downloads to the one state both paths share.
 //   .bl      lib/ovl.c:339-362 (out_bl): one line per read at the end of the run, in the order the reference's hash table
 //            (util/khash.h, identity hash, triangular probing, in-place rehash at 77 % load) iterates; ReadTable below lays its
 //            keys out the same way, so the lines come out in the same order.
@@ -16,10 +19,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/ndgpu_overlap.h"
+#include "ovl_host.h"
 
 namespace {
 
@@ -334,6 +339,101 @@ int update_regs(const Reg *rn, int n_new, Reg *reg, int s, int e, int t_l, const
 	return c;
 }
 
+// ---- K23: one call on the device.  The table stays the authority: the device names the reads a call touches, the table says how
+// often each has looked contained so far, and what comes back -- per read, not per record -- is applied to it.
+std::mutex g_s2_mutex;
+ndgpu_s2_stats g_s2_stats;
+constexpr int64_t kS2Declined = INT64_MIN;
+
+void s2_count(int64_t n, int device_call, uint64_t n_kept)
+{
+	std::lock_guard<std::mutex> lock(g_s2_mutex);
+	g_s2_stats.calls++, g_s2_stats.records += (uint64_t)n, g_s2_stats.device_calls += (uint64_t)device_call, g_s2_stats.kept += n_kept;
+}
+
+int64_t s2_decline(int why)
+{
+	std::lock_guard<std::mutex> lock(g_s2_mutex);
+	g_s2_stats.declined[why]++;
+	return kS2Declined;
+}
+
+// kS2Declined: nothing was applied, the call is the host loop's
+int64_t s2_on_device(ndgpu_s2_state *st, const ndgpu_ovl_rec10 *recs, int64_t n, int32_t maxhan1, int32_t maxhan2, uint32_t prev[2],
+                     uint8_t **out, uint8_t *kept)
+{
+	if (const char *e = getenv("NDGPU_S2_DECLINE")) if (atoi(e) == 1) return s2_decline(5);
+	if (n >= (int64_t)1 << 31) return s2_decline(4);
+	if (n == 0) {
+		*out = (uint8_t*)malloc(1);
+		return *out ? 0 : -1;
+	}
+	ndovl::S2Call c;
+	struct Release { ndovl::S2Call &c; ~Release() { ndovl::s2_release(c); } } release{c};
+	c.recs = (const ndovl::OvlRec10*)recs, c.n = (uint32_t)n, c.h1 = (uint32_t)maxhan1, c.h2 = (uint32_t)maxhan2;
+	c.prev[0] = prev[0], c.prev[1] = prev[1], c.kept = kept;
+	if (const char *e = getenv("NDGPU_S2_MAX_ROUNDS")) if (atoi(e) > 0) c.max_rounds = (uint32_t)atoi(e);
+	ReadTable &T = st->table;
+	size_t d = 0;
+	std::vector<uint32_t> slot;
+	try {
+		ndovl::s2_group(c);
+		if (c.decline & 1) return s2_decline(0);
+		if (c.decline & 2) return s2_decline(1);
+		d = c.name.size();
+		slot.resize(d), c.con0.resize(d);
+		for (size_t s = 0; s < d; ++s) {
+			slot[s] = T.find(c.name[s]);
+			c.con0[s] = slot[s] == ReadTable::npos ? 0u : std::min(T.at(slot[s]).con, kMaxCon);
+		}
+		ndovl::s2_solve(c);
+		if (!c.converged) return s2_decline(3);
+		// (the reference's 16-bit end counters stop at their limit, the target side's by a test of the OTHER counter, lib/ovl.c:480)
+		for (size_t s = 0; s < d; ++s) {
+			if (c.con[s] >= kMaxCon) continue;
+			const uint32_t lc0 = slot[s] == ReadTable::npos ? 0u : T.at(slot[s]).lc, rc0 = slot[s] == ReadTable::npos ? 0u : T.at(slot[s]).rc;
+			if ((uint64_t)lc0 + c.out[s].lc >= UINT16_MAX || (uint64_t)rc0 + c.out[s].rc >= UINT16_MAX) return s2_decline(2);
+		}
+	} catch (...) {
+		return s2_decline(4);   // no usable device, out of device memory
+	}
+	try {
+		for (size_t x = 0; x < d; ++x) {   // unseen reads enter the table in the order the host loop meets them
+			const uint32_t s = c.order[x];
+			if (slot[s] != ReadTable::npos) continue;
+			ReadState &r = T.at(T.insert(c.name[s]));
+			const ndgpu_ovl_rec10 &o = recs[c.first[s] >> 1];
+			r.len = (c.first[s] & 1) ? o.tlen : o.qlen;
+			r.spans.assign(kListStep, Span());
+		}
+		for (size_t s = 0; s < d; ++s) {
+			ReadState &r = T.at(T.find(c.name[s]));
+			if (r.con >= kMaxCon) continue;
+			const ndovl::S2ReadOut &a = c.out[s];
+			if (c.con[s] < kMaxCon) {
+				r.lc = (uint16_t)(r.lc + a.lc), r.rc = (uint16_t)(r.rc + a.rc);
+				r.lim = std::max(r.lim, a.lim), r.rim = std::max(r.rim, a.rim), r.llm = std::max(r.llm, a.llm), r.rlm = std::max(r.rlm, a.rlm);
+				if (a.long_e - a.long_s > r.longest.e - r.longest.s) r.longest.s = a.long_s, r.longest.e = a.long_e;
+				for (uint64_t k = c.span_off[s]; k < c.span_off[s + 1]; ++k) r.cover(c.spans[k].x - kEdgeBack, c.spans[k].y + kEdgeBack);
+				r.con = c.con[s];
+			} else {
+				r.con = kMaxCon - 1;
+				r.contained_once_more();
+			}
+		}
+	} catch (...) {
+		return -1;
+	}
+	prev[0] = c.prev_out[0], prev[1] = c.prev_out[1];
+	*out = c.bytes;
+	c.bytes = nullptr;
+	std::lock_guard<std::mutex> lock(g_s2_mutex);
+	ndgpu_s2_stats &S = g_s2_stats;
+	S.kept += c.n_kept, S.rounds += c.rounds, S.max_rounds = std::max<uint64_t>(S.max_rounds, c.rounds), S.reads_touched += d;
+	S.spans_down += c.spans.size(), S.bytes_up += c.bytes_up, S.bytes_down += c.bytes_down, S.launches += c.launches, S.ms += c.ms;
+	return (int64_t)c.n_bytes;
+}
+
 } // namespace
 
 extern "C" {
@@ -554,22 +654,56 @@ void ndgpu_s2_free(ndgpu_s2_state *st) { delete st; }
 int64_t ndgpu_s2_filter_encode(ndgpu_s2_state *st, const ndgpu_ovl_rec10 *recs, int64_t n, int32_t maxhan1, int32_t maxhan2,
                                uint32_t prev[2], uint8_t **out, uint8_t *kept)
 {
+	return ndgpu_s2_filter_encode_flags(st, recs, n, maxhan1, maxhan2, prev, 0, out, kept);
+}
+
+void ndgpu_s2_get_stats(ndgpu_s2_stats *out)
+{
+	std::lock_guard<std::mutex> lock(g_s2_mutex);
+	if (out) *out = g_s2_stats;
+}
+
+void ndgpu_s2_reset_stats(void)
+{
+	std::lock_guard<std::mutex> lock(g_s2_mutex);
+	g_s2_stats = ndgpu_s2_stats();
+}
+
+int64_t ndgpu_s2_filter_encode_flags(ndgpu_s2_state *st, const ndgpu_ovl_rec10 *recs, int64_t n, int32_t maxhan1, int32_t maxhan2,
+                                     uint32_t prev[2], int flags, uint8_t **out, uint8_t *kept)
+{
+	if ((flags & ~3) || (flags & 3) == 3) return -2;
 	*out = nullptr;
 	if (!st || n < 0) return -1;
+	bool device = (flags & 2) != 0;
+	if (!(flags & 3)) {
+		const char *e = getenv("NDGPU_S2_DEVICE");
+		device = e && atoi(e) == 1;
+	}
+	if (device) {
+		const int64_t r = s2_on_device(st, recs, n, maxhan1, maxhan2, prev, out, kept);
+		if (r != kS2Declined) {
+			s2_count(n, r < 0 ? 0 : 1, 0);
+			return r;
+		}
+		*out = nullptr;
+	}
 	uint8_t *buf = (uint8_t*)malloc((size_t)(n > 0 ? n : 1) * 50);
 	if (!buf) return -1;
 	int64_t bytes = 0;
+	uint64_t n_kept = 0;
 	try {
 		for (int64_t i = 0; i < n; ++i) {
 			const bool k = st->keep(recs[i], maxhan1, maxhan2);
 			if (kept) kept[i] = k ? 1 : 0;
-			if (k) bytes += put_record10(buf + bytes, recs[i], prev);
+			if (k) bytes += put_record10(buf + bytes, recs[i], prev), ++n_kept;
 		}
 	} catch (...) {
 		free(buf);
 		return -1;
 	}
 	*out = buf;
+	s2_count(n, 0, n_kept);
 	return bytes;
 }
 

@@ -1315,3 +1315,173 @@ extern "C" int64_t ndgpu_ovl_sort_piles_sets(const ndgpu_ovl_recset *const *file
 	                       max_cov_aln, min_cov_seed, use_bl, skip_ids, n_skip, flags, bl_id, bl_kind, n_bl, recs8, pile_off, seeds, n_piles, sorted,
 	                       n_sorted, stats, astats);
 }
+
+// ---- K23: the step-2 writer on the device (kernels: ovlsort_kernels.hip; the run's state and the C entry: ovl_step2.cpp) ----
+namespace {
+struct S2Dev {
+	SortRun R;
+	EvTimer *tm = nullptr;
+	uint32_t n = 0, d = 0;
+	uint64_t m = 0;
+	DevBuf<OvlRec10> recs;
+	DevBuf<uint32_t> skey, sval, rinfo, flagw, seg_start, seg_name, seg_first, segof;
+	~S2Dev()   // the stream ends before the buffers go back to the pool
+	{
+		if (R.st) { (void)hipStreamSynchronize(R.st); delete tm; (void)hipStreamDestroy(R.st); }
+		R.tmp.buf.release();
+	}
+};
+// declared behind a step's buffers: whatever still runs when the step fails has finished before they go back to the pool
+struct S2Sync { hipStream_t s; ~S2Sync() { (void)hipStreamSynchronize(s); } };
+}
+
+namespace ndovl {
+
+void s2_group(S2Call &c)
+{
+	if (select_device(true) < 0) throw std::runtime_error("no device");
+	S2Dev *D = new S2Dev();
+	c.dev = D;
+	HIP_OK(create_stage_stream(&D->R.st));
+	hipStream_t st = D->R.st;
+	D->tm = new EvTimer(st);
+	D->tm->start();
+	const uint32_t n = D->n = c.n;
+	const uint64_t m = D->m = 2 * (uint64_t)n;
+	D->recs.alloc(n), D->rinfo.alloc(n), D->flagw.alloc(2);
+	D->skey.alloc(m), D->sval.alloc(m), D->segof.alloc(m);
+	D->seg_start.alloc(m + 1), D->seg_name.alloc(m + 1), D->seg_first.alloc(m + 1);
+	D->recs.upload(c.recs, n, st);
+	D->flagw.zero(st);
+	c.bytes_up += (uint64_t)n * sizeof(OvlRec10);
+	uint64_t d64 = 0;
+	{
+		DevBuf<uint32_t> ekey, eval, head;
+		DevBuf<uint64_t> rank;
+		const S2Sync sync{st};
+		ekey.alloc(m), eval.alloc(m), head.alloc(m + 1), rank.alloc(m + 1);
+		launch_s2_classify(D->recs.p, n, c.h2, ekey.p, eval.p, D->rinfo.p, D->flagw.p, st);
+		D->R.tmp.run([&](void *t, size_t &tb) { sort_pairs_u32(t, tb, ekey.p, D->skey.p, eval.p, D->sval.p, m, st); });   // stable: record order inside a read
+		launch_s2_segments(D->skey.p, D->sval.p, m, head.p, rank.p, false, nullptr, nullptr, nullptr, nullptr, st);
+		D->R.exscan(head.p, rank.p, m + 1);
+		launch_s2_segments(D->skey.p, D->sval.p, m, head.p, rank.p, true, D->seg_start.p, D->seg_name.p, D->seg_first.p, D->segof.p, st);
+		c.launches += 5;
+		rank.download(&d64, 1, st, m);
+		D->flagw.download(&c.decline, 1, st);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		c.bytes_down += 12;
+	}
+	if (c.decline) { c.ms += D->tm->stop(); return; }
+	const uint32_t d = D->d = (uint32_t)d64;
+	c.name.resize(d), c.first.resize(d), c.order.resize(d);
+	{
+		DevBuf<uint32_t> idx, key2, ord;
+		const S2Sync sync{st};
+		idx.alloc(d), key2.alloc(d), ord.alloc(d);
+		launch_iota(idx.p, d, st);
+		D->R.tmp.run([&](void *t, size_t &tb) { sort_pairs_u32(t, tb, D->seg_first.p, key2.p, idx.p, ord.p, d, st); });
+		c.launches += 2;
+		D->seg_name.download(c.name.data(), d, st);
+		D->seg_first.download(c.first.data(), d, st);
+		ord.download(c.order.data(), d, st);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		c.bytes_down += 12ull * d;
+	}
+	c.ms += D->tm->stop();
+}
+
+void s2_solve(S2Call &c)
+{
+	S2Dev *D = (S2Dev*)c.dev;
+	hipStream_t st = D->R.st;
+	const uint32_t n = D->n, d = D->d;
+	const uint64_t m = D->m;
+	DevBuf<uint32_t> con0, alive_a, alive_b, con, einfo, keptw, kidx, len, n_alive, n_merged;
+	DevBuf<uint8_t> kept, bytes;
+	DevBuf<uint64_t> krank, boff, ioff, moff, key, val, key2, val2;
+	DevBuf<S2ReadOut> out;
+	DevBuf<uint2> merged, dense;
+	const S2Sync sync{st};
+	D->tm->start();
+	con0.alloc(d), alive_a.alloc(d), alive_b.alloc(d), con.alloc(d);
+	con0.upload(c.con0.data(), d, st);
+	c.bytes_up += 4ull * d;
+	launch_s2_init(con0.p, d, alive_a.p, st);
+	c.launches++;
+	uint32_t *cur = alive_a.p, *nxt = alive_b.p;
+	c.converged = false;
+	while (c.rounds < c.max_rounds) {
+		uint32_t changed = 0;
+		HIP_OK(hipMemsetAsync(D->flagw.p + 1, 0, sizeof(uint32_t), st));
+		launch_s2_events(D->seg_start.p, d, D->sval.p, D->rinfo.p, D->segof.p, con0.p, cur, nxt, con.p, D->flagw.p + 1, st);
+		D->flagw.download(&changed, 1, st, 1);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		c.launches++, c.rounds++, c.bytes_down += 4;
+		std::swap(cur, nxt);
+		if (!changed) { c.converged = true; break; }
+	}
+	if (!c.converged) { c.ms += D->tm->stop(); return; }
+
+	// the verdicts and the encoder's plan
+	einfo.alloc(m), keptw.alloc((size_t)n + 1), kidx.alloc(n), len.alloc((size_t)n + 1), kept.alloc(n);
+	krank.alloc((size_t)n + 1), boff.alloc((size_t)n + 1);
+	launch_s2_verdict(D->recs.p, n, c.h1, c.h2, D->rinfo.p, D->segof.p, cur, einfo.p, keptw.p, kept.p, st);
+	D->R.exscan(keptw.p, krank.p, (size_t)n + 1);
+	launch_s2_compact(keptw.p, krank.p, n, kidx.p, st);
+	launch_s2_size10(D->recs.p, kidx.p, krank.p, n, c.prev[0], c.prev[1], len.p, st);
+	D->R.exscan(len.p, boff.p, (size_t)n + 1);
+	// the reads: counts and maxima, then the union of their intervals
+	out.alloc(d), n_alive.alloc((size_t)d + 1), n_merged.alloc((size_t)d + 1), ioff.alloc((size_t)d + 1), moff.alloc((size_t)d + 1);
+	key.alloc(m), val.alloc(m), key2.alloc(m), val2.alloc(m), merged.alloc(m);
+	launch_s2_reduce(D->seg_start.p, d, D->sval.p, einfo.p, D->recs.p, con.p, out.p, n_alive.p, st);
+	D->R.exscan(n_alive.p, ioff.p, (size_t)d + 1);
+	launch_s2_span_keys(D->sval.p, m, D->segof.p, einfo.p, con.p, D->recs.p, key.p, val.p, st);
+	unsigned bits = 1;
+	while (bits < 32 && (d >> bits)) ++bits;   // d < 2^bits: a live key's read field is never all ones, the keys of dead entries sort last
+	D->R.tmp.run([&](void *t, size_t &tb) { sort_pairs_u64(t, tb, key.p, key2.p, val.p, val2.p, m, 0, 32 + bits, st); });
+	launch_s2_union(ioff.p, d, key2.p, val2.p, merged.p, n_merged.p, st);
+	D->R.exscan(n_merged.p, moff.p, (size_t)d + 1);
+	c.launches += 11;
+	uint64_t nk = 0, nb = 0, ns = 0;
+	krank.download(&nk, 1, st, n);
+	boff.download(&nb, 1, st, n);
+	moff.download(&ns, 1, st, d);
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	if (nk > n || nb > 47 * nk || nb < 10 * nk || ns > m) throw std::runtime_error("step-2 sizes out of range");
+
+	bytes.alloc(nb + 4), dense.alloc(ns);
+	launch_s2_write10(D->recs.p, kidx.p, nk, c.prev[0], c.prev[1], boff.p, bytes.p, st);
+	launch_s2_span_gather(ioff.p, moff.p, d, n_merged.p, merged.p, dense.p, st);
+	c.launches += 2;
+	c.con.resize(d), c.out.resize(d), c.span_off.resize((size_t)d + 1), c.spans.resize(ns);
+	c.bytes = (uint8_t*)malloc(nb ? nb : 1);
+	if (!c.bytes) throw std::runtime_error("malloc");
+	uint32_t last = 0;
+	con.download(c.con.data(), d, st);
+	out.download(c.out.data(), d, st);
+	moff.download(c.span_off.data(), (size_t)d + 1, st);
+	dense.download(c.spans.data(), ns, st);
+	bytes.download(c.bytes, nb, st);
+	if (c.kept) kept.download(c.kept, n, st);
+	if (nk) kidx.download(&last, 1, st, nk - 1);
+	c.ms += D->tm->stop();   // (waits for the downloads)
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	c.bytes_down += 24 + 4ull * d + sizeof(S2ReadOut) * (uint64_t)d + 8ull * (d + 1) + 8 * ns + nb + (c.kept ? n : 0) + (nk ? 4 : 0);
+	c.n_bytes = nb, c.n_kept = nk;
+	c.prev_out[0] = nk ? c.recs[last].qname : c.prev[0], c.prev_out[1] = nk ? c.recs[last].tname : c.prev[1];
+}
+
+void s2_release(S2Call &c)
+{
+	delete (S2Dev*)c.dev;
+	c.dev = nullptr;
+	free(c.bytes);
+	c.bytes = nullptr;
+}
+
+} // namespace ndovl

@@ -1257,4 +1257,400 @@ void launch_file_fill(const uint64_t *fstart, uint32_t n_files, uint64_t n, uint
 	if (n) ND_LAUNCH(file_fill_kernel, GRID1(n), 0, s, fstart, n_files, n, file_of);
 }
 
+// ------------------------------------------------------------------------------------------------
+// K23: the step-2 writer -- filter_ovl (lib/ovl.c:449-563) and encode_ovl_i (lib/ovl.c:205-253) over the records of one call,
+// without the record-by-record pass (host side: ndovl::s2_group / s2_solve in ovlsort_engine.hip, the state in ovl_step2.cpp).
+//
+// A read is alive before record i while it has looked contained fewer than two times; alive[r] = the number of leading records before
+// which read r is alive (0: dead when the call starts, kS2Never: never dies).  With qc(i) / tc(i) = "record i covers its query / target
+// end to end within maxhan2", read r is bumped as the query of i when qc(i), and as the target of i when tc(i) and not (qc(i) and the
+// query is alive before i); r dies at its (2 - con0)-th bump.  Only the last condition couples reads, and only at records where qc and
+// tc both hold: the alive[] of all reads are recomputed from the previous estimate until none changes (s2_events_kernel, one launch a
+// round).  Everything else follows from alive[] alone: the verdicts, and per read the end counts, the dovetail maxima, the longest
+// internal overlap and the union of the covered intervals.
+//
+// Every record contributes two entries, 2 * i (its query) and 2 * i + 1 (its target); a stable sort by read name groups them, in
+// record order inside a read (a "segment").  The kernels over segments give one wavefront to a segment, 64 entries a step.
+constexpr uint32_t kS2Never = 0xffffffffu;
+constexpr uint32_t kS2Alive = 1, kS2Lo = 2, kS2Hi = 4, kS2Feed = 8, kS2End3 = 16, kS2Internal = 32;   // bits of an entry's einfo
+#define GRIDW(n) dim3((unsigned)(((uint64_t)(n) + 3) / 4)), dim3(256)   // one wavefront per item
+
+// rinfo[i] = qc | tc << 1; flagw[0] |= 1: a span under 21 bases (the stored interval (s + 10, e - 10) would be empty or inverted),
+// |= 2: an identity beyond the 15-bit fields -- the call is then the host loop's
+__global__ void s2_classify_kernel(const OvlRec10 *__restrict__ recs, uint32_t n, uint32_t h2, uint32_t *__restrict__ ekey,
+                                   uint32_t *__restrict__ eval, uint32_t *__restrict__ rinfo, uint32_t *__restrict__ flagw)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const OvlRec10 r = recs[i];
+	const uint32_t qc = r.qs <= h2 && r.qe + h2 >= r.qlen, tc = r.ts <= h2 && r.te + h2 >= r.tlen;
+	rinfo[i] = qc | tc << 1;
+	ekey[2 * i] = r.qname, ekey[2 * i + 1] = r.tname;
+	eval[2 * i] = 2 * i, eval[2 * i + 1] = 2 * i + 1;
+	uint32_t bad = 0;
+	if ((uint64_t)r.qs + 21 > r.qe || (uint64_t)r.ts + 21 > r.te) bad |= 1;
+	if (r.identity > 0x7fffu) bad |= 2;
+	if (bad) atomicOr(flagw, bad);
+}
+
+// head[j] = entry j of the sorted order starts a segment (m entries; head[m] = 0 closes the scan)
+__global__ void s2_head_kernel(const uint32_t *__restrict__ skey, uint64_t m, uint32_t *__restrict__ head)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j > m) return;
+	head[j] = j < m && (j == 0 || skey[j] != skey[j - 1]);
+}
+
+// rank = the exclusive scan of head (m + 1 entries): the segments' first entries, names and first records; segof[entry] = its segment
+__global__ void s2_segment_kernel(const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval, const uint32_t *__restrict__ head,
+                                  const uint64_t *__restrict__ rank, uint64_t m, uint32_t *__restrict__ seg_start, uint32_t *__restrict__ seg_name,
+                                  uint32_t *__restrict__ seg_first, uint32_t *__restrict__ segof)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j > m) return;
+	if (j == m) { seg_start[rank[m]] = (uint32_t)m; return; }
+	const uint32_t h = head[j], s = (uint32_t)rank[j] + h - 1;
+	segof[sval[j]] = s;
+	if (h) seg_start[s] = (uint32_t)j, seg_name[s] = skey[j], seg_first[s] = sval[j];
+}
+
+__global__ void s2_init_kernel(const uint32_t *__restrict__ con0, uint32_t d, uint32_t *__restrict__ alive)
+{
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s < d) alive[s] = con0[s] >= 2 ? 0u : kS2Never;
+}
+
+// One round: alive_new[s] and con[s] (the count after the call, 2 at most) of every segment from alive_old.  The entries of a segment
+// are in record order, so the k-th bump is the k-th set bit of the ballots; the wavefront stops there.
+__global__ void __launch_bounds__(256) s2_events_kernel(const uint32_t *__restrict__ seg_start, uint32_t d, const uint32_t *__restrict__ sval,
+                                                         const uint32_t *__restrict__ rinfo, const uint32_t *__restrict__ segof,
+                                                         const uint32_t *__restrict__ con0, const uint32_t *__restrict__ alive_old,
+                                                         uint32_t *__restrict__ alive_new, uint32_t *__restrict__ con, uint32_t *__restrict__ changed)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (s >= d) return;
+	const uint32_t c0 = con0[s];
+	uint32_t a = kS2Never, c = c0 < 2 ? c0 : 2;
+	if (c0 >= 2) a = 0;
+	else {
+		const uint64_t j0 = seg_start[s], j1 = seg_start[s + 1];
+		uint32_t need = 2 - c0;
+		for (uint64_t base = j0; base < j1; base += 64) {
+			const uint64_t j = base + lane;
+			bool ev = false;
+			uint32_t i = 0;
+			if (j < j1) {
+				const uint32_t e = sval[j];
+				i = e >> 1;
+				const uint32_t info = rinfo[i];
+				if (e & 1) {
+					ev = (info & 2) != 0;
+					if (ev && (info & 1)) ev = !(i < alive_old[segof[e - 1]]);   // the query took the bump
+				} else ev = (info & 1) != 0;
+			}
+			unsigned long long m = __ballot(ev);
+			const uint32_t cnt = (uint32_t)__popcll(m);
+			if (cnt >= need) {
+				if (need == 2) m &= m - 1;
+				a = __shfl(i, __ffsll((long long)m) - 1, 64) + 1;   // alive before that record too, not after it
+				c = 2;
+				break;
+			}
+			need -= cnt, c += cnt;
+		}
+	}
+	if (lane == 0) {
+		alive_new[s] = a, con[s] = c;
+		if (a != alive_old[s]) *changed = 1;
+	}
+}
+
+// the verdict of record i (the rules of filter_ovl behind the two bumps) and what its two entries feed into their reads
+__global__ void s2_verdict_kernel(const OvlRec10 *__restrict__ recs, uint32_t n, uint32_t h1, uint32_t h2, const uint32_t *__restrict__ rinfo,
+                                  const uint32_t *__restrict__ segof, const uint32_t *__restrict__ alive, uint32_t *__restrict__ einfo,
+                                  uint32_t *__restrict__ keptw, uint8_t *__restrict__ kept)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i > n) return;
+	if (i == n) { keptw[n] = 0; return; }
+	const OvlRec10 o = recs[i];
+	const uint32_t info = rinfo[i];
+	const bool aq = i < alive[segof[2 * i]], at = i < alive[segof[2 * i + 1]];
+	const uint32_t q_lo = o.qs, q_hi = o.qlen - o.qe, t_lo = o.ts, t_hi = o.tlen - o.te;
+	uint32_t eq = 0, et = 0, v = 0;
+	if (aq) eq = kS2Alive | (q_lo <= h2 ? kS2Lo : 0) | (q_hi <= h2 ? kS2Hi : 0);
+	if (at) et = kS2Alive | (t_lo <= h2 ? kS2Lo : 0) | (t_hi <= h2 ? kS2Hi : 0);
+	if (aq && (info & 1)) v = 0;
+	else if (at && (info & 2)) v = 0;
+	else if (!aq || !at) v = 0;
+	else {
+		int q_end = -1, t_end = -1;
+		uint32_t gq = 0, gt = 0;
+		if (o.rev) {
+			if (q_lo <= h1 && t_lo <= h1) q_end = 0, t_end = 0, gq = q_lo, gt = t_lo;
+			else if (q_hi <= h1 && t_hi <= h1) q_end = 1, t_end = 1, gq = q_hi, gt = t_hi;
+		} else {
+			if (q_hi <= h1 && t_lo <= h1) q_end = 1, t_end = 0, gq = q_hi, gt = t_lo;
+			else if (q_lo <= h1 && t_hi <= h1) q_end = 0, t_end = 1, gq = q_lo, gt = t_hi;
+		}
+		if (q_end >= 0) {
+			if (gq <= h2 && gt <= h2) eq |= kS2Feed | (q_end ? kS2End3 : 0), et |= kS2Feed | (t_end ? kS2End3 : 0);
+			v = 1;
+		} else if (o.qs <= h1 && o.qe + h1 >= o.qlen) v = 1;
+		else if (o.ts <= h1 && o.te + h1 >= o.tlen) v = 1;
+		else eq |= kS2Internal, et |= kS2Internal;
+	}
+	einfo[2 * i] = eq, einfo[2 * i + 1] = et;
+	keptw[i] = v, kept[i] = (uint8_t)v;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { for (int k = 32; k; k >>= 1) v += __shfl_xor(v, k, 64); return v; }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { for (int k = 32; k; k >>= 1) { const uint32_t o = __shfl_xor(v, k, 64); v = o > v ? o : v; } return v; }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+	for (int k = 32; k; k >>= 1) { const unsigned long long o = __shfl_xor(v, k, 64); v = o > v ? o : v; }
+	return v;
+}
+
+// per read: the counts, the four maxima, the first longest internal overlap and how many intervals it covers while alive (none for a
+// read that ends the call dead: it prints nothing but its name)
+__global__ void __launch_bounds__(256) s2_reduce_kernel(const uint32_t *__restrict__ seg_start, uint32_t d, const uint32_t *__restrict__ sval,
+                                                         const uint32_t *__restrict__ einfo, const OvlRec10 *__restrict__ recs,
+                                                         const uint32_t *__restrict__ con, S2ReadOut *__restrict__ out, uint32_t *__restrict__ n_alive)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (s > d) return;
+	if (s == d) { if (lane == 0) n_alive[d] = 0; return; }
+	const uint64_t j0 = seg_start[s], j1 = seg_start[s + 1];
+	uint32_t lc = 0, rc = 0, lim = 0, rim = 0, llm = 0, rlm = 0, na = 0;
+	unsigned long long best = 0;   // length << 32 | ~entry position: the greatest length, the earliest record among equals
+	for (uint64_t j = j0 + lane; j < j1; j += 64) {
+		const uint32_t e = sval[j], f = einfo[e];
+		if (!(f & kS2Alive)) continue;
+		const uint32_t *w = reinterpret_cast<const uint32_t*>(recs + (e >> 1));
+		na++, lc += (f & kS2Lo) != 0, rc += (f & kS2Hi) != 0;
+		if (f & kS2Feed) {
+			const uint32_t qspan = w[3] - w[2], tspan = w[7] - w[6], span = qspan > tspan ? qspan : tspan, ide = w[9];
+			if (f & kS2End3) rlm = span > rlm ? span : rlm, rim = ide > rim ? ide : rim;
+			else llm = span > llm ? span : llm, lim = ide > lim ? ide : lim;
+		}
+		if (f & kS2Internal) {
+			const uint32_t len = (e & 1) ? w[7] - w[6] : w[3] - w[2];
+			const unsigned long long key = (unsigned long long)len << 32 | (uint32_t)~(uint32_t)j;
+			if (len && key > best) best = key;
+		}
+	}
+	lc = wave_sum_u32(lc), rc = wave_sum_u32(rc), na = wave_sum_u32(na);
+	lim = wave_max_u32(lim), rim = wave_max_u32(rim), llm = wave_max_u32(llm), rlm = wave_max_u32(rlm);
+	best = wave_max_u64(best);
+	if (lane) return;
+	S2ReadOut r = {lc, rc, lim, rim, llm, rlm, 0, 0, na};
+	if (best) {
+		const uint32_t e = sval[(uint32_t)~(uint32_t)best];
+		const uint32_t *w = reinterpret_cast<const uint32_t*>(recs + (e >> 1));
+		r.long_s = (e & 1) ? w[6] : w[2], r.long_e = (e & 1) ? w[7] : w[3];
+	}
+	if (con[s] >= 2) r.n_alive = 0;
+	out[s] = r;
+	n_alive[s] = r.n_alive;
+}
+
+// sort key of entry position j's interval: segment << 32 | start + 10, value: end - 10; all ones for an entry that covers nothing
+__global__ void s2_span_keys_kernel(const uint32_t *__restrict__ sval, uint64_t m, const uint32_t *__restrict__ segof,
+                                    const uint32_t *__restrict__ einfo, const uint32_t *__restrict__ con, const OvlRec10 *__restrict__ recs,
+                                    uint64_t *__restrict__ key, uint64_t *__restrict__ val)
+{
+	const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= m) return;
+	const uint32_t e = sval[j], s = segof[e];
+	const uint32_t *w = reinterpret_cast<const uint32_t*>(recs + (e >> 1));
+	const uint32_t a = (e & 1) ? w[6] : w[2], b = (e & 1) ? w[7] : w[3];
+	const bool live = (einfo[e] & kS2Alive) && con[s] < 2;
+	key[j] = live ? (uint64_t)s << 32 | (uint32_t)(a + 10) : ~0ull;
+	val[j] = b - 10;
+}
+
+// The union of a read's intervals, sorted by start at [off[s], off[s + 1]): a running maximum of the ends; an interval whose start lies
+// beyond it opens a new one (one that starts AT it joins, merge_spans of ovl_step2.cpp).  The merged intervals go to merged[off[s] ..),
+// their number to n_merged[s].
+__global__ void __launch_bounds__(256) s2_union_kernel(const uint64_t *__restrict__ off, uint32_t d, const uint64_t *__restrict__ key,
+                                                        const uint64_t *__restrict__ val, uint2 *__restrict__ merged, uint32_t *__restrict__ n_merged)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (s > d) return;
+	if (s == d) { if (lane == 0) n_merged[d] = 0; return; }
+	const uint64_t j0 = off[s], j1 = off[s + 1];
+	uint32_t carry = 0, heads = 0;
+	for (uint64_t base = j0; base < j1; base += 64) {
+		const uint64_t j = base + lane;
+		const bool live = j < j1;
+		const uint32_t start = live ? (uint32_t)key[j] : 0u, end = live ? (uint32_t)val[j] : 0u;
+		uint32_t run = end;   // inclusive running maximum of the ends
+		for (int k = 1; k < 64; k <<= 1) {
+			const uint32_t o = __shfl_up(run, k, 64);
+			if (lane >= k && o > run) run = o;
+		}
+		uint32_t before = __shfl_up(run, 1, 64);
+		if (lane == 0 || carry > before) before = carry;
+		if (carry > run) run = carry;
+		const bool head = live && (j == j0 || start > before);
+		const bool tail = live && (j + 1 == j1 || (uint32_t)key[j + 1] > run);
+		const unsigned long long hm = __ballot(head);
+		const uint32_t idx = heads + (uint32_t)__popcll(hm & (~0ull >> (63 - lane))) - 1;
+		if (head) merged[j0 + idx].x = start;
+		if (tail) merged[j0 + idx].y = run;
+		heads += (uint32_t)__popcll(hm);
+		carry = __shfl(run, 63, 64);
+	}
+	if (lane == 0) n_merged[s] = heads;
+}
+
+__global__ void __launch_bounds__(256) s2_span_gather_kernel(const uint64_t *__restrict__ off, const uint64_t *__restrict__ dense_off, uint32_t d,
+                                                              const uint32_t *__restrict__ n_merged, const uint2 *__restrict__ merged,
+                                                              uint2 *__restrict__ dense)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (s >= d) return;
+	const uint64_t a = off[s], b = dense_off[s];
+	for (uint32_t k = lane; k < n_merged[s]; k += 64) dense[b + k] = merged[a + k];
+}
+
+// ---- the 10-field encoder over the kept records
+__global__ void s2_compact_kernel(const uint32_t *__restrict__ keptw, const uint64_t *__restrict__ rank, uint32_t n, uint32_t *__restrict__ kidx)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n && keptw[i]) kidx[rank[i]] = i;
+}
+
+// put_record10 of ovl_step2.cpp for kept record k (record kidx[k]) behind the kept record in front of it (the first: the caller's prev);
+// a lane without a record computes on zeros
+__device__ __forceinline__ void encode_fields10(const OvlRec10 *__restrict__ recs, const uint32_t *__restrict__ kidx, uint64_t k, bool live,
+                                                uint32_t prev_q, uint32_t prev_t, uint32_t f[10])
+{
+	OvlRec10 o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	uint32_t pq = prev_q, pt = prev_t;
+	if (live) {
+		o = recs[kidx[k]];
+		if (k > 0) { const OvlRec10 *p = recs + kidx[k - 1]; pq = p->qname, pt = p->tname; }
+	}
+	uint32_t flags = o.rev;
+	const uint32_t qspan = o.qe - o.qs, tspan = o.te - o.ts;
+	if (o.qname >= pq) f[0] = o.qname - pq; else flags |= 2, f[0] = pq - o.qname;
+	if (o.tname >= pt) f[4] = o.tname - pt; else flags |= 4, f[4] = pt - o.tname;
+	f[7] = o.qname == pq ? 0 : o.qlen;
+	f[8] = o.tname == pt ? 0 : o.tlen;
+	if (qspan >= tspan) f[6] = qspan - tspan; else flags |= 8, f[6] = tspan - qspan;
+	f[1] = flags & 0xff, f[2] = o.qs, f[3] = qspan, f[5] = o.ts, f[9] = o.identity;
+}
+
+// len[k] for k <= n: the bytes of kept record k, 0 behind the last (rank[n] = the number of kept records)
+__global__ void s2_size10_kernel(const OvlRec10 *__restrict__ recs, const uint32_t *__restrict__ kidx, const uint64_t *__restrict__ rank, uint32_t n,
+                                 uint32_t prev_q, uint32_t prev_t, uint32_t *__restrict__ len)
+{
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k > n) return;
+	const bool live = k < rank[n];
+	uint32_t f[10], nb = 0;
+	encode_fields10(recs, kidx, k, live, prev_q, prev_t, f);
+#pragma unroll
+	for (int x = 0; x < 10; ++x) nb += varint_len(f[x]);
+	len[k] = live ? nb : 0;   // 10 .. 47: nine values of up to 5 bytes, the flags of up to 2
+}
+
+constexpr uint32_t kEnc10StageWords = (64 * 48 + 3 + 3) / 4 + 1;   // 64 records of up to 47 bytes behind up to 3 bytes of alignment
+
+// off = the exclusive scan of len; out is 4-byte aligned (the staging of codec_write_kernel)
+__global__ void __launch_bounds__(64) s2_write10_kernel(const OvlRec10 *__restrict__ recs, const uint32_t *__restrict__ kidx, uint64_t nk,
+                                                         uint32_t prev_q, uint32_t prev_t, const uint64_t *__restrict__ off, uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage_w[kEnc10StageWords];
+	uint8_t *const stage = reinterpret_cast<uint8_t*>(stage_w);
+	const int lane = threadIdx.x;
+	const uint64_t k0 = (uint64_t)blockIdx.x * 64, k = k0 + lane;
+	const uint64_t k1 = k0 + 64 < nk ? k0 + 64 : nk;
+	const uint64_t g0 = off[k0], g1 = off[k1];
+	const uint32_t head = (uint32_t)(g0 & 3);
+	uint32_t f[10];
+	encode_fields10(recs, kidx, k, k < nk, prev_q, prev_t, f);
+	if (k < nk) {
+		uint32_t at = head + (uint32_t)(off[k] - g0);
+#pragma unroll
+		for (int x = 0; x < 10; ++x) {
+			const uint32_t v = f[x];
+			for (int g = (int)varint_len(v) - 1; g >= 0; --g) stage[at++] = (uint8_t)((v >> (7 * g) & 127u) | (g ? 128u : 0u));
+		}
+	}
+	__syncthreads();
+	const uint32_t end = head + (uint32_t)(g1 - g0);
+	const uint32_t w_lo = (head + 3) & ~3u, w_hi = end & ~3u;
+	const uint32_t head_end = w_lo < end ? w_lo : end;
+	uint8_t *const base = out + (g0 - head);
+	if (head + lane < head_end) base[head + lane] = stage[head + lane];
+	for (uint32_t x = w_lo + 4 * (uint32_t)lane; x < w_hi; x += 256) *reinterpret_cast<uint32_t*>(base + x) = stage_w[x >> 2];
+	const uint32_t tail = w_hi > head_end ? w_hi : head_end;
+	if (tail + lane < end) base[tail + lane] = stage[tail + lane];
+}
+
+void launch_s2_classify(const OvlRec10 *recs, uint32_t n, uint32_t h2, uint32_t *ekey, uint32_t *eval, uint32_t *rinfo, uint32_t *flagw, hipStream_t s)
+{
+	if (n) ND_LAUNCH(s2_classify_kernel, GRID1(n), 0, s, recs, n, h2, ekey, eval, rinfo, flagw);
+}
+void launch_s2_segments(const uint32_t *skey, const uint32_t *sval, uint64_t m, uint32_t *head, uint64_t *rank, bool second, uint32_t *seg_start,
+                        uint32_t *seg_name, uint32_t *seg_first, uint32_t *segof, hipStream_t s)
+{
+	if (!second) ND_LAUNCH(s2_head_kernel, GRID1(m + 1), 0, s, skey, m, head);
+	else ND_LAUNCH(s2_segment_kernel, GRID1(m + 1), 0, s, skey, sval, head, rank, m, seg_start, seg_name, seg_first, segof);
+}
+void launch_s2_init(const uint32_t *con0, uint32_t d, uint32_t *alive, hipStream_t s)
+{
+	if (d) ND_LAUNCH(s2_init_kernel, GRID1(d), 0, s, con0, d, alive);
+}
+void launch_s2_events(const uint32_t *seg_start, uint32_t d, const uint32_t *sval, const uint32_t *rinfo, const uint32_t *segof, const uint32_t *con0,
+                      const uint32_t *alive_old, uint32_t *alive_new, uint32_t *con, uint32_t *changed, hipStream_t s)
+{
+	if (d) ND_LAUNCH(s2_events_kernel, GRIDW(d), 0, s, seg_start, d, sval, rinfo, segof, con0, alive_old, alive_new, con, changed);
+}
+void launch_s2_verdict(const OvlRec10 *recs, uint32_t n, uint32_t h1, uint32_t h2, const uint32_t *rinfo, const uint32_t *segof, const uint32_t *alive,
+                       uint32_t *einfo, uint32_t *keptw, uint8_t *kept, hipStream_t s)
+{
+	ND_LAUNCH(s2_verdict_kernel, GRID1((uint64_t)n + 1), 0, s, recs, n, h1, h2, rinfo, segof, alive, einfo, keptw, kept);
+}
+void launch_s2_reduce(const uint32_t *seg_start, uint32_t d, const uint32_t *sval, const uint32_t *einfo, const OvlRec10 *recs, const uint32_t *con,
+                      S2ReadOut *out, uint32_t *n_alive, hipStream_t s)
+{
+	ND_LAUNCH(s2_reduce_kernel, GRIDW((uint64_t)d + 1), 0, s, seg_start, d, sval, einfo, recs, con, out, n_alive);
+}
+void launch_s2_span_keys(const uint32_t *sval, uint64_t m, const uint32_t *segof, const uint32_t *einfo, const uint32_t *con, const OvlRec10 *recs,
+                         uint64_t *key, uint64_t *val, hipStream_t s)
+{
+	if (m) ND_LAUNCH(s2_span_keys_kernel, GRID1(m), 0, s, sval, m, segof, einfo, con, recs, key, val);
+}
+void launch_s2_union(const uint64_t *off, uint32_t d, const uint64_t *key, const uint64_t *val, uint2 *merged, uint32_t *n_merged, hipStream_t s)
+{
+	ND_LAUNCH(s2_union_kernel, GRIDW((uint64_t)d + 1), 0, s, off, d, key, val, merged, n_merged);
+}
+void launch_s2_span_gather(const uint64_t *off, const uint64_t *dense_off, uint32_t d, const uint32_t *n_merged, const uint2 *merged, uint2 *dense,
+                           hipStream_t s)
+{
+	if (d) ND_LAUNCH(s2_span_gather_kernel, GRIDW(d), 0, s, off, dense_off, d, n_merged, merged, dense);
+}
+void launch_s2_compact(const uint32_t *keptw, const uint64_t *rank, uint32_t n, uint32_t *kidx, hipStream_t s)
+{
+	if (n) ND_LAUNCH(s2_compact_kernel, GRID1(n), 0, s, keptw, rank, n, kidx);
+}
+void launch_s2_size10(const OvlRec10 *recs, const uint32_t *kidx, const uint64_t *rank, uint32_t n, uint32_t prev_q, uint32_t prev_t, uint32_t *len,
+                      hipStream_t s)
+{
+	ND_LAUNCH(s2_size10_kernel, GRID1((uint64_t)n + 1), 0, s, recs, kidx, rank, n, prev_q, prev_t, len);
+}
+void launch_s2_write10(const OvlRec10 *recs, const uint32_t *kidx, uint64_t nk, uint32_t prev_q, uint32_t prev_t, const uint64_t *off, uint8_t *out,
+                       hipStream_t s)
+{
+	if (nk) ND_LAUNCH(s2_write10_kernel, dim3((unsigned)((nk + 63) / 64)), dim3(64), 0, s, recs, kidx, nk, prev_q, prev_t, off, out);
+}
+
 } // namespace ndovl

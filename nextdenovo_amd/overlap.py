@@ -51,6 +51,13 @@ class CigarStats(C.Structure):
                                          "splits", "chains_ns", "ksw_ns", "ksw_ll_ns", "total_ns")]
 
 
+class S2Stats(C.Structure):
+    """ndgpu_s2_stats: the step-2 filter / encoder calls of the process (K23)."""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "records", "kept", "device_calls")] + [("declined", C.c_uint64 * 6)] \
+        + [(n, C.c_uint64) for n in ("rounds", "max_rounds", "reads_touched", "spans_down", "bytes_up", "bytes_down", "launches")] \
+        + [("ms", C.c_double)]
+
+
 def aln_opt(**kw) -> AlnOpt:
     o = AlnOpt()
     load().ndgpu_ovl_aln_opt_default(C.byref(o), 40)
@@ -112,6 +119,12 @@ def _bind(lib):
     lib.ndgpu_s2_free.argtypes = [P]
     lib.ndgpu_s2_filter_encode.argtypes = [P, P, C.c_int64, C.c_int32, C.c_int32, P, C.POINTER(P), P]
     lib.ndgpu_s2_filter_encode.restype = C.c_int64
+    lib.ndgpu_s2_filter_encode_flags.argtypes = [P, P, C.c_int64, C.c_int32, C.c_int32, P, C.c_int, C.POINTER(P), P]
+    lib.ndgpu_s2_filter_encode_flags.restype = C.c_int64
+    lib.ndgpu_s2_get_stats.argtypes = [C.POINTER(S2Stats)]
+    lib.ndgpu_s2_get_stats.restype = None
+    lib.ndgpu_s2_reset_stats.argtypes = []
+    lib.ndgpu_s2_reset_stats.restype = None
     lib.ndgpu_s2_bl.argtypes = [P, C.POINTER(P)]
     lib.ndgpu_s2_bl.restype = C.c_int64
     # record sets (K18)
@@ -641,6 +654,17 @@ def pack_2bit(ascii_buf: np.ndarray, ascii_off: np.ndarray, lens: np.ndarray):
     return words[:n], word_off
 
 
+def s2_stats() -> dict:
+    """Counters of the step-2 filter / encoder calls of the process since the last reset (ndgpu_s2_stats)."""
+    st = S2Stats()
+    load().ndgpu_s2_get_stats(C.byref(st))
+    return {k: (list(getattr(st, k)) if k == "declined" else getattr(st, k)) for k, _ in S2Stats._fields_}
+
+
+def s2_reset_stats() -> None:
+    load().ndgpu_s2_reset_stats()
+
+
 class Step2Filter:
     """filter_ovl / encode_ovl_i / out_bl of one `minimap2-nd --step 2` run (lib/ovl.c:449-563, 205-253, 339-362): the state
     lives from the first record to the `.bl` table."""
@@ -652,14 +676,16 @@ class Step2Filter:
             raise MemoryError("ndgpu_s2_new")
         self.prev = np.zeros(2, dtype=np.uint32)
 
-    def feed(self, recs: np.ndarray, maxhan1: int, maxhan2: int, want_verdicts: bool = False):
-        """Records of one map2 call -> bytes of the kept ones (and their verdicts)."""
+    def feed(self, recs: np.ndarray, maxhan1: int, maxhan2: int, want_verdicts: bool = False, device=None):
+        """Records of one map2 call -> bytes of the kept ones (and their verdicts).  device: True = K23 on the device, False = the
+        host loop, None = what NDGPU_S2_DEVICE says (unset: the host loop); the answers are the same."""
         recs = np.ascontiguousarray(recs, dtype=REC10)
         out = C.c_void_p()
         kept = np.zeros(max(1, recs.size), dtype=np.uint8)
-        n = self.lib.ndgpu_s2_filter_encode(self.h, _ptr(recs), recs.size, maxhan1, maxhan2, _ptr(self.prev), C.byref(out), _ptr(kept))
+        flags = 0 if device is None else 2 if device else 1
+        n = self.lib.ndgpu_s2_filter_encode_flags(self.h, _ptr(recs), recs.size, maxhan1, maxhan2, _ptr(self.prev), flags, C.byref(out), _ptr(kept))
         if n < 0:
-            raise RuntimeError("ndgpu_s2_filter_encode failed (%d)" % n)
+            raise RuntimeError("ndgpu_s2_filter_encode_flags failed (%d)" % n)
         b = _take(self.lib, out, n, np.uint8).tobytes()
         return (b, kept[:recs.size].astype(bool)) if want_verdicts else b
 
