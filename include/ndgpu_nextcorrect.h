@@ -219,6 +219,43 @@ typedef struct ndgpu_cns_walk_result {
 int ndgpu_cns_walk_batch(const ndgpu_cns_walk_job *jobs, int n, int flags, ndgpu_cns_walk_result *res, uint32_t **bases, uint32_t **regions,
                          char **seqs);
 
+/* The end of a pile for many piles in one call: the splice of the regions' pseudo-seeds into the consensus with its table of
+ * lower-case runs (update_consensus_trimed and update_lqreg, reference lib/nextcorrect.c:1340-1482) and the clipping of terminal
+ * simple-sequence repeats (trim_terminal_ssr, :2008-2128).  A job holds the consensus words pos << 8 | char in ascending positions
+ * (n_words of them; the loop reads [lstrip, n_words - rstrip)), its regions in the engine's order (the index counts down while the
+ * positions go up; a region is usable when len > 0 or len == -2; sudoseed holds sudoseed_len bytes) and read_type (3: HiFi).
+ * The result: len as the engine reports it (2: a HiFi string of lower case alone; 4: the clips leave 10 bases or fewer), lq_total_len
+ * and identity as they stand before the trim, out_len (characters emitted before the stretch was chosen), the stretch [lq_m, hq_m),
+ * lq_i, the two clips, and seq_len bytes from (*seqs)[seq_off] on: the result string (len 2: none; the len = 4 outcome of the trim:
+ * the first four bytes of the untrimmed stretch, which is what the engine's record carries).  *seqs is one malloc'd byte block of
+ * exact size (free() it; one byte when empty), the strings one behind the other.  flags bit 0: the host statement (nd_splice.h).
+ * Returns 0; -2, with nothing computed or written, for n < 0, a NULL pointer with n > 0 (jobs, res, seqs, a job's words with
+ * n_words > 0, its regions with n_regions > 0, a pseudo-seed with sudoseed_len > 0), lstrip + rstrip > n_words, descending positions
+ * among the words read, and a region with start > end; < 0 when no device can be used.  n = 0 is valid.  A job the kernel must not
+ * compute (a position above 2^21 - 2, more than 2^30 words and pseudo-seed bytes) is answered by the host statement. */
+typedef struct ndgpu_splice_region {
+    uint32_t start, end;
+    int32_t len;
+    uint32_t sudoseed_len;
+    const char *sudoseed;
+} ndgpu_splice_region;
+typedef struct ndgpu_splice_job {
+    const uint32_t *words;
+    uint32_t n_words, lstrip, rstrip, n_regions;
+    const ndgpu_splice_region *regions;
+    int32_t read_type;
+    uint32_t pad_;
+} ndgpu_splice_job;
+typedef struct ndgpu_splice_result {
+    uint32_t len, lq_total_len;
+    float identity;
+    uint32_t out_len, lq_m, hq_m;
+    int32_t lq_i, clip_s, clip_e;
+    uint32_t seq_len;
+    uint64_t seq_off;
+} ndgpu_splice_result;
+int ndgpu_splice_batch(const ndgpu_splice_job *jobs, int n, int flags, ndgpu_splice_result *res, char **seqs);
+
 /* The phasing and ranking of the low-quality-region candidates of HiFi piles (generate_lqseqs_from_tags_kmer, lib/nextcorrect.c:787-948
  * with the helpers of 512-737: from the candidates as extracted up to the sort by score), for many piles in one call.  A job is a
  * pile: n_aligned reads, n_regions regions in order, each with its inclusive seed columns start / end and n_cand candidates (0..40):
@@ -430,6 +467,19 @@ typedef struct {
     uint64_t seed_lower;            /* seed regions whose pseudo-seed goes to lower case */
 } ndgpu_phase_stats;
 void ndgpu_get_phase_stats(ndgpu_phase_stats *out);
+
+/* The splice, its table of lower-case runs and the SSR trim on the device (K24: ndgpu_splice_batch).  Counters of their own:
+ * ndgpu_stats keeps its layout.  ndgpu_reset_stats clears these too. */
+typedef struct ndgpu_splice_stats {
+    uint64_t jobs;        /* jobs offered to the device */
+    uint64_t declined;    /* ... of which the host statement answered */
+    uint64_t launches;    /* launches of K24 (each with its gather) */
+    uint64_t h2d_bytes;   /* records, words and pseudo-seed bytes sent up */
+    uint64_t d2h_bytes;   /* result records and result strings brought back */
+    uint64_t trimmed;     /* jobs whose gate let the SSR trim run */
+    double ms;            /* K24's HIP-event time */
+} ndgpu_splice_stats;
+void ndgpu_get_splice_stats(ndgpu_splice_stats *out);
 /* The device contexts keep their (grow-only) buffers between calls.  This hands them back -- for a caller that alternates
  * the consensus with another memory-hungry stage on the same device (the overlap stage of a genome-scale read set) and
  * finds that stage short of memory.  Safe to call at any time from any thread: a context that is in the middle of a batch

@@ -72,6 +72,30 @@ class CnsModeStats(C.Structure):
                 ("fast_declined", C.c_uint64), ("launches", C.c_uint64), ("ms", C.c_double), ("d2h_bytes", C.c_uint64)]
 
 
+class SpliceRegion(C.Structure):
+    # ndgpu_splice_region
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("len", C.c_int32), ("sudoseed_len", C.c_uint32), ("sudoseed", C.c_char_p)]
+
+
+class SpliceJob(C.Structure):
+    # ndgpu_splice_job
+    _fields_ = [("words", C.c_void_p), ("n_words", C.c_uint32), ("lstrip", C.c_uint32), ("rstrip", C.c_uint32), ("n_regions", C.c_uint32),
+                ("regions", C.POINTER(SpliceRegion)), ("read_type", C.c_int32), ("pad_", C.c_uint32)]
+
+
+class SpliceResult(C.Structure):
+    # ndgpu_splice_result
+    _fields_ = [("len", C.c_uint32), ("lq_total_len", C.c_uint32), ("identity", C.c_float), ("out_len", C.c_uint32), ("lq_m", C.c_uint32),
+                ("hq_m", C.c_uint32), ("lq_i", C.c_int32), ("clip_s", C.c_int32), ("clip_e", C.c_int32), ("seq_len", C.c_uint32),
+                ("seq_off", C.c_uint64)]
+
+
+class SpliceStats(C.Structure):
+    # ndgpu_splice_stats
+    _fields_ = [("jobs", C.c_uint64), ("declined", C.c_uint64), ("launches", C.c_uint64), ("h2d_bytes", C.c_uint64),
+                ("d2h_bytes", C.c_uint64), ("trimmed", C.c_uint64), ("ms", C.c_double)]
+
+
 class PhaseRegionIn(C.Structure):
     # ndgpu_phase_region_in
     _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_cand", C.c_int32), ("pad_", C.c_uint32), ("seqs", C.POINTER(C.c_char_p)),
@@ -205,6 +229,10 @@ def _bind(lib):
     lib.ndgpu_hifi_phase_batch.restype = C.c_int
     lib.ndgpu_get_phase_stats.argtypes = [C.POINTER(PhaseStats)]
     lib.ndgpu_get_phase_stats.restype = None
+    lib.ndgpu_splice_batch.argtypes = [C.POINTER(SpliceJob), C.c_int, C.c_int, C.POINTER(SpliceResult), C.POINTER(C.c_void_p)]
+    lib.ndgpu_splice_batch.restype = C.c_int
+    lib.ndgpu_get_splice_stats.argtypes = [C.POINTER(SpliceStats)]
+    lib.ndgpu_get_splice_stats.restype = None
     lib.ndgpu_align_batch.argtypes = [C.POINTER(AlnJob), C.c_int, C.c_int, C.POINTER(AlnResult), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.ndgpu_align_batch.restype = C.c_int
@@ -594,6 +622,50 @@ def cns_mode_stats() -> dict:
     s = CnsModeStats()
     load().ndgpu_get_cns_mode_stats(C.byref(s))
     return {n: getattr(s, n) for n, _ in CnsModeStats._fields_}
+
+
+def splice_batch(jobs, host=False):
+    """jobs: [(words, lstrip, rstrip, regions, read_type)]: words a uint32 array of pos << 8 | char in ascending positions, regions
+    [(start, end, len, sudoseed bytes)] in the engine's order (the index counts down while the positions go up), read_type 3 for HiFi
+    -> one dict per job through ndgpu_splice_batch: len and identity (numpy.float32) as the engine reports them (len 2 and 4: the two
+    error outcomes), lq_total_len, out_len, lq_m, hq_m, lq_i, clip_s, clip_e, seq (bytes).  host=True: the host statement instead of
+    the device.  ValueError for what the entry refuses (-2)."""
+    import numpy as np
+    lib = load()
+    n = len(jobs)
+    if n == 0:
+        return []
+    arr = (SpliceJob * n)()
+    keep = []
+    for i, (words, lstrip, rstrip, regions, read_type) in enumerate(jobs):
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        rg = (SpliceRegion * max(1, len(regions)))()
+        for k, (start, end, ln, seed) in enumerate(regions):
+            seed = bytes(seed)
+            keep.append(seed)
+            rg[k] = SpliceRegion(int(start), int(end), int(ln), len(seed), seed)
+        keep.append((w, rg))
+        arr[i] = SpliceJob(w.ctypes.data if w.size else None, int(w.size), int(lstrip), int(rstrip), len(regions),
+                           rg if len(regions) else None, int(read_type), 0)
+    res = (SpliceResult * n)()
+    sw = C.c_void_p()
+    rc = lib.ndgpu_splice_batch(arr, n, 1 if host else 0, res, C.byref(sw))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("ndgpu_splice_batch failed (%d)" % rc)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    seqs = C.string_at(sw, sum(r.seq_len for r in res))
+    libc.free(sw)
+    return [dict(len=int(r.len), identity=np.float32(r.identity), lq_total_len=int(r.lq_total_len), out_len=int(r.out_len), lq_m=int(r.lq_m),
+                 hq_m=int(r.hq_m), lq_i=int(r.lq_i), clip_s=int(r.clip_s), clip_e=int(r.clip_e), seq=seqs[r.seq_off:r.seq_off + r.seq_len])
+            for r in res]
+
+
+def splice_stats() -> dict:
+    """ndgpu_splice_stats: the counters of the splice and the SSR trim on the device (K24), cleared by reset_stats()."""
+    s = SpliceStats()
+    load().ndgpu_get_splice_stats(C.byref(s))
+    return {n: getattr(s, n) for n, _ in SpliceStats._fields_}
 
 
 PHASE_EMPTY, PHASE_DROPPED, PHASE_SEED, PHASE_RANKED = 0, 1, 2, 3

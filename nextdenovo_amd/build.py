@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libndgpu_nextcorrect.so")
 SOURCES = ["ond_kernels.hip", "msa_kernels.hip", "lq_kernels.hip", "ext_kernels.hip", "device_runtime.hip", "consensus.cpp", "poa.cpp", "readdb.cpp", "capi.cpp"]
-HEADERS = ["nd_device.h", "nd_host.h", "nd_runtime.h", "nd_subplan.h", "nd_lqplan.h", "nd_phase.h", os.path.join("..", "..", "include", "ndgpu_nextcorrect.h")]
+HEADERS = ["nd_device.h", "nd_host.h", "nd_runtime.h", "nd_subplan.h", "nd_lqplan.h", "nd_phase.h", "nd_cns.h", "nd_splice.h", os.path.join("..", "..", "include", "ndgpu_nextcorrect.h")]
 OVL_LIB = os.path.join(HERE, "libndgpu_overlap.so")
 OVL_SOURCES = ["ovl_kernels.hip", "ovl_engine.hip", "ovlsort_kernels.hip", "ovlsort_engine.hip", "fastx_reader.cpp", "pinflate.cpp", "ovl_step2.cpp", "ovl_cigar.cpp", "ksw2_kernels.hip"]
 OVL_HEADERS = ["ovl_device.h", "ovl_host.h", "ovl_pool.h", "ovl_recset.h", "nd_lockstep.h", "pinflate.h", os.path.join("..", "..", "include", "ndgpu_overlap.h")]

@@ -263,6 +263,10 @@ void print_prof(int drivers, int threads_each) {  // NDGPU_PROF: the host driver
                 (unsigned long long)s.phase_regions, (unsigned long long)s.phase_kind[2], (unsigned long long)s.phase_kind[3],
                 (unsigned long long)s.phase_kind[1], (unsigned long long)declined, (unsigned long long)s.phase_launches, s.phase_ms,
                 (unsigned long long)s.phase_d2h_records, (unsigned long long)s.phase_d2h_strings);
+        fprintf(stderr, "[ndgpu prof] K24 since the last reset: %llu jobs, %llu declined, %llu trimmed | %llu launches, %.3f ms | h2d %llu bytes, "
+                        "d2h %llu bytes\n", (unsigned long long)s.splice_jobs, (unsigned long long)s.splice_declined,
+                (unsigned long long)s.splice_trimmed, (unsigned long long)s.splice_launches, s.splice_ms,
+                (unsigned long long)s.splice_h2d_bytes, (unsigned long long)s.splice_d2h_bytes);
     }
     for (auto &a : g_prof.adv_ns) a = 0;
     g_prof.main_ns = g_prof.extract_ns = g_prof.align_ns = g_prof.advance_ns = g_prof.jobs = 0;
@@ -1137,6 +1141,95 @@ int ndgpu_cns_walk_batch(const ndgpu_cns_walk_job *jobs, int n, int flags, ndgpu
     return 0;
 }
 
+// The end of a batch of piles: K24 (DeviceAligner::run_splice) or -- flags bit 0, or a job the runtime declines -- splice_host and
+// ssr_trim_host.  Length and identity are formed here from either's integers (splice_finish of nd_splice.h).
+int ndgpu_splice_batch(const ndgpu_splice_job *jobs, int n, int flags, ndgpu_splice_result *res, char **seqs) {
+    if (n == 0) return 0;
+    if (n < 0 || !jobs || !res || !seqs) return -2;
+    size_t n_reg = 0;
+    for (int i = 0; i < n; i++) {
+        const ndgpu_splice_job &j = jobs[i];
+        if ((j.n_words && !j.words) || (j.n_regions && !j.regions)) return -2;
+        if ((uint64_t)j.lstrip + j.rstrip > j.n_words) return -2;
+        for (uint32_t k = j.lstrip + 1; k < j.n_words - j.rstrip; k++)
+            if ((j.words[k] >> 8) < (j.words[k - 1] >> 8)) return -2;
+        for (uint32_t k = 0; k < j.n_regions; k++)
+            if (j.regions[k].start > j.regions[k].end || (j.regions[k].sudoseed_len && !j.regions[k].sudoseed)) return -2;
+        n_reg += j.n_regions;
+    }
+    std::vector<SpliceRegion> regs(n_reg);
+    std::vector<SpliceReq> reqs((size_t)n);
+    for (size_t i = 0, at = 0; i < (size_t)n; i++) {
+        const ndgpu_splice_job &j = jobs[i];
+        for (uint32_t k = 0; k < j.n_regions; k++) {
+            SpliceRegion &r = regs[at + k];
+            r.start = j.regions[k].start, r.end = j.regions[k].end, r.len = j.regions[k].len;
+            r.sudoseed_len = j.regions[k].sudoseed_len, r.sudoseed = j.regions[k].sudoseed;
+        }
+        SpliceReq &rq = reqs[i];
+        rq.words = j.words, rq.len = j.n_words, rq.lstrip = j.lstrip, rq.rstrip = j.rstrip;
+        rq.regions = regs.data() + at, rq.n_regions = j.n_regions, rq.hifi = j.read_type == 3;
+        at += j.n_regions;
+    }
+    std::vector<SpliceReq *> ptr(reqs.size());
+    for (size_t i = 0; i < reqs.size(); i++) ptr[i] = &reqs[i];
+    if (!(flags & 1)) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+            fprintf(stderr, "[ndgpu] FATAL: no HIP device visible: ndgpu_splice_batch runs on the device unless flags bit 0 is set\n");
+            return -1;
+        }
+        std::vector<std::pair<size_t, size_t>> todo{{0, reqs.size()}};   // (out of device memory: the range is halved until it fits)
+        while (!todo.empty()) {
+            const auto [a, b] = todo.back();
+            todo.pop_back();
+            try {
+                HipBackend be(0, 1);
+                (void)be.run_splice(ptr.data() + a, b - a);
+            } catch (const DeviceOom &) {
+                DeviceAligner::context(0).release_memory();
+                DeviceAligner::forget_sizes();
+                if (b - a <= 1) return -3;
+                todo.push_back({a + (b - a) / 2, b});
+                todo.push_back({a, a + (b - a) / 2});
+            }
+        }
+    }
+    std::vector<SpliceAnswer> ans((size_t)n);
+    host_each(reqs.size(), effective_cpus() <= 1 || reqs.size() <= 1, effective_cpus(), reqs.size(), false, [&](size_t i) {
+        SpliceReq &rq = reqs[i];
+        SpliceAnswer &a = ans[i];
+        if (!rq.done) {
+            splice_answer_host(rq.words, rq.len, rq.lstrip, rq.rstrip, rq.regions, rq.n_regions, rq.hifi, a);
+            return;
+        }
+        // the device's integers; the host forms the float
+        a.out_len = rq.out_len, a.lq_m = rq.lq_m, a.hq_m = rq.hq_m, a.lq_i = rq.lq_i, a.lq_total_len = rq.lq_total_len;
+        a.clip_s = rq.clip_s, a.clip_e = rq.clip_e, a.trimmed = rq.trimmed;
+        const unsigned len0 = splice_len(rq.lq_m, rq.hq_m, rq.code == 2u);
+        a.identity = splice_identity(rq.lq_total_len, len0, rq.code == 2u);
+        a.len = rq.code ? rq.code : (uint32_t)rq.seq.size();
+        a.seq.swap(rq.seq);
+    });
+    size_t n_seq = 0;
+    for (const SpliceAnswer &a : ans) n_seq += a.seq.size();
+    char *sw = (char *)malloc(std::max<size_t>(1, n_seq));
+    if (!sw) return -3;
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        const SpliceAnswer &a = ans[(size_t)i];
+        ndgpu_splice_result &o = res[i];
+        memset(&o, 0, sizeof(o));
+        o.len = a.len, o.lq_total_len = a.lq_total_len, o.identity = a.identity, o.out_len = a.out_len, o.lq_m = a.lq_m, o.hq_m = a.hq_m;
+        o.lq_i = a.lq_i, o.clip_s = a.clip_s, o.clip_e = a.clip_e;
+        o.seq_len = (uint32_t)a.seq.size(), o.seq_off = at;
+        if (!a.seq.empty()) memcpy(sw + at, a.seq.data(), a.seq.size());
+        at += a.seq.size();
+    }
+    *seqs = sw;
+    return 0;
+}
+
 // ---- batched global alignment: align() / align_hq() for many pairs in one call, CIGARs built on the device (K15) ----
 namespace {
 struct AlnBatchSrc {            // where job i's bases are, for the strings flag
@@ -1347,6 +1440,13 @@ void ndgpu_get_phase_stats(ndgpu_phase_stats *o) {
     o->launches = s.phase_launches, o->ms = s.phase_ms;
     o->d2h_record_bytes = s.phase_d2h_records, o->d2h_string_bytes = s.phase_d2h_strings;
     o->seed_lower = s.phase_lower;
+}
+
+void ndgpu_get_splice_stats(ndgpu_splice_stats *o) {
+    if (!o) return;
+    const RuntimeStats s = DeviceAligner::total_stats();
+    o->jobs = s.splice_jobs, o->declined = s.splice_declined, o->launches = s.splice_launches;
+    o->h2d_bytes = s.splice_h2d_bytes, o->d2h_bytes = s.splice_d2h_bytes, o->trimmed = s.splice_trimmed, o->ms = s.splice_ms;
 }
 
 uint64_t ndgpu_release_memory(void) {

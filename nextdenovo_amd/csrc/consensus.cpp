@@ -15,6 +15,7 @@
 // Reference locations are cited at each step.
 #include "nd_host.h"
 #include "nd_cns.h"
+#include "nd_splice.h"
 
 #include <algorithm>
 #include <cctype>
@@ -250,36 +251,6 @@ struct CnsData {
     std::vector<CnsBase> bases;
 };
 
-struct LqReg {
-    unsigned start = 0, end = 0, lqlen = 0, lq_total_len = 0;
-};
-constexpr int kLqRegMax = 10;  // LQREG_MAX_COUNT
-
-// lib/nextcorrect.c:1340-1363
-int update_lqreg(LqReg *lq, const std::string &seq, unsigned p, int i, unsigned *hq_m, unsigned *lq_m) {
-    if (seq[p] >= 'a') {
-        if (!lq[i].lqlen) lq[i].start = p;
-        if ((*lq_m)++ > 2) *hq_m = 0;
-        lq[i].end = p;
-        lq[i].lqlen++;
-        lq[i].lq_total_len++;
-    } else {
-        if (lq[i].lqlen && lq[i].start == 0) {
-            i++;
-            *hq_m = 0;
-        } else if (*hq_m + lq[i].start > lq[i].end || (*hq_m)++ > 10) {
-            if (lq[i].end > lq[i].start + 100) i++;
-            else lq[i].lqlen = lq[i].end = 0;
-            *hq_m = 0;
-        } else if (*hq_m >= lq[i].lqlen) {
-            lq[i].lqlen = lq[i].end = 0;
-            *hq_m = 0;
-        }
-        *lq_m = 0;
-    }
-    return i;
-}
-
 // ---- 8-mer ranking of low-quality-region candidates (lib/nextcorrect.c:281-337)
 constexpr int kKmerLen = 8, kKmerRange = 40, kKmerBins = 65536, kKmerMaxSeq = 10;
 constexpr int kLqCanMax = 40, kLqSeqMax = 30, kLqRevLen = 2000;
@@ -399,101 +370,11 @@ void lq_rank_host(const char *const *seqs, const uint16_t *len, int n, uint8_t *
 
 namespace {
 
-// ---- terminal SSR clipping (lib/nextcorrect.c:2008-2128)
-int terminal_ssr(int *bins, int range, int klen, const char *seq, int s) {
-    memset(bins, 0, sizeof(int) * 256);
-    uint8_t km = 0;
-    for (int i = 0; i < range; i++) {
-        if (i) km = (uint8_t)(km << 2 | base_code(seq[s + i + klen - 1]));
-        else
-            for (int k = 0; k < klen; k++) km = (uint8_t)(km << 2 | base_code(seq[s + k]));
-        bins[km]++;
-    }
-    int best = 0;
-    for (int i = 0; i < 256; i++)
-        if (bins[i] > best) {
-            best = bins[i];
-            km = (uint8_t)i;
-        }
-    return km;
-}
-
-int clip_ssr(const char *seq, int seq_len, int klen, int kmer, int from_end) {
-    const int gap = 20;
-    int i, p = 0, p1 = 0, p2 = 0;
-    uint8_t cur = 0;
-    if (from_end) {
-        uint8_t rk = 0;
-        for (i = 0; i < 8; i += 2) rk = (uint8_t)(rk << 2 | (kmer >> i & 3));
-        seq_len--;
-        kmer = rk;
-        for (i = 0; i < seq_len - klen; i++) {
-            if (i) cur = (uint8_t)(cur << 2 | base_code(seq[seq_len - i - klen + 1]));
-            else
-                for (int k = 0; k < klen; k++) cur = (uint8_t)(cur << 2 | base_code(seq[seq_len - k]));
-            if (cur != kmer) {
-                if (i - p > gap) {
-                    if (!p1) p1 = p;
-                    else if (p2) {
-                        if (i - p2 < 100) { p = p1; break; }
-                        else p1 = p2 = 0;
-                    }
-                }
-            } else {
-                p = i;
-                if (p1 && p2 == 0) p2 = p;
-            }
-        }
-    } else {
-        for (i = 0; i < seq_len - klen; i++) {
-            if (i) cur = (uint8_t)(cur << 2 | base_code(seq[i + klen - 1]));
-            else
-                for (int k = 0; k < klen; k++) cur = (uint8_t)(cur << 2 | base_code(seq[k]));
-            if (cur != kmer) {
-                if (i - p > gap) {
-                    if (!p1) p1 = p;
-                    else if (p2) {
-                        if (i - p2 < 100) { p = p1; break; }
-                        else p1 = p2 = 0;
-                    }
-                }
-            } else {
-                p = i;
-                if (p1 && p2 == 0) p2 = p;
-            }
-        }
-    }
-    return p > 100 ? p + klen : 0;
-}
-
 struct Result {
     unsigned len = 0;
     float identity = 0;
     std::string seq;
 };
-
-void trim_terminal_ssr(Result &r) {
-    int bins[256];
-    const int range = 24, klen = 4;
-    int clip_s = 0, clip_e = 0;
-    const int L = (int)r.len;
-    int km = terminal_ssr(bins, range, klen, r.seq.c_str(), 0);
-    if (bins[km] >= 4) {
-        clip_s = clip_ssr(r.seq.c_str(), L, klen, km, 0);
-        while (clip_s < L && r.seq[clip_s] >= 'a') clip_s++;
-    }
-    km = terminal_ssr(bins, range, klen, r.seq.c_str(), L - range - klen + 1);
-    if (bins[km] >= 4) {
-        clip_e = clip_ssr(r.seq.c_str(), L, klen, km, 1);
-        while (clip_e < L && r.seq[L - clip_e - 1] >= 'a') clip_e++;
-    }
-    if (clip_s + clip_e < L - 10) {
-        r.seq = r.seq.substr(clip_s, L - clip_s - clip_e);
-        r.len = (unsigned)(L - clip_s - clip_e);
-    } else {
-        r.len = 4;
-    }
-}
 
 }  // namespace
 
@@ -511,6 +392,9 @@ class PileImpl {
     std::vector<int64_t> dev_off;
     int seed_len = 0;
     Phase phase = PileEngine::MAIN;
+    SpliceReq sp_req;                       // the splice as a backend request (NDGPU_SPLICE_DEVICE=1)
+    std::vector<uint32_t> sp_words;
+    std::vector<SpliceRegion> sp_regions;
     MainPile main;
     ExtractPile extract;
     std::vector<AlnJob> jobs;
@@ -600,6 +484,7 @@ class PileImpl {
         else if (phase == PileEngine::EXTRACT) after_extract();
         else if (phase == PileEngine::POA) after_poa();
         else if (phase == PileEngine::LQ_ROUND) after_lq_round();
+        else if (phase == PileEngine::SPLICE) after_splice();
         g_prof.adv_ns[ph] += now_ns() - t0;  // per-thread sums: after main / after extract / after LQ round 1 / after round 2 + splice
     }
 
@@ -1235,102 +1120,60 @@ class PileImpl {
             start_lq_round();
             return;
         }
-        splice();
+        if (splice_on_device()) post_splice();
+        else splice();
     }
 
-    // update_consensus_trimed (lib/nextcorrect.c:1365-1482), non-HiFi branch, then
-    // trim_terminal_ssr (nextcorrect.c:2214)
-    void splice() {
-        std::string out;
-        out.reserve((size_t)seed_len * 2 + 1);
-        unsigned p = 0, i = cns.lstrip;
-        int update = 1;
-        int idx = (int)regions.size() - 1;
-        LqReg lq[kLqRegMax + 1];  // +1 guard slot (the reference indexes lq[10] in one corner case)
-        unsigned lq_m = 0, hq_m = 0;
-        int lq_i = 0;
-        auto usable = [&](int k) { return regions[k].len > 0 || regions[k].len == -2; };
-        bool stop = false;
-        while (!stop && i < cns.len - cns.rstrip) {
-            p = cns.bases[i].pos;
-            if (idx >= 0 && (!usable(idx) || p > regions[idx].end)) {
-                idx--;
-                update = 1;
-            }
-            if (idx >= 0 && usable(idx) && p >= regions[idx].start && p <= regions[idx].end) {
-                if (update) {
-                    const LqRegion &r = regions[idx];
-                    for (unsigned j = 0; j < r.sudoseed_len; j++) {
-                        out.push_back(r.sudoseed[j]);
-                        lq_i = update_lqreg(lq, out, (unsigned)out.size() - 1, lq_i, &hq_m, &lq_m);
-                        if (lq_i >= kLqRegMax) { stop = true; break; }
-                    }
-                    update = 0;
-                }
-            } else {
-                out.push_back(cns.bases[i].base);
-                update = 1;
-                lq_i = update_lqreg(lq, out, (unsigned)out.size() - 1, lq_i, &hq_m, &lq_m);
-                if (lq_i >= kLqRegMax) break;
-            }
-            i++;
-        }
-        unsigned olen = (unsigned)out.size();
-        if (lq_i < kLqRegMax + 1 && lq[lq_i].end == olen - 1) lq_i++;
-
-        if (prm.read_type == 3) {
-            unsigned a = 0, z = 0, lq_total_len = 0;
-            while (a < olen && out[a] >= 'a') a++;
-            while (z < olen && out[olen - 1 - z] >= 'a') z++;
-            if (a + z < olen) {
-                if (a > 0 || z > 0) out = out.substr(a, olen - a - z);
-                const int removed = (int)(a + z);
-                for (int q = 0; q < lq_i && q < kLqRegMax + 1; q++) lq_total_len += lq[q].lq_total_len;
-                result.len = (unsigned)out.size();
-                result.seq = out;
-                result.identity = 1 - (float)(lq_total_len - (unsigned)removed) / result.len;
-            } else {
-                result.len = 2;
-                result.identity = 0;
-                result.seq.clear();
-            }
-            if (result.len > 1000 && result.identity > 0.8) trim_terminal_ssr(result);
-            phase = PileEngine::DONE;
+    // K24 (opt-in): NDGPU_SPLICE_DEVICE=1 -- the splice goes to the backend as a request, whatever the read type.
+    static bool splice_on_device() {
+        static const bool on = getenv("NDGPU_SPLICE_DEVICE") != nullptr && atoi(getenv("NDGPU_SPLICE_DEVICE")) != 0;
+        return on;
+    }
+    // The request: the words go up with it (the batch's own copy of K20's words is gone by now: its slot is reused by the next
+    // launch of the main phase), the regions point into this pile's.
+    void post_splice() {
+        sp_words.resize(cns.len);
+        for (unsigned i = 0; i < cns.len; i++) sp_words[i] = cns.bases[i].pos << 8 | (unsigned char)cns.bases[i].base;
+        fill_splice_regions();
+        sp_req = SpliceReq();
+        sp_req.words = sp_words.data(), sp_req.len = cns.len, sp_req.lstrip = cns.lstrip, sp_req.rstrip = cns.rstrip;
+        sp_req.regions = sp_regions.data(), sp_req.n_regions = sp_regions.size(), sp_req.hifi = prm.read_type == 3;
+        phase = PileEngine::SPLICE;
+    }
+    // What came back: the host contributes the identity alone (a declined request, or a backend without the entry: splice()).
+    void after_splice() {
+        if (!sp_req.done) {
+            splice();
             return;
         }
-        if (lq_i) {
-            lq_m = 0;
-            hq_m = lq[0].start;
-            p = lq[0].start;
-            unsigned lq_total_len = lq[0].lq_total_len - lq[0].lqlen;
-            for (i = 1; i < (unsigned)kLqRegMax && lq[i].end; i++) {
-                if (lq[i].start - lq[i - 1].end > p) {
-                    lq_m = lq[i - 1].end + 1;
-                    hq_m = lq[i].start;
-                    lq_total_len = lq[i].lq_total_len - lq[i].lqlen;
-                    p = lq[i].start - lq[i - 1].end;
-                }
-            }
-            if (i < (unsigned)kLqRegMax && olen - lq[i - 1].end > p) {
-                lq_m = lq[i - 1].end + 1;
-                hq_m = olen;
-                lq_total_len = lq[i].lq_total_len;
-            }
-            result.len = hq_m - lq_m;
-            result.seq = lq_m <= out.size() ? out.substr(lq_m, result.len) : std::string();
-            result.identity = 1 - (float)lq_total_len / result.len;
-        } else {
-            if (!out.empty() && out[0] >= 'a') {
-                unsigned k = 0;
-                while (k < out.size() && out[k] >= 'a') k++;
-                out.erase(0, k);
-                lq[0].lq_total_len -= k;
-            }
-            result.len = (unsigned)out.size();
-            result.seq = out;
-            result.identity = 1 - (float)lq[0].lq_total_len / result.len;
+        const bool empty2 = sp_req.code == 2u;
+        result.identity = splice_identity(sp_req.lq_total_len, splice_len(sp_req.lq_m, sp_req.hq_m, empty2), empty2);
+        result.len = sp_req.code ? sp_req.code : (unsigned)sp_req.seq.size();
+        result.seq.swap(sp_req.seq);
+        std::vector<uint32_t>().swap(sp_words);
+        phase = PileEngine::DONE;
+    }
+    void fill_splice_regions() {
+        sp_regions.resize(regions.size());
+        for (size_t k = 0; k < regions.size(); k++) {
+            const LqRegion &r = regions[k];
+            sp_regions[k].start = r.start, sp_regions[k].end = r.end, sp_regions[k].len = r.len;
+            sp_regions[k].sudoseed_len = r.sudoseed_len, sp_regions[k].sudoseed = r.sudoseed.data();
         }
-        if (result.len > 1000 && result.identity > 0.8) trim_terminal_ssr(result);
+    }
+
+    // update_consensus_trimed (lib/nextcorrect.c:1365-1482) and trim_terminal_ssr (:2008-2128): the rule is nd_splice.h's
+    void splice() {
+        struct Words {
+            const CnsBase *b;
+            uint32_t operator[](size_t i) const { return b[i].pos << 8 | (unsigned char)b[i].base; }
+        };
+        fill_splice_regions();
+        SpliceAnswer a;
+        splice_answer_host(Words{cns.bases.data()}, cns.len, cns.lstrip, cns.rstrip, sp_regions.data(), sp_regions.size(), prm.read_type == 3, a);
+        result.len = a.len;
+        result.identity = a.identity;
+        result.seq.swap(a.seq);
         phase = PileEngine::DONE;
     }
 
@@ -1364,6 +1207,7 @@ ExtractPile *PileEngine::extract_request() { return &impl_->extract; }
 void PileEngine::collect_jobs(std::vector<AlnJob *> &out) { impl_->collect(out); }
 LqRound *PileEngine::lq_request() { return impl_->phase == LQ_ROUND && !impl_->jobs.empty() ? &impl_->lq : nullptr; }
 void PileEngine::collect_poa(std::vector<PoaReq *> &out) { impl_->collect_poa(out); }
+SpliceReq *PileEngine::splice_request() { return &impl_->sp_req; }
 void PileEngine::advance() { impl_->advance(); }
 ConsensusTrimed *PileEngine::take_result() { return impl_->take(); }
 
@@ -1487,6 +1331,7 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
     std::vector<AlnJob *> jobs;
     std::vector<LqRound *> lqs;
     std::vector<PoaReq *> poas;
+    std::vector<SpliceReq *> splices;
     std::vector<size_t> live, in_lq;
     for (;;) {
         mains.clear();
@@ -1494,6 +1339,7 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
         jobs.clear();
         lqs.clear();
         poas.clear();
+        splices.clear();
         live.clear();
         in_lq.clear();
         for (size_t i = 0; i < n; i++) {
@@ -1501,6 +1347,7 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
                 case PileEngine::MAIN: mains.push_back(eng[i]->main_request()); break;
                 case PileEngine::EXTRACT: extracts.push_back(eng[i]->extract_request()); break;
                 case PileEngine::POA: eng[i]->collect_poa(poas); break;
+                case PileEngine::SPLICE: splices.push_back(eng[i]->splice_request()); break;
                 case PileEngine::LQ_ROUND:
                     in_lq.push_back(i);
                     if (LqRound *r = eng[i]->lq_request()) lqs.push_back(r);
@@ -1522,6 +1369,8 @@ void run_engines(PileEngine **eng, size_t n, Backend &be, int threads) {
         if (!lqs.empty()) (void)be.run_lq(lqs.data(), lqs.size());
         for (size_t i : in_lq) eng[i]->collect_jobs(jobs);
         if (!jobs.empty()) be.run_align(jobs.data(), jobs.size());
+        // the piles behind their last LQ round: the splices as one batch where the backend offers that; the rest is computed in advance()
+        if (!splices.empty()) (void)be.run_splice(splices.data(), splices.size());
         uint64_t t3 = now_ns();
         {
             CoreLease lease(threads);

@@ -362,6 +362,14 @@ enum class BufLevel { levelled, on_demand };
     X(uint8_t, d_cnsw_chars, device, levelled)                                                                                            \
     X(uint8_t, d_cnsw_seq, device, levelled)                                                                                              \
     X(uint8_t, d_cnsw_seed, device, levelled)                                                                                             \
+    /* K24: jobs, regions, words, pseudo-seed bytes, a slice of emitted characters per job, result records, the dense strings */          \
+    X(SpliceJobDev, d_splice_jobs, device, levelled)                                                                                      \
+    X(SpliceRegDev, d_splice_regs, device, levelled)                                                                                      \
+    X(uint32_t, d_splice_words, device, levelled)                                                                                         \
+    X(uint8_t, d_splice_seeds, device, levelled)                                                                                          \
+    X(uint8_t, d_splice_chars, device, levelled)                                                                                          \
+    X(SpliceOutDev, d_splice_out, device, levelled)                                                                                       \
+    X(uint8_t, d_splice_seq, device, levelled)                                                                                            \
     X(RegionDev, d_regions, device, levelled)                                                                                             \
     X(char, d_strpool, device, levelled)                                                                                                  \
     X(unsigned long long, d_cursor, device, levelled)                                                                                     \
@@ -406,6 +414,14 @@ struct MsaResult {  // count_and_score: the last attempt's error words, its pile
     std::vector<PileDev> piles;
     std::vector<CnsOutDev> cns;        // K20's records, one per pile
     std::vector<CnsWalkOutDev> cnsw;   // or K21's (CnsPlan::walk)
+};
+struct SplicePack {                        // one launch of run_splice: the jobs it takes (ids into the requests) and their arenas
+    std::vector<SpliceJobDev> jobs;
+    std::vector<SpliceRegDev> regs;
+    std::vector<uint32_t> words;
+    std::vector<uint8_t> seeds;
+    std::vector<size_t> ids;
+    uint64_t chars = 0;
 };
 struct CnsPlan {  // plan_cns: K20's jobs of a launch (one per pile, or per walk of run_cns) and the window slots they share
     std::vector<CnsJobDev> jobs;
@@ -541,6 +557,7 @@ struct DeviceAligner::State {
         kEvCnsBegin, kEvCnsEnd,                            // launch_cns: around K20 and its gather
         kEvCnswBegin, kEvCnswEnd,                          // launch_cns_walk: around K21 and its gather
         kEvPhaseBegin, kEvPhaseEnd,                        // phase_on_pool: around K22's two kernels
+        kEvSpliceBegin, kEvSpliceEnd,                      // launch_splice_jobs: around K24 and its gather
         kEvCount
     };
     hipEvent_t evs[kEvCount] = {nullptr};
@@ -636,6 +653,10 @@ struct DeviceAligner::State {
     void reserve_cns_walk(const CnsPlan &cns, size_t slots);
     void launch_cns_walk_jobs(const CnsPlan &cns, const PileDev *dev_piles, const PathItem *dev_path);
     void fetch_cns_walk(const CnsPlan &cns, const MsaResult &res, const std::vector<uint8_t> &bad_pile, MainPile **mp);
+    // The steps of run_splice, in its order (defined above it)
+    size_t pack_splice(SpliceReq **reqs, size_t a, size_t n, SplicePack &P);
+    void launch_splice_jobs(const SplicePack &P);
+    void fetch_splice(SpliceReq **reqs, const SplicePack &P);
     void score_pass(const MsaPlan &plan, const K10Args &k10);
     void rescue_pass(const MsaPlan &plan, const K10Args &k10);
     void k9_digest_trace(const K9Args &k9, size_t np);
@@ -793,6 +814,9 @@ RuntimeStats DeviceAligner::total_stats() {
         for (int k = 0; k < 5; k++) t.phase_declined[k] += s.phase_declined[k];
         t.phase_launches += s.phase_launches; t.phase_ms += s.phase_ms;
         t.phase_d2h_records += s.phase_d2h_records; t.phase_d2h_strings += s.phase_d2h_strings;
+        t.splice_jobs += s.splice_jobs; t.splice_declined += s.splice_declined; t.splice_launches += s.splice_launches;
+        t.splice_h2d_bytes += s.splice_h2d_bytes; t.splice_d2h_bytes += s.splice_d2h_bytes; t.splice_trimmed += s.splice_trimmed;
+        t.splice_ms += s.splice_ms;
     }
     t.allocs = g_alloc_calls.load(), t.alloc_ms = (double)g_alloc_ns.load() * 1e-6;
     t.level_allocs = g_level_calls.load(), t.level_ms = (double)g_level_ns.load() * 1e-6;
@@ -2489,6 +2513,137 @@ void DeviceAligner::run_cns_walk(CnsWalkReq *reqs, size_t n) {
                     (unsigned long long)n_wins, (unsigned long long)n_bytes);
         a = b;
     }
+}
+
+// ---- K24: the splice, the table of lower-case runs and the SSR trim on the device (nd_splice.h states the rule; DESIGN.md section
+// 0a, K24).  run_splice is: pack_splice (the jobs of a launch into four arenas, bounded by a byte budget; what the kernel must
+// not compute is marked declined) -> launch_splice_jobs (the arenas up, K24 and its gather) -> fetch_splice (the records, then the
+// strings at exact size).  A declined job keeps done == false and the caller takes splice_host.
+
+// Test hook NDGPU_SPLICE_DECLINE=<k>: every k-th job offered to K24 is left to the host (counted over the process).
+static bool splice_decline_hook() {
+    static const uint64_t k = env_u64("NDGPU_SPLICE_DECLINE", 0);
+    static std::atomic<uint64_t> seen{0};
+    return k && seen.fetch_add(1) % k == k - 1;
+}
+
+size_t DeviceAligner::State::pack_splice(SpliceReq **reqs, size_t a, size_t n, SplicePack &P) {
+    constexpr size_t kJobs = 4096, kBytes = (size_t)256 << 20;   // a launch's jobs, and the bytes of its arenas
+    constexpr uint64_t kJobCap = (uint64_t)1 << 30;              // words, and words + pseudo-seed bytes, of one job
+    P.jobs.clear(), P.regs.clear(), P.words.clear(), P.seeds.clear(), P.ids.clear();
+    P.chars = 0;
+    size_t b = a;
+    for (; b < n && P.jobs.size() < kJobs; b++) {
+        SpliceReq &rq = *reqs[b];
+        rq.done = false;
+        const uint32_t nw = rq.len - rq.lstrip - rq.rstrip;
+        uint64_t seed_bytes = 0;
+        for (size_t k = 0; k < rq.n_regions; k++)
+            if (splice_usable(rq.regions[k].len)) seed_bytes += rq.regions[k].sudoseed_len;
+        bool take = (uint64_t)nw + seed_bytes < kJobCap && rq.n_regions < kJobCap;
+        for (uint32_t k = 0; take && k < nw; k++) take = (rq.words[rq.lstrip + k] >> 8) <= kSpliceMaxPos;
+        if (splice_decline_hook()) take = false;
+        if (!take) continue;
+        const size_t bytes = (size_t)nw * 5 + 2 * (size_t)seed_bytes + rq.n_regions * sizeof(SpliceRegDev);
+        if (!P.jobs.empty() && (P.words.size() * 4 + P.chars + P.seeds.size() + P.regs.size() * sizeof(SpliceRegDev)) + bytes > kBytes) break;
+        SpliceJobDev J;
+        memset(&J, 0, sizeof(J));
+        J.word_off = P.words.size(), J.reg_off = P.regs.size(), J.seed_off = P.seeds.size(), J.out_off = P.chars;
+        J.n_words = nw, J.n_regions = (uint32_t)rq.n_regions, J.out_cap = (uint32_t)(nw + seed_bytes), J.hifi = rq.hifi ? 1u : 0u;
+        P.words.insert(P.words.end(), rq.words + rq.lstrip, rq.words + rq.lstrip + nw);
+        P.regs.resize(P.regs.size() + rq.n_regions);
+        SpliceRegDev *R = P.regs.data() + J.reg_off;
+        uint32_t reach = 0;
+        for (size_t k = rq.n_regions; k-- > 0;) {   // (from the top: reach is a running maximum)
+            const SpliceRegion &r = rq.regions[k];
+            const bool usable = splice_usable(r.len);
+            R[k].start = r.start, R[k].end = r.end, R[k].usable = usable ? 1u : 0u;
+            R[k].seed_off = 0, R[k].seed_len = usable ? r.sudoseed_len : 0u;
+            if (usable) reach = std::max(reach, std::min(r.end, 1u << 21) + 1u);
+            R[k].reach = reach;
+        }
+        for (size_t k = 0; k < rq.n_regions; k++)
+            if (R[k].usable && R[k].seed_len) {
+                R[k].seed_off = (uint32_t)(P.seeds.size() - J.seed_off);
+                P.seeds.insert(P.seeds.end(), rq.regions[k].sudoseed, rq.regions[k].sudoseed + R[k].seed_len);
+            }
+        P.chars += J.out_cap;
+        P.jobs.push_back(J);
+        P.ids.push_back(b);
+    }
+    return b;
+}
+
+void DeviceAligner::State::launch_splice_jobs(const SplicePack &P) {
+    hipStream_t st = stream;
+    const size_t m = P.jobs.size();
+    d_splice_jobs.reserve(m), d_splice_out.reserve(m);
+    d_splice_regs.reserve(P.regs.size() + 1), d_splice_words.reserve(P.words.size() + 1), d_splice_seeds.reserve(P.seeds.size() + 1);
+    d_splice_chars.reserve(P.chars + 1), d_splice_seq.reserve(P.chars + 1);
+    h2d(d_splice_jobs.p, P.jobs.data(), m * sizeof(SpliceJobDev), st);
+    h2d(d_splice_regs.p, P.regs.data(), P.regs.size() * sizeof(SpliceRegDev), st);
+    h2d(d_splice_words.p, P.words.data(), P.words.size() * sizeof(uint32_t), st);
+    h2d(d_splice_seeds.p, P.seeds.data(), P.seeds.size(), st);
+    stats.splice_h2d_bytes += m * sizeof(SpliceJobDev) + P.regs.size() * sizeof(SpliceRegDev) + P.words.size() * sizeof(uint32_t) + P.seeds.size();
+    mark(kEvSpliceBegin, st);
+    NDGPU_DBG(st, "splice: %zu jobs", m);
+    launch_splice(d_splice_jobs.p, d_splice_words.p, d_splice_regs.p, d_splice_seeds.p, d_splice_chars.p, d_splice_out.p, d_splice_seq.p,
+                  (int)m, st);
+    mark(kEvSpliceEnd, st);
+    HIP_CHECK(hipGetLastError());
+    stats.splice_launches++;
+}
+
+void DeviceAligner::State::fetch_splice(SpliceReq **reqs, const SplicePack &P) {
+    hipStream_t st = stream;
+    const size_t m = P.jobs.size();
+    std::vector<SpliceOutDev> outs(m);
+    d2h(outs.data(), d_splice_out.p, m * sizeof(SpliceOutDev), st);
+    sync_drain(st);
+    stats.splice_ms += ms(kEvSpliceBegin, kEvSpliceEnd);
+    uint64_t n_bytes = 0;
+    for (const SpliceOutDev &O : outs)
+        if (!O.err) n_bytes += O.n_bytes;
+    reserve_down(n_bytes + 2048, st);
+    const char *sq = (const char *)d2h(nullptr, d_splice_seq.p, n_bytes, st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    stats.splice_d2h_bytes += m * sizeof(SpliceOutDev) + n_bytes;
+    for (size_t i = 0; i < m; i++) {
+        SpliceReq &rq = *reqs[P.ids[i]];
+        const SpliceOutDev &O = outs[i];
+        if (O.err) {
+            if (O.err != kSpliceErrHook)
+                fprintf(stderr, "[ndgpu] splice: a job of %u words left to the host statement (error word %u)\n", P.jobs[i].n_words, O.err);
+            continue;
+        }
+        rq.done = true;
+        rq.out_len = O.out_len, rq.lq_m = O.lq_m, rq.hq_m = O.hq_m, rq.lq_total_len = O.lq_total_len, rq.lq_i = O.lq_i;
+        rq.clip_s = O.clip_s, rq.clip_e = O.clip_e, rq.code = O.code, rq.trimmed = O.trimmed;
+        rq.seq.assign(sq, sq + O.n_bytes);
+        sq += O.n_bytes;
+        stats.splice_trimmed += O.trimmed;
+    }
+    drain();
+    if (trace_on())
+        fprintf(stderr, "[ndgpu trace] splice %zu jobs | K24 %.3f ms | %zu words, %zu regions up, %llu bytes down\n", m,
+                ms(kEvSpliceBegin, kEvSpliceEnd), P.words.size(), P.regs.size(), (unsigned long long)n_bytes);
+}
+
+void DeviceAligner::run_splice(SpliceReq **reqs, size_t n) {
+    if (n == 0) return;
+    State &S = *s_;
+    const State::Phase phase(S);
+    SplicePack P;
+    S.stats.splice_jobs += n;
+    size_t taken = 0;
+    for (size_t a = 0; a < n;) {
+        a = S.pack_splice(reqs, a, n, P);
+        if (P.jobs.empty()) continue;
+        S.launch_splice_jobs(P);
+        S.fetch_splice(reqs, P);
+    }
+    for (size_t i = 0; i < n; i++) taken += reqs[i]->done ? 1 : 0;
+    S.stats.splice_declined += n - taken;
 }
 
 void DeviceAligner::run_main(MainPile **mp, size_t np) {

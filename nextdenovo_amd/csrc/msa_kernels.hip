@@ -2240,6 +2240,343 @@ __global__ __launch_bounds__(64) void cns_walk_gather_kernel(const CnsWalkJobDev
     for (uint32_t k = lane; k < O.n_bytes; k += 64u) dense_seq[sb + k] = chars[path_off + O.hq_m - 1u - k];
 }
 
+// ---- K24: the splice, its table of lower-case runs and the terminal SSR trim ---------------------------------------------------------
+// The device form of splice_host and ssr_trim_host (nd_splice.h; lib/nextcorrect.c:1340-1482 and :2008-2128): one wavefront per job,
+// 64 items a chunk; what an item is on its own in the lanes, what depends on the items before it as a scan or wave-uniform.
+//
+// Emission.  The region index steps down at most one region a word (an `if`, not a `while`): with ascending positions
+// idx_i = max(T(p_i), idx_{i-1} - 1), T(p) the largest index whose region is usable and ends at or behind p -- no usable region above
+// idx_{i-1} ends at or behind p_i, or the index would not have passed it.  So idx_i + i is the running maximum of T(p_i) + i, started
+// at n_regions - 2: a prefix maximum, carried over the chunk edge.  The lag stays: a word inside a region the index has not reached yet
+// comes out as a plain base.  T comes from a bisection over `reach` (non-increasing in the index, built where the job is packed),
+// bounded above by the index the chunk before ended with.  A word outside its region emits its character; the first word of a visit
+// (the word before it was outside, or had another index) emits the whole pseudo-seed, copied by all lanes; offsets are an exclusive
+// scan.  Everything is emitted, also behind the place where the table fills: the cut is made by the automaton, which knows it.
+//
+// update_lqreg.  Per 64 emitted characters a ballot of ch >= 'a'; the automaton is wave-uniform and goes from run to run:
+//   * a lower-case run of k characters from q0 on: start = q0 if the slot is empty (lqlen == 0), end = q0 + k - 1, lqlen and
+//     lq_total_len += k, lq_m += k, and hq_m = 0 if lq_m passed 3 on the way;
+//   * an upper-case run: with an empty slot (lqlen == 0, hence end == 0) every branch leaves lqlen = end = 0, hq_m = 0 -- nothing to do;
+//     with an open one each character either closes / empties the slot (after which the slot is empty) or adds one to hq_m, and
+//     hq_m > 10 closes or empties: at most 12 characters of a run are stepped through, statement for statement.
+// A closed slot goes to the table in LDS (44 words); the open one lives in registers.  Where the tenth slot would open the string
+// ends, that character included.  The stretch is chosen from the table as the host does it, the HiFi end runs are counted on the way.
+//
+// The trim.  Gate: identity > 0.8, a float compared as a double.  1 - (float)t / len needs a correctly rounded float quotient: the
+// two floats are divided as doubles and the quotient rounded to float, which is the correctly rounded float quotient (a 53-bit
+// intermediate is wide enough for 24-bit operands: 53 >= 2 * 24 + 2), whatever the float division of the build is.  The 4-mers
+// of the 24 windows sit in lanes 0..23 (uint8_t shift-or of base_to_int: a code above 3 bleeds into the base before it); clip_ssr
+// walks along the set bits of ballot(cur == kmer) -- between two matches only the mismatches 21 and 22 behind the last match can act
+// (the first sets p1, or tests `i - p2 < 100` and breaks or resets; the second sets p1 again after a reset) -- and the tail direction
+// is the same walk over the reversed string with the bit-reversed 4-mer, one position shorter as in the reference.
+__device__ __forceinline__ uint32_t splice_code(uint32_t c) {   // base_to_int
+    uint32_t r = 4u;
+    if (c == 'A' || c == 'a') r = 0u;
+    else if (c == 'T' || c == 't') r = 1u;
+    else if (c == 'G' || c == 'g') r = 2u;
+    else if (c == 'C' || c == 'c') r = 3u;
+    else if (c == 'N') r = 5u;
+    else if (c == 'M') r = 6u;
+    return r;
+}
+// the 4-mer at index i of S[0, L), forward or over the reversed string
+__device__ __forceinline__ uint32_t splice_kmer4(const uint8_t *S, int L, int i, bool rev) {
+    uint32_t km = 0;
+    for (int k = 0; k < 4; k++) km = km << 2 | splice_code(rev ? S[L - 1 - i - k] : S[i + k]);
+    return km & 0xffu;
+}
+// terminal_ssr over the 24 windows from s on: the most frequent 4-mer (the lowest on a tie) and its count
+__device__ __forceinline__ void splice_top_kmer(const uint8_t *S, int L, int s, int lane, uint32_t &kmer, int &count) {
+    const uint32_t km = lane < 24 ? splice_kmer4(S, L, s + lane, false) : 0x100u;
+    int cnt = 0;
+    for (int j = 0; j < 24; j++) cnt += __shfl(km, j) == km ? 1 : 0;
+    uint32_t key = lane < 24 ? (uint32_t)cnt << 8 | (255u - km) : 0u;
+    for (int m = 32; m; m >>= 1) {
+        const uint32_t o = __shfl_xor(key, m);
+        key = o > key ? o : key;
+    }
+    count = (int)(key >> 8);
+    kmer = 255u - (key & 0xffu);
+}
+__device__ __forceinline__ int splice_clip(const uint8_t *S, int L, uint32_t kmer, bool rev, int lane) {
+    const int n = rev ? L - 5 : L - 4;   // the loop's indices [0, n)
+    if (rev) {
+        uint32_t rk = 0;
+        for (int i = 0; i < 8; i += 2) rk = rk << 2 | (kmer >> i & 3u);
+        kmer = rk & 0xffu;
+    }
+    int p = 0, p1 = 0, p2 = 0;
+    bool brk = false;
+    auto gap = [&](int g_end) {   // the mismatches between p and g_end
+        if (p + 21 < g_end) {
+            if (!p1) p1 = p;
+            else if (p2) {
+                if (p + 21 - p2 < 100) {
+                    p = p1;
+                    brk = true;
+                } else {
+                    p1 = p2 = 0;
+                    if (p + 22 < g_end) p1 = p;
+                }
+            }
+        }
+    };
+    for (int i0 = 0; i0 < n && !brk; i0 += 64) {   // (trip bound: n / 64 + 1)
+        const int i = i0 + lane;
+        unsigned long long mm = wave_ballot(i < n && splice_kmer4(S, L, i, rev) == kmer);
+        while (mm) {   // (trip bound: 64)
+            const int m = i0 + __builtin_ctzll(mm);
+            mm &= mm - 1ull;
+            gap(m);
+            if (brk) break;
+            p = m;
+            if (p1 && !p2) p2 = p;
+        }
+    }
+    if (!brk) gap(n);
+    return p > 100 ? p + 4 : 0;
+}
+// from `from` on, the first index that is not lower case (L if there is none), forward or over the reversed string
+__device__ __forceinline__ int splice_skip_lower(const uint8_t *S, int L, int from, bool rev, int lane) {
+    for (int c = from; c < L; c += 64) {   // (trip bound: L / 64 + 1)
+        const int j = c + lane;
+        const unsigned long long up = wave_ballot(j < L && (rev ? S[L - 1 - j] : S[j]) < 'a');
+        if (up) return c + __builtin_ctzll(up);
+    }
+    return from < L ? L : from;
+}
+
+__global__ __launch_bounds__(64) void splice_kernel(const SpliceJobDev *__restrict__ jobs, const uint32_t *__restrict__ words,
+                                                     const SpliceRegDev *__restrict__ regs, const uint8_t *__restrict__ seeds,
+                                                     uint8_t *chars, SpliceOutDev *__restrict__ out) {
+    __shared__ uint32_t tab[4 * 11];   // the ten slots and the guard slot: start, end, lqlen, lq_total_len
+    const SpliceJobDev J = jobs[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    SpliceOutDev O;
+    O.err = O.out_len = O.lq_m = O.hq_m = O.lq_total_len = O.code = O.trimmed = O.n_bytes = O.src = 0u;
+    O.lq_i = O.clip_s = O.clip_e = 0;
+    if (J.decline || J.n_words >= (1u << 30)) {
+        O.err = J.decline ? kSpliceErrHook : kSpliceErrCap;
+        if (lane == 0) out[blockIdx.x] = O;
+        return;
+    }
+    if (lane < 44) tab[lane] = 0u;
+    const uint32_t *W = words + J.word_off;
+    const SpliceRegDev *R = regs + J.reg_off;
+    const uint8_t *SD = seeds + J.seed_off;
+    uint8_t *OUT = chars + J.out_off;
+    const uint32_t n = J.n_words;
+    uint32_t err = 0;
+
+    // ---- emission
+    int g = (int)J.n_regions - 2;   // idx + i before the first word
+    int hi = (int)J.n_regions - 1;
+    int carry_idx = -2, carry_in = 0;
+    uint32_t total = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64u) {   // (trip bound: n / 64 + 1)
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool valid = i < n;
+        const uint32_t w = valid ? W[i] : 0u;
+        const uint32_t p = w >> 8;
+        int v = -0x7fffffff;
+        if (valid) {
+            int a = 0, b = hi + 1;   // the first index in [0, hi + 1] whose reach is not beyond p
+            while (a < b) {          // (trip bound: 32)
+                const int mid = (a + b) >> 1;
+                if (R[mid].reach > p) a = mid + 1;
+                else b = mid;
+            }
+            v = a - 1 + (int)i;
+        }
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(v, d);
+            if (lane >= d && o > v) v = o;
+        }
+        v = v > g ? v : g;
+        const int idx = valid ? v - (int)i : -1;
+        int in = 0;
+        uint32_t slen = 0, soff = 0;
+        if (valid && idx >= 0) {
+            const SpliceRegDev r = R[idx];
+            in = r.usable && p >= r.start && p <= r.end ? 1 : 0;
+            slen = r.seed_len, soff = r.seed_off;
+        }
+        int prev_in = __shfl_up(in, 1), prev_idx = __shfl_up(idx, 1);
+        if (lane == 0) prev_in = carry_in, prev_idx = carry_idx;
+        const bool emit = in && !(prev_in && prev_idx == idx);
+        const uint32_t cnt = !valid ? 0u : in ? (emit ? slen : 0u) : 1u;
+        uint32_t incl = cnt;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        const uint32_t chunk = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        if (chunk > J.out_cap - total) {   // (cannot happen: a region is emitted once at most)
+            err |= kSpliceErrCap;
+            break;
+        }
+        const uint32_t off = total + incl - cnt;
+        if (valid && !in) OUT[off] = (uint8_t)(w & 0xffu);
+        unsigned long long em = wave_ballot(emit && slen > 0u);
+        while (em) {   // (trip bound: 64)
+            const int b = __builtin_ctzll(em);
+            em &= em - 1ull;
+            const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)off, b);
+            const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)slen, b);
+            const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)soff, b);
+            for (uint32_t k = (uint32_t)lane; k < l; k += 64u) OUT[o + k] = SD[s + k];
+        }
+        total += chunk;
+        const int last = n - 1u - i0 < 63u ? (int)(n - 1u - i0) : 63;
+        g = __builtin_amdgcn_readlane(v, last);
+        hi = carry_idx = __builtin_amdgcn_readlane(idx, last);
+        carry_in = __builtin_amdgcn_readlane(in, last);
+    }
+    // hand-over: the automaton and the trim read characters other lanes wrote
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- update_lqreg along the runs
+    uint32_t c_start = 0, c_end = 0, c_lqlen = 0, c_total = 0;   // the open slot lq[lq_i]
+    int lq_i = 0;
+    uint32_t hq = 0, lqm = 0, olen = total;
+    uint32_t head_run = 0, tail_run = 0;
+    bool head_open = true, stop = false;
+    auto close_slot = [&]() {
+        if (lane == 0) tab[4 * lq_i] = c_start, tab[4 * lq_i + 1] = c_end, tab[4 * lq_i + 2] = c_lqlen, tab[4 * lq_i + 3] = c_total;
+        lq_i++;
+        c_start = c_end = c_lqlen = c_total = 0u;
+    };
+    for (uint32_t q0c = 0; q0c < total && !stop && !err; q0c += 64u) {   // (trip bound: total / 64 + 1)
+        const uint32_t q = q0c + (uint32_t)lane;
+        const unsigned long long vm = total - q0c >= 64u ? ~0ull : lanes_lt((int)(total - q0c));
+        const unsigned long long lowm = wave_ballot(q < total && OUT[q] >= 'a');
+        unsigned long long todo = vm;
+        while (todo) {   // (trip bound: 64, a run leaves `todo` every turn)
+            const int L0 = __builtin_ctzll(todo);
+            const bool low = (lowm >> L0) & 1ull;
+            const unsigned long long other = todo & (low ? ~lowm : lowm);
+            const unsigned long long run = other ? todo & lanes_lt(__builtin_ctzll(other)) : todo;
+            todo &= ~run;
+            const uint32_t k = (uint32_t)__popcll(run), q0 = q0c + (uint32_t)L0;
+            if (low) {
+                if (!c_lqlen) c_start = q0;
+                if (lqm + k > 3u) hq = 0u;
+                lqm += k;
+                c_end = q0 + k - 1u;
+                c_lqlen += k, c_total += k;
+                if (head_open) head_run += k;
+                tail_run += k;
+            } else {
+                head_open = false;
+                tail_run = 0u;
+                for (uint32_t j = 0; j < k; j++) {   // (trip bound: 12, see above)
+                    if (!c_lqlen) {
+                        c_end = 0u, hq = 0u;
+                        break;
+                    }
+                    const int before = lq_i;
+                    if (c_start == 0u) {
+                        close_slot();
+                        hq = 0u;
+                    } else if (hq + c_start > c_end || hq++ > 10u) {
+                        if (c_end > c_start + 100u) close_slot();
+                        else c_lqlen = c_end = 0u;
+                        hq = 0u;
+                    } else if (hq >= c_lqlen) {
+                        c_lqlen = c_end = 0u;
+                        hq = 0u;
+                    }
+                    if (lq_i != before && lq_i >= 10) {   // LQREG_MAX_COUNT: the string ends here, this character included
+                        olen = q0 + j + 1u;
+                        stop = true;
+                        break;
+                    }
+                }
+                lqm = 0u;
+                if (stop) break;
+            }
+        }
+    }
+    if (lane == 0) tab[4 * lq_i] = c_start, tab[4 * lq_i + 1] = c_end, tab[4 * lq_i + 2] = c_lqlen, tab[4 * lq_i + 3] = c_total;
+    __syncthreads();
+
+    // ---- the stretch
+    if (lq_i < 11 && tab[4 * lq_i + 1] == olen - 1u) lq_i++;
+    uint32_t lq_m = 0, hq_m = 0, lq_total = 0, code = 0;
+    if (J.hifi) {
+        if (head_run + tail_run < olen) {
+            for (int s = 0; s < lq_i && s < 11; s++) lq_total += tab[4 * s + 3];
+            lq_m = head_run, hq_m = olen - tail_run;
+            lq_total -= head_run + tail_run;
+        } else code = 2u;
+    } else if (lq_i) {
+        hq_m = tab[0];
+        uint32_t best = tab[0];
+        lq_total = tab[3] - tab[2];
+        int s = 1;
+        for (; s < 10 && tab[4 * s + 1]; s++) {
+            if (tab[4 * s] - tab[4 * (s - 1) + 1] > best) {
+                lq_m = tab[4 * (s - 1) + 1] + 1u;
+                hq_m = tab[4 * s];
+                lq_total = tab[4 * s + 3] - tab[4 * s + 2];
+                best = tab[4 * s] - tab[4 * (s - 1) + 1];
+            }
+        }
+        if (s < 10 && olen - tab[4 * (s - 1) + 1] > best) {
+            lq_m = tab[4 * (s - 1) + 1] + 1u;
+            hq_m = olen;
+            lq_total = tab[4 * s + 3];
+        }
+    } else {
+        lq_m = head_run, hq_m = olen;
+        lq_total = tab[3] - head_run;
+    }
+    if (lq_m > hq_m || hq_m > olen) err |= kSpliceErrRange;   // (cannot happen: the slots lie inside the string, in order)
+
+    // ---- the trim
+    int clip_s = 0, clip_e = 0;
+    uint32_t len = code ? 0u : hq_m - lq_m, trimmed = 0;
+    if (!err && !code && len > 1000u && len < 0x7fffffffu) {
+        const float quot = (float)((double)(float)lq_total / (double)(float)len);
+        const float identity = 1.0f - quot;
+        if ((double)identity > 0.8) {
+            trimmed = 1u;
+            const uint8_t *S = OUT + lq_m;
+            const int L = (int)len;
+            uint32_t kmer;
+            int count;
+            splice_top_kmer(S, L, 0, lane, kmer, count);
+            if (count >= 4) clip_s = splice_skip_lower(S, L, splice_clip(S, L, kmer, false, lane), false, lane);
+            splice_top_kmer(S, L, L - 27, lane, kmer, count);
+            if (count >= 4) clip_e = splice_skip_lower(S, L, splice_clip(S, L, kmer, true, lane), true, lane);
+            if (clip_s + clip_e < L - 10) len = (uint32_t)(L - clip_s - clip_e);
+            else code = 4u;
+        }
+    }
+    O.err = err;
+    O.out_len = olen;
+    O.lq_m = lq_m, O.hq_m = hq_m, O.lq_total_len = lq_total, O.lq_i = lq_i;
+    O.clip_s = clip_s, O.clip_e = clip_e;
+    O.code = code, O.trimmed = trimmed;
+    O.n_bytes = err || code == 2u ? 0u : code == 4u ? 4u : len;
+    O.src = lq_m + (code == 4u ? 0u : (uint32_t)clip_s);
+    if (lane == 0) out[blockIdx.x] = O;
+}
+
+__global__ __launch_bounds__(64) void splice_gather_kernel(const SpliceJobDev *__restrict__ jobs, const SpliceOutDev *__restrict__ out,
+                                                            const uint8_t *__restrict__ chars, uint8_t *__restrict__ dense_seq) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    unsigned long long sb = 0;
+    for (uint32_t j = lane; j < b; j += 64u)
+        if (!out[j].err) sb += out[j].n_bytes;
+    for (int m = 32; m; m >>= 1) sb += __shfl_xor(sb, m);
+    const SpliceOutDev O = out[b];
+    if (O.err) return;
+    const uint8_t *src = chars + jobs[b].out_off + O.src;
+    for (uint32_t k = lane; k < O.n_bytes; k += 64u) dense_seq[sb + k] = src[k];
+}
+
 // ---- K11 -------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void extract_kernel(const PileDev *__restrict__ piles,
                                                       const ReadDev *__restrict__ reads,
@@ -2474,6 +2811,13 @@ void launch_cns_walk(const CnsWalkJobDev *jobs, const PileDev *piles, const Path
                        words, wins, chars, out);
     hipLaunchKernelGGL(cns_walk_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, piles, out, words, wins, chars,
                        dense_words, dense_wins, dense_seq);
+}
+
+void launch_splice(const SpliceJobDev *jobs, const uint32_t *words, const SpliceRegDev *regs, const uint8_t *seeds, uint8_t *chars,
+                   SpliceOutDev *out, uint8_t *dense_seq, int n, void *stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(splice_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, words, regs, seeds, chars, out);
+    hipLaunchKernelGGL(splice_gather_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, jobs, out, chars, dense_seq);
 }
 
 void launch_extract(const PileDev *piles, const ReadDev *reads, const uint32_t *acc_list, const uint32_t *tags,

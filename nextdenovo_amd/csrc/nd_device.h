@@ -356,6 +356,43 @@ void launch_cns_walk(const CnsWalkJobDev *jobs, const PileDev *piles, const Path
                      const uint8_t *seed_codes, uint32_t *words, uint32_t *wins, uint8_t *chars, CnsWalkOutDev *out, uint32_t *dense_words,
                      uint32_t *dense_wins, uint8_t *dense_seq, int n, void *stream);
 
+// ---- K24: the splice, its table of lower-case runs and the terminal SSR trim (splice_kernel, msa_kernels.hip; the rule: nd_splice.h) ----
+struct SpliceRegDev {       // one region of a job, in the engine's order
+    uint32_t start, end;    // inclusive positions
+    uint32_t seed_off;      // its pseudo-seed's first byte behind the job's seed_off
+    uint32_t seed_len;
+    uint32_t usable;        // len > 0 or len == -2
+    uint32_t reach;         // 1 + the largest end (capped at 2^21) among the usable regions of this index and above; 0: there is none
+};
+struct SpliceJobDev {
+    uint64_t word_off;      // the first word the loop reads (the word at lstrip)
+    uint64_t reg_off;       // its first SpliceRegDev
+    uint64_t seed_off;      // its pseudo-seed bytes
+    uint64_t out_off;       // its slice of the emitted characters
+    uint32_t n_words;       // len - lstrip - rstrip
+    uint32_t n_regions;
+    uint32_t out_cap;       // n_words + the usable regions' pseudo-seed bytes: a region is emitted once at most
+    uint32_t hifi;
+    uint32_t decline;       // test hook: the kernel leaves the job with kSpliceErrHook
+    uint32_t pad_;
+};
+struct SpliceOutDev {       // what the host reads per job: 48 bytes
+    uint32_t err;           // kSpliceErr* bits; nonzero: declined, splice_host takes the job
+    uint32_t out_len;       // characters emitted (cut where the tenth slot would open)
+    uint32_t lq_m, hq_m;    // the chosen stretch
+    uint32_t lq_total_len;
+    int32_t lq_i;
+    int32_t clip_s, clip_e;
+    uint32_t code;          // 0, or the outcomes 2 (HiFi: all lower case) and 4 (the clips leave 10 bases or fewer)
+    uint32_t trimmed;       // the gate let the trim run
+    uint32_t n_bytes;       // bytes the gather writes for the job ...
+    uint32_t src;           // ... from this index of its emitted characters on
+};
+enum : uint32_t { kSpliceErrHook = 1u, kSpliceErrCap = 2u, kSpliceErrRange = 4u };
+// K24 over jobs [0, n), then its gather: job i's result string to dense_seq at the sum of n_bytes in front of it (declined jobs count as empty).
+void launch_splice(const SpliceJobDev *jobs, const uint32_t *words, const SpliceRegDev *regs, const uint8_t *seeds, uint8_t *chars,
+                   SpliceOutDev *out, uint8_t *dense_seq, int n, void *stream);
+
 struct ColBlock {           // work item of the link-counting kernel
     uint32_t pile;
     uint32_t col0;

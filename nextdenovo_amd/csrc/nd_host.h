@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "nd_phase.h"
+#include "nd_splice.h"
 
 namespace ndgpu {
 
@@ -193,6 +194,21 @@ bool pack_2bit_lsb(uint32_t *out, const char *s, size_t n);
 
 struct PoaReq;   // one POA problem as a backend request (below)
 
+// The end of a pile as a backend request (Backend::run_splice; the jobs of ndgpu_splice_batch take the same form): the integers
+// splice_host and ssr_trim_host (nd_splice.h) give for it, and the result string.
+struct SpliceReq {
+    const uint32_t *words = nullptr;       // pos << 8 | char, ascending positions; [lstrip, len - rstrip) is read
+    uint32_t len = 0, lstrip = 0, rstrip = 0;
+    const SpliceRegion *regions = nullptr;
+    size_t n_regions = 0;
+    bool hifi = false;
+    bool done = false;                     // false: declined, the host statement takes the job
+    uint32_t out_len = 0, lq_m = 0, hq_m = 0, lq_total_len = 0;
+    int32_t lq_i = 0, clip_s = 0, clip_e = 0;
+    uint32_t code = 0, trimmed = 0;        // code: 0, 2 (HiFi, all lower case) or 4 (the clips leave 10 bases or fewer)
+    std::string seq;
+};
+
 // Executes the device-side work of a batch of piles.  The product has exactly one
 // implementation (HipBackend, device_runtime.hip); tests plug the CPU oracle here to
 // exercise the host logic without a GPU.
@@ -206,6 +222,8 @@ class Backend {
     virtual bool run_lq(LqRound **rounds, size_t n) { (void)rounds; (void)n; return false; }
     // a batch of POA problems on the backend; false: not offered (the caller computes every one on the host)
     virtual bool run_poa(PoaReq **reqs, size_t n) { (void)reqs; (void)n; return false; }
+    // the piles' final splices on the backend; false: not offered.  A request whose done stays false is the caller's to compute.
+    virtual bool run_splice(SpliceReq **reqs, size_t n) { (void)reqs; (void)n; return false; }
     virtual void end_batch() = 0;  // releases whatever run_main kept for run_extract
 };
 
@@ -266,10 +284,12 @@ class PileImpl;
 
 // Per-seed consensus state machine.  Device work is exposed as requests so that many
 // piles share each launch:
-//     MAIN (MainPile) -> EXTRACT (ExtractPile) [-> POA (PoaReq)] -> LQ round 1 (AlnJob) -> LQ round 2 -> DONE
+//     MAIN (MainPile) -> EXTRACT (ExtractPile) [-> POA (PoaReq)] -> LQ round 1 (AlnJob) -> LQ round 2 [-> SPLICE (SpliceReq)] -> DONE
 class PileEngine {
   public:
-    enum Phase { MAIN = 0, EXTRACT = 1, LQ_ROUND = 2, DONE = 3, POA = 4 };  // POA: between EXTRACT and LQ round 1, when the regions' POA problems go out as requests
+    // POA: between EXTRACT and LQ round 1, when the regions' POA problems go out as requests; SPLICE: behind the last LQ round, when
+    // the splice goes out as a request (NDGPU_SPLICE_DEVICE=1)
+    enum Phase { MAIN = 0, EXTRACT = 1, LQ_ROUND = 2, DONE = 3, POA = 4, SPLICE = 5 };
     // ASCII form (the nextCorrect ABI): seqs[i] NUL-terminated.
     PileEngine(const char *const *seqs, const unsigned *aln_start, const unsigned *aln_end, unsigned seq_count,
                const CorrectParams &prm);
@@ -288,6 +308,7 @@ class PileEngine {
     void collect_jobs(std::vector<AlnJob *> &out);  // LQ_ROUND (host path)
     LqRound *lq_request();           // LQ_ROUND: the round as one device request (nullptr: nothing to hand over)
     void collect_poa(std::vector<PoaReq *> &out);   // POA: the regions' problems
+    SpliceReq *splice_request();     // valid in SPLICE
     void advance();                  // consume the finished request(s), move on
     ConsensusTrimed *take_result();  // malloc'd, caller frees with free_consensus_trimed
 

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "nd_host.h"
@@ -112,6 +113,14 @@ struct RuntimeStats {
     double phase_ms = 0;                 // their HIP-event time
     uint64_t phase_d2h_records = 0;      // bytes of pile and region records brought back
     uint64_t phase_d2h_strings = 0;      // bytes of candidate strings brought back beside them (run_extract)
+    // the splice, its table of lower-case runs and the SSR trim on the device (K24; ndgpu_get_splice_stats)
+    uint64_t splice_jobs = 0;            // jobs offered to run_splice
+    uint64_t splice_declined = 0;        // ... of which the host statement took (arena caps, a position outside the words' range, the hook)
+    uint64_t splice_launches = 0;        // launches of K24 (each with its gather)
+    uint64_t splice_h2d_bytes = 0;       // job and region records, words and pseudo-seed bytes sent up
+    uint64_t splice_d2h_bytes = 0;       // result records and result strings brought back
+    uint64_t splice_trimmed = 0;         // jobs whose gate let the SSR trim run
+    double splice_ms = 0;                // K24's HIP-event time
 };
 
 // One pile of the batched entry ndgpu_hifi_phase_batch (DeviceAligner::run_phase): what hifi_phase_host (nd_phase.h) returns for it.
@@ -190,6 +199,7 @@ class DeviceAligner {
     void run_cns(CnsReq *reqs, size_t n);     // the batched entry's walks through K20; req.done = false: declined, the host routine takes it
     void run_cns_walk(CnsWalkReq *reqs, size_t n);   // ... of modes 1 and 2 through K21
     void run_phase(PhaseReq *reqs, size_t n);        // the batched entry's HiFi piles through K22: one pool up, the records back
+    void run_splice(SpliceReq **reqs, size_t n);     // the splices of the batched entry or of the engine through K24: four arenas up, records and strings back
     void run_lq(LqRound **rounds, size_t n);
     // req.done = false: declined, the caller's host path takes it.  form 0: NDGPU_POA_RESIDENT decides; 1: resident graphs (K19);
     // 2: K13's rounds with the graphs on the host
@@ -245,6 +255,12 @@ class HipBackend : public Backend {
     void run_cns(CnsReq *reqs, size_t n) { dev_.run_cns(reqs, n); }
     void run_cns_walk(CnsWalkReq *reqs, size_t n) { dev_.run_cns_walk(reqs, n); }
     void run_phase(PhaseReq *reqs, size_t n) { dev_.run_phase(reqs, n); }
+    bool run_splice(SpliceReq **reqs, size_t n) override {
+        static const bool host_splice = getenv("NDGPU_SPLICE_HOST") != nullptr;  // test hook: a backend without the entry
+        if (host_splice) return false;
+        dev_.run_splice(reqs, n);
+        return true;
+    }
     void run_align(AlnJob **jobs, size_t n) override { dev_.align_batch(jobs, n); }
     void run_align_runs(AlnJob **jobs, size_t n, AlnRunsResult *res, std::vector<uint32_t> &runs) { dev_.align_batch_runs(jobs, n, res, runs); }
     bool run_lq(LqRound **rounds, size_t n) override {
